@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- frames/s of the ITAViTLSTM int8 forward on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
 
 One "step" = one pass of module.main_graph (tokenizer -> int8 MHA -> int8 FFN -> fusion tail ->
@@ -11,7 +11,10 @@ decoder -> 3-layer LSTM -> fc) over one batch of synthetic 60x90 depth frames pe
 plus -- for N > 1 -- the RCCL all-gather of the (frames, 3) velocities.  Weak scaling: every GPU
 always processes `--frames-per-gpu` independent streams.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0): frames/s over exactly K timed steps and ms_per_step.  A plain run does nothing else.
+--dump-outputs DIR writes what the last timed step returned to its caller as float32 .npy files: velocity (all GPUs'
+frames, gathered), h and c (3, frames, 128) of rank 0 (over 64 MB in all: the same seeded sample of frames in each).
+--full adds these objects (--no-cpu-baseline / --no-latency / --no-configs drop single legs of it):
   roofline      dominant kernel: algorithmic ops per launch / its HIP-event time measured in the
                 timed region, against the MI355X peak for its arithmetic (guide: int8 MFMA
                 5.0 POP/s dense, f32 157.3 TFLOP/s)
@@ -23,6 +26,8 @@ Prints ONE JSON line (rank 0).  Extra objects:
                 c5_mha: config 5 as worded, the int8 attention block on 8192 tokens per frame (three-sweep integer softmax);
                 vit2l: the second graph family (E = 128, two layers, no fusion tail), whole forward at 1024 frames;
                 b1 / b128 / b256: step time of the whole forward at 1, 128, 256 frames per GPU (config 3; config 4 cut over 8 GPUs)
+  stages        per-stage times from an untimed eager pass with events around every stage
+  p50_latency_ms_b1[_hipgraph]  single-frame latency, host enqueue -> result
 --schedule selects one stream / the library's two-stream pipeline / its HIP-graph form (default: graph up to 256 frames per GPU).
 --global-batch G gives the strong-scaling form of config 4 (G frames per step cut over the GPUs, "scaling": "strong").
 """
@@ -68,6 +73,22 @@ def pmc_traffic(kernel, frames):
         return int(k["hbm_bytes_per_launch"] * frames / 1024), t["source"]
     except Exception:
         return None, None
+
+
+DUMP_LIMIT = 60_000_000     # bytes of all --dump-outputs arrays together
+
+
+def dump_outputs(path, arrays):
+    """arrays: name -> (tensor, frame axis); written as path/<name>.npy in float32.  Beyond DUMP_LIMIT bytes in all, every
+    array keeps the same fraction of its frames, chosen by a fixed seed, so that runs with the same arguments compare."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: (t.detach().float().cpu().numpy(), ax) for k, (t, ax) in arrays.items()}
+    keep = min(1.0, DUMP_LIMIT / sum(x.nbytes for x, _ in arrays.values()))
+    for name, (x, ax) in arrays.items():
+        if keep < 1.0:
+            n = x.shape[ax]
+            x = np.take(x, np.sort(np.random.default_rng(0).choice(n, max(1, int(n * keep)), replace=False)), axis=ax)
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(x, dtype=np.float32))
 
 
 def _cpu_worker(job):
@@ -389,6 +410,11 @@ def main():
                          "gets at most 256 frames per step (the encoder then leaves CUs free for the LSTM kernels), else stream")
     ap.add_argument("--hip-graph", choices=["auto", "on", "off"], default=None,
                     help="older spelling: on = --schedule graph, off = --schedule stream")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline and per-stage table, p50 latency, "
+                         "CPU baseline, the other BASELINE configurations (each in runs of its own after the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the velocities and LSTM state of the last timed step as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-latency", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip the BASELINE config 2 / config 5 legs (configs.c2, configs.c5)")
@@ -409,7 +435,7 @@ def main():
     fp0 = synth.float_params(0, E=64)
     blob = params.blob_from_record(fx, fp0, E=64)     # weights: seed 0 synthetic-QAT
     cpu = None
-    if world == 1 and not a.no_cpu_baseline:      # before anything touches the GPU: the CPU workers are forked
+    if a.full and world == 1 and not a.no_cpu_baseline:      # before anything touches the GPU: the CPU workers are forked
         cpu = cpu_baseline(blob, fp0)
 
     import torch
@@ -554,29 +580,30 @@ def main():
         step(i)
     flush()
     fence()
-    # Untimed eager pass with HIP events around EVERY stage: the per-stage table and the dominant stage.
-    # (Each event costs a ~5 us bubble in the stream, so this pass is slower than the timed one.)
-    NP = 20
-    eng.profile_begin(NP)
-    for i in range(NP):
-        src, dst = state[(W + i) & 1], state[(W + i + 1) & 1]
-        eng.forward(img, dv, qt, src, out=(vels[0], dst[0], dst[1]))
-    fence()
-    stage_all, n_all = eng.profile_end()
-    per = {k: v / max(n_all, 1) for k, v in stage_all.items()}
-    per["tail_decoder"] = per.pop("tail") + per.pop("decoder")
-    per["encoder"] = per.pop("mha") + per.pop("ffn")
     # u8 wire frames: the tokenizer runs inside the encoder kernel (ita_stream_kernel<64, true, 1>), one stage;
     # f32 frames go through the stand-alone tokenizer launch
     fused_tok = not os.environ.get("ITA_SPLIT_TOKENIZER") and a.image_dtype == "u8"
-    if fused_tok:
-        per["encoder"] += per.pop("tokenizer")
-    dom = max(per, key=per.get)
-    dom_plugin_stage = {"encoder": "mha", "tail_decoder": "tail", "lstm_fc": "lstm_fc", "tokenizer": "tokenizer"}[dom]
-    # Timed region: exactly K steps.  Eager schedule: HIP events around the dominant kernel only, on every 8th step (its
-    # launch duration for the roofline is measured here, live, on the compute stream).  Pipelined / graph schedules: no timing
-    # events inside, so the dominant kernel is timed the same way in an eager pass right after the timed region.
-    live = graph is None and not os.environ.get("ITA_BENCH_NOPROF")
+    if a.full:
+        # Untimed eager pass with HIP events around EVERY stage: the per-stage table and the dominant stage.
+        # (Each event costs a ~5 us bubble in the stream, so this pass is slower than the timed one.)
+        NP = 20
+        eng.profile_begin(NP)
+        for i in range(NP):
+            src, dst = state[(W + i) & 1], state[(W + i + 1) & 1]
+            eng.forward(img, dv, qt, src, out=(vels[0], dst[0], dst[1]))
+        fence()
+        stage_all, n_all = eng.profile_end()
+        per = {k: v / max(n_all, 1) for k, v in stage_all.items()}
+        per["tail_decoder"] = per.pop("tail") + per.pop("decoder")
+        per["encoder"] = per.pop("mha") + per.pop("ffn")
+        if fused_tok:
+            per["encoder"] += per.pop("tokenizer")
+        dom = max(per, key=per.get)
+        dom_plugin_stage = {"encoder": "mha", "tail_decoder": "tail", "lstm_fc": "lstm_fc", "tokenizer": "tokenizer"}[dom]
+    # Timed region: exactly K steps.  With --full, eager schedule: HIP events around the dominant kernel only, on every 8th
+    # step (its launch duration for the roofline is measured here, live, on the compute stream).  Pipelined / graph schedules:
+    # no timing events inside, so the dominant kernel is timed the same way in an eager pass right after the timed region.
+    live = a.full and graph is None and not os.environ.get("ITA_BENCH_NOPROF")
     if live:
         eng.profile_begin(min(K, 512), every_n=8, only_stage=dom_plugin_stage)
     t0 = time.perf_counter()
@@ -585,26 +612,64 @@ def main():
     flush()
     fence()
     elapsed = time.perf_counter() - t0
-    if live:
-        stage_ms, nprof = eng.profile_end()
-        timing = "HIP events around this kernel on every 8th step of the timed region"
-    else:
-        eng.profile_begin(64, every_n=2, only_stage=dom_plugin_stage)
-        for i in range(128):
-            src, dst = state[i & 1], state[(i + 1) & 1]
-            eng.forward(img, dv, qt, src, out=(vels[0], dst[0], dst[1]))
-        fence()
-        stage_ms, nprof = eng.profile_end()
-        timing = ("HIP events around this kernel on every 2nd step of a 128-step eager pass right after the timed region "
-                  "(the timed region replays HIP graphs, which cannot carry timing events)")
-    dom_ms = stage_ms[dom_plugin_stage] / max(nprof, 1)
     if world > 1:
         t = torch.tensor([elapsed], device=dev if a.backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs and rank == 0:
+        # what step K - 1 handed its caller, taken before --full's passes below reuse these buffers
+        if graph is not None:           # one replay / library call = NG steps; its last step wrote vel[NG - 1]
+            vel, (h, c) = graph.vel[NG - 1], (graph.h, graph.c)
+        elif batched_gather:
+            vel, (h, c) = velring[((K - 1) // NG) & 1][(K - 1) % NG], state[K & 1]
+        else:
+            vel, (h, c) = vels[(K - 1) % 3], state[K & 1]
+        if world > 1:                   # the caller's velocities are those of every GPU: the last all-gather started
+            vel = gather.result(gather.i ^ 1)
+            if gather_every == NG:      # each rank sent NG steps x its shard: keep every rank's last step
+                vel = torch.cat([r.reshape(NG, -1, 3)[NG - 1] for r in torch.split(vel, gather.sizes)])
+        dump_outputs(a.dump_outputs, {"velocity": (vel, 0), "h": (h, 1), "c": (c, 1)})
+    if a.full:
+        if live:
+            stage_ms, nprof = eng.profile_end()
+            timing = "HIP events around this kernel on every 8th step of the timed region"
+        else:
+            eng.profile_begin(64, every_n=2, only_stage=dom_plugin_stage)
+            for i in range(128):
+                src, dst = state[i & 1], state[(i + 1) & 1]
+                eng.forward(img, dv, qt, src, out=(vels[0], dst[0], dst[1]))
+            fence()
+            stage_ms, nprof = eng.profile_end()
+            timing = ("HIP events around this kernel on every 2nd step of a 128-step eager pass right after the timed region "
+                      "(the timed region replays HIP graphs, which cannot carry timing events)")
+        dom_ms = stage_ms[dom_plugin_stage] / max(nprof, 1)
 
     out = None
     if rank == 0:
+        frames_per_step = total
+        wl = (f"{a.global_batch} synthetic 60x90 depth frames per step in all, contiguous shards over {world} GPU(s)" if strong
+              else f"{B} synthetic 60x90 depth frames per GPU per step")
+        out = {
+            "metric": "frames/s on ITAViTLSTM int8, 60x90 depth input",
+            "value": round(frames_per_step * K / elapsed, 1), "unit": "frames/s", "n_gpus": world, "steps": K, "warmup": W, "settle_steps": settle,
+            "ms_per_step": round(elapsed / K * 1e3, 5), "higher_is_better": True, "scaling": "strong" if strong else "weak",
+            "vs_baseline": None, "dtype": "int8+f32", "data": "synthetic",
+            "config": {"workload": "ITAViTLSTM int8 end-to-end forward (BASELINE config 4): " + wl +
+                                   ", LSTM state carried, velocity all-gather",
+                       "frames_per_gpu": B, "global_batch": frames_per_step, "parallelism": f"dp{world}",
+                       "image_dtype": a.image_dtype, "weights": "seed-0 synthetic QAT (tests/golden)",
+                       "gather_every": gather_every,
+                       "gather": ("none (one GPU)" if world == 1 else
+                                  f"asynchronous all-gather of the (frames, 3) velocities every {gather_every} step(s), "
+                                  f"double-buffered, backend {a.backend}"
+                                  + (", each enqueued behind the next step's encoder launch (it runs beside the folded GEMM, not "
+                                     "in a race with the encoder's 256 persistent workgroups for CUs)" if gather_every == 1 and graph is None else "")),
+                       "schedule": {"stream": "one stream",
+                                    "graph": f"{NG} steps per HIP-graph replay on three streams: encoder(t+2) | folded GEMM(t+1) | LSTM + fc(t)",
+                                    "pipelined": f"{NG} steps per ita_vitlstm_pipelined call: the library's two-stream loop, "
+                                                 "front(t+1) overlaps back(t)"}[sched]},
+        }
+    if rank == 0 and a.full:
         ops, bound, peak, arith = STAGE_WORK[dom]
         if nprof == 0:
             dom_ms = per[dom]
@@ -643,32 +708,11 @@ def main():
             ach = o * B / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
             stages[k] = {"ms": round(ms, 5), "achieved_Tops": round(ach, 3), "peak_Tops": pk, "frac": round(ach / pk, 5),
                          "arithmetic": ar}
-        frames_per_step = total
-        wl = (f"{a.global_batch} synthetic 60x90 depth frames per step in all, contiguous shards over {world} GPU(s)" if strong
-              else f"{B} synthetic 60x90 depth frames per GPU per step")
-        out = {
-            "metric": "frames/s on ITAViTLSTM int8, 60x90 depth input",
-            "value": round(frames_per_step * K / elapsed, 1), "unit": "frames/s", "n_gpus": world, "steps": K, "warmup": W, "settle_steps": settle,
-            "ms_per_step": round(elapsed / K * 1e3, 5), "higher_is_better": True, "scaling": "strong" if strong else "weak",
-            "vs_baseline": None, "dtype": "int8+f32", "data": "synthetic",
-            "config": {"workload": "ITAViTLSTM int8 end-to-end forward (BASELINE config 4): " + wl +
-                                   ", LSTM state carried, velocity all-gather",
-                       "frames_per_gpu": B, "global_batch": frames_per_step, "parallelism": f"dp{world}",
-                       "image_dtype": a.image_dtype, "weights": "seed-0 synthetic QAT (tests/golden)",
-                       "gather_every": gather_every,
-                       "gather": ("none (one GPU)" if world == 1 else
-                                  f"asynchronous all-gather of the (frames, 3) velocities every {gather_every} step(s), "
-                                  f"double-buffered, backend {a.backend}"
-                                  + (", each enqueued behind the next step's encoder launch (it runs beside the folded GEMM, not "
-                                     "in a race with the encoder's 256 persistent workgroups for CUs)" if gather_every == 1 and graph is None else "")),
-                       "schedule": {"stream": "one stream",
-                                    "graph": f"{NG} steps per HIP-graph replay on three streams: encoder(t+2) | folded GEMM(t+1) | LSTM + fc(t)",
-                                    "pipelined": f"{NG} steps per ita_vitlstm_pipelined call: the library's two-stream loop, "
-                                                 "front(t+1) overlaps back(t)"}[sched]},
+        out.update({
             "roofline": roof, "stages": stages,
             "stages_note": "per-stage times from an untimed 20-step eager pass with events around every stage (each event "
                            "costs a ~5 us stream bubble, so they sum to more than ms_per_step)",
-        }
+        })
         if not a.no_latency:      # p50 single-frame latency, host enqueue -> result ready
             e1 = host.Engine(blob, device=local_rank)
             i1, d1, q1 = img[:1].contiguous(), dv[:1].contiguous(), qt[:1].contiguous()

@@ -1,8 +1,8 @@
 """Row n4: checkpoint -> blob.  (1) A converted-model state_dict is synthesised from a golden fixture
 with the key names training/qa_train.py's finalize() produces, incl. spectral-norm triplets, and must
-export to exactly the blob the fixture record gives.  (2) Where the reference is present (build
-container), its real QAT flow is run, the converted state_dict saved with torch.save, and the CLI
-must reproduce the blob built from hooks."""
+export to exactly the blob the fixture record gives.  (2) The state_dict the reference's real QAT flow
+converts to (recorded by tools/gen_golden.py) is saved with torch.save, and the CLI must reproduce the
+blob built from hooks."""
 import os
 import subprocess
 import sys
@@ -55,23 +55,31 @@ def test_export_from_synthesised_state_dict():
     assert "decoder.weight" in params.float_tensors(got_sn) or True
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/models"), reason="reference checkout not present")
+def _converted_state_dict(path):
+    """the reference's converted state_dict as tools/gen_golden.py (gen_checkpoint) recorded it: key order, packed
+    quantized Linears, observer scales; the unchanged float parameters are the fixture seed's synthetic ones"""
+    d = np.load(path)
+    fp = synth.float_params(int(d["meta.seed"]), E=64)
+    assert str(d["meta.params_sha256"]) == synth.digest(fp)
+    sd = {}
+    for k in d["keys"]:
+        k = str(k)
+        if "d." + k in d:
+            sd[k] = getattr(torch, str(d["d." + k]))
+        elif "q." + k + ".int_repr" in d:
+            w = torch._make_per_tensor_quantized_tensor(torch.from_numpy(d["q." + k + ".int_repr"]),
+                                                        float(d["q." + k + ".scale"]), int(d["q." + k + ".zero_point"]))
+            sd[k] = (w, torch.from_numpy(d["q." + k + ".bias"]))
+        elif "t." + k in d:
+            sd[k] = torch.from_numpy(d["t." + k])
+        else:
+            sd[k] = torch.from_numpy(fp[k])
+    return sd
+
+
 def test_cli_on_real_converted_checkpoint(tmp_path):
-    code = f"""
-import sys, torch
-sys.path.insert(0, {REPO!r}); sys.path.insert(0, {os.path.join(REPO, 'tools')!r})
-import gen_golden as g
-fp = g.synth.float_params(0, E=64)
-m = g.ITALSTMNetVIT_QAT(num_layers=1)
-m.load_state_dict({{k: torch.from_numpy(v) for k, v in fp.items()}}, strict=True)
-m.attention_blocks.qconfig = g.ita_symmetric_qconfig; m.ffn_blocks.qconfig = g.ita_symmetric_qconfig
-p = torch.ao.quantization.prepare_qat(m.train()); p.lstm.dropout = 0.0
-with torch.no_grad():
-    for it in range(4): p(g.to_X(g.synth.frames(50 + it, 8, gain=0.8)))
-c = torch.ao.quantization.convert(p.eval())
-torch.save(c.state_dict(), {str(tmp_path / 'model_quantized_final.pth')!r})     # training/qa_train.py:91-92
-"""
-    subprocess.run([sys.executable, "-c", code], check=True, capture_output=True)
+    torch.save(_converted_state_dict(golden_files("qatckpt_E64_s0.npz")[0]),
+               str(tmp_path / "model_quantized_final.pth"))     # training/qa_train.py:91-92
     out = tmp_path / "w.itaw"
     r = subprocess.run([sys.executable, os.path.join(REPO, "tools", "export_blob.py"), "--checkpoint",
                         str(tmp_path / "model_quantized_final.pth"), "--out", str(out), "--unsafe-load"],

@@ -13,6 +13,7 @@ import sys
 import pytest
 
 from conftest import REPO
+from test_gpu_bench_dump import check_dump
 
 pytestmark = pytest.mark.gpu
 
@@ -39,7 +40,7 @@ def _run(extra, steps=8):
 
 def test_weak_scaling_line_per_step_gather():
     """default: 1024 frames per GPU is too slow a rehearsal; 300 frames per rank, one stream, one all-gather per step"""
-    out = _run(["--frames-per-gpu", "300"])
+    out = _run(["--frames-per-gpu", "300", "--full"])
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["steps"] == 8
     cfg = out["config"]
     assert cfg["frames_per_gpu"] == 300 and cfg["global_batch"] == 600 and cfg["parallelism"] == "dp2"
@@ -53,18 +54,20 @@ def test_weak_scaling_line_batched_gather():
     assert out["config"]["gather_every"] == 8 and out["scaling"] == "weak" and out["config"]["global_batch"] == 600
 
 
-def test_strong_scaling_uneven_shards_graph_schedule():
+def test_strong_scaling_uneven_shards_graph_schedule(tmp_path):
     """config 4 cut over the GPUs with a total that does not divide: 257 frames -> shards of 129 and 128, which at
     <= 256 frames per GPU run the HIP-graph schedule (one velocity buffer per replay, staged into the gather's own send
     buffers; rank 1's rows padded to rank 0's)"""
-    out = _run(["--global-batch", "257"])
+    out = _run(["--global-batch", "257", "--dump-outputs", str(tmp_path)])
     assert out["n_gpus"] == 2 and out["scaling"] == "strong"
     cfg = out["config"]
     assert cfg["global_batch"] == 257 and cfg["frames_per_gpu"] == 129 and cfg["gather_every"] == 8
     assert "HIP-graph" in cfg["schedule"]
     assert abs(out["value"] - 257 / (out["ms_per_step"] * 1e-3)) <= 1e-3 * out["value"]
+    check_dump(str(tmp_path), [129, 128], 16)      # the last replay's last step, both ranks' rows out of the all-gather
 
 
-def test_strong_scaling_uneven_shards_one_stream():
-    out = _run(["--global-batch", "601", "--schedule", "stream"])
+def test_strong_scaling_uneven_shards_one_stream(tmp_path):
+    out = _run(["--global-batch", "601", "--schedule", "stream", "--dump-outputs", str(tmp_path)])
     assert out["scaling"] == "strong" and out["config"]["frames_per_gpu"] == 301 and out["config"]["gather_every"] == 1
+    check_dump(str(tmp_path), [301, 300], 16)

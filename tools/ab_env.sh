@@ -9,7 +9,7 @@ for i in $(seq 1 ${ROUNDS:-2}); do
   for spec in "$@"; do
     tag=${spec%%:*}; envs=""; [[ "$spec" == *:* ]] && envs=$(echo "${spec#*:}" | tr ',' ' ')
     cp $D/libita_mi355x_$tag.so $D/libita_mi355x.so
-    env $envs python bench.py --steps ${STEPS:-300} --warmup 50 --no-cpu-baseline --no-latency --no-configs $BENCH_ARGS 2>/dev/null | python -c "
+    env $envs python bench.py --full --steps ${STEPS:-300} --warmup 50 --no-cpu-baseline --no-latency --no-configs $BENCH_ARGS 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$spec', round(d['value']), d['ms_per_step'], d['roofline']['avg_launch_ms'])"
   done
 done

@@ -5,7 +5,7 @@
 cd "$(dirname "$0")/.."
 D=drone-oa-iree-vit-accelerator_amd/csrc
 cp $D/libita_mi355x.so $D/libita_mi355x_base.so
-run() { python bench.py --steps 300 --warmup 50 --no-cpu-baseline --no-latency $BENCH_ARGS 2>/dev/null | python -c "
+run() { python bench.py --full --steps 300 --warmup 50 --no-cpu-baseline --no-latency $BENCH_ARGS 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$1', round(d['value']), d['ms_per_step'], d['roofline']['avg_launch_ms'])"; }
 for i in $(seq 1 ${ROUNDS:-2}); do
   for t in "$@"; do

@@ -476,10 +476,48 @@ def gen_float_twin(seed, B, out_dir):
     print("wrote", path, os.path.getsize(path) // 1024, "KiB")
 
 
+def gen_checkpoint(seed, out_dir):
+    """The state_dict of the reference's converted int8 model, as training/qa_train.py:91-92 saves it
+    (model_quantized_final.pth), from the QAT flow of gen_vitlstm with the same seed and calibration frames.  Stored:
+    the key list, every quantized Linear's packed (int8 weight, scale, zero point, bias), every other tensor that is not
+    the seed's synthetic float parameter -- those are asserted equal to synth.float_params(seed) and left out."""
+    fp = synth.float_params(seed, E=64)
+    model = ITALSTMNetVIT_QAT(num_layers=1)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in fp.items()}, strict=True)
+    model.attention_blocks.qconfig = ita_symmetric_qconfig
+    model.ffn_blocks.qconfig = ita_symmetric_qconfig
+    prepared = torch.ao.quantization.prepare_qat(model.train())
+    prepared.lstm.dropout = 0.0
+    with torch.no_grad():
+        for it in range(4):
+            prepared(to_X(synth.frames(100 * seed + 50 + it, 8, gain=0.8)))
+    sd = torch.ao.quantization.convert(prepared.eval()).state_dict()
+    rec = {"meta.seed": np.int64(seed), "meta.params_sha256": np.array(synth.digest(fp)),
+           "meta.torch": np.array(torch.__version__), "keys": np.array(list(sd))}
+    for k, v in sd.items():
+        if isinstance(v, torch.dtype):
+            rec["d." + k] = np.array(str(v).replace("torch.", ""))
+        elif isinstance(v, tuple):                  # quantized Linear: (per-tensor qint8 weight, f32 bias)
+            w, b = v
+            assert w.qscheme() == torch.per_tensor_affine and w.dtype == torch.qint8, k
+            rec["q." + k + ".int_repr"] = w.int_repr().numpy()
+            rec["q." + k + ".scale"] = np.float64(w.q_scale())
+            rec["q." + k + ".zero_point"] = np.int64(w.q_zero_point())
+            rec["q." + k + ".bias"] = b.detach().numpy()
+        elif k in fp:
+            assert np.array_equal(v.numpy(), fp[k]), k
+        else:
+            rec["t." + k] = v.numpy()
+    path = os.path.join(out_dir, f"qatckpt_E64_s{seed}.npz")
+    np.savez_compressed(path, **rec)
+    print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
-    ap.add_argument("--only", default="", help="comma list of: softmax, vitlstm, blocks, tail_large, float_twin, vit2l, vit2l_us, vit1l (default: all)")
+    ap.add_argument("--only", default="", help="comma list of: softmax, vitlstm, blocks, tail_large, float_twin, vit2l, vit2l_us, vit1l, "
+                                               "checkpoint (default: all)")
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
     only = set(filter(None, a.only.split(",")))
@@ -495,6 +533,7 @@ def main():
         if "vit2l" in only: gen_vit2l(0, 2, a.out)
         if "vit2l_us" in only: gen_vit2l(1, 2, a.out, upsample_shuffle_file=True)
         if "vit1l" in only: gen_vit1l(0, 2, a.out)
+        if "checkpoint" in only: gen_checkpoint(0, a.out)
         return
     gen_float_twin(0, 2, a.out)
     gen_vit2l(0, 2, a.out)
@@ -507,6 +546,7 @@ def main():
         gen_blocks(seed, 128, 1, a.out)
     gen_blocks(2, 64, 1, a.out, gain_qk=6.0)
     gen_tail_large(a.out)
+    gen_checkpoint(0, a.out)
 
 
 if __name__ == "__main__":

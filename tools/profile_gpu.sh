@@ -10,7 +10,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # (no --no-configs: the same command also runs BASELINE config 2 and 5, so ita_stream_kernel<128, false, ...> and
 #  ita_tail_big_kernel get their kernel stats and counters from this run too)
-ARGS="--steps 24 --warmup 8 --no-cpu-baseline --no-latency $*"
+ARGS="--full --steps 24 --warmup 8 --no-cpu-baseline --no-latency $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py $ARGS > $OUT/stats.log 2>&1
 i=0
 for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY" \

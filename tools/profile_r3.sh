@@ -12,7 +12,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 for S in $SETS; do
   case $S in
-    main)  SCRIPT=bench.py; ARGS="--steps 24 --warmup 8 --no-cpu-baseline --no-latency --no-configs" ;;
+    main)  SCRIPT=bench.py; ARGS="--full --steps 24 --warmup 8 --no-cpu-baseline --no-latency --no-configs" ;;
     c2)    SCRIPT=tools/bench_mha_block.py; ARGS="" ;;
     c5)    SCRIPT=tools/bench_tail_large.py; ARGS="" ;;
     c5mha) SCRIPT=tools/bench_c5_mha.py; ARGS="8 8192" ;;
