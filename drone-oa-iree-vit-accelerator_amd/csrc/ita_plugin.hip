@@ -11,6 +11,7 @@
 #include <mutex>
 #include <string>
 #include <atomic>
+#include <functional>
 #include <thread>
 #include <vector>
 
@@ -22,6 +23,7 @@
 #include "ita_int8_kernels.h"
 #include "ita_stream_kernel.h"
 #include "ita_long_attn_kernel.h"
+#include "ita_ffn_f32_kernel.h"
 
 namespace {
 
@@ -52,6 +54,9 @@ struct Layer {
   const int32_t *bq, *bk, *bv, *bo, *b1, *b2;
   float ascal[ITA_A_NSCAL], fscal[ITA_F_NSCAL];
   const float *n1w, *n1b, *n2w, *n2b;
+  // float32 FFN of an ITAW0002 blob (the attention-only graph), device pointers; the int8 FFN fields are then null
+  bool ffn_f32 = false;
+  const float *w1f = nullptr, *b1f = nullptr, *w2f = nullptr, *b2f = nullptr;
   // LDS images of the stream kernels (ita_stream_kernel.h), device copies: whole layer, whole layer with the
   // tokenizer in front (layer 0 of the E = 64 model), attention block only
   char *simg_enc = nullptr, *simg_tok = nullptr, *simg_mha = nullptr;
@@ -278,6 +283,7 @@ int launch_mha(ita_context* c, int layer, const float* x, float* y, int B, bool 
 int launch_ffn(ita_context* c, int layer, const float* x, float* y, int B, bool fuse, const ita_ffn_taps* t,
                hipStream_t s, _Float16* y_hi = nullptr, _Float16* y_lo = nullptr) {
   const Layer& L = c->layers[layer];
+  if (L.ffn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's FFN is float32 (ITAW0002 blob): ita_ffn_f32 runs it");
   if (fuse && !L.n2w) return fail(ITA_ERR_BAD_BLOB, "norm2 parameters missing from the blob");
   ItaFfnArgs a{};
   a.x = x; a.y = y; a.w1 = L.w1; a.w2 = L.w2; a.b1 = L.b1; a.b2 = L.b2;
@@ -295,6 +301,25 @@ int launch_ffn(ita_context* c, int layer, const float* x, float* y, int B, bool 
   return ITA_OK;
 }
 
+// the float32 FFN (ita_ffn_f32_kernel.h) of an ITAW0002 layer, fuse: + residual + LayerNorm2
+int launch_ffn_f32(ita_context* c, int layer, const float* x, float* y, int B, bool fuse, hipStream_t s,
+                   _Float16* y_hi = nullptr, _Float16* y_lo = nullptr, const float* h0_src = nullptr, float* h0_dst = nullptr,
+                   const int* slots = nullptr) {
+  const Layer& L = c->layers[layer];
+  if (!L.ffn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's FFN is int8 (ITAW0001 blob): ita_ffn_int8 runs it");
+  if (c->hdr.E != 64) return fail(ITA_ERR_UNSUPPORTED, "the float32 FFN is built for E = 64");
+  if (fuse && !L.n2w) return fail(ITA_ERR_BAD_BLOB, "norm2 parameters missing from the blob");
+  ItaFfnF32Args a{};
+  a.x = x; a.y = y; a.w1 = L.w1f; a.b1 = L.b1f; a.w2 = L.w2f; a.b2 = L.b2f; a.ln_w = L.n2w; a.ln_b = L.n2b;
+  a.B = B; a.fuse_ln = fuse ? 1 : 0;
+  a.y_hi = y_hi; a.y_lo = y_lo; a.ld_planes = c->ldfold;
+  a.h0_src = h0_src; a.h0_dst = h0_dst; a.slots = slots;
+  static const int wg_per_cu = getenv("ITA_FFN_F32_WG_PER_CU") ? atoi(getenv("ITA_FFN_F32_WG_PER_CU")) : 2;   // A/B switch
+  const int ntile = B * (128 / ItaFfnF32Lds::TT), cap = (wg_per_cu > 0 ? wg_per_cu : 2) * c->num_cus;
+  hipLaunchKernelGGL(ita_ffn_f32_kernel, dim3(ntile < cap ? ntile : cap), dim3(256), ItaFfnF32Lds::TOTAL, s, a);
+  HIPCHK(hipGetLastError());
+  return ITA_OK;
+}
 
 // ---- stream kernels (ita_stream_kernel.h): the LDS image a workgroup copies verbatim at start-up.
 // Natural-k matrices (Wq, Wk, Wv, W1) are chunk-major [k/16][row][16].  The block output projections (Wo, fc2)
@@ -538,12 +563,25 @@ int launch_mha_stream(ita_context* c, int layer, const float* x, float* y, int B
 
 // One encoder layer: the stream kernel (ita_stream_kernel.h) when the layer has an LDS image -- E = 64 and every
 // accumulator provably inside the biased-float range (stream_range_ok) -- else the two block kernels through bufB.
+// A float-FFN layer (ITAW0002) is always two launches: the attention block with the fused residual + LayerNorm1 into bufB
+// (stream kernel mode 1, or ita_mha_kernel for a layer without an attention image), then ita_ffn_f32_kernel; `mid`, when
+// given, runs between the two (the profiler's stage-2 mark).
 int launch_encoder(ita_context* c, int layer, const float* x, float* y, _Float16* y_hi, _Float16* y_lo, float* x1_tap,
                    int B, hipStream_t s, unsigned long long* stamps = nullptr, const float* h0_src = nullptr,
                    float* h0_dst = nullptr, const int* slots = nullptr, const void* img = nullptr,
-                   float* tok_tap = nullptr) {
+                   float* tok_tap = nullptr, const std::function<int()>* mid = nullptr) {
   const Layer& L = c->layers[layer];
   if (!L.n1w || !L.n2w) return fail(ITA_ERR_BAD_BLOB, "LayerNorm parameters missing from the blob");
+  if (L.ffn_f32) {
+    if (img || stamps) return fail(ITA_ERR_UNSUPPORTED, "a float-FFN layer runs behind the stand-alone tokenizer, without stamps");
+    if (c->hdr.E != 64) return fail(ITA_ERR_UNSUPPORTED, "the float32 FFN is built for E = 64");
+    int rc = ensure_workspace(c, B, s);
+    if (rc) return rc;
+    if ((rc = launch_mha(c, layer, x, c->bufB, B, true, nullptr, s))) return rc;
+    if (x1_tap) HIPCHK(hipMemcpyAsync(x1_tap, c->bufB, sizeof(float) * (size_t)B * 128 * c->hdr.E, hipMemcpyDeviceToDevice, s));
+    if (mid && (rc = (*mid)())) return rc;
+    return launch_ffn_f32(c, layer, c->bufB, y, B, true, s, y_hi, y_lo, h0_src, h0_dst, slots);
+  }
   if (img ? L.simg_tok != nullptr : L.simg_enc != nullptr) {
     StreamIo io;
     io.x = x; io.y = y; io.y_hi = y_hi; io.y_lo = y_lo; io.x1_tap = x1_tap; io.stamps = stamps;
@@ -915,8 +953,8 @@ int ita_destroy(ita_handle h) {
 
 int ita_load_weights(ita_handle h, const void* blob, size_t nbytes) {
   if (!h || !blob) return fail(ITA_ERR_INVALID_ARG, "null argument");
-  if (nbytes < sizeof(ita_blob_header) || memcmp(blob, ITA_BLOB_MAGIC, 8) != 0)
-    return fail(ITA_ERR_BAD_BLOB, "not an ITAW0001 blob");
+  const int ffn_kind = nbytes < sizeof(ita_blob_header) ? -1 : ita_blob_ffn_kind(blob, nbytes);
+  if (ffn_kind < 0) return fail(ITA_ERR_BAD_BLOB, "not an ITAW0001 / ITAW0002 blob");
   HIPCHK(hipSetDevice(h->device));
   ita_blob_header hdr;
   memcpy(&hdr, blob, sizeof hdr);
@@ -925,6 +963,7 @@ int ita_load_weights(ita_handle h, const void* blob, size_t nbytes) {
   if ((hdr.E != 64 && hdr.E != 128) || hdr.S != 128 || hdr.P != 192 || hdr.F != 256 || hdr.H != 1 ||
       hdr.num_layers < 1 || hdr.num_layers > 16)
     return fail(ITA_ERR_UNSUPPORTED, "kernels are built for E in {64,128}, S=128, P=192, F=256, H=1");
+  if (ffn_kind == 1 && hdr.E != 64) return fail(ITA_ERR_UNSUPPORTED, "the float32 FFN (ITAW0002) is built for E = 64");
   {
     const ita_blob_entry* e = (const ita_blob_entry*)((const char*)blob + sizeof(hdr));
     for (int i = 0; i < hdr.n_tensors; ++i)
@@ -955,24 +994,31 @@ int ita_load_weights(ita_handle h, const void* blob, size_t nbytes) {
     Layer& L = h->layers[i];
 #define NM(fmt) (snprintf(nm, sizeof nm, fmt, i), nm)
     expect(NM("attn%d.wq"), P * E); expect(NM("attn%d.wo"), E * P); expect(NM("attn%d.bq"), P * 4);
-    expect(NM("attn%d.bo"), E * 4); expect(NM("ffn%d.w1"), F * E); expect(NM("ffn%d.w2"), E * F);
-    expect(NM("attn%d.scal"), ITA_A_NSCAL * 4); expect(NM("ffn%d.scal"), ITA_F_NSCAL * 4);
+    expect(NM("attn%d.bo"), E * 4); expect(NM("attn%d.scal"), ITA_A_NSCAL * 4);
     L.wq = dptr<int8_t>(h, NM("attn%d.wq"), true, &ok); L.wk = dptr<int8_t>(h, NM("attn%d.wk"), true, &ok);
     L.wv = dptr<int8_t>(h, NM("attn%d.wv"), true, &ok); L.wo = dptr<int8_t>(h, NM("attn%d.wo"), true, &ok);
     L.bq = dptr<int32_t>(h, NM("attn%d.bq"), true, &ok); L.bk = dptr<int32_t>(h, NM("attn%d.bk"), true, &ok);
     L.bv = dptr<int32_t>(h, NM("attn%d.bv"), true, &ok); L.bo = dptr<int32_t>(h, NM("attn%d.bo"), true, &ok);
-    L.w1 = dptr<int8_t>(h, NM("ffn%d.w1"), true, &ok); L.w2 = dptr<int8_t>(h, NM("ffn%d.w2"), true, &ok);
-    L.b1 = dptr<int32_t>(h, NM("ffn%d.b1"), true, &ok); L.b2 = dptr<int32_t>(h, NM("ffn%d.b2"), true, &ok);
     const float* as = hptr<float>(h, NM("attn%d.scal"));
-    const float* fs = hptr<float>(h, NM("ffn%d.scal"));
-    if (!as || !fs) { ok = false; break; }
+    if (!as) { ok = false; break; }
     memcpy(L.ascal, as, sizeof L.ascal);
-    memcpy(L.fscal, fs, sizeof L.fscal);
+    if (ffn_kind == 1) {   // float32 FFN (sizes checked by ita_blob_validate)
+      L.ffn_f32 = true;
+      L.w1f = dptr<float>(h, NM("ffn%d.w1f"), true, &ok); L.b1f = dptr<float>(h, NM("ffn%d.b1f"), true, &ok);
+      L.w2f = dptr<float>(h, NM("ffn%d.w2f"), true, &ok); L.b2f = dptr<float>(h, NM("ffn%d.b2f"), true, &ok);
+    } else {
+      expect(NM("ffn%d.w1"), F * E); expect(NM("ffn%d.w2"), E * F); expect(NM("ffn%d.scal"), ITA_F_NSCAL * 4);
+      L.w1 = dptr<int8_t>(h, NM("ffn%d.w1"), true, &ok); L.w2 = dptr<int8_t>(h, NM("ffn%d.w2"), true, &ok);
+      L.b1 = dptr<int32_t>(h, NM("ffn%d.b1"), true, &ok); L.b2 = dptr<int32_t>(h, NM("ffn%d.b2"), true, &ok);
+      const float* fs = hptr<float>(h, NM("ffn%d.scal"));
+      if (!fs) { ok = false; break; }
+      memcpy(L.fscal, fs, sizeof L.fscal);
+    }
     L.n1w = dptr<float>(h, NM("norm1_%d.w"), false, &ok); L.n1b = dptr<float>(h, NM("norm1_%d.b"), false, &ok);
     L.n2w = dptr<float>(h, NM("norm2_%d.w"), false, &ok); L.n2b = dptr<float>(h, NM("norm2_%d.b"), false, &ok);
 #undef NM
   }
-  if (!ok) { free_weights(h); return fail(ITA_ERR_BAD_BLOB, "a required int8 block tensor is missing or mis-sized"); }
+  if (!ok) { free_weights(h); return fail(ITA_ERR_BAD_BLOB, "a required block tensor is missing or mis-sized"); }
   h->tok_w = dptr<float>(h, "tok.conv_w", false, &ok); h->tok_b = dptr<float>(h, "tok.conv_b", false, &ok);
   h->tok_lw = dptr<float>(h, "tok.ln_w", false, &ok); h->tok_lb = dptr<float>(h, "tok.ln_b", false, &ok);
   h->tail_b = dptr<float>(h, "tail.conv_b", false, &ok);
@@ -992,7 +1038,8 @@ int ita_load_weights(ita_handle h, const void* blob, size_t nbytes) {
     sp.tlw = hptr<float>(h, "tok.ln_w"); sp.tlb = hptr<float>(h, "tok.ln_b");
     sp.conv_w = hptr<float>(h, "tok.conv_w"); sp.conv_b = hptr<float>(h, "tok.conv_b");
     int rc2 = ITA_OK;
-    const bool lns = sp.n1w && sp.n1b && sp.n2w && sp.n2b && stream_range_ok(sp, hdr.E, true, L.ascal, L.fscal);
+    // a float-FFN layer gets the attention image only: its FFN is ita_ffn_f32_kernel (no simg_enc / simg_tok)
+    const bool lns = !L.ffn_f32 && sp.n1w && sp.n1b && sp.n2w && sp.n2b && stream_range_ok(sp, hdr.E, true, L.ascal, L.fscal);
     if (!stream_range_ok(sp, hdr.E, false, L.ascal, L.fscal)) continue;   // no images: this layer runs on the block kernels
     L.fast_sites = fast_sites_of(L.ascal);
     if (hdr.E == 64) {
@@ -1218,6 +1265,20 @@ int ita_ffn_int8(ita_handle h, int layer, const float* x, float* y, int batch, v
   return ita_ffn_int8_taps(h, layer, x, y, batch, nullptr, stream);
 }
 
+int ita_get_ffn_kind(ita_handle h, int layer, int* kind) {
+  if (!h || !h->loaded) return fail(ITA_ERR_NO_WEIGHTS, "no weights loaded");
+  if (!kind || layer < 0 || layer >= h->hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
+  *kind = h->layers[layer].ffn_f32 ? ITA_FFN_F32 : ITA_FFN_INT8;
+  return ITA_OK;
+}
+
+int ita_ffn_f32(ita_handle h, int layer, const float* x, float* y, int batch, void* stream) {
+  int rc = check(h, batch);
+  if (rc) return rc;
+  if (!x || !y || layer < 0 || layer >= h->hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
+  return launch_ffn_f32(h, layer, x, y, batch, false, (hipStream_t)stream);
+}
+
 int ita_encoder_layer(ita_handle h, int layer, const float* x, float* y, int batch, void* stream) {
   int rc = check(h, batch);
   if (rc) return rc;
@@ -1438,7 +1499,7 @@ static int forward_impl(ita_handle h, const void* image, int image_dtype, const 
   const bool fused_tok = !x2_in && fuse_tokenizer(h, image_dtype);
   if (slots && !x2_in) {   // refuse before the first launch: the slot-indexed side copy of h lives in the stream kernel
     const Layer& LL = h->layers.back();
-    if (!((fused_tok && h->hdr.num_layers == 1) ? LL.simg_tok : LL.simg_enc))
+    if (!LL.ffn_f32 && !((fused_tok && h->hdr.num_layers == 1) ? LL.simg_tok : LL.simg_enc))
       return fail(ITA_ERR_UNSUPPORTED, "slot-indexed state needs the stream kernel (this blob's accumulator range rules it out)");
   }
   if (x2_in) {
@@ -1457,12 +1518,14 @@ static int forward_impl(ita_handle h, const void* image, int image_dtype, const 
     const bool last = l == h->hdr.num_layers - 1;
     const bool planes = fast && last;
     float* yout = (planes && !(taps && taps->x2)) ? nullptr : h->bufA;
+    bool marked = false;   // a float-FFN layer records the attention / FFN boundary between its two launches
+    const std::function<int()> mid = [&]() -> int { MARK(); marked = true; return ITA_OK; };
     // one encoder layer, in place on bufA
     if ((rc = launch_encoder(h, l, h->bufA, yout, planes ? h->x2_hi : nullptr, planes ? h->x2_lo : nullptr,
                              (taps && last) ? taps->x1 : nullptr, B, s, nullptr, (planes && stage_h0) ? h_in : nullptr,
                              (planes && stage_h0) ? h->gates : nullptr, slots, (fused_tok && l == 0) ? image : nullptr,
-                             (fused_tok && l == 0 && taps) ? taps->tokens : nullptr))) return rc;
-    MARK();
+                             (fused_tok && l == 0 && taps) ? taps->tokens : nullptr, &mid))) return rc;
+    if (!marked) MARK();
     MARK();
   }
   if (x2_in) { MARK(); MARK(); }

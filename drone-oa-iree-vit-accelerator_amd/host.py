@@ -26,10 +26,12 @@ _LIB = None
 
 IMAGE_F32, IMAGE_U8 = 0, 1
 DISPATCH_F16, DISPATCH_F32 = 0, 1
+FFN_INT8, FFN_F32 = 0, 1
 
 EXPORTED_SYMBOLS = (
     "ita_abi_version", "ita_create", "ita_destroy", "ita_load_weights", "ita_validate_blob", "ita_reserve", "ita_get_dims",
     "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_ffn_int8", "ita_ffn_int8_taps",
+    "ita_ffn_f32", "ita_get_ffn_kind",
     "ita_encoder_layer", "ita_tokenizer", "ita_fusion_tail", "ita_vitlstm_forward", "ita_bind_dispatch",
     "ita_profile_begin", "ita_profile_begin_sampled", "ita_profile_end", "ita_set_tail_mode", "ita_debug_encoder_stamps",
     "ita_fusion_tail_load", "ita_fusion_tail_large",
@@ -108,6 +110,8 @@ def lib():
         L.ita_mha_int8_taps.argtypes = [vp, i, vp, vp, i, C.POINTER(_MhaTaps), vp]
         L.ita_ffn_int8.argtypes = [vp, i, vp, vp, i, vp]
         L.ita_ffn_int8_taps.argtypes = [vp, i, vp, vp, i, C.POINTER(_FfnTaps), vp]
+        L.ita_ffn_f32.argtypes = [vp, i, vp, vp, i, vp]
+        L.ita_get_ffn_kind.argtypes = [vp, i, C.POINTER(i)]
         L.ita_encoder_layer.argtypes = [vp, i, vp, vp, i, vp]
         L.ita_tokenizer.argtypes = [vp, vp, i, vp, i, vp]
         L.ita_fusion_tail.argtypes = [vp, vp, vp, i, vp]
@@ -248,8 +252,27 @@ class Engine:
         _chk(lib().ita_mha_int8_taps(self._h, layer, x.data_ptr(), y.data_ptr(), B, C.byref(st), _stream_ptr(self.device)))
         return y, t
 
+    def ffn_kind(self, layer: int = 0) -> int:
+        """FFN_INT8 (ITAW0001 blob) or FFN_F32 (ITAW0002: the attention-only graph's float32 FFN)"""
+        k = C.c_int(-1)
+        _chk(lib().ita_get_ffn_kind(self._h, layer, C.byref(k)))
+        return k.value
+
+    def ffn_f32(self, x, layer: int = 0):
+        """ITAFeedForward.forward (float32, no residual / LayerNorm) of a float-FFN layer: (B,128,E) f32 -> (B,128,E) f32"""
+        x = _dev_f32(x)
+        y = _torch().empty_like(x)
+        _chk(lib().ita_ffn_f32(self._h, layer, x.data_ptr(), y.data_ptr(), x.shape[0], _stream_ptr(self.device)))
+        return y
+
     def ffn(self, x, layer: int = 0, taps: bool = False):
+        """the layer's FFN block without residual / LayerNorm: ITAFeedForward_QAT (int8; taps: its int8 tensors) or, on
+        an ITAW0002 blob, the float32 ITAFeedForward (no taps)"""
         torch = _torch()
+        if self.ffn_kind(layer) == FFN_F32:
+            if taps:
+                raise ITAError("a float32 FFN layer has no int8 taps")
+            return self.ffn_f32(x, layer)
         x = _dev_f32(x)
         B = x.shape[0]
         y = torch.empty_like(x)

@@ -1,4 +1,4 @@
-"""Weight/scale blob ("ITAW0001", include/ita_weights.h) packer.
+"""Weight/scale blob ("ITAW0001", or "ITAW0002" for a float32 FFN; include/ita_weights.h) packer.
 
 Turns the reference's converted int8 blocks (int8 weights, float biases, scales -- what
 training/qa_train.py:81-95 saves and tests/export_and_validation_W_B.py:47-62 extracts)
@@ -20,6 +20,7 @@ import numpy as np
 
 f32 = np.float32
 MAGIC = b"ITAW0001"
+MAGIC_FFN_F32 = b"ITAW0002"   # the attention-only QAT graph: int8 attention, float32 FFN (ffn%d.w1f / b1f / w2f / b2f)
 _DT = {np.dtype(np.float32): 0, np.dtype(np.int8): 1, np.dtype(np.int32): 2, np.dtype(np.uint8): 3,
        np.dtype(np.float16): 4}
 A_NSCAL, F_NSCAL = 8, 4
@@ -81,6 +82,10 @@ def float_tensors(fp: dict, num_layers: int = 1) -> Dict[str, np.ndarray]:
     for i in range(num_layers):
         t[f"norm1_{i}.w"], t[f"norm1_{i}.b"] = fp[f"norms1.{i}.weight"], fp[f"norms1.{i}.bias"]
         t[f"norm2_{i}.w"], t[f"norm2_{i}.b"] = fp[f"norms2.{i}.weight"], fp[f"norms2.{i}.bias"]
+        if f"ffn_blocks.{i}.fc1.weight" in fp:   # float FFN (QAT_only_attn): [out][in] as nn.Linear stores it
+            f = f"ffn_blocks.{i}."
+            t[f"ffn{i}.w1f"], t[f"ffn{i}.b1f"] = fp[f + "fc1.weight"], fp[f + "fc1.bias"]
+            t[f"ffn{i}.w2f"], t[f"ffn{i}.b2f"] = fp[f + "fc2.weight"], fp[f + "fc2.bias"]
     if "down_sample.weight" in fp:
         t["tail.conv_w"], t["tail.conv_b"] = fp["down_sample.weight"], fp["down_sample.bias"]
     if "decoder.weight" in fp:
@@ -93,7 +98,7 @@ def float_tensors(fp: dict, num_layers: int = 1) -> Dict[str, np.ndarray]:
 
 
 def pack_blob(tensors: Dict[str, np.ndarray], E: int, S: int = 128, P: int = 192, F: int = 256, H: int = 1,
-              num_layers: int = 1, has_tail: bool = True) -> bytes:
+              num_layers: int = 1, has_tail: bool = True, ffn_f32: bool = False) -> bytes:
     names = list(tensors)
     n = len(names)
     hdr_sz, ent_sz = 8 + 4 * 14, 32 + 4 * 6 + 8 * 2
@@ -110,21 +115,30 @@ def pack_blob(tensors: Dict[str, np.ndarray], E: int, S: int = 128, P: int = 192
         entries.append(struct.pack("<32sii4iqq", nm.encode(), _DT[a.dtype], a.ndim, *shape, off, a.nbytes))
         chunks.append(a.tobytes())
         off += a.nbytes
-    hdr = struct.pack("<8s14i", MAGIC, n, E, S, P, F, H, num_layers, int(has_tail), 0, 0, 0, 0, 0, 0)
+    hdr = struct.pack("<8s14i", MAGIC_FFN_F32 if ffn_f32 else MAGIC, n, E, S, P, F, H, num_layers, int(has_tail), 0, 0, 0, 0, 0, 0)
     assert len(hdr) == hdr_sz and all(len(e) == ent_sz for e in entries)
     return hdr + b"".join(entries) + b"".join(chunks)
 
 
 def blob_from_record(rec: dict, float_params: dict | None, E: int, num_layers: int = 1) -> bytes:
+    """A record without the int8 FFN (no ``ffn0.fc1.w_q``) is the attention-only graph: its FFN comes from
+    float_params (``ffn_blocks.{i}.fc1.weight`` ...) and the blob is an ITAW0002 one."""
+    ffn_f32 = "ffn0.fc1.w_q" not in rec
+    if ffn_f32 and (float_params is None or "ffn_blocks.0.fc1.weight" not in float_params):
+        raise KeyError("the record has no int8 FFN and float_params no ffn_blocks.{i}.fc1.weight")
     t: Dict[str, np.ndarray] = {}
     for i in range(num_layers):
         t.update(attention_tensors(rec, f"attn{i}.", i))
-        t.update(ffn_tensors(rec, f"ffn{i}.", i))
+        if not ffn_f32:
+            t.update(ffn_tensors(rec, f"ffn{i}.", i))
     has_tail = False
     if float_params is not None:
-        t.update(float_tensors(float_params, num_layers))
+        ft = float_tensors(float_params, num_layers)
+        if not ffn_f32:   # an int8-FFN blob stays byte-identical whatever else float_params holds
+            ft = {k: v for k, v in ft.items() if not (k.startswith("ffn") and k[-1] == "f")}
+        t.update(ft)
         has_tail = "tail.conv_w" in t     # without it the decoder reads the flattened tokens (models/ITA/QAT/model.py:80-81)
-    return pack_blob(t, E=E, num_layers=num_layers, has_tail=has_tail)
+    return pack_blob(t, E=E, num_layers=num_layers, has_tail=has_tail, ffn_f32=ffn_f32)
 
 
 def load_fixture(path: str) -> dict:
@@ -141,6 +155,12 @@ def load_fixture(path: str) -> dict:
 # QuantStubs as ``<block>.quant.scale``; QFunctional matmuls as ``<block>.matmulN.scale``.
 # tests/export_and_validation_W_B.py:47-62,233-245 extracts the same items through module hooks;
 # here they are read straight from the state_dict, so no reference code is needed.
+
+def _float_ffn(sd: dict, i: int) -> bool:
+    """layer i's FFN is a float nn.Linear pair (QAT_only_attn's ITAFeedForward), not a converted int8 one"""
+    f = f"ffn_blocks.{i}.fc1."
+    return f + "weight" in sd and f + "_packed_params._packed_params" not in sd
+
 
 def record_from_state_dict(sd: dict, num_layers: int = 1) -> dict:
     """converted-model state_dict -> the fixture-style record consumed by blob_from_record"""
@@ -166,6 +186,8 @@ def record_from_state_dict(sd: dict, num_layers: int = 1) -> dict:
         rec[f"attn{i}.matmul1.scale"] = scalar(a + "matmul1.scale")
         rec[f"attn{i}.matmul2.scale"] = scalar(a + "matmul2.scale")
         f = f"ffn_blocks.{i}."
+        if _float_ffn(sd, i):   # QAT_only_attn: float_params_from_state_dict carries the FFN
+            continue
         for nm in ("fc1", "fc2"):
             wq, ws, b = packed(f + nm)
             rec[f"ffn{i}.{nm}.w_q"], rec[f"ffn{i}.{nm}.w_scale"], rec[f"ffn{i}.{nm}.bias"] = wq, ws, b
@@ -198,6 +220,9 @@ def float_params_from_state_dict(sd: dict, num_layers: int = 1) -> dict:
     for i in range(num_layers):
         for nm in (f"norms1.{i}", f"norms2.{i}"):
             fp[nm + ".weight"], fp[nm + ".bias"] = g(nm + ".weight"), g(nm + ".bias")
+        if _float_ffn(sd, i):   # float FFN (QAT_only_attn)
+            for nm in ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"):
+                fp[f"ffn_blocks.{i}.{nm}"] = g(f"ffn_blocks.{i}.{nm}")
     for l in range(3):
         for nm in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"):
             fp[f"lstm.{nm}_l{l}"] = g(f"lstm.{nm}_l{l}")

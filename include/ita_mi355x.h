@@ -108,8 +108,18 @@ typedef struct ita_ffn_taps { int8_t *x_q, *h, *out_q; } ita_ffn_taps;
 int ita_ffn_int8_taps(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch,
                       const ita_ffn_taps* taps, void* stream);
 
+/* FFN kind of a loaded layer: ITA_FFN_INT8 (ITAW0001 blob, ita_ffn_int8) or ITA_FFN_F32 (ITAW0002 blob: the
+ * attention-only QAT graph, models/ITA_single_layer_upsample_shuffle/QAT_only_attn/model.py, whose FFN, residual and
+ * LayerNorm2 are float32).  ita_ffn_int8 / _taps on an F32 layer, ita_ffn_f32 on an INT8 layer and the drop-in
+ * ITAFeedForward_workgroup bound to an F32 layer fail with ITA_ERR_UNSUPPORTED. */
+enum { ITA_FFN_INT8 = 0, ITA_FFN_F32 = 1 };
+int ita_get_ffn_kind(ita_handle h, int layer, int* kind);
+/* the float32 FFN of layer `layer` alone (no residual, no LayerNorm): y = fc2(relu(fc1(x) + b1)) + b2, (B,128,E) f32,
+ * bit-identical to two ascending-k fmaf chains per output started from the bias (E = 64) */
+int ita_ffn_f32(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, void* stream);
 /* One encoder layer as the model wires it (QAT/model.py:100-113):
- * y = LN2(x1 + ffn(x1)),  x1 = LN1(x + mha(x)).  x_dev and y_dev may alias. */
+ * y = LN2(x1 + ffn(x1)),  x1 = LN1(x + mha(x)).  x_dev and y_dev may alias.
+ * A float-FFN layer (ITA_FFN_F32) runs ffn, the residual and LN2 in float32 (QAT_only_attn/model.py:76-88). */
 int ita_encoder_layer(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, void* stream);
 
 /* OverlapPatchMerging (models/ITA/QAT/layers.py:39-45): image (B,60,90) -> tokens (B,128,E).

@@ -6,6 +6,7 @@ reference's own modules
     models/ITA_single_layer_upsample_shuffle/QAT/model.py   (ITALSTMNetVIT_QAT, E=64)
     models/ITA/QAT/layers.py                                (ITASelfAttention_QAT, ITAFeedForward_QAT)
     models/ITA/QAT/ITA_softmax.py                           (IntegerApproximatedSoftmax)
+    models/ITA_single_layer_upsample_shuffle/QAT_only_attn/model.py   (int8 attention, float32 FFN)
 loads this repo's seeded synthetic float parameters into them, does the reference's
 QAT flow (qconfig on attention_blocks/ffn_blocks -> prepare_qat -> calibration
 forwards -> convert; training/qa_train.py:60-95, tests/export_and_validation_W_B.py:359-382),
@@ -476,22 +477,73 @@ def gen_float_twin(seed, B, out_dir):
     print("wrote", path, os.path.getsize(path) // 1024, "KiB")
 
 
-def gen_checkpoint(seed, out_dir):
-    """The state_dict of the reference's converted int8 model, as training/qa_train.py:91-92 saves it
-    (model_quantized_final.pth), from the QAT flow of gen_vitlstm with the same seed and calibration frames.  Stored:
-    the key list, every quantized Linear's packed (int8 weight, scale, zero point, bias), every other tensor that is not
-    the seed's synthetic float parameter -- those are asserted equal to synth.float_params(seed) and left out."""
-    fp = synth.float_params(seed, E=64)
-    model = ITALSTMNetVIT_QAT(num_layers=1)
+def _only_attn_converted(seed, num_layers, calib_seed):
+    """models/ITA_single_layer_upsample_shuffle/QAT_only_attn/model.py:25-106 (int8 attention, float32 FFN, residual and
+    LayerNorm2) through the same QAT flow as gen_vitlstm, with the qconfig on attention_blocks ONLY: ffn_blocks stay
+    torch.nn.Linear after convert()."""
+    from models.ITA_single_layer_upsample_shuffle.QAT_only_attn.model import ITALSTMNetVIT_QAT as OnlyAttn
+    fp = synth.float_params(seed, E=64, num_layers=num_layers)
+    model = OnlyAttn(num_layers=num_layers)
+    sd = model.state_dict()
+    for k, v in fp.items():
+        assert k in sd and tuple(sd[k].shape) == v.shape, k
     model.load_state_dict({k: torch.from_numpy(v) for k, v in fp.items()}, strict=True)
     model.attention_blocks.qconfig = ita_symmetric_qconfig
-    model.ffn_blocks.qconfig = ita_symmetric_qconfig
     prepared = torch.ao.quantization.prepare_qat(model.train())
     prepared.lstm.dropout = 0.0
     with torch.no_grad():
         for it in range(4):
-            prepared(to_X(synth.frames(100 * seed + 50 + it, 8, gain=0.8)))
-    sd = torch.ao.quantization.convert(prepared.eval()).state_dict()
+            prepared(to_X(synth.frames(calib_seed + it, 8, gain=0.8)))
+    conv = torch.ao.quantization.convert(prepared.eval())
+    for blk in conv.attention_blocks:
+        blk.matmul2.matmul = patched_matmul2(blk.matmul2.scale, blk.matmul2.zero_point)
+    for blk in conv.ffn_blocks:
+        assert type(blk.fc1) is torch.nn.Linear and type(blk.fc2) is torch.nn.Linear
+    return fp, conv
+
+
+def gen_only_attn(seed, B, num_layers, out_dir):
+    """The attention-only QAT graph: inputs of two steps with carried (h, c), the int8 attention record of every layer,
+    the taps tok.out, attn{i}.* (the x_q / probs / out_q int8 codes), x1 / x2 (LayerNorm1 / LayerNorm2 output of the LAST
+    layer; with two layers also x1_0 / x2_0), dec, and vel / h / c of both steps."""
+    fp, conv = _only_attn_converted(seed, num_layers, 100 * seed + 80)
+    tap = Tap()
+    tap.add(conv.tokenizer, "tok.out")
+    for i in range(num_layers):
+        tap_attention(tap, conv.attention_blocks[i], f"attn{i}.")
+        tap.add(conv.norms1[i], f"x1_{i}")
+        tap.add(conv.norms2[i], f"x2_{i}")
+    tap.add(conv.decoder, "dec")
+    fr0, fr1 = synth.frames(10 * seed + 7, B), synth.frames(10 * seed + 8, B)
+    with torch.no_grad():
+        vel0, (h0, c0) = conv(to_X(fr0, None))
+        stage = dict(tap.t)
+        vel1, (h1, c1) = conv(to_X(fr1, (h0, c0)))
+    rec = {"meta.seed": np.int64(seed), "meta.B": np.int64(B), "meta.E": np.int64(64),
+           "meta.num_layers": np.int64(num_layers), "meta.params_sha256": np.array(synth.digest(fp)),
+           "meta.torch": np.array(torch.__version__), "meta.engine": np.array("qnnpack")}
+    for i in range(num_layers):
+        rec.update(block_quant_record(f"attn{i}.", attn=conv.attention_blocks[i]))
+    for k, v in fr0.items():
+        rec["in0." + k] = v
+    for k, v in fr1.items():
+        rec["in1." + k] = v
+    keep = ["tok.out", "dec", f"x1_{num_layers - 1}", f"x2_{num_layers - 1}"]
+    for i in range(num_layers):
+        keep += [f"attn{i}.x_q", f"attn{i}.probs", f"attn{i}.out_q"]
+    if num_layers > 1:
+        keep += ["x1_0", "x2_0"]
+    for k in keep:
+        rec["s0." + k] = stage[k]
+    rec["s0.x1"], rec["s0.x2"] = stage[f"x1_{num_layers - 1}"], stage[f"x2_{num_layers - 1}"]
+    rec["s0.vel"] = vel0.numpy(); rec["s0.h"] = h0.numpy(); rec["s0.c"] = c0.numpy()
+    rec["s1.vel"] = vel1.numpy(); rec["s1.h"] = h1.numpy(); rec["s1.c"] = c1.numpy()
+    path = os.path.join(out_dir, f"onlyattn{num_layers}l_E64_s{seed}_B{B}.npz")
+    np.savez_compressed(path, **rec)
+    print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+
+
+def _checkpoint_record(sd, fp, seed):
     rec = {"meta.seed": np.int64(seed), "meta.params_sha256": np.array(synth.digest(fp)),
            "meta.torch": np.array(torch.__version__), "keys": np.array(list(sd))}
     for k, v in sd.items():
@@ -508,6 +560,36 @@ def gen_checkpoint(seed, out_dir):
             assert np.array_equal(v.numpy(), fp[k]), k
         else:
             rec["t." + k] = v.numpy()
+    return rec
+
+
+def gen_only_attn_checkpoint(seed, out_dir):
+    """The converted attention-only model's state_dict, in gen_checkpoint's form (its float ffn_blocks.* tensors are the
+    seed's synthetic parameters, so they are asserted and left out like every other float parameter), from the QAT flow
+    of gen_only_attn(seed, num_layers=1)."""
+    fp, conv = _only_attn_converted(seed, 1, 100 * seed + 80)
+    rec = _checkpoint_record(conv.state_dict(), fp, seed)
+    path = os.path.join(out_dir, f"onlyattn_qatckpt_E64_s{seed}.npz")
+    np.savez_compressed(path, **rec)
+    print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+
+
+def gen_checkpoint(seed, out_dir):
+    """The state_dict of the reference's converted int8 model, as training/qa_train.py:91-92 saves it
+    (model_quantized_final.pth), from the QAT flow of gen_vitlstm with the same seed and calibration frames.  Stored:
+    the key list, every quantized Linear's packed (int8 weight, scale, zero point, bias), every other tensor that is not
+    the seed's synthetic float parameter -- those are asserted equal to synth.float_params(seed) and left out."""
+    fp = synth.float_params(seed, E=64)
+    model = ITALSTMNetVIT_QAT(num_layers=1)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in fp.items()}, strict=True)
+    model.attention_blocks.qconfig = ita_symmetric_qconfig
+    model.ffn_blocks.qconfig = ita_symmetric_qconfig
+    prepared = torch.ao.quantization.prepare_qat(model.train())
+    prepared.lstm.dropout = 0.0
+    with torch.no_grad():
+        for it in range(4):
+            prepared(to_X(synth.frames(100 * seed + 50 + it, 8, gain=0.8)))
+    rec = _checkpoint_record(torch.ao.quantization.convert(prepared.eval()).state_dict(), fp, seed)
     path = os.path.join(out_dir, f"qatckpt_E64_s{seed}.npz")
     np.savez_compressed(path, **rec)
     print("wrote", path, os.path.getsize(path) // 1024, "KiB")
@@ -517,7 +599,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
     ap.add_argument("--only", default="", help="comma list of: softmax, vitlstm, blocks, tail_large, float_twin, vit2l, vit2l_us, vit1l, "
-                                               "checkpoint (default: all)")
+                                               "checkpoint, only_attn, only_attn_checkpoint (default: all)")
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
     only = set(filter(None, a.only.split(",")))
@@ -534,6 +616,10 @@ def main():
         if "vit2l_us" in only: gen_vit2l(1, 2, a.out, upsample_shuffle_file=True)
         if "vit1l" in only: gen_vit1l(0, 2, a.out)
         if "checkpoint" in only: gen_checkpoint(0, a.out)
+        if "only_attn" in only:
+            gen_only_attn(0, 2, 1, a.out)
+            gen_only_attn(1, 2, 2, a.out)
+        if "only_attn_checkpoint" in only: gen_only_attn_checkpoint(0, a.out)
         return
     gen_float_twin(0, 2, a.out)
     gen_vit2l(0, 2, a.out)
@@ -547,6 +633,9 @@ def main():
     gen_blocks(2, 64, 1, a.out, gain_qk=6.0)
     gen_tail_large(a.out)
     gen_checkpoint(0, a.out)
+    gen_only_attn(0, 2, 1, a.out)
+    gen_only_attn(1, 2, 2, a.out)
+    gen_only_attn_checkpoint(0, a.out)
 
 
 if __name__ == "__main__":
