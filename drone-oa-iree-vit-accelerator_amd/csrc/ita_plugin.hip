@@ -24,6 +24,7 @@
 #include "ita_stream_kernel.h"
 #include "ita_long_attn_kernel.h"
 #include "ita_ffn_f32_kernel.h"
+#include "ita_attn_f32_kernel.h"
 
 namespace {
 
@@ -57,6 +58,10 @@ struct Layer {
   // float32 FFN of an ITAW0002 blob (the attention-only graph), device pointers; the int8 FFN fields are then null
   bool ffn_f32 = false;
   const float *w1f = nullptr, *b1f = nullptr, *w2f = nullptr, *b2f = nullptr;
+  // float32 attention of an ITAW0003 blob (the float graph), device pointers; the int8 attention fields are then null
+  bool attn_f32 = false;
+  const float *wqf = nullptr, *wkf = nullptr, *wvf = nullptr, *bqf = nullptr, *bkf = nullptr, *bvf = nullptr,
+              *wof = nullptr, *bof = nullptr;
   // LDS images of the stream kernels (ita_stream_kernel.h), device copies: whole layer, whole layer with the
   // tokenizer in front (layer 0 of the E = 64 model), attention block only
   char *simg_enc = nullptr, *simg_tok = nullptr, *simg_mha = nullptr;
@@ -266,6 +271,8 @@ int launch_mha_stream(ita_context* c, int layer, const float* x, float* y, int B
 // registers); with taps, or for a layer without an LDS image, on the tile-phased kernel that can expose every tensor
 int launch_mha(ita_context* c, int layer, const float* x, float* y, int B, bool fuse, const ita_mha_taps* t,
                hipStream_t s) {
+  if (c->layers[layer].attn_f32)
+    return fail(ITA_ERR_UNSUPPORTED, "this layer's attention is float32 (ITAW0003 blob): ita_mha_f32 runs it");
   if (fuse && !c->layers[layer].n1w) return fail(ITA_ERR_BAD_BLOB, "norm1 parameters missing from the blob");
   static const bool block_only = getenv("ITA_MHA_BLOCK_KERNEL") != nullptr;   // A/B switch
   if (!t && c->layers[layer].simg_mha && !block_only) return launch_mha_stream(c, layer, x, y, B, fuse, s);
@@ -317,6 +324,22 @@ int launch_ffn_f32(ita_context* c, int layer, const float* x, float* y, int B, b
   static const int wg_per_cu = getenv("ITA_FFN_F32_WG_PER_CU") ? atoi(getenv("ITA_FFN_F32_WG_PER_CU")) : 2;   // A/B switch
   const int ntile = B * (128 / ItaFfnF32Lds::TT), cap = (wg_per_cu > 0 ? wg_per_cu : 2) * c->num_cus;
   hipLaunchKernelGGL(ita_ffn_f32_kernel, dim3(ntile < cap ? ntile : cap), dim3(256), ItaFfnF32Lds::TOTAL, s, a);
+  HIPCHK(hipGetLastError());
+  return ITA_OK;
+}
+
+// the float32 attention block (ita_attn_f32_kernel.h) of an ITAW0003 layer, fuse: + residual + LayerNorm1
+int launch_attn_f32(ita_context* c, int layer, const float* x, float* y, int B, bool fuse, hipStream_t s) {
+  const Layer& L = c->layers[layer];
+  if (!L.attn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's attention is int8 (ITAW0001 / ITAW0002 blob): ita_mha_int8 runs it");
+  if (c->hdr.E != 64) return fail(ITA_ERR_UNSUPPORTED, "the float32 attention is built for E = 64");
+  if (fuse && !L.n1w) return fail(ITA_ERR_BAD_BLOB, "norm1 parameters missing from the blob");
+  ItaAttnF32Args a{};
+  a.x = x; a.y = y;
+  a.wq = L.wqf; a.wk = L.wkf; a.wv = L.wvf; a.bq = L.bqf; a.bk = L.bkf; a.bv = L.bvf; a.wo = L.wof; a.bo = L.bof;
+  a.ln_w = L.n1w; a.ln_b = L.n1b; a.B = B; a.fuse_ln = fuse ? 1 : 0;
+  // 130 KB of LDS: one workgroup per CU, frames in a grid stride
+  hipLaunchKernelGGL(ita_attn_f32_kernel, dim3(B < c->num_cus ? B : c->num_cus), dim3(512), ItaAttnF32Lds::TOTAL, s, a);
   HIPCHK(hipGetLastError());
   return ITA_OK;
 }
@@ -507,6 +530,7 @@ struct StreamIo {
 // mode 0: whole encoder layer; 1: attention block only (fuse_ln: + residual + LayerNorm1)
 int launch_stream(ita_context* c, int layer, int mode, bool fuse_ln, const StreamIo& io, int B, hipStream_t s) {
   const Layer& L = c->layers[layer];
+  if (L.attn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's attention is float32 (ITAW0003 blob): it has no int8 stream kernel");
   ItaStreamArgs a{};
   a.x = io.x; a.y = io.y; a.y_hi = io.y_hi; a.y_lo = io.y_lo; a.ld_planes = c->ldfold; a.x1_tap = io.x1_tap;
   a.inv_sx = L.ascal[ITA_A_INV_SX]; a.mq = L.ascal[ITA_A_MQ]; a.mk = L.ascal[ITA_A_MK]; a.mv = L.ascal[ITA_A_MV];
@@ -565,7 +589,8 @@ int launch_mha_stream(ita_context* c, int layer, const float* x, float* y, int B
 // accumulator provably inside the biased-float range (stream_range_ok) -- else the two block kernels through bufB.
 // A float-FFN layer (ITAW0002) is always two launches: the attention block with the fused residual + LayerNorm1 into bufB
 // (stream kernel mode 1, or ita_mha_kernel for a layer without an attention image), then ita_ffn_f32_kernel; `mid`, when
-// given, runs between the two (the profiler's stage-2 mark).
+// given, runs between the two (the profiler's stage-2 mark).  A float layer (ITAW0003) is the same two launches with
+// ita_attn_f32_kernel as the first.
 int launch_encoder(ita_context* c, int layer, const float* x, float* y, _Float16* y_hi, _Float16* y_lo, float* x1_tap,
                    int B, hipStream_t s, unsigned long long* stamps = nullptr, const float* h0_src = nullptr,
                    float* h0_dst = nullptr, const int* slots = nullptr, const void* img = nullptr,
@@ -577,7 +602,8 @@ int launch_encoder(ita_context* c, int layer, const float* x, float* y, _Float16
     if (c->hdr.E != 64) return fail(ITA_ERR_UNSUPPORTED, "the float32 FFN is built for E = 64");
     int rc = ensure_workspace(c, B, s);
     if (rc) return rc;
-    if ((rc = launch_mha(c, layer, x, c->bufB, B, true, nullptr, s))) return rc;
+    if ((rc = L.attn_f32 ? launch_attn_f32(c, layer, x, c->bufB, B, true, s)
+                         : launch_mha(c, layer, x, c->bufB, B, true, nullptr, s))) return rc;
     if (x1_tap) HIPCHK(hipMemcpyAsync(x1_tap, c->bufB, sizeof(float) * (size_t)B * 128 * c->hdr.E, hipMemcpyDeviceToDevice, s));
     if (mid && (rc = (*mid)())) return rc;
     return launch_ffn_f32(c, layer, c->bufB, y, B, true, s, y_hi, y_lo, h0_src, h0_dst, slots);
@@ -883,6 +909,7 @@ int ita_create(ita_handle* out, int device_ordinal) {
   c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   int rc = ITA_OK;
   if ((rc = set_lds(ita_mha_kernel<64>, ItaMhaLds<64>::TOTAL))) { delete c; return rc; }
+  if ((rc = set_lds(ita_attn_f32_kernel, ItaAttnF32Lds::TOTAL))) { delete c; return rc; }
   if ((rc = set_lds(ita_mha_kernel<128>, ItaMhaLds<128>::TOTAL))) { delete c; return rc; }
   if ((rc = set_lds(ita_ffn_kernel<64>, ItaFfnLds<64>::TOTAL))) { delete c; return rc; }
   if ((rc = set_lds(ita_ffn_kernel<128>, ItaFfnLds<128>::TOTAL))) { delete c; return rc; }
@@ -954,7 +981,8 @@ int ita_destroy(ita_handle h) {
 int ita_load_weights(ita_handle h, const void* blob, size_t nbytes) {
   if (!h || !blob) return fail(ITA_ERR_INVALID_ARG, "null argument");
   const int ffn_kind = nbytes < sizeof(ita_blob_header) ? -1 : ita_blob_ffn_kind(blob, nbytes);
-  if (ffn_kind < 0) return fail(ITA_ERR_BAD_BLOB, "not an ITAW0001 / ITAW0002 blob");
+  const int attn_kind = nbytes < sizeof(ita_blob_header) ? -1 : ita_blob_attn_kind(blob, nbytes);
+  if (ffn_kind < 0 || attn_kind < 0) return fail(ITA_ERR_BAD_BLOB, "not an ITAW0001 / ITAW0002 / ITAW0003 blob");
   HIPCHK(hipSetDevice(h->device));
   ita_blob_header hdr;
   memcpy(&hdr, blob, sizeof hdr);
@@ -963,6 +991,7 @@ int ita_load_weights(ita_handle h, const void* blob, size_t nbytes) {
   if ((hdr.E != 64 && hdr.E != 128) || hdr.S != 128 || hdr.P != 192 || hdr.F != 256 || hdr.H != 1 ||
       hdr.num_layers < 1 || hdr.num_layers > 16)
     return fail(ITA_ERR_UNSUPPORTED, "kernels are built for E in {64,128}, S=128, P=192, F=256, H=1");
+  if (attn_kind == 1 && hdr.E != 64) return fail(ITA_ERR_UNSUPPORTED, "the float32 attention (ITAW0003) is built for E = 64");
   if (ffn_kind == 1 && hdr.E != 64) return fail(ITA_ERR_UNSUPPORTED, "the float32 FFN (ITAW0002) is built for E = 64");
   {
     const ita_blob_entry* e = (const ita_blob_entry*)((const char*)blob + sizeof(hdr));
@@ -993,15 +1022,23 @@ int ita_load_weights(ita_handle h, const void* blob, size_t nbytes) {
   for (int i = 0; i < hdr.num_layers; ++i) {
     Layer& L = h->layers[i];
 #define NM(fmt) (snprintf(nm, sizeof nm, fmt, i), nm)
-    expect(NM("attn%d.wq"), P * E); expect(NM("attn%d.wo"), E * P); expect(NM("attn%d.bq"), P * 4);
-    expect(NM("attn%d.bo"), E * 4); expect(NM("attn%d.scal"), ITA_A_NSCAL * 4);
-    L.wq = dptr<int8_t>(h, NM("attn%d.wq"), true, &ok); L.wk = dptr<int8_t>(h, NM("attn%d.wk"), true, &ok);
-    L.wv = dptr<int8_t>(h, NM("attn%d.wv"), true, &ok); L.wo = dptr<int8_t>(h, NM("attn%d.wo"), true, &ok);
-    L.bq = dptr<int32_t>(h, NM("attn%d.bq"), true, &ok); L.bk = dptr<int32_t>(h, NM("attn%d.bk"), true, &ok);
-    L.bv = dptr<int32_t>(h, NM("attn%d.bv"), true, &ok); L.bo = dptr<int32_t>(h, NM("attn%d.bo"), true, &ok);
-    const float* as = hptr<float>(h, NM("attn%d.scal"));
-    if (!as) { ok = false; break; }
-    memcpy(L.ascal, as, sizeof L.ascal);
+    if (attn_kind == 1) {   // float32 attention (sizes checked by ita_blob_validate)
+      L.attn_f32 = true;
+      L.wqf = dptr<float>(h, NM("attn%d.wqf"), true, &ok); L.wkf = dptr<float>(h, NM("attn%d.wkf"), true, &ok);
+      L.wvf = dptr<float>(h, NM("attn%d.wvf"), true, &ok); L.bqf = dptr<float>(h, NM("attn%d.bqf"), true, &ok);
+      L.bkf = dptr<float>(h, NM("attn%d.bkf"), true, &ok); L.bvf = dptr<float>(h, NM("attn%d.bvf"), true, &ok);
+      L.wof = dptr<float>(h, NM("attn%d.wof"), true, &ok); L.bof = dptr<float>(h, NM("attn%d.bof"), true, &ok);
+    } else {
+      expect(NM("attn%d.wq"), P * E); expect(NM("attn%d.wo"), E * P); expect(NM("attn%d.bq"), P * 4);
+      expect(NM("attn%d.bo"), E * 4); expect(NM("attn%d.scal"), ITA_A_NSCAL * 4);
+      L.wq = dptr<int8_t>(h, NM("attn%d.wq"), true, &ok); L.wk = dptr<int8_t>(h, NM("attn%d.wk"), true, &ok);
+      L.wv = dptr<int8_t>(h, NM("attn%d.wv"), true, &ok); L.wo = dptr<int8_t>(h, NM("attn%d.wo"), true, &ok);
+      L.bq = dptr<int32_t>(h, NM("attn%d.bq"), true, &ok); L.bk = dptr<int32_t>(h, NM("attn%d.bk"), true, &ok);
+      L.bv = dptr<int32_t>(h, NM("attn%d.bv"), true, &ok); L.bo = dptr<int32_t>(h, NM("attn%d.bo"), true, &ok);
+      const float* as = hptr<float>(h, NM("attn%d.scal"));
+      if (!as) { ok = false; break; }
+      memcpy(L.ascal, as, sizeof L.ascal);
+    }
     if (ffn_kind == 1) {   // float32 FFN (sizes checked by ita_blob_validate)
       L.ffn_f32 = true;
       L.w1f = dptr<float>(h, NM("ffn%d.w1f"), true, &ok); L.b1f = dptr<float>(h, NM("ffn%d.b1f"), true, &ok);
@@ -1026,6 +1063,7 @@ int ita_load_weights(ita_handle h, const void* blob, size_t nbytes) {
   h->fc_w = dptr<float>(h, "fc.w", false, &ok); h->fc_b = dptr<float>(h, "fc.b", false, &ok);
   for (int i = 0; i < hdr.num_layers; ++i) {
     Layer& L = h->layers[i];
+    if (L.attn_f32) continue;   // no int8 attention: no stream images (ita_attn_f32_kernel + ita_ffn_f32_kernel)
     StreamHostParams sp{};
 #define NM(fmt) (snprintf(nm, sizeof nm, fmt, i), nm)
     sp.wq = hptr<int8_t>(h, NM("attn%d.wq")); sp.wk = hptr<int8_t>(h, NM("attn%d.wk")); sp.wv = hptr<int8_t>(h, NM("attn%d.wv"));
@@ -1208,6 +1246,7 @@ int ita_mha_long_q8(ita_handle h, int layer, const int8_t* x_q, int8_t* out_q, i
   int rc = check(h, batch);
   if (rc) return rc;
   if (!x_q || !out_q || layer < 0 || layer >= h->hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
+  if (h->layers[layer].attn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's attention is float32 (ITAW0003 blob): no int8 long attention");
   if (h->hdr.E != 128) return fail(ITA_ERR_UNSUPPORTED, "long-sequence attention is built for E = 128 (models/ITA, models/ITA_upsample_shuffle)");
   if (seq_len < 128 || seq_len % 128 || seq_len > 65536 || batch > 65535)
     return fail(ITA_ERR_UNSUPPORTED, "seq_len must be a multiple of 128 in [128, 65536], batch <= 65535");
@@ -1279,6 +1318,20 @@ int ita_ffn_f32(ita_handle h, int layer, const float* x, float* y, int batch, vo
   return launch_ffn_f32(h, layer, x, y, batch, false, (hipStream_t)stream);
 }
 
+int ita_get_attn_kind(ita_handle h, int layer, int* kind) {
+  if (!h || !h->loaded) return fail(ITA_ERR_NO_WEIGHTS, "no weights loaded");
+  if (!kind || layer < 0 || layer >= h->hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
+  *kind = h->layers[layer].attn_f32 ? ITA_ATTN_F32 : ITA_ATTN_INT8;
+  return ITA_OK;
+}
+
+int ita_mha_f32(ita_handle h, int layer, const float* x, float* y, int batch, void* stream) {
+  int rc = check(h, batch);
+  if (rc) return rc;
+  if (!x || !y || layer < 0 || layer >= h->hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
+  return launch_attn_f32(h, layer, x, y, batch, false, (hipStream_t)stream);
+}
+
 int ita_encoder_layer(ita_handle h, int layer, const float* x, float* y, int batch, void* stream) {
   int rc = check(h, batch);
   if (rc) return rc;
@@ -1292,6 +1345,7 @@ int ita_debug_encoder_stamps(ita_handle h, int layer, const float* x, const void
   if (rc) return rc;
   if ((!x && !image_u8) || !y || !stamps || layer < 0 || layer >= h->hdr.num_layers)
     return fail(ITA_ERR_INVALID_ARG, "bad argument");
+  if (h->layers[layer].attn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's attention is float32 (ITAW0003 blob): no stream kernel, no stamps");
   if (image_u8 ? !h->layers[layer].simg_tok : !h->layers[layer].simg_enc)
     return fail(ITA_ERR_UNSUPPORTED, "this layer does not run on the stream kernel");
   return launch_encoder(h, layer, x, y, nullptr, nullptr, nullptr, batch, (hipStream_t)stream, stamps, nullptr, nullptr,

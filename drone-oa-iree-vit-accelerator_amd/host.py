@@ -27,11 +27,12 @@ _LIB = None
 IMAGE_F32, IMAGE_U8 = 0, 1
 DISPATCH_F16, DISPATCH_F32 = 0, 1
 FFN_INT8, FFN_F32 = 0, 1
+ATTN_INT8, ATTN_F32 = 0, 1
 
 EXPORTED_SYMBOLS = (
     "ita_abi_version", "ita_create", "ita_destroy", "ita_load_weights", "ita_validate_blob", "ita_reserve", "ita_get_dims",
     "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_ffn_int8", "ita_ffn_int8_taps",
-    "ita_ffn_f32", "ita_get_ffn_kind",
+    "ita_ffn_f32", "ita_get_ffn_kind", "ita_mha_f32", "ita_get_attn_kind",
     "ita_encoder_layer", "ita_tokenizer", "ita_fusion_tail", "ita_vitlstm_forward", "ita_bind_dispatch",
     "ita_profile_begin", "ita_profile_begin_sampled", "ita_profile_end", "ita_set_tail_mode", "ita_debug_encoder_stamps",
     "ita_fusion_tail_load", "ita_fusion_tail_large",
@@ -112,6 +113,8 @@ def lib():
         L.ita_ffn_int8_taps.argtypes = [vp, i, vp, vp, i, C.POINTER(_FfnTaps), vp]
         L.ita_ffn_f32.argtypes = [vp, i, vp, vp, i, vp]
         L.ita_get_ffn_kind.argtypes = [vp, i, C.POINTER(i)]
+        L.ita_mha_f32.argtypes = [vp, i, vp, vp, i, vp]
+        L.ita_get_attn_kind.argtypes = [vp, i, C.POINTER(i)]
         L.ita_encoder_layer.argtypes = [vp, i, vp, vp, i, vp]
         L.ita_tokenizer.argtypes = [vp, vp, i, vp, i, vp]
         L.ita_fusion_tail.argtypes = [vp, vp, vp, i, vp]
@@ -236,8 +239,13 @@ class Engine:
 
     # ---- int8 blocks -------------------------------------------------------------------
     def mha(self, x, layer: int = 0, taps: bool = False):
-        """ITASelfAttention_QAT.forward: (B,128,E) f32 -> (B,128,E) f32 [, dict of int tensors]."""
+        """the layer's attention block without residual / LayerNorm: ITASelfAttention_QAT.forward, (B,128,E) f32 ->
+        (B,128,E) f32 [, dict of int tensors], or, on an ITAW0003 blob, the float32 ITASelfAttention (no taps)"""
         torch = _torch()
+        if self.attn_kind(layer) == ATTN_F32:
+            if taps:
+                raise ITAError("a float32 attention layer has no int8 taps")
+            return self.mha_f32(x, layer)
         x = _dev_f32(x)
         B = x.shape[0]
         y = torch.empty_like(x)
@@ -251,6 +259,20 @@ class Engine:
         st = _MhaTaps(**{k: v.data_ptr() for k, v in t.items()})
         _chk(lib().ita_mha_int8_taps(self._h, layer, x.data_ptr(), y.data_ptr(), B, C.byref(st), _stream_ptr(self.device)))
         return y, t
+
+    def attn_kind(self, layer: int = 0) -> int:
+        """ATTN_INT8 (ITAW0001 / ITAW0002 blob) or ATTN_F32 (ITAW0003: the float graph's float32 attention)"""
+        k = C.c_int(-1)
+        _chk(lib().ita_get_attn_kind(self._h, layer, C.byref(k)))
+        return k.value
+
+    def mha_f32(self, x, layer: int = 0):
+        """ITASelfAttention.forward (float32, softmax(Q K^T) V, no residual / LayerNorm) of a float-attention layer:
+        (B,128,E) f32 -> (B,128,E) f32"""
+        x = _dev_f32(x)
+        y = _torch().empty_like(x)
+        _chk(lib().ita_mha_f32(self._h, layer, x.data_ptr(), y.data_ptr(), x.shape[0], _stream_ptr(self.device)))
+        return y
 
     def ffn_kind(self, layer: int = 0) -> int:
         """FFN_INT8 (ITAW0001 blob) or FFN_F32 (ITAW0002: the attention-only graph's float32 FFN)"""

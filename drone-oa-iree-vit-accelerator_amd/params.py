@@ -1,4 +1,5 @@
-"""Weight/scale blob ("ITAW0001", or "ITAW0002" for a float32 FFN; include/ita_weights.h) packer.
+"""Weight/scale blob ("ITAW0001", "ITAW0002" for a float32 FFN, "ITAW0003" for the float graph; include/ita_weights.h)
+packer.
 
 Turns the reference's converted int8 blocks (int8 weights, float biases, scales -- what
 training/qa_train.py:81-95 saves and tests/export_and_validation_W_B.py:47-62 extracts)
@@ -21,6 +22,7 @@ import numpy as np
 f32 = np.float32
 MAGIC = b"ITAW0001"
 MAGIC_FFN_F32 = b"ITAW0002"   # the attention-only QAT graph: int8 attention, float32 FFN (ffn%d.w1f / b1f / w2f / b2f)
+MAGIC_F32 = b"ITAW0003"       # the float graph: float32 attention (attn%d.wqf ... bof) and float32 FFN
 _DT = {np.dtype(np.float32): 0, np.dtype(np.int8): 1, np.dtype(np.int32): 2, np.dtype(np.uint8): 3,
        np.dtype(np.float16): 4}
 A_NSCAL, F_NSCAL = 8, 4
@@ -98,7 +100,8 @@ def float_tensors(fp: dict, num_layers: int = 1) -> Dict[str, np.ndarray]:
 
 
 def pack_blob(tensors: Dict[str, np.ndarray], E: int, S: int = 128, P: int = 192, F: int = 256, H: int = 1,
-              num_layers: int = 1, has_tail: bool = True, ffn_f32: bool = False) -> bytes:
+              num_layers: int = 1, has_tail: bool = True, ffn_f32: bool = False, attn_f32: bool = False) -> bytes:
+    """attn_f32: an ITAW0003 blob (float attention and float FFN); else ffn_f32: ITAW0002; else ITAW0001"""
     names = list(tensors)
     n = len(names)
     hdr_sz, ent_sz = 8 + 4 * 14, 32 + 4 * 6 + 8 * 2
@@ -115,7 +118,8 @@ def pack_blob(tensors: Dict[str, np.ndarray], E: int, S: int = 128, P: int = 192
         entries.append(struct.pack("<32sii4iqq", nm.encode(), _DT[a.dtype], a.ndim, *shape, off, a.nbytes))
         chunks.append(a.tobytes())
         off += a.nbytes
-    hdr = struct.pack("<8s14i", MAGIC_FFN_F32 if ffn_f32 else MAGIC, n, E, S, P, F, H, num_layers, int(has_tail), 0, 0, 0, 0, 0, 0)
+    magic = MAGIC_F32 if attn_f32 else MAGIC_FFN_F32 if ffn_f32 else MAGIC
+    hdr = struct.pack("<8s14i", magic, n, E, S, P, F, H, num_layers, int(has_tail), 0, 0, 0, 0, 0, 0)
     assert len(hdr) == hdr_sz and all(len(e) == ent_sz for e in entries)
     return hdr + b"".join(entries) + b"".join(chunks)
 
@@ -141,6 +145,32 @@ def blob_from_record(rec: dict, float_params: dict | None, E: int, num_layers: i
     return pack_blob(t, E=E, num_layers=num_layers, has_tail=has_tail, ffn_f32=ffn_f32)
 
 
+def float_attention_tensors(fp: dict, i: int) -> Dict[str, np.ndarray]:
+    """layer i's float attention (models/ITA/layers.py:47-88), [out][in] as nn.Linear stores it -> attn%d.wqf ... bof"""
+    a = f"attention_blocks.{i}."
+    t = {}
+    for nm, key in (("q_proj", "q"), ("k_proj", "k"), ("v_proj", "v"), ("out_proj", "o")):
+        t[f"attn{i}.w{key}f"], t[f"attn{i}.b{key}f"] = fp[a + nm + ".weight"], fp[a + nm + ".bias"]
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in t.items()}
+
+
+def blob_from_float_params(fp: dict, num_layers: int = 1) -> bytes:
+    """The float graph (models/ITA_single_layer_upsample_shuffle/model.py:35-140, nothing quantised) -> an ITAW0003 blob.
+    fp: every parameter under the reference's state_dict names, spectral norm folded (synth.float_params, or
+    float_params_from_state_dict of a float checkpoint)."""
+    for i in range(num_layers):
+        for k in (f"attention_blocks.{i}.q_proj.weight", f"ffn_blocks.{i}.fc1.weight"):
+            if k not in fp:
+                raise KeyError(f"float parameters lack {k}")
+    t: Dict[str, np.ndarray] = {}
+    for i in range(num_layers):
+        t.update(float_attention_tensors(fp, i))
+    t.update(float_tensors(fp, num_layers))
+    E = int(fp["tokenizer.conv.weight"].shape[0])
+    P, F = (int(fp[f"{n}.0.{m}.weight"].shape[0]) for n, m in (("attention_blocks", "q_proj"), ("ffn_blocks", "fc1")))
+    return pack_blob(t, E=E, P=P, F=F, num_layers=num_layers, has_tail="tail.conv_w" in t, ffn_f32=True, attn_f32=True)
+
+
 def load_fixture(path: str) -> dict:
     with np.load(path) as z:
         return {k: z[k] for k in z.files}
@@ -160,6 +190,12 @@ def _float_ffn(sd: dict, i: int) -> bool:
     """layer i's FFN is a float nn.Linear pair (QAT_only_attn's ITAFeedForward), not a converted int8 one"""
     f = f"ffn_blocks.{i}.fc1."
     return f + "weight" in sd and f + "_packed_params._packed_params" not in sd
+
+
+def _float_attn(sd: dict, i: int) -> bool:
+    """layer i's attention is the float ITASelfAttention (a float checkpoint), not a converted int8 one"""
+    a = f"attention_blocks.{i}.q_proj."
+    return a + "weight" in sd and a + "_packed_params._packed_params" not in sd
 
 
 def record_from_state_dict(sd: dict, num_layers: int = 1) -> dict:
@@ -220,9 +256,13 @@ def float_params_from_state_dict(sd: dict, num_layers: int = 1) -> dict:
     for i in range(num_layers):
         for nm in (f"norms1.{i}", f"norms2.{i}"):
             fp[nm + ".weight"], fp[nm + ".bias"] = g(nm + ".weight"), g(nm + ".bias")
-        if _float_ffn(sd, i):   # float FFN (QAT_only_attn)
+        if _float_ffn(sd, i):   # float FFN (QAT_only_attn, or the float model)
             for nm in ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"):
                 fp[f"ffn_blocks.{i}.{nm}"] = g(f"ffn_blocks.{i}.{nm}")
+        if _float_attn(sd, i):  # float attention (the float model)
+            for nm in ("q_proj", "k_proj", "v_proj", "out_proj"):
+                for w in ("weight", "bias"):
+                    fp[f"attention_blocks.{i}.{nm}.{w}"] = g(f"attention_blocks.{i}.{nm}.{w}")
     for l in range(3):
         for nm in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"):
             fp[f"lstm.{nm}_l{l}"] = g(f"lstm.{nm}_l{l}")
@@ -230,6 +270,13 @@ def float_params_from_state_dict(sd: dict, num_layers: int = 1) -> dict:
 
 
 def blob_from_state_dict(sd: dict, num_layers: int = 1) -> bytes:
+    """a converted (QAT) checkpoint -> ITAW0001 / ITAW0002; a float checkpoint (training's model_000205.pth: float
+    attention_blocks.{i}.q_proj.weight, no _packed_params) -> ITAW0003"""
     fp = float_params_from_state_dict(sd, num_layers)
+    kinds = {_float_attn(sd, i) for i in range(num_layers)}
+    if kinds == {True}:
+        return blob_from_float_params(fp, num_layers)
+    if len(kinds) > 1:
+        raise ValueError("a checkpoint mixing float and converted attention layers has no blob format")
     E = fp["tokenizer.conv.weight"].shape[0]
     return blob_from_record(record_from_state_dict(sd, num_layers), fp, E=E, num_layers=num_layers)

@@ -117,9 +117,20 @@ int ita_get_ffn_kind(ita_handle h, int layer, int* kind);
 /* the float32 FFN of layer `layer` alone (no residual, no LayerNorm): y = fc2(relu(fc1(x) + b1)) + b2, (B,128,E) f32,
  * bit-identical to two ascending-k fmaf chains per output started from the bias (E = 64) */
 int ita_ffn_f32(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, void* stream);
+/* Attention kind of a loaded layer: ITA_ATTN_INT8 (ITAW0001 / ITAW0002 blob, ita_mha_int8) or ITA_ATTN_F32 (ITAW0003
+ * blob: the float graph, models/ITA_single_layer_upsample_shuffle/model.py, nothing quantised).  ita_mha_int8 / _taps,
+ * ita_mha_q8, ita_mha_long_q8, ita_debug_encoder_stamps and the drop-in ITASelfAttention_workgroup on an F32 layer, and
+ * ita_mha_f32 on an INT8 layer, fail with ITA_ERR_UNSUPPORTED. */
+enum { ITA_ATTN_INT8 = 0, ITA_ATTN_F32 = 1 };
+int ita_get_attn_kind(ita_handle h, int layer, int* kind);
+/* the float32 attention block of layer `layer` alone (no residual, no LayerNorm), ITASelfAttention.forward
+ * (models/ITA/layers.py:67-88): y = out_proj(softmax(Q K^T) V), Q / K / V = x W^T + b, one head, no 1/sqrt(d);
+ * (B,128,E) f32, E = 64.  A frame's result does not depend on the batch it runs in. */
+int ita_mha_f32(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, void* stream);
 /* One encoder layer as the model wires it (QAT/model.py:100-113):
  * y = LN2(x1 + ffn(x1)),  x1 = LN1(x + mha(x)).  x_dev and y_dev may alias.
- * A float-FFN layer (ITA_FFN_F32) runs ffn, the residual and LN2 in float32 (QAT_only_attn/model.py:76-88). */
+ * A float-FFN layer (ITA_FFN_F32) runs ffn, the residual and LN2 in float32 (QAT_only_attn/model.py:76-88); a
+ * float-attention layer (ITA_ATTN_F32) also mha, the residual and LN1 (model.py:96-106). */
 int ita_encoder_layer(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, void* stream);
 
 /* OverlapPatchMerging (models/ITA/QAT/layers.py:39-45): image (B,60,90) -> tokens (B,128,E).

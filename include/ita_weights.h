@@ -15,6 +15,9 @@
  * LayerNorm2 stay float32: each layer holds ffn%d.w1f F32 [F][E], ffn%d.b1f F32 [F], ffn%d.w2f F32 [E][F], ffn%d.b2f F32 [E]
  * instead of the int8 FFN tensors.  A consumer that compares the magic with ITA_BLOB_MAGIC alone refuses such a blob
  * rather than reading int8 FFN tensors that are not there.
+ * "ITAW0003": the float ViT+LSTM graph (models/ITA_single_layer_upsample_shuffle/model.py, blocks of
+ * models/ITA/layers.py), nothing quantised: the float32 FFN of ITAW0002 and, instead of the int8 attention tensors,
+ * attn%d.wqf / wkf / wvf F32 [P][E], attn%d.bqf / bkf / bvf F32 [P], attn%d.wof F32 [E][P], attn%d.bof F32 [E].
  *
  * Layout (little endian):
  *   ita_blob_header | ita_blob_entry[n_tensors] | data (each tensor 64-byte aligned)
@@ -32,12 +35,22 @@ extern "C" {
 
 #define ITA_BLOB_MAGIC "ITAW0001"
 #define ITA_BLOB_MAGIC_FFN_F32 "ITAW0002"
+#define ITA_BLOB_MAGIC_F32 "ITAW0003"
 
-/* FFN kind of a blob from its magic: 0 int8 FFN (ITAW0001), 1 float32 FFN (ITAW0002), -1 neither */
+/* FFN kind of a blob from its magic: 0 int8 FFN (ITAW0001), 1 float32 FFN (ITAW0002, ITAW0003), -1 none of the three */
 static inline int ita_blob_ffn_kind(const void* blob, size_t nbytes) {
   if (!blob || nbytes < 8) return -1;
   if (memcmp(blob, ITA_BLOB_MAGIC, 8) == 0) return 0;
-  if (memcmp(blob, ITA_BLOB_MAGIC_FFN_F32, 8) == 0) return 1;
+  if (memcmp(blob, ITA_BLOB_MAGIC_FFN_F32, 8) == 0 || memcmp(blob, ITA_BLOB_MAGIC_F32, 8) == 0) return 1;
+  return -1;
+}
+
+/* attention kind of a blob from its magic: 0 int8 attention (ITAW0001, ITAW0002), 1 float32 attention (ITAW0003),
+ * -1 none of the three */
+static inline int ita_blob_attn_kind(const void* blob, size_t nbytes) {
+  if (!blob || nbytes < 8) return -1;
+  if (memcmp(blob, ITA_BLOB_MAGIC, 8) == 0 || memcmp(blob, ITA_BLOB_MAGIC_FFN_F32, 8) == 0) return 0;
+  if (memcmp(blob, ITA_BLOB_MAGIC_F32, 8) == 0) return 1;
   return -1;
 }
 
@@ -100,15 +113,15 @@ static inline const void* ita_blob_data(const void* blob, const ita_blob_entry* 
 /* Structural validation of a whole blob BEFORE anything dereferences a tensor: header, table bounds, 16-byte
  * alignment, and for every tensor name the loader knows its exact dtype and byte size as derived from
  * E / P / F / num_layers (a truncated or wrong-E tensor would otherwise be read past its end on the host and on
- * the device).  Required: the int8 attention tensors of every layer, and its int8 FFN tensors (ITAW0001) or its float32
- * FFN tensors (ITAW0002); everything else is optional but, when present, must have the right size.  Unknown names are ignored.  Returns 0, or a negative code and the offending tensor
+ * the device).  Required: the int8 attention tensors of every layer (ITAW0001, ITAW0002) or its float32 attention
+ * tensors (ITAW0003), and its int8 FFN tensors (ITAW0001) or its float32 FFN tensors (ITAW0002, ITAW0003); everything else is optional but, when present, must have the right size.  Unknown names are ignored.  Returns 0, or a negative code and the offending tensor
  * name in bad_name[32] (may be NULL):  -1 header / table, -2 a required tensor is missing, -3 wrong dtype or size. */
 static inline int ita_blob_validate(const void* blob, size_t nbytes, char* bad_name) {
   if (bad_name) bad_name[0] = 0;
   if (!blob || nbytes < sizeof(ita_blob_header)) return -1;
   const ita_blob_header* h = (const ita_blob_header*)blob;
-  const int kind = ita_blob_ffn_kind(blob, nbytes);
-  if (kind < 0) return -1;
+  const int kind = ita_blob_ffn_kind(blob, nbytes), akind = ita_blob_attn_kind(blob, nbytes);
+  if (kind < 0 || akind < 0) return -1;
   if (h->n_tensors < 0 || sizeof(ita_blob_header) + (size_t)h->n_tensors * sizeof(ita_blob_entry) > nbytes) return -1;
   if (h->E <= 0 || h->E % 64 || h->E > 1024 || h->S != 128 || h->P <= 0 || h->P % 64 || h->F <= 0 || h->F % 64 || h->H != 1 ||
       h->num_layers < 1 || h->num_layers > 16)
@@ -122,13 +135,17 @@ static inline int ita_blob_validate(const void* blob, size_t nbytes, char* bad_n
     }
   }
   const size_t E = (size_t)h->E, P = (size_t)h->P, F = (size_t)h->F, CIN = E / 4 + E;
-  /* required: 1 always, 0 never, 2 only in an int8-FFN blob, 3 only in a float-FFN blob */
+  /* required: 1 always, 0 never, 2 only in an int8-FFN blob, 3 only in a float-FFN blob, 4 only in an int8-attention
+   * blob, 5 only in a float-attention blob */
   struct spec { const char* fmt; int dtype; size_t nbytes; int required; int per_layer; };
   const size_t dec_k = h->has_tail ? 4608 : (size_t)h->S * E;   /* decoder input: fusion-tail map, or the flattened tokens */
   const struct spec specs[] = {
-    {"attn%d.wq", ITA_I8, P * E, 1, 1}, {"attn%d.wk", ITA_I8, P * E, 1, 1}, {"attn%d.wv", ITA_I8, P * E, 1, 1},
-    {"attn%d.wo", ITA_I8, E * P, 1, 1}, {"attn%d.bq", ITA_I32, P * 4, 1, 1}, {"attn%d.bk", ITA_I32, P * 4, 1, 1},
-    {"attn%d.bv", ITA_I32, P * 4, 1, 1}, {"attn%d.bo", ITA_I32, E * 4, 1, 1}, {"attn%d.scal", ITA_F32, ITA_A_NSCAL * 4, 1, 1},
+    {"attn%d.wq", ITA_I8, P * E, 4, 1}, {"attn%d.wk", ITA_I8, P * E, 4, 1}, {"attn%d.wv", ITA_I8, P * E, 4, 1},
+    {"attn%d.wo", ITA_I8, E * P, 4, 1}, {"attn%d.bq", ITA_I32, P * 4, 4, 1}, {"attn%d.bk", ITA_I32, P * 4, 4, 1},
+    {"attn%d.bv", ITA_I32, P * 4, 4, 1}, {"attn%d.bo", ITA_I32, E * 4, 4, 1}, {"attn%d.scal", ITA_F32, ITA_A_NSCAL * 4, 4, 1},
+    {"attn%d.wqf", ITA_F32, P * E * 4, 5, 1}, {"attn%d.wkf", ITA_F32, P * E * 4, 5, 1}, {"attn%d.wvf", ITA_F32, P * E * 4, 5, 1},
+    {"attn%d.bqf", ITA_F32, P * 4, 5, 1}, {"attn%d.bkf", ITA_F32, P * 4, 5, 1}, {"attn%d.bvf", ITA_F32, P * 4, 5, 1},
+    {"attn%d.wof", ITA_F32, E * P * 4, 5, 1}, {"attn%d.bof", ITA_F32, E * 4, 5, 1},
     {"ffn%d.w1", ITA_I8, F * E, 2, 1}, {"ffn%d.w2", ITA_I8, E * F, 2, 1}, {"ffn%d.b1", ITA_I32, F * 4, 2, 1},
     {"ffn%d.b2", ITA_I32, E * 4, 2, 1}, {"ffn%d.scal", ITA_F32, ITA_F_NSCAL * 4, 2, 1},
     {"ffn%d.w1f", ITA_F32, F * E * 4, 3, 1}, {"ffn%d.b1f", ITA_F32, F * 4, 3, 1}, {"ffn%d.w2f", ITA_F32, E * F * 4, 3, 1},
@@ -162,7 +179,7 @@ static inline int ita_blob_validate(const void* blob, size_t nbytes, char* bad_n
       const ita_blob_entry* t = ita_blob_find(blob, nbytes, nm);
       if (!t) {
         const int req = specs[s].required;
-        if (req == 1 || (req == 2 && kind == 0) || (req == 3 && kind == 1)) { if (bad_name) strcpy(bad_name, nm); return -2; }
+        if (req == 1 || (req == 2 && kind == 0) || (req == 3 && kind == 1) || (req == 4 && akind == 0) || (req == 5 && akind == 1)) { if (bad_name) strcpy(bad_name, nm); return -2; }
         continue;
       }
       if (t->dtype != specs[s].dtype || (size_t)t->nbytes != specs[s].nbytes) { if (bad_name) strcpy(bad_name, nm); return -3; }

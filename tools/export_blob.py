@@ -2,7 +2,9 @@
 """Row n4: reference checkpoint (training/qa_train.py's model_quantized_final.pth, i.e. the
 state_dict of the converted int8 model) -> ITAW0001 weight blob for ita_load_weights / ita_udp_server.
 A converted attention-only model (QAT_only_attn: float ffn_blocks.{i}.fc1.weight ...) gives an ITAW0002
-blob with the float32 FFN; the command line is the same.
+blob with the float32 FFN.  A float checkpoint (the float ITALSTMNetVIT that training produces, e.g.
+model_000205.pth: float attention_blocks.{i}.q_proj.weight, no _packed_params; decoder / nn_fc2 under
+spectral_norm are folded) gives an ITAW0003 blob, the whole float graph.  The command line is the same.
 
     python tools/export_blob.py --checkpoint model_quantized_final.pth --out weights.itaw [--num-layers 1]
 

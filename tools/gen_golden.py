@@ -435,15 +435,17 @@ def gen_tail_large(out_dir):
         print("wrote", name, tuple(out.shape))
 
 
-def gen_float_twin(seed, B, out_dir):
+def gen_float_twin(seed, B, out_dir, num_layers=1):
     """The reference's FLOAT model (models/ITA_single_layer_upsample_shuffle/model.py:35-140 with the float blocks of
     models/ITA/layers.py: nn.Softmax attention) -- the graph its CPU .vmfb holds.  decoder and
     nn_fc2 are declared under spectral_norm (model.py:81,84); the parametrisation is removed on the instance
     (torch.nn.utils.remove_spectral_norm leaves a plain weight) so that the synthetic weights ARE the effective ones --
-    in eval mode the module then computes exactly F.linear(x, weight, bias).  Two time steps, state carried."""
+    in eval mode the module then computes exactly F.linear(x, weight, bias).  Two time steps, state carried.
+    num_layers > 1: floattwin{L}l_E64_s{seed}_B{B}.npz, with meta.num_layers and the per-layer taps x1_{i} / x2_{i}
+    besides x1 / x2 (the last layer's); the one-layer file keeps its name and its keys."""
     from models.ITA_single_layer_upsample_shuffle.model import ITALSTMNetVIT
-    fp = synth.float_params(seed, E=64)
-    model = ITALSTMNetVIT(num_layers=1)
+    fp = synth.float_params(seed, E=64, num_layers=num_layers)
+    model = ITALSTMNetVIT(num_layers=num_layers)
     for lin in (model.decoder, model.nn_fc2):
         torch.nn.utils.remove_spectral_norm(lin)
         lin._load_state_dict_pre_hooks.clear()   # the removal leaves spectral_norm's load hook behind (it demands weight_orig)
@@ -454,16 +456,25 @@ def gen_float_twin(seed, B, out_dir):
     model.eval()
     tap = Tap()
     tap.add(model.tokenizer, "tok.out")
-    tap.add(model.norms1[0], "x1")
-    tap.add(model.norms2[0], "x2")
+    if num_layers == 1:
+        tap.add(model.norms1[0], "x1")
+        tap.add(model.norms2[0], "x2")
+    else:
+        for i in range(num_layers):
+            tap.add(model.norms1[i], f"x1_{i}")
+            tap.add(model.norms2[i], f"x2_{i}")
     tap.add(model.decoder, "dec")
     fr0, fr1 = synth.frames(10 * seed, B), synth.frames(10 * seed + 1, B)
     with torch.no_grad():
         vel0, (h0, c0) = model(to_X(fr0, None))
         stage = dict(tap.t)
         vel1, (h1, c1) = model(to_X(fr1, (h0, c0)))
+    if num_layers > 1:
+        stage["x1"], stage["x2"] = stage[f"x1_{num_layers - 1}"], stage[f"x2_{num_layers - 1}"]
     rec = {"meta.seed": np.int64(seed), "meta.B": np.int64(B), "meta.params_sha256": np.array(synth.digest(fp)),
            "meta.torch": np.array(torch.__version__)}
+    if num_layers > 1:
+        rec["meta.num_layers"] = np.int64(num_layers)
     for k, v in fr0.items():
         rec["in0." + k] = v
     for k, v in fr1.items():
@@ -472,7 +483,8 @@ def gen_float_twin(seed, B, out_dir):
         rec["s0." + k] = v
     rec["s0.vel"] = vel0.numpy(); rec["s0.h"] = h0.numpy(); rec["s0.c"] = c0.numpy()
     rec["s1.vel"] = vel1.numpy(); rec["s1.h"] = h1.numpy(); rec["s1.c"] = c1.numpy()
-    path = os.path.join(out_dir, f"floattwin_E64_s{seed}_B{B}.npz")    # (not "*_seed*": that glob selects the int8 fixtures)
+    stem = "floattwin_" if num_layers == 1 else f"floattwin{num_layers}l_"
+    path = os.path.join(out_dir, f"{stem}E64_s{seed}_B{B}.npz")    # (not "*_seed*": that glob selects the int8 fixtures)
     np.savez_compressed(path, **rec)
     print("wrote", path, os.path.getsize(path) // 1024, "KiB")
 
@@ -611,7 +623,9 @@ def main():
             for seed in (0, 1): gen_blocks(seed, 128, 1, a.out)
             gen_blocks(2, 64, 1, a.out, gain_qk=6.0)
         if "tail_large" in only: gen_tail_large(a.out)
-        if "float_twin" in only: gen_float_twin(0, 2, a.out)
+        if "float_twin" in only:
+            gen_float_twin(0, 2, a.out)
+            gen_float_twin(1, 2, a.out, num_layers=2)
         if "vit2l" in only: gen_vit2l(0, 2, a.out)
         if "vit2l_us" in only: gen_vit2l(1, 2, a.out, upsample_shuffle_file=True)
         if "vit1l" in only: gen_vit1l(0, 2, a.out)
@@ -622,6 +636,7 @@ def main():
         if "only_attn_checkpoint" in only: gen_only_attn_checkpoint(0, a.out)
         return
     gen_float_twin(0, 2, a.out)
+    gen_float_twin(1, 2, a.out, num_layers=2)
     gen_vit2l(0, 2, a.out)
     gen_vit2l(1, 2, a.out, upsample_shuffle_file=True)
     gen_vit1l(0, 2, a.out)
