@@ -221,7 +221,7 @@ __global__ __launch_bounds__(512) void ita_attn_f32_kernel(const ItaAttnF32Args 
         const f32x4 v = *(const f32x4*)(xl + (t0 + tok) * XS + qtr * EC + i);
         r[i] = v.x; r[i + 1] = v.y; r[i + 2] = v.z; r[i + 3] = v.w;
       }
-      if (a.fuse_ln) layernorm_lanes<E, 4>(r, a.ln_w, a.ln_b, qtr * EC);
+      if (a.fuse_ln) layernorm_lanes<E>(r, a.ln_w, a.ln_b, qtr * EC);
       float* yrow = a.y + ((size_t)b * S + t0 + tok) * E + qtr * EC;
 #pragma unroll
       for (int i = 0; i < EC; i += 4) *(f32x4*)(yrow + i) = (f32x4){r[i], r[i + 1], r[i + 2], r[i + 3]};

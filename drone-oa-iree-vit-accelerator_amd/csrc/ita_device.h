@@ -90,14 +90,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // scale step is written on float2 values.
 template <int N, typename ACC>
 __device__ __forceinline__ void scale_clamp(const ACC& acc, float mult, float lo, float (&f)[N]) {
-#ifdef ITA_SCALAR_SCALE
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    float v = (float)acc[i];
-    asm("v_mul_f32 %0, %1, %2" : "=v"(v) : "v"(v), "v"(mult));   // asm: keeps the SLP vectoriser from re-packing it
-    f[i] = __builtin_amdgcn_fmed3f(v, lo, 127.0f);
-  }
-#else
   const f32x2 m2 = {mult, mult};
 #pragma unroll
   for (int i = 0; i < N; i += 2) {
@@ -106,7 +98,6 @@ __device__ __forceinline__ void scale_clamp(const ACC& acc, float mult, float lo
     f[i] = __builtin_amdgcn_fmed3f(v.x, lo, 127.0f);
     f[i + 1] = __builtin_amdgcn_fmed3f(v.y, lo, 127.0f);
   }
-#endif
 }
 // The same for accumulators that were started at ITA_ACC_BIAS (+ bias) instead of (bias): while |sum| < 2^22 the
 // int32 bit pattern 0x4B400000 + sum IS the float 1.5 * 2^23 + sum, so the int -> float conversion becomes an exact
@@ -129,12 +120,10 @@ __device__ __forceinline__ void scale_clamp_b(const ACC& acc, float mult, float 
 // issues ~1.7x slower).  mult / lo / scale must be wave-uniform.
 // Hazard: hipcc pads MFMA -> VALU read wait states for its own instructions, not for inline asm; an accumulator may come
 // from a 4-pass MFMA issued immediately before (7-8 wait states on gfx950), so the first block opens with ten.
-template <int NP>   // NP register pairs: x = (x - 1.5 * 2^23) * mult
-__device__ __forceinline__ void pk_unbias_scale(f32x2 (&x)[NP], float mult) {
-  static_assert(NP == 8 || NP == 4, "");
+// eight register pairs: x = (x - 1.5 * 2^23) * mult
+__device__ __forceinline__ void pk_unbias_scale(f32x2 (&x)[8], float mult) {
   const f32x2 c2 = {-ITA_MAGIC_F, -ITA_MAGIC_F}, m2 = {mult, mult};
-  if constexpr (NP == 8) {
-    asm("s_nop 7\n\ts_nop 1\n\t"
+  asm("s_nop 7\n\ts_nop 1\n\t"
       "v_pk_add_f32 %0, %0, %8\n\t"
       "v_pk_add_f32 %1, %1, %8\n\t"
       "v_pk_add_f32 %2, %2, %8\n\t"
@@ -151,121 +140,15 @@ __device__ __forceinline__ void pk_unbias_scale(f32x2 (&x)[NP], float mult) {
       "v_pk_mul_f32 %5, %5, %9\n\t"
       "v_pk_mul_f32 %6, %6, %9\n\t"
       "v_pk_mul_f32 %7, %7, %9"
-        : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7])
-        : "s"(c2), "s"(m2));
-  } else {
-    asm("s_nop 7\n\ts_nop 1\n\t"
-      "v_pk_add_f32 %0, %0, %4\n\t"
-      "v_pk_add_f32 %1, %1, %4\n\t"
-      "v_pk_add_f32 %2, %2, %4\n\t"
-      "v_pk_add_f32 %3, %3, %4\n\t"
-      "v_pk_mul_f32 %0, %0, %5\n\t"
-      "v_pk_mul_f32 %1, %1, %5\n\t"
-      "v_pk_mul_f32 %2, %2, %5\n\t"
-      "v_pk_mul_f32 %3, %3, %5"
-        : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3])
-        : "s"(c2), "s"(m2));
-  }
-}
-// clamp sixteen floats, round them to nearest-even integers and pack their low bytes: pk[g] byte b = rne(clamp(f[4g+b]))
-__device__ __forceinline__ i32x4 clamp_round_pack16(float (&f)[16], float lo) {
-  unsigned p0, p1, p2, p3;
-  const float hi = 127.0f, mg = ITA_MAGIC_F;
-  asm(
-      "v_med3_f32 %4, %4, %20, %21\n\t"
-      "v_med3_f32 %5, %5, %20, %21\n\t"
-      "v_med3_f32 %6, %6, %20, %21\n\t"
-      "v_med3_f32 %7, %7, %20, %21\n\t"
-      "v_med3_f32 %8, %8, %20, %21\n\t"
-      "v_med3_f32 %9, %9, %20, %21\n\t"
-      "v_med3_f32 %10, %10, %20, %21\n\t"
-      "v_med3_f32 %11, %11, %20, %21\n\t"
-      "v_med3_f32 %12, %12, %20, %21\n\t"
-      "v_med3_f32 %13, %13, %20, %21\n\t"
-      "v_med3_f32 %14, %14, %20, %21\n\t"
-      "v_med3_f32 %15, %15, %20, %21\n\t"
-      "v_med3_f32 %16, %16, %20, %21\n\t"
-      "v_med3_f32 %17, %17, %20, %21\n\t"
-      "v_med3_f32 %18, %18, %20, %21\n\t"
-      "v_med3_f32 %19, %19, %20, %21\n\t"
-      "v_add_f32_sdwa %0, %4, %22 dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:DWORD\n\t"
-      "v_add_f32_sdwa %1, %8, %22 dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:DWORD\n\t"
-      "v_add_f32_sdwa %2, %12, %22 dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:DWORD\n\t"
-      "v_add_f32_sdwa %3, %16, %22 dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:DWORD\n\t"
-      "v_add_f32_sdwa %0, %5, %22 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\t"
-      "v_add_f32_sdwa %1, %9, %22 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\t"
-      "v_add_f32_sdwa %2, %13, %22 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\t"
-      "v_add_f32_sdwa %3, %17, %22 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\t"
-      "v_add_f32_sdwa %0, %6, %22 dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\t"
-      "v_add_f32_sdwa %1, %10, %22 dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\t"
-      "v_add_f32_sdwa %2, %14, %22 dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\t"
-      "v_add_f32_sdwa %3, %18, %22 dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\t"
-      "v_add_f32_sdwa %0, %7, %22 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\t"
-      "v_add_f32_sdwa %1, %11, %22 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\t"
-      "v_add_f32_sdwa %2, %15, %22 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\t"
-      "v_add_f32_sdwa %3, %19, %22 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\t"
-      "s_nop 0"
-      : "=&v"(p0), "=&v"(p1), "=&v"(p2), "=&v"(p3), "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]),
-        "+v"(f[6]), "+v"(f[7]), "+v"(f[8]), "+v"(f[9]), "+v"(f[10]), "+v"(f[11]), "+v"(f[12]), "+v"(f[13]), "+v"(f[14]),
-        "+v"(f[15])
-      : "s"(lo), "v"(hi), "v"(mg));
-  return (i32x4){(int)p0, (int)p1, (int)p2, (int)p3};
-}
-// the same arithmetic left to the compiler's scheduler (it interleaves the VALU work with the MFMAs and LDS reads
-// around it; only the byte-insert block is fixed): experiment switch ITA_RQ_STYLE=1
-__device__ __forceinline__ i32x4 rq_pack16_c(const i32x4 (&acc)[4], float mult, float lo) {
-  const f32x2 c2 = {-ITA_MAGIC_F, -ITA_MAGIC_F}, m2 = {mult, mult};
-  float f[16];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    f32x2 v = {__int_as_float(acc[k >> 1][2 * (k & 1)]), __int_as_float(acc[k >> 1][2 * (k & 1) + 1])};
-    v = (v + c2) * m2;
-    f[2 * k] = __builtin_amdgcn_fmed3f(v.x, lo, 127.0f);
-    f[2 * k + 1] = __builtin_amdgcn_fmed3f(v.y, lo, 127.0f);
-  }
-  unsigned p4[4];
-  round_pack16(f, p4);
-  return (i32x4){(int)p4[0], (int)p4[1], (int)p4[2], (int)p4[3]};
-}
-__device__ __forceinline__ void dq16_c(const i32x4 (&acc)[4], float mult, float scale, float (&d)[16]) {
-  const f32x2 c2 = {-ITA_MAGIC_F, -ITA_MAGIC_F}, m2 = {mult, mult}, s2 = {scale, scale};
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    f32x2 v = {__int_as_float(acc[k >> 1][2 * (k & 1)]), __int_as_float(acc[k >> 1][2 * (k & 1) + 1])};
-    v = (v + c2) * m2;
-    f32x2 r = {__builtin_rintf(__builtin_amdgcn_fmed3f(v.x, -128.0f, 127.0f)), __builtin_rintf(__builtin_amdgcn_fmed3f(v.y, -128.0f, 127.0f))};
-    r = r * s2;
-    d[2 * k] = r.x; d[2 * k + 1] = r.y;
-  }
-}
-__device__ __forceinline__ void lg8_c(const i32x4 (&acc)[2], float mult, unsigned (&bits)[8]) {
-  const f32x2 c2 = {-ITA_MAGIC_F, -ITA_MAGIC_F}, m2 = {mult, mult}, mg2 = {ITA_MAGIC_F, ITA_MAGIC_F};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    f32x2 v = {__int_as_float(acc[k >> 1][2 * (k & 1)]), __int_as_float(acc[k >> 1][2 * (k & 1) + 1])};
-    v = (v + c2) * m2;
-    f32x2 r = {__builtin_amdgcn_fmed3f(v.x, -128.0f, 127.0f), __builtin_amdgcn_fmed3f(v.y, -128.0f, 127.0f)};
-    r = r + mg2;
-    bits[2 * k] = __float_as_uint(r.x); bits[2 * k + 1] = __float_as_uint(r.y);
-  }
-}
-// requantise + pack sixteen biased accumulators (four 16x16 tiles): 8 + 8 + 16 + 16 VALU instructions
-__device__ __forceinline__ i32x4 rq_pack16_b(const i32x4 (&acc)[4], float mult, float lo) {
-  f32x2 x[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) x[k] = (f32x2){__int_as_float(acc[k >> 1][2 * (k & 1)]), __int_as_float(acc[k >> 1][2 * (k & 1) + 1])};
-  pk_unbias_scale<8>(x, mult);
-  float f[16];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) { f[2 * k] = x[k].x; f[2 * k + 1] = x[k].y; }
-  return clamp_round_pack16(f, lo);
+      : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7])
+      : "s"(c2), "s"(m2));
 }
 // block output: d[4t+i] = float(int8 code) * scale for sixteen biased accumulators: 8 + 8 + 16 + 16 + 8
 __device__ __forceinline__ void dq16_b(const i32x4 (&acc)[4], float mult, float scale, float (&d)[16]) {
   f32x2 x[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) x[k] = (f32x2){__int_as_float(acc[k >> 1][2 * (k & 1)]), __int_as_float(acc[k >> 1][2 * (k & 1) + 1])};
-  pk_unbias_scale<8>(x, mult);
+  pk_unbias_scale(x, mult);
   float f[16];
 #pragma unroll
   for (int k = 0; k < 8; ++k) { f[2 * k] = x[k].x; f[2 * k + 1] = x[k].y; }
@@ -311,34 +194,6 @@ __device__ __forceinline__ void dq16_b(const i32x4 (&acc)[4], float mult, float 
   for (int k = 0; k < 8; ++k) {
     const f32x2 v = (f32x2){f[2 * k], f[2 * k + 1]} * s2;
     d[2 * k] = v.x; d[2 * k + 1] = v.y;
-  }
-}
-// logits: eight biased accumulators (two key tiles) -> float bit patterns whose low 16 bits hold rne(clamp(acc * mult))
-__device__ __forceinline__ void lg8_b(const i32x4 (&acc)[2], float mult, unsigned (&bits)[8]) {
-  f32x2 x[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) x[k] = (f32x2){__int_as_float(acc[k >> 1][2 * (k & 1)]), __int_as_float(acc[k >> 1][2 * (k & 1) + 1])};
-  pk_unbias_scale<4>(x, mult);
-  float f[8];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { f[2 * k] = x[k].x; f[2 * k + 1] = x[k].y; }
-  const float lo = -128.0f, hi = 127.0f;
-  asm(
-      "v_med3_f32 %0, %0, %8, %9\n\t"
-      "v_med3_f32 %1, %1, %8, %9\n\t"
-      "v_med3_f32 %2, %2, %8, %9\n\t"
-      "v_med3_f32 %3, %3, %8, %9\n\t"
-      "v_med3_f32 %4, %4, %8, %9\n\t"
-      "v_med3_f32 %5, %5, %8, %9\n\t"
-      "v_med3_f32 %6, %6, %8, %9\n\t"
-      "v_med3_f32 %7, %7, %8, %9"
-      : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]), "+v"(f[6]), "+v"(f[7])
-      : "s"(lo), "v"(hi));
-  const f32x2 mg2 = {ITA_MAGIC_F, ITA_MAGIC_F};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const f32x2 v = (f32x2){f[2 * k], f[2 * k + 1]} + mg2;
-    bits[2 * k] = __float_as_uint(v.x); bits[2 * k + 1] = __float_as_uint(v.y);
   }
 }
 // ---- round-3 requantisation of biased accumulators: the clamp moves behind the rounding, into the integer domain, where
@@ -617,45 +472,24 @@ __device__ __forceinline__ void bilinear_src_dev(int dst, float scale, int in, i
   l1 = src - (float)i;
 }
 
-// LayerNorm over E channels spread over NT adjacent lanes (NT = 2 or 4), each holding EC = E/NT
-// consecutive channels, in the oracle's summation order: 4 blocks of E/4 consecutive channels
-// summed sequentially, combined (p0+p1)+(p2+p3).   r[] is overwritten with the result.
-template <int E, int NT, typename WP, typename BP>
-__device__ __forceinline__ void layernorm_lanes(float (&r)[E / NT], const WP& w, const BP& b, int c0) {
-  constexpr int EC = E / NT, Q = E / 4;
+// LayerNorm over E channels spread over 4 adjacent lanes, each holding EC = E/4 consecutive channels,
+// in the oracle's summation order: 4 blocks of E/4 consecutive channels summed sequentially, combined
+// (p0+p1)+(p2+p3).   r[] is overwritten with the result.
+template <int E, typename WP, typename BP>
+__device__ __forceinline__ void layernorm_lanes(float (&r)[E / 4], const WP& w, const BP& b, int c0) {
+  constexpr int EC = E / 4;
   const float inv_e = 1.0f / (float)E;
-  float tot;
-  if constexpr (NT == 4) {
-    float p = 0.0f;
+  float p = 0.0f;
 #pragma unroll
-    for (int i = 0; i < EC; ++i) p = p + r[i];
-    float s1 = p + xor1_f(p);
-    tot = s1 + xor2_f(s1);
-  } else {
-    float pa = 0.0f, pb = 0.0f;
-#pragma unroll
-    for (int i = 0; i < Q; ++i) pa = pa + r[i];
-#pragma unroll
-    for (int i = 0; i < Q; ++i) pb = pb + r[Q + i];
-    float s1 = pa + pb;
-    tot = s1 + xor1_f(s1);
-  }
+  for (int i = 0; i < EC; ++i) p = p + r[i];
+  float s1 = p + xor1_f(p);
+  float tot = s1 + xor2_f(s1);
   const float mean = tot * inv_e;
-  if constexpr (NT == 4) {
-    float p = 0.0f;
+  p = 0.0f;
 #pragma unroll
-    for (int i = 0; i < EC; ++i) { float d = r[i] - mean; p = fmaf(d, d, p); }
-    float s1 = p + xor1_f(p);
-    tot = s1 + xor2_f(s1);
-  } else {
-    float pa = 0.0f, pb = 0.0f;
-#pragma unroll
-    for (int i = 0; i < Q; ++i) { float d = r[i] - mean; pa = fmaf(d, d, pa); }
-#pragma unroll
-    for (int i = 0; i < Q; ++i) { float d = r[Q + i] - mean; pb = fmaf(d, d, pb); }
-    float s1 = pa + pb;
-    tot = s1 + xor1_f(s1);
-  }
+  for (int i = 0; i < EC; ++i) { float d = r[i] - mean; p = fmaf(d, d, p); }
+  s1 = p + xor1_f(p);
+  tot = s1 + xor2_f(s1);
   const float var = tot * inv_e;
   const float rstd = 1.0f / sqrtf(var + 1e-5f);
 #pragma unroll

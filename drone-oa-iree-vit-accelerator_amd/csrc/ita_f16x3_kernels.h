@@ -791,12 +791,6 @@ struct ItaTailUpLds {
   static_assert(WL2 >= TOTAL1 && WH2 >= W + 2 * WPL && 2 * A_PLANE <= WH2 && 48 * 516 * 4 <= WH2, "phase-2 LDS");
 };
 
-#ifndef ITA_UP_NB
-#define ITA_UP_NB 2
-#endif
-#ifndef ITA_UP_PKFMA
-#define ITA_UP_PKFMA 0
-#endif
 #ifdef ITA_UP_STAMP
 // diagnostic build only (tools/tail_up_stamps.py): s_memrealtime (100 MHz) of every wave at the phase boundaries (<= 2048 workgroups)
 __device__ unsigned long long ita_up_stamp_buf[2048 * 8 * 12];
@@ -938,7 +932,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int u = 0; u < 5; ++u) c[u] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
     // weight fragments of one k-step, N tiles in the order (nt3, 1, 2 - nt3): units 0..2 = tile A x them, 3 and 4 = tile B x the first two
     f16x8 wh[3], wl[3];
-    constexpr int NB = ITA_UP_NB;                        // blend groups in flight
+    constexpr int NB = 2;                                // blend groups in flight
     f32x4 v[NB][4];
     auto ntq = [&](int q) { return q == 1 ? 1 : (q == 0 ? nt3 : 2 - nt3); };
     auto ldwh = [&](int j) {
@@ -978,12 +972,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
       if (DO_B) {
         // (explicit fma: the library is built with -ffp-contract=off)
-#if ITA_UP_PKFMA
-        acc[i] = __builtin_elementwise_fma(q00, v[i % NB][0], acc[i]);
-        acc[i] = __builtin_elementwise_fma(q01, v[i % NB][1], acc[i]);
-        acc[i] = __builtin_elementwise_fma(q10, v[i % NB][2], acc[i]);
-        acc[i] = __builtin_elementwise_fma(q11, v[i % NB][3], acc[i]);
-#else
         // scalar v_fmac_f32, not v_pk_fma_f32: beside MFMAs a packed f32 FMA costs ~20 cycles more than the two scalar ones
         // (MI355X guide, 'price of one filler beside MFMAs'); hipcc packs whatever it sees, hence the asm
 #pragma unroll
@@ -996,7 +984,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             acc[i][e] = r;
           }
         }
-#endif
         __builtin_amdgcn_sched_barrier(0);
         if (i + NB < 12) ldv(i + NB);
         __builtin_amdgcn_sched_barrier(0);

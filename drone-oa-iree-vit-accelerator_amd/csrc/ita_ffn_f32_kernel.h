@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void i
           const f32x4 v = *(const f32x4*)(xl + tok * XS + qtr * EC + i);
           r[i] = v.x + r[i]; r[i + 1] = v.y + r[i + 1]; r[i + 2] = v.z + r[i + 2]; r[i + 3] = v.w + r[i + 3];
         }
-        layernorm_lanes<E, 4>(r, a.ln_w, a.ln_b, qtr * EC);
+        layernorm_lanes<E>(r, a.ln_w, a.ln_b, qtr * EC);
       }
       if (a.y) {
         float* yrow = a.y + ((size_t)tile * TT + tok) * E + qtr * EC;

@@ -116,7 +116,7 @@ __device__ __forceinline__ void finish_tokens(const char* lds_outq, float so, co
   if (fuse_ln) {
 #pragma unroll
     for (int i = 0; i < EC; ++i) r[i] = xr[i] + r[i];
-    layernorm_lanes<E, 4>(r, ln_w, ln_b, qtr * EC);
+    layernorm_lanes<E>(r, ln_w, ln_b, qtr * EC);
   }
   if (yrow) {
 #pragma unroll

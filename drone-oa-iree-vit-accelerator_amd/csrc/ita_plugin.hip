@@ -79,13 +79,11 @@ struct ita_context {
   char* dblob = nullptr;
   std::vector<Layer> layers;
   // float layers (device pointers into dblob)
-  const float *tok_w = nullptr, *tok_b = nullptr, *tok_lw = nullptr, *tok_lb = nullptr;
   const float *tail_b = nullptr, *dec_w = nullptr, *dec_b = nullptr, *fc_w = nullptr, *fc_b = nullptr;
   // derived device buffers
   float* tail_wT = nullptr;
   char* tok_simg = nullptr;                // LDS images of ita_tok_stream_kernel: [u8 frames (conv weights x 1/65280) | f32 frames]
   size_t tok_simg_bytes = 0;               // size of one of the two
-  float* tok_wT = nullptr;                 // [2][50][E] conv7x7 weights k-major, row 49 = 0; second copy x 1/65280 (u8 frames)
   float* wcat[3] = {nullptr, nullptr, nullptr};
   float* bsum[3] = {nullptr, nullptr, nullptr};
   // split-precision (f16 hi/lo) tail: folded tail+decoder matrix and LSTM weights, pre-scaled
@@ -163,9 +161,7 @@ void free_weights(ita_context* c) {
   }
   if (c->dblob) (void)hipFree(c->dblob);
   if (c->tail_wT) (void)hipFree(c->tail_wT);
-  if (c->tok_wT) (void)hipFree(c->tok_wT);
   if (c->tok_simg) (void)hipFree(c->tok_simg);
-  c->tok_wT = nullptr;
   c->tok_simg = nullptr;
   for (int l = 0; l < 3; ++l) {
     if (c->wcat[l]) (void)hipFree(c->wcat[l]);
@@ -274,8 +270,7 @@ int launch_mha(ita_context* c, int layer, const float* x, float* y, int B, bool 
   if (c->layers[layer].attn_f32)
     return fail(ITA_ERR_UNSUPPORTED, "this layer's attention is float32 (ITAW0003 blob): ita_mha_f32 runs it");
   if (fuse && !c->layers[layer].n1w) return fail(ITA_ERR_BAD_BLOB, "norm1 parameters missing from the blob");
-  static const bool block_only = getenv("ITA_MHA_BLOCK_KERNEL") != nullptr;   // A/B switch
-  if (!t && c->layers[layer].simg_mha && !block_only) return launch_mha_stream(c, layer, x, y, B, fuse, s);
+  if (!t && c->layers[layer].simg_mha) return launch_mha_stream(c, layer, x, y, B, fuse, s);
   const ItaMhaArgs a = mha_args(c, layer, x, y, B, fuse, t);
   const int grid = B < c->num_cus ? B : c->num_cus;
   if (c->hdr.E == 64) {
@@ -321,8 +316,7 @@ int launch_ffn_f32(ita_context* c, int layer, const float* x, float* y, int B, b
   a.B = B; a.fuse_ln = fuse ? 1 : 0;
   a.y_hi = y_hi; a.y_lo = y_lo; a.ld_planes = c->ldfold;
   a.h0_src = h0_src; a.h0_dst = h0_dst; a.slots = slots;
-  static const int wg_per_cu = getenv("ITA_FFN_F32_WG_PER_CU") ? atoi(getenv("ITA_FFN_F32_WG_PER_CU")) : 2;   // A/B switch
-  const int ntile = B * (128 / ItaFfnF32Lds::TT), cap = (wg_per_cu > 0 ? wg_per_cu : 2) * c->num_cus;
+  const int ntile = B * (128 / ItaFfnF32Lds::TT), cap = 2 * c->num_cus;
   hipLaunchKernelGGL(ita_ffn_f32_kernel, dim3(ntile < cap ? ntile : cap), dim3(256), ItaFfnF32Lds::TOTAL, s, a);
   HIPCHK(hipGetLastError());
   return ITA_OK;
@@ -503,8 +497,6 @@ bool fast_site_ok(float m) {
   return true;
 }
 unsigned fast_sites_of(const float* ascal) {
-  static const char* env = getenv("ITA_FAST_SITES");   // diagnostic: force a mask (0 = the exact form everywhere)
-  if (env) return (unsigned)strtoul(env, nullptr, 0);
   unsigned mask = 0;
   const int idx[6] = {ITA_A_MQ, ITA_A_MK, ITA_A_MV, ITA_A_ML, ITA_A_MC, ITA_A_MO};
   for (int i = 0; i < 6; ++i)
@@ -627,7 +619,7 @@ int launch_encoder(ita_context* c, int layer, const float* x, float* y, _Float16
 }
 
 // frames into the E = 64 model: the tokenizer runs inside the first encoder layer's kernel
-// (ITA_SPLIT_TOKENIZER=1 keeps the separate ita_tokenizer_kernel launch, for comparison)
+// (ITA_SPLIT_TOKENIZER=1 keeps the separate ita_tok_stream_kernel launch, for comparison)
 bool fuse_tokenizer(const ita_context* c, int image_dtype) {
   static const bool split = getenv("ITA_SPLIT_TOKENIZER") != nullptr;
   // f32 frames go through the stand-alone tokenizer: the stream kernel's private pixel windows are sized for bytes
@@ -635,35 +627,17 @@ bool fuse_tokenizer(const ita_context* c, int image_dtype) {
 }
 
 int launch_tokenizer(ita_context* c, const void* img, int dtype, float* tokens, int B, hipStream_t s) {
-  if (!c->tok_w) return fail(ITA_ERR_BAD_BLOB, "tokenizer parameters missing from the blob");
-  static const int tok_dbg = getenv("ITA_TOK_DBG") ? atoi(getenv("ITA_TOK_DBG")) : 0;
+  // (the image exists when the blob has the conv weights and bias and the LayerNorm: ita_load_weights)
+  if (!c->tok_simg) return fail(ITA_ERR_BAD_BLOB, "tokenizer parameters missing from the blob");
   const bool u8 = dtype == ITA_IMAGE_U8;
-  // diagnostic: the older tokenizer kernel (f32 frames only: its u8 form predates the integer conv and is no longer the
-  // oracle's arithmetic; without a stream image -- E outside {64, 128} never loads -- u8 frames have no other path)
-  static const bool block_tok = getenv("ITA_TOK_BLOCK_KERNEL") != nullptr;
-  if (c->tok_simg && !(block_tok && !u8)) {
-    ItaTokStreamArgs ta{c->tok_simg + (u8 ? 0 : c->tok_simg_bytes), img, tokens, B};
-    static const int tok_wg = getenv("ITA_TOK_WG_PER_CU") ? atoi(getenv("ITA_TOK_WG_PER_CU")) : 2;   // 35 KB of LDS, <= 128 registers: two workgroups per CU
-    const int g = B < tok_wg * c->num_cus ? B : tok_wg * c->num_cus;
-    if (c->hdr.E == 64) {
-      if (u8) hipLaunchKernelGGL((ita_tok_stream_kernel<64, true>), dim3(g), dim3(512), (ItaTokStreamLds<64, true>::TOTAL), s, ta);
-      else hipLaunchKernelGGL((ita_tok_stream_kernel<64, false>), dim3(g), dim3(512), (ItaTokStreamLds<64, false>::TOTAL), s, ta);
-    } else {
-      if (u8) hipLaunchKernelGGL((ita_tok_stream_kernel<128, true>), dim3(g), dim3(512), (ItaTokStreamLds<128, true>::TOTAL), s, ta);
-      else hipLaunchKernelGGL((ita_tok_stream_kernel<128, false>), dim3(g), dim3(512), (ItaTokStreamLds<128, false>::TOTAL), s, ta);
-    }
-    HIPCHK(hipGetLastError());
-    return ITA_OK;
-  }
-  if (u8) return fail(ITA_ERR_UNSUPPORTED, "u8 frames need the stream tokenizer image");
-  ItaTokArgs a{img, c->tok_wT, c->tok_b, c->tok_lw, c->tok_lb, tokens, B, tok_dbg};
-  const int grid = B < 2 * c->num_cus ? B : 2 * c->num_cus;
+  ItaTokStreamArgs ta{c->tok_simg + (u8 ? 0 : c->tok_simg_bytes), img, tokens, B};
+  const int g = B < 2 * c->num_cus ? B : 2 * c->num_cus;   // 35 KB of LDS, <= 128 registers: two workgroups per CU
   if (c->hdr.E == 64) {
-    if (u8) hipLaunchKernelGGL((ita_tokenizer_kernel<64, true>), dim3(grid), dim3(256), ita_tok_lds_bytes<64>(), s, a);
-    else hipLaunchKernelGGL((ita_tokenizer_kernel<64, false>), dim3(grid), dim3(256), ita_tok_lds_bytes<64>(), s, a);
+    if (u8) hipLaunchKernelGGL((ita_tok_stream_kernel<64, true>), dim3(g), dim3(512), (ItaTokStreamLds<64, true>::TOTAL), s, ta);
+    else hipLaunchKernelGGL((ita_tok_stream_kernel<64, false>), dim3(g), dim3(512), (ItaTokStreamLds<64, false>::TOTAL), s, ta);
   } else {
-    if (u8) hipLaunchKernelGGL((ita_tokenizer_kernel<128, true>), dim3(grid), dim3(256), ita_tok_lds_bytes<128>(), s, a);
-    else hipLaunchKernelGGL((ita_tokenizer_kernel<128, false>), dim3(grid), dim3(256), ita_tok_lds_bytes<128>(), s, a);
+    if (u8) hipLaunchKernelGGL((ita_tok_stream_kernel<128, true>), dim3(g), dim3(512), (ItaTokStreamLds<128, true>::TOTAL), s, ta);
+    else hipLaunchKernelGGL((ita_tok_stream_kernel<128, false>), dim3(g), dim3(512), (ItaTokStreamLds<128, false>::TOTAL), s, ta);
   }
   HIPCHK(hipGetLastError());
   return ITA_OK;
@@ -712,13 +686,10 @@ int launch_tail_big_w(const ItaTailBigArgs& a, hipStream_t s) {
 }
 // 16-row tiles on 8 waves with a whole chunk's weights resident when the map height allows (measured best:
 // 0.61 ms for 32 frames of BASELINE config 5); else 8-row tiles on 4 waves with a third of the chunk's taps
-// resident (70 KB of LDS, two workgroups per CU: 0.66 ms).  ITA_TAIL_BIG=2 / 3 force the 4-wave forms.
+// resident (70 KB of LDS, two workgroups per CU: 0.66 ms).
 template <int NT>
-int launch_tail_big(ita_context* c, const ItaTailBigArgs& a, hipStream_t s) {
-  (void)c;
-  static const int mode = getenv("ITA_TAIL_BIG") ? atoi(getenv("ITA_TAIL_BIG")) : 0;
-  if (mode == 2) return launch_tail_big_w<NT, 4, 9>(a, s);
-  if (mode == 3 || (2 * a.TH) % 16 != 0) return launch_tail_big_w<NT, 4, 3>(a, s);
+int launch_tail_big(const ItaTailBigArgs& a, hipStream_t s) {
+  if ((2 * a.TH) % 16 != 0) return launch_tail_big_w<NT, 4, 3>(a, s);
   return launch_tail_big_w<NT, 8, 9>(a, s);
 }
 
@@ -729,23 +700,17 @@ int launch_gemm_split(const _Float16* a_hi, const _Float16* a_lo, int lda, const
   if (N % BN || K % (64 * nsplit)) return fail(ITA_ERR_UNSUPPORTED, "split gemm shape");
   static const int dbg = getenv("ITA_GEMM_DBG") ? atoi(getenv("ITA_GEMM_DBG")) : 0;
   ItaGemmSplitArgs g{a_hi, a_lo, lda, w_hi, w_lo, ldw, out, M, N, K, nsplit, dbg, wf_hi, wf_lo};
-  static const int small_max = getenv("ITA_GEMM_SMALL_MAX") ? atoi(getenv("ITA_GEMM_SMALL_MAX")) : 256;
-  static const int tiny_max = getenv("ITA_GEMM_TINY_MAX") ? atoi(getenv("ITA_GEMM_TINY_MAX")) : 32;
-  if (M <= tiny_max && M <= 32 && N % 32 == 0 && wf_hi && wf_lo) {   // one M tile: one wave per 32 x 32 tile and K slice
+  if (M <= 32 && N % 32 == 0 && wf_hi && wf_lo) {   // one M tile: one wave per 32 x 32 tile and K slice
     hipLaunchKernelGGL(ita_gemm_f16x3_tiny_kernel, dim3(N / 32, 1, nsplit), dim3(64), 0, s, g);
     HIPCHK(hipGetLastError());
     return ITA_OK;
   }
-  if (M <= small_max && N % 32 == 0) {   // a few M tiles: four-wave workgroups share the staging, same arithmetic
+  if (M <= 256 && N % 32 == 0) {   // a few M tiles: four-wave workgroups share the staging, same arithmetic
     // M tiles per workgroup: up to four (128 frames: 128 workgroups).  Fewer tiles per workgroup fill the chip -- MT = ceil(M / 64)
     // gives 256 workgroups from 64 frames on and the kernel alone gets 1.4-2.9 us faster (64 / 128 frames, one stream) -- but in
     // the three-branch graph schedule that bench.py uses at these sizes a 256-workgroup GEMM leaves no CU to the LSTM branch
-    // and the step gets SLOWER (128 frames: 36.6 -> 38.3 us).  Per output element the arithmetic does not depend on MT;
-    // ITA_GEMM_SMALL_MT forces one (A/B runs, one-stream hosts).
-    static const int mt_env = getenv("ITA_GEMM_SMALL_MT") ? atoi(getenv("ITA_GEMM_SMALL_MT")) : 0;
-    int mt = mt_env >= 1 && mt_env <= 4 ? mt_env : (M >= 128 ? 4 : (M + 31) / 32);
-    if (mt > 4) mt = 4;
-    if (mt < 1) mt = 1;
+    // and the step gets SLOWER (128 frames: 36.6 -> 38.3 us).  Per output element the arithmetic does not depend on MT.
+    const int mt = M >= 128 ? 4 : (M + 31) / 32;
     const dim3 grid((N / 32) * nsplit, (M + 32 * mt - 1) / (32 * mt));
     switch (mt) {
       case 1: hipLaunchKernelGGL(ita_gemm_f16x3_small_kernel<1>, grid, dim3(256), ita_gemm_small_lds(1), s, g); break;
@@ -917,10 +882,6 @@ int ita_create(ita_handle* out, int device_ordinal) {
   if ((rc = set_lds(ita_tok_stream_kernel<128, true>, ItaTokStreamLds<128, true>::TOTAL))) { delete c; return rc; }
   if ((rc = set_lds(ita_tok_stream_kernel<64, false>, ItaTokStreamLds<64, false>::TOTAL))) { delete c; return rc; }
   if ((rc = set_lds(ita_tok_stream_kernel<128, false>, ItaTokStreamLds<128, false>::TOTAL))) { delete c; return rc; }
-  if ((rc = set_lds(ita_tokenizer_kernel<64, true>, ita_tok_lds_bytes<64>()))) { delete c; return rc; }
-  if ((rc = set_lds(ita_tokenizer_kernel<64, false>, ita_tok_lds_bytes<64>()))) { delete c; return rc; }
-  if ((rc = set_lds(ita_tokenizer_kernel<128, true>, ita_tok_lds_bytes<128>()))) { delete c; return rc; }
-  if ((rc = set_lds(ita_tokenizer_kernel<128, false>, ita_tok_lds_bytes<128>()))) { delete c; return rc; }
   if ((rc = set_lds(ita_tail_kernel<64>, ita_tail_lds_bytes<64>()))) { delete c; return rc; }
   if ((rc = set_lds(ita_tail_up_kernel, ItaTailUpLds::TOTAL))) { delete c; return rc; }
   if ((rc = set_lds(ita_long_proj_kernel<false>, ItaStreamLds<128, false, false>::TOTAL))) { delete c; return rc; }
@@ -1056,8 +1017,6 @@ int ita_load_weights(ita_handle h, const void* blob, size_t nbytes) {
 #undef NM
   }
   if (!ok) { free_weights(h); return fail(ITA_ERR_BAD_BLOB, "a required block tensor is missing or mis-sized"); }
-  h->tok_w = dptr<float>(h, "tok.conv_w", false, &ok); h->tok_b = dptr<float>(h, "tok.conv_b", false, &ok);
-  h->tok_lw = dptr<float>(h, "tok.ln_w", false, &ok); h->tok_lb = dptr<float>(h, "tok.ln_b", false, &ok);
   h->tail_b = dptr<float>(h, "tail.conv_b", false, &ok);
   h->dec_w = dptr<float>(h, "dec.w", false, &ok); h->dec_b = dptr<float>(h, "dec.b", false, &ok);
   h->fc_w = dptr<float>(h, "fc.w", false, &ok); h->fc_b = dptr<float>(h, "fc.b", false, &ok);
@@ -1092,14 +1051,6 @@ int ita_load_weights(ita_handle h, const void* blob, size_t nbytes) {
   }
   if (const float* cw = hptr<float>(h, "tok.conv_w")) {
     const int Ei = hdr.E;
-    std::vector<float> wT((size_t)100 * Ei, 0.0f);   // [0]: for f32 frames; [1]: x 1/65280 for u8 frames (integer blend)
-    for (int c = 0; c < Ei; ++c)
-      for (int k = 0; k < 49; ++k) {
-        wT[(size_t)k * Ei + c] = cw[(size_t)c * 49 + k];
-        wT[(size_t)(50 + k) * Ei + c] = cw[(size_t)c * 49 + k] * (1.0f / 65280.0f);
-      }
-    HIPCHK(hipMalloc(&h->tok_wT, wT.size() * sizeof(float)));
-    HIPCHK(hipMemcpy(h->tok_wT, wT.data(), wT.size() * sizeof(float), hipMemcpyHostToDevice));
     const float *cb = hptr<float>(h, "tok.conv_b"), *lw = hptr<float>(h, "tok.ln_w"), *lb = hptr<float>(h, "tok.ln_b");
     if (cb && lw && lb && (Ei == 64 || Ei == 128)) {   // the LDS images of ita_tok_stream_kernel<E, U8>
       // [0]: u8 frames (integer conv tables), [1]: f32 frames (f32 MFMA A fragments); each padded to the larger of the two
@@ -1478,11 +1429,10 @@ int ita_fusion_tail_large(ita_handle h, const float* x, float* out, int batch, i
   ItaTailBigArgs a{x, h->tl_hi, h->tl_lo, h->tl_bias, h->tl_inv_scale, out, batch, h->tl_E, tok_h, tok_w, h->tl_CO, h->tl_nchunk, 0};
   hipStream_t s = (hipStream_t)stream;
   // E = 128: the upsampled channels (4/5 of the contraction) by linearity on the low-resolution tokens (ita_tail_up_kernel),
-  // the pixel-shuffle channels (= chunk 0 of the implicit GEMM) added by ita_tail_big_kernel.  Needs whole 16 x 32 tiles and
+  // the pixel-shuffle channels (= chunk 0 of the implicit GEMM) in phase 2 of the same kernel.  Needs whole 16 x 32 tiles and
   // every tile's source region inside 10 x 18 tokens (same float expressions as the kernel; true for every x2 grid tried,
-  // checked instead of assumed).  ITA_TAIL_UP=0: the round-2 single-kernel path.
-  static const bool up_off = getenv("ITA_TAIL_UP") && atoi(getenv("ITA_TAIL_UP")) == 0;
-  if (h->tu_hi && !up_off && (2 * tok_h) % 16 == 0 && (2 * tok_w) % 32 == 0) {
+  // checked instead of assumed).  Every other shape runs on ita_tail_big_kernel.
+  if (h->tu_hi && (2 * tok_h) % 16 == 0 && (2 * tok_w) % 32 == 0) {
     const int OH = 2 * tok_h, OW = 2 * tok_w;
     auto span_ok = [](int T, int O, int tile, int lim) {
       const float sc = (float)(T - 1) / (float)(O - 1);
@@ -1505,10 +1455,10 @@ int ita_fusion_tail_large(ita_handle h, const float* x, float* out, int batch, i
     }
   }
   switch (h->tl_nt) {
-    case 1: return launch_tail_big<1>(h, a, s);
-    case 2: return launch_tail_big<2>(h, a, s);
-    case 3: return launch_tail_big<3>(h, a, s);
-    default: return launch_tail_big<4>(h, a, s);
+    case 1: return launch_tail_big<1>(a, s);
+    case 2: return launch_tail_big<2>(a, s);
+    case 3: return launch_tail_big<3>(a, s);
+    default: return launch_tail_big<4>(a, s);
   }
 }
 

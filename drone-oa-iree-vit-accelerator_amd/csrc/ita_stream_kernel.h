@@ -61,24 +61,7 @@ struct ItaStreamArgs {
 };
 enum { ITA_SITE_Q = 1, ITA_SITE_K = 2, ITA_SITE_V = 4, ITA_SITE_L = 8, ITA_SITE_C = 16, ITA_SITE_O = 32, ITA_SITES_ALL = 63 };
 
-#ifdef ITA_NO_SCHEDBAR
-#define ITA_SCHED_BARRIER() do {} while (0)
-#else
 #define ITA_SCHED_BARRIER() __builtin_amdgcn_sched_barrier(0)
-#endif
-// Where the four conv tiles of the NEXT frame's tokenizer run inside a frame (each: six int8 MFMAs + 24 VALU + 8 LDS reads):
-//   0 (default) after LayerNorm2 and the output stores, where the kernel has registers to spare;
-//   1 spread over the out_proj / fc1 steps (needs ~20 more live registers at the kernel's tightest point: 7 spilled);
-//   2 all four right after the blend, in front of out_proj.
-// Measured on one box, encoder launch of 1024 frames: round-2 kernel 58.4 us, placement 0 with the blend at the end too
-// (ITA_TOK_BLEND_END, default) 52.1, placement 0 with the blend after B2 52.5, placement 2 52.9, placement 1 (another box) +1.5.
-#ifndef ITA_TOK_PLACE
-#define ITA_TOK_PLACE 0
-#endif
-#define ITA_TOK_MID (ITA_TOK_PLACE == 1)
-#ifndef ITA_TOK_BLEND_END   // placement 0 only: blend the taps at the end of the frame too (nothing of the tokenizer is then live across the FFN: 244 VGPRs)
-#define ITA_TOK_BLEND_END 1
-#endif
 
 // ---- the conv7x7 of the u8 tokenizer as int8 MFMA (oracle/ita_oracle.c: ita_oracle_tokenizer_u8).  The blended tap is the
 // exact integer B256 = 256 a1 + a0 <= 65280, the conv weight of a channel 23-bit fixed point Wq = 65536 w2 + 256 w1 + w0 with
@@ -219,7 +202,7 @@ __device__ __forceinline__ int max1632_i(int v) {
 
 // LayerNorm over E channels held E/4 per lane by the four lanes qi, qi+16, qi+32, qi+48, in the oracle's
 // summation order: the quarter sums p_kq sequentially over consecutive channels, combined (p0+p1)+(p2+p3)
-// -- layernorm_lanes<E, 4> (ita_device.h) with the lane exchange 16 / 32 apart instead of 1 / 2.
+// -- layernorm_lanes<E> (ita_device.h) with the lane exchange 16 / 32 apart instead of 1 / 2.
 template <int E>
 __device__ __forceinline__ void layernorm_q16(float (&r)[E / 4], const float* w, const float* b, int c0) {
   constexpr int EC = E / 4;
@@ -370,19 +353,13 @@ __device__ __forceinline__ void mm_group(const ItaFr<4 * NKS>& f, const i32x4 (&
 }
 // requantise four tiles and pack them: ONE B fragment of the next GEMM (byte 4t+i <-> row 4kq+i of tile t).
 // fast (wave-uniform): this site's multiplier passed the load-time single-rounding proof (ita_device.h: rq_pack16_v3);
-// RELU: fc1, clamp to [0, 127].  -DITA_RQ_STYLE=2 keeps the round-2 form (float clamp, 3.0 instructions per value).
+// RELU: fc1, clamp to [0, 127].
 template <bool RELU = false>
 __device__ __forceinline__ i32x4 rq_group(const i32x4 (&acc)[4], float mult, bool fast) {
   if constexpr (ITA_ABLATE & 1) return acc[0] ^ acc[1] ^ acc[2] ^ acc[3];
-#if defined(ITA_RQ_STYLE) && ITA_RQ_STYLE == 1
-  return rq_pack16_c(acc, mult, RELU ? 0.0f : -128.0f);
-#elif defined(ITA_RQ_STYLE) && ITA_RQ_STYLE == 2
-  return rq_pack16_b(acc, mult, RELU ? 0.0f : -128.0f);
-#else
   if constexpr (RELU) return rq_pack16_v3<ITA_RQ_RELU>(acc, mult);
   if (fast) return rq_pack16_v3<ITA_RQ_FAST>(acc, mult);
   return rq_pack16_v3<ITA_RQ_EXACT>(acc, mult);
-#endif
 }
 // block output: d[4t+i] = dequantised int8 code of channel (E/4)kq + 4(et0+t) + i
 __device__ __forceinline__ void dq_group(const i32x4 (&acc)[4], float mult, float scale, float (&d)[16]) {
@@ -391,11 +368,7 @@ __device__ __forceinline__ void dq_group(const i32x4 (&acc)[4], float mult, floa
     for (int i = 0; i < 16; ++i) d[i] = __int_as_float(acc[i >> 2][i & 3]);
     return;
   }
-#if defined(ITA_RQ_STYLE) && ITA_RQ_STYLE == 1
-  dq16_c(acc, mult, scale, d);
-#else
   dq16_b(acc, mult, scale, d);
-#endif
 }
 
 // ---- f32 token rows in and out.  Lane (qi, kq) owns the quarter [E/4 kq, E/4 (kq+1)) of token qi's row.  Loaded or stored
@@ -485,9 +458,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
   // waves 4-7 were dispatched second and lose every VALU arbitration against their SIMD partner (MI355X guide,
   // "Two waves per SIMD", item 4): static priority evens the pair out
-#ifndef ITA_NO_SETPRIO
   if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
   int fi = 0;
 #define ITA_SSTAMP(ph)                                                                                  \
   do {                                                                                                  \
@@ -496,7 +467,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   } while (0)
 
   // ---- fused tokenizer (OverlapPatchMerging, reference models/ITA/QAT/layers.py:39-45; same arithmetic and
-  // operation order as ita_tokenizer_kernel).  Conv7x7/s2 and the bilinear 30x45 -> 8x16 resize are both linear,
+  // operation order as the oracle's ita_oracle_tokenizer_u8).  Conv7x7/s2 and the bilinear 30x45 -> 8x16 resize are both linear,
   // so the 7x7 patch is blended first and convolved once per token.  Wave w = token row w needs image rows
   // 2*y0-3 .. 2*y0+5 only (y0 = source row of the resize), a private 9 x 96 byte window with a zero border:
   //   fetch  : five dwords per lane of the next frame (issued a phase early, consumed by fill)
@@ -593,9 +564,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // diagnostic: s_memrealtime (100 MHz, one clock for the whole chip) at kernel entry [12], prologue end [13], exit [14]
   if (STAMP && a.stamps && (tid & 255) == 0)
     a.stamps[(((size_t)blockIdx.x * 8) * 2 + (wave >> 2)) * 16 + 12] = __builtin_amdgcn_s_memrealtime();
-  // ---- once per workgroup.  Order matters (it is 10+ % of a 4-frame launch): the first frame's pixels are requested
-  // first, then the tokenizer's tables (the tail of the image), then the 84 KB of weights -- which stay in flight, in
-  // registers, while the first frame is tokenized, and only then go to LDS.
+  // ---- once per workgroup.  Order matters (it is 10+ % of a 4-frame launch): with the fused tokenizer the first frame's
+  // pixels are requested after the image (see below).
   float xr[EC];
   i32x4 xq_cur[NK];       // IO8: this lane's k-slots of the block input, as they stand in memory
   f32x4 h0_cur = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -603,16 +573,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   {
     int ol = lane;
     asm volatile("" : "+v"(ol));
-#ifndef ITA_PROLOGUE_ORDER
-#define ITA_PROLOGUE_ORDER 1     // 1: weights before pixels (round 3); 0: the round-2 order, pixels first
-#endif
-    if constexpr (TOK != 0) {
-      if (ITA_PROLOGUE_ORDER == 0) tok_fetch(blockIdx.x, ol);
-    } else if constexpr (IO8) {
+    if constexpr (IO8) {
       const int8_t* xrow = a.xq + ((size_t)blockIdx.x * S + wave * 16 + (ol & 15)) * E + EC * (ol >> 4);
 #pragma unroll
       for (int c = 0; c < NK; ++c) xq_cur[c] = *(const i32x4*)(xrow + 16 * c);
-    } else {
+    } else if constexpr (TOK == 0) {
       ld_tok_items<E>(a.x + ((size_t)blockIdx.x * S + wave * 16 + (ol & 15)) * E, ol >> 4, xr);   // transposed where it is first used
     }
     if (a.h0_dst && tid < 32) {
@@ -637,39 +602,27 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     // Loads return in order.  The image (tables, weights) is L2-resident after the first workgroups, the first frame's pixels come
     // from HBM: requested LAST, the 100 KB of the image reach LDS while the pixels are still on their way, and the tokenizer of the
-    // first frame is the only thing left between their arrival and the frame loop (the round-2 order -- pixels first, weights
-    // parked in registers until the tokenizer was done -- put the weights' LDS stores behind it)
-    if constexpr (TOK != 0) {
-      if (ITA_PROLOGUE_ORDER != 0) tok_fetch(blockIdx.x, ol);
-    }
+    // first frame is the only thing left between their arrival and the frame loop (pixels first, with the weights parked in
+    // registers until the tokenizer was done, put the weights' LDS stores behind it)
+    if constexpr (TOK != 0) tok_fetch(blockIdx.x, ol);
     if (tid < 2 * P) colsum[tid] = ITA_ACC_BIAS;
 #pragma unroll
     for (int j = 0; j < NTJ; ++j) {
       const int p = tid + 512 * j;
       if (p < NT) *(i32x4*)(lds + (T0 + p) * 16) = vt[j];
     }
-    if constexpr (TOK != 0 && ITA_PROLOGUE_ORDER != 0) {
 #pragma unroll
-      for (int j = 0; j < NWJ; ++j) {
-        const int p = tid + 512 * j;
-        if (p < NW) *(i32x4*)(lds + p * 16) = vw[j];
-      }
+    for (int j = 0; j < NWJ; ++j) {
+      const int p = tid + 512 * j;
+      if (p < NW) *(i32x4*)(lds + p * 16) = vw[j];
     }
+    if constexpr (TOK != 0) tok_fill(ol);
+    lds_barrier();   // tables, weights, biases and column-sum bases in place
     if constexpr (TOK != 0) {
-      tok_fill(ol);
-      lds_barrier();   // tables (and, in the round-3 order, weights) in place
       tok_blend(ol);
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) tok_step(ct, ol);
       tok_finish(blockIdx.x, true, xr, ol);
-    }
-    if constexpr (!(TOK != 0 && ITA_PROLOGUE_ORDER != 0)) {
-#pragma unroll
-      for (int j = 0; j < NWJ; ++j) {
-        const int p = tid + 512 * j;
-        if (p < NW) *(i32x4*)(lds + p * 16) = vw[j];
-      }
-      lds_barrier();   // weights, biases and column-sum bases in place
     }
     if constexpr (TOK == 0 && !IO8) tok_items_transpose<E>(xr);   // the first frame's rows were fetched as items (ld_tok_items)
   }
@@ -856,13 +809,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       mm_ks(ob[0], cf[0], oa);
       cf[2] = rq_group(va[2], a.mc, fc);
     }
-    if constexpr (TOK != 0 && !(ITA_ABLATE & 4) && !(ITA_TOK_PLACE == 0 && ITA_TOK_BLEND_END)) { if (more) tok_blend(ol); }
-    if constexpr (TOK != 0 && ITA_TOK_PLACE == 2 && !(ITA_ABLATE & 4)) {
-      if (more) {
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) tok_step(ct, ol);
-      }
-    }
 
     // ---------------- out_proj + residual + LayerNorm1 (k-step 0 of the first group is already in flight)
     const char* w1p = lds + L::W1;   // fc1 / fc2 weights: LDS image, or (E = 128) the global image behind it
@@ -883,7 +829,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         mm_ks(ob[cur], cf[ks], oa);
         ITA_SCHED_BARRIER();   // keep the step's loads ahead of the next step's MFMAs
       }
-      if constexpr (TOK != 0 && ITA_TOK_MID && !(ITA_ABLATE & 4)) { if (more) tok_step(0, ol); }
       if constexpr (IO8) {   // the int8 codes themselves: 16 channels of this lane's token, one 16-byte store
         *(i32x4*)(a.yq + ((size_t)b * S + token) * E + EC * kq + 16 * eg) = rq_group(oa, a.mo, fo);
         if (eg + 1 < EG) ld_obias<E>(oa, l_bo, 4 * (eg + 1), kq);
@@ -928,7 +873,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         if (g >= 1) ld_frg_ks<E>(wb[(g - 1) & 1], w2p, 0, g - 1, qi, kq);
         mm_group<NK, false>(ffr[g & 1], x1f, fa[g % 3]);
         if (g >= 2) mm_ks(wb[(g - 2) & 1], hf[g - 2], ya);
-        if constexpr (TOK != 0 && ITA_TOK_MID && !(ITA_ABLATE & 4)) { if (g < 3 && more) tok_step(1 + g, ol); }
         if (g >= 1) hf[g - 1] = rq_group<true>(fa[(g - 1) % 3], a.m1, false);
         ITA_SCHED_BARRIER();   // keep the step's loads ahead of the next step's MFMAs
       }
@@ -988,16 +932,18 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
     }
     ITA_SSTAMP(11);
-    // ---------------- the next frame's tokens
+    // ---------------- the next frame's tokens: blend and the four conv tiles (each: six int8 MFMAs + 24 VALU + 8 LDS reads) here,
+    // after LayerNorm2 and the output stores, where the kernel has registers to spare -- nothing of the tokenizer is live across
+    // the FFN (244 VGPRs).  Measured on one box, encoder launch of 1024 frames: round-2 kernel 58.4 us, this placement 52.1; the
+    // blend after B2 52.5, the four tiles right after the blend in front of out_proj 52.9, the tiles spread over the out_proj /
+    // fc1 steps +1.5 (~20 more live registers at the kernel's tightest point: 7 spilled).  Those placements were removed.
     if constexpr (TOK != 0 && !(ITA_ABLATE & 4)) {
-      if constexpr (ITA_TOK_PLACE == 0) {
-        if constexpr (ITA_TOK_BLEND_END) { if (more) tok_blend(ol); }   // (the window written after B2 is still in LDS: private to this wave)
-        if (more) {
+      if (more) {
+        tok_blend(ol);   // (the window written after B2 is still in LDS: private to this wave)
 #pragma unroll
-          for (int ct = 0; ct < 4; ++ct) tok_step(ct, ol);
-        }
+        for (int ct = 0; ct < 4; ++ct) tok_step(ct, ol);
+        tok_finish(nb, true, xr, ol);
       }
-      if (more) tok_finish(nb, true, xr, ol);
     } else {
       tok_items_transpose<E>(xn);
 #pragma unroll
@@ -1026,7 +972,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 //         oracle: ita_oracle_tokenizer_u8) -- the fused tokenizer's functions, bit-identical to it;
 //   !U8 : the oracle's float blend  h0 (w0 a + w1 b) + h1 (w0 c + w1 d)  of pixels already scaled by the caller
 //         (ita_oracle_tokenizer), conv weights as they are, v_mfma_f32_16x16x4_f32; same results as
-//         ita_tokenizer_kernel<E, false> bit for bit (same operation order), at a fraction of its time.
+//         ita_oracle_tokenizer bit for bit (same operation order).
 template <int E, bool U8>
 struct ItaTokStreamLds {
   static constexpr int NCT = E / 16;                           // 16-channel output tiles

@@ -372,6 +372,19 @@ def test_error_codes_on_gpu(torch_cuda):
     # a block-only blob cannot run the whole graph
     assert lib.ita_vitlstm_forward(h, x.data_ptr(), 0, x.data_ptr(), x.data_ptr(), x.data_ptr(), x.data_ptr(),
                                    x.data_ptr(), x.data_ptr(), x.data_ptr(), 1, None, None) == -2
+    # the tokenizer's conv weights without its LayerNorm: a valid blob, but no tokenizer, whatever the frame dtype
+    rec = params.load_fixture(FIX_VIT[0])
+    t = dict(params.attention_tensors(rec, "attn0.", 0))
+    t.update(params.ffn_tensors(rec, "ffn0.", 0))
+    t.update({k: v for k, v in params.float_tensors(synth.float_params(0, E=64)).items() if k not in ("tok.ln_w", "tok.ln_b")})
+    assert "tok.conv_w" in t
+    blob = params.pack_blob(t, E=64)
+    buf = ctypes.create_string_buffer(blob, len(blob))
+    assert lib.ita_load_weights(h, buf, len(blob)) == 0
+    img_u8 = torch_cuda.zeros((1, 60, 90), dtype=torch_cuda.uint8, device="cuda")
+    img_f32 = torch_cuda.zeros((1, 60, 90), device="cuda")
+    assert lib.ita_tokenizer(h, img_u8.data_ptr(), host.IMAGE_U8, x.data_ptr(), 1, None) == -2
+    assert lib.ita_tokenizer(h, img_f32.data_ptr(), host.IMAGE_F32, x.data_ptr(), 1, None) == -2
     assert lib.ita_destroy(h) == 0
 
 

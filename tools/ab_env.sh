@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B on one GPU box of library builds AND environment switches, alternated for ROUNDS rounds:
 #   tools/ab_env.sh "tag[:VAR=value[,VAR=value...]]" ...      tag "base" = the current libita_mi355x.so, others = libita_mi355x_<tag>.so
-# e.g. tools/ab_env.sh base base:ITA_FAST_SITES=0 r2        Prints frames/s, ms/step, encoder launch ms per run.
+# e.g. tools/ab_env.sh base base:ITA_SPLIT_TOKENIZER=1 r2        Prints frames/s, ms/step, encoder launch ms per run.
 cd "$(dirname "$0")/.."
 D=drone-oa-iree-vit-accelerator_amd/csrc
 cp $D/libita_mi355x.so $D/libita_mi355x_base.so

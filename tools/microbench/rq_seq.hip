@@ -1,6 +1,7 @@
 // Cycles per requantisation of sixteen accumulators (one rq_group call of the encoder kernel), by form, with 1 / 2 waves per
-// SIMD, nothing else in the loop: round-2 float clamp (rq_pack16_b), round-3 exact (rq_pack16_v3<EXACT>), single rounding
-// (<FAST>), ReLU (<RELU>), and the logits forms.  hipcc --offload-arch=gfx950 -O3 -I ../../drone-oa-iree-vit-accelerator_amd/csrc rq_seq.hip
+// SIMD, nothing else in the loop: round-3 exact (rq_pack16_v3<EXACT>), single rounding (<FAST>), ReLU (<RELU>), and the logits
+// forms.  (The round-2 float-clamp forms, OP 0 and 4, were removed; their results are in profiles/r03_rq_seq_microbench.txt.)
+// hipcc --offload-arch=gfx950 -O3 -I ../../drone-oa-iree-vit-accelerator_amd/csrc rq_seq.hip
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
@@ -17,11 +18,9 @@ __global__ void k(unsigned long long* out, int* sink, int iters, float mult) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       i32x4 p;
-      if constexpr (OP == 0) p = rq_pack16_b(acc, mult, -128.0f);
       if constexpr (OP == 1) p = rq_pack16_v3<ITA_RQ_EXACT>(acc, mult);
       if constexpr (OP == 2) p = rq_pack16_v3<ITA_RQ_FAST>(acc, mult);
       if constexpr (OP == 3) p = rq_pack16_v3<ITA_RQ_RELU>(acc, mult);
-      if constexpr (OP == 4) { unsigned b[8]; i32x4 a2[2] = {acc[0], acc[1]}; lg8_b(a2, mult, b); p = (i32x4){(int)(b[0] ^ b[1]), (int)(b[2] ^ b[3]), (int)(b[4] ^ b[5]), (int)(b[6] ^ b[7])}; }
       if constexpr (OP == 5) { unsigned w[4]; i32x4 a2[2] = {acc[0], acc[1]}; lg8_v3<ITA_RQ_EXACT>(a2, mult, w); p = (i32x4){(int)w[0], (int)w[1], (int)w[2], (int)w[3]}; }
       if constexpr (OP == 6) { unsigned w[4]; i32x4 a2[2] = {acc[0], acc[1]}; lg8_v3<ITA_RQ_FAST>(a2, mult, w); p = (i32x4){(int)w[0], (int)w[1], (int)w[2], (int)w[3]}; }
       r ^= p;
@@ -56,11 +55,9 @@ void run(const char* name) {
   (void)hipFree(d); (void)hipFree(sink);
 }
 int main() {
-  run<0>("round 2: float clamp, 16 values");
   run<1>("round 3 exact, 16 values");
   run<2>("round 3 fast, 16 values");
   run<3>("round 3 relu, 16 values");
-  run<4>("logits round 2, 8 values");
   run<5>("logits round 3 exact, 8 values");
   run<6>("logits round 3 fast, 8 values");
   return 0;

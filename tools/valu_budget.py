@@ -4,7 +4,7 @@ Compiles csrc/ita_plugin.hip to assembly, takes ita_stream_kernel<64, true, 1> f
 function (the loop body; inline-asm requantisation blocks are expanded in the assembly) and groups the opcodes.
 Counts are per WAVE and frame; a frame is 8 waves.  usage: python tools/valu_budget.py [extra hipcc flags]
 The single-rounding permission of the requantisation sites is a template argument: the default counts the FAST instantiation
-(all six sites of the layer proven at load time), --exact the other one; -DITA_RQ_STYLE=2 is the round-2 form."""
+(all six sites of the layer proven at load time), --exact the other one; -DITA_FORCE_SITES=<mask> fixes the form per site."""
 import collections, os, re, subprocess, sys, tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
