@@ -25,6 +25,8 @@
 #include "ita_long_attn_kernel.h"
 #include "ita_ffn_f32_kernel.h"
 #include "ita_attn_f32_kernel.h"
+#include "ita_ffn_f32_e128_kernel.h"
+#include "ita_attn_f32_e128_kernel.h"
 
 namespace {
 
@@ -58,6 +60,7 @@ struct Layer {
   // float32 FFN of an ITAW0002 blob (the attention-only graph), device pointers; the int8 FFN fields are then null
   bool ffn_f32 = false;
   const float *w1f = nullptr, *b1f = nullptr, *w2f = nullptr, *b2f = nullptr;
+  float *w1p = nullptr, *w2p = nullptr;   // E = 128: B-fragment images of W1 / W2 (ita_ffn_f32_frag_image), owned
   // float32 attention of an ITAW0003 blob (the float graph), device pointers; the int8 attention fields are then null
   bool attn_f32 = false;
   const float *wqf = nullptr, *wkf = nullptr, *wvf = nullptr, *bqf = nullptr, *bkf = nullptr, *bvf = nullptr,
@@ -155,6 +158,11 @@ void free_weights(ita_context* c) {
   for (Layer& L : c->layers) {
     char** im[] = {&L.simg_enc, &L.simg_tok, &L.simg_mha};
     for (char** q : im) {
+      if (*q) (void)hipFree(*q);
+      *q = nullptr;
+    }
+    float** fim[] = {&L.w1p, &L.w2p};
+    for (float** q : fim) {
       if (*q) (void)hipFree(*q);
       *q = nullptr;
     }
@@ -309,15 +317,22 @@ int launch_ffn_f32(ita_context* c, int layer, const float* x, float* y, int B, b
                    const int* slots = nullptr) {
   const Layer& L = c->layers[layer];
   if (!L.ffn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's FFN is int8 (ITAW0001 blob): ita_ffn_int8 runs it");
-  if (c->hdr.E != 64) return fail(ITA_ERR_UNSUPPORTED, "the float32 FFN is built for E = 64");
+  if (c->hdr.E != 64 && !L.w1p) return fail(ITA_ERR_UNSUPPORTED, "the float32 FFN of an ITAW0002 blob is built for E = 64");
   if (fuse && !L.n2w) return fail(ITA_ERR_BAD_BLOB, "norm2 parameters missing from the blob");
   ItaFfnF32Args a{};
   a.x = x; a.y = y; a.w1 = L.w1f; a.b1 = L.b1f; a.w2 = L.w2f; a.b2 = L.b2f; a.ln_w = L.n2w; a.ln_b = L.n2b;
   a.B = B; a.fuse_ln = fuse ? 1 : 0;
   a.y_hi = y_hi; a.y_lo = y_lo; a.ld_planes = c->ldfold;
   a.h0_src = h0_src; a.h0_dst = h0_dst; a.slots = slots;
-  const int ntile = B * (128 / ItaFfnF32Lds::TT), cap = 2 * c->num_cus;
-  hipLaunchKernelGGL(ita_ffn_f32_kernel, dim3(ntile < cap ? ntile : cap), dim3(256), ItaFfnF32Lds::TOTAL, s, a);
+  const int cap = 2 * c->num_cus;
+  if (c->hdr.E == 64) {
+    const int ntile = B * (128 / ItaFfnF32Lds::TT);
+    hipLaunchKernelGGL(ita_ffn_f32_kernel, dim3(ntile < cap ? ntile : cap), dim3(256), ItaFfnF32Lds::TOTAL, s, a);
+  } else {   // E = 128: the weights stream as fragment images (66 KB of LDS: two workgroups per CU)
+    a.w1 = L.w1p; a.w2 = L.w2p;
+    const int ntile = B * (128 / ItaFfnF32E128Lds::TT);
+    hipLaunchKernelGGL(ita_ffn_f32_e128_kernel, dim3(ntile < cap ? ntile : cap), dim3(256), ItaFfnF32E128Lds::TOTAL, s, a);
+  }
   HIPCHK(hipGetLastError());
   return ITA_OK;
 }
@@ -326,14 +341,16 @@ int launch_ffn_f32(ita_context* c, int layer, const float* x, float* y, int B, b
 int launch_attn_f32(ita_context* c, int layer, const float* x, float* y, int B, bool fuse, hipStream_t s) {
   const Layer& L = c->layers[layer];
   if (!L.attn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's attention is int8 (ITAW0001 / ITAW0002 blob): ita_mha_int8 runs it");
-  if (c->hdr.E != 64) return fail(ITA_ERR_UNSUPPORTED, "the float32 attention is built for E = 64");
   if (fuse && !L.n1w) return fail(ITA_ERR_BAD_BLOB, "norm1 parameters missing from the blob");
   ItaAttnF32Args a{};
   a.x = x; a.y = y;
   a.wq = L.wqf; a.wk = L.wkf; a.wv = L.wvf; a.bq = L.bqf; a.bk = L.bkf; a.bv = L.bvf; a.wo = L.wof; a.bo = L.bof;
   a.ln_w = L.n1w; a.ln_b = L.n1b; a.B = B; a.fuse_ln = fuse ? 1 : 0;
-  // 130 KB of LDS: one workgroup per CU, frames in a grid stride
-  hipLaunchKernelGGL(ita_attn_f32_kernel, dim3(B < c->num_cus ? B : c->num_cus), dim3(512), ItaAttnF32Lds::TOTAL, s, a);
+  // 130 KB (E = 64) / 96 KB (E = 128) of LDS: one workgroup per CU, frames in a grid stride
+  if (c->hdr.E == 64)
+    hipLaunchKernelGGL(ita_attn_f32_kernel, dim3(B < c->num_cus ? B : c->num_cus), dim3(512), ItaAttnF32Lds::TOTAL, s, a);
+  else
+    hipLaunchKernelGGL(ita_attn_f32_e128_kernel, dim3(B < c->num_cus ? B : c->num_cus), dim3(512), ItaAttnF32E128Lds::TOTAL, s, a);
   HIPCHK(hipGetLastError());
   return ITA_OK;
 }
@@ -591,7 +608,7 @@ int launch_encoder(ita_context* c, int layer, const float* x, float* y, _Float16
   if (!L.n1w || !L.n2w) return fail(ITA_ERR_BAD_BLOB, "LayerNorm parameters missing from the blob");
   if (L.ffn_f32) {
     if (img || stamps) return fail(ITA_ERR_UNSUPPORTED, "a float-FFN layer runs behind the stand-alone tokenizer, without stamps");
-    if (c->hdr.E != 64) return fail(ITA_ERR_UNSUPPORTED, "the float32 FFN is built for E = 64");
+    if (c->hdr.E != 64 && !L.w1p) return fail(ITA_ERR_UNSUPPORTED, "the float32 FFN of an ITAW0002 blob is built for E = 64");
     int rc = ensure_workspace(c, B, s);
     if (rc) return rc;
     if ((rc = L.attn_f32 ? launch_attn_f32(c, layer, x, c->bufB, B, true, s)
@@ -875,6 +892,8 @@ int ita_create(ita_handle* out, int device_ordinal) {
   int rc = ITA_OK;
   if ((rc = set_lds(ita_mha_kernel<64>, ItaMhaLds<64>::TOTAL))) { delete c; return rc; }
   if ((rc = set_lds(ita_attn_f32_kernel, ItaAttnF32Lds::TOTAL))) { delete c; return rc; }
+  if ((rc = set_lds(ita_attn_f32_e128_kernel, ItaAttnF32E128Lds::TOTAL))) { delete c; return rc; }
+  if ((rc = set_lds(ita_ffn_f32_e128_kernel, ItaFfnF32E128Lds::TOTAL))) { delete c; return rc; }
   if ((rc = set_lds(ita_mha_kernel<128>, ItaMhaLds<128>::TOTAL))) { delete c; return rc; }
   if ((rc = set_lds(ita_ffn_kernel<64>, ItaFfnLds<64>::TOTAL))) { delete c; return rc; }
   if ((rc = set_lds(ita_ffn_kernel<128>, ItaFfnLds<128>::TOTAL))) { delete c; return rc; }
@@ -952,8 +971,10 @@ int ita_load_weights(ita_handle h, const void* blob, size_t nbytes) {
   if ((hdr.E != 64 && hdr.E != 128) || hdr.S != 128 || hdr.P != 192 || hdr.F != 256 || hdr.H != 1 ||
       hdr.num_layers < 1 || hdr.num_layers > 16)
     return fail(ITA_ERR_UNSUPPORTED, "kernels are built for E in {64,128}, S=128, P=192, F=256, H=1");
-  if (attn_kind == 1 && hdr.E != 64) return fail(ITA_ERR_UNSUPPORTED, "the float32 attention (ITAW0003) is built for E = 64");
-  if (ffn_kind == 1 && hdr.E != 64) return fail(ITA_ERR_UNSUPPORTED, "the float32 FFN (ITAW0002) is built for E = 64");
+  // the float graph (ITAW0003) runs at E = 64 with its fusion tail, and at E = 128 without one (ITA_upsample_shuffle)
+  if (attn_kind == 1 && hdr.E != 64 && hdr.has_tail)
+    return fail(ITA_ERR_UNSUPPORTED, "the float32 graph's fusion tail (ITAW0003) is built for E = 64; at E = 128 it runs without one");
+  if (attn_kind == 0 && ffn_kind == 1 && hdr.E != 64) return fail(ITA_ERR_UNSUPPORTED, "the float32 FFN (ITAW0002) is built for E = 64");
   {
     const ita_blob_entry* e = (const ita_blob_entry*)((const char*)blob + sizeof(hdr));
     for (int i = 0; i < hdr.n_tensors; ++i)
@@ -1004,6 +1025,20 @@ int ita_load_weights(ita_handle h, const void* blob, size_t nbytes) {
       L.ffn_f32 = true;
       L.w1f = dptr<float>(h, NM("ffn%d.w1f"), true, &ok); L.b1f = dptr<float>(h, NM("ffn%d.b1f"), true, &ok);
       L.w2f = dptr<float>(h, NM("ffn%d.w2f"), true, &ok); L.b2f = dptr<float>(h, NM("ffn%d.b2f"), true, &ok);
+      const float *w1 = hptr<float>(h, NM("ffn%d.w1f")), *w2 = hptr<float>(h, NM("ffn%d.w2f"));
+      if (E == 128 && w1 && w2) {   // ita_ffn_f32_e128_kernel streams W1 / W2 as B-fragment images
+        std::vector<float> img(F * E);
+        float** dst[2] = {&L.w1p, &L.w2p};
+        for (int m = 0; m < 2; ++m) {
+          if (m == 0) ita_ffn_f32_frag_image(w1, (int)F, (int)E, img.data());
+          else ita_ffn_f32_frag_image(w2, (int)E, (int)F, img.data());
+          if (hipMalloc(dst[m], img.size() * sizeof(float)) != hipSuccess ||
+              hipMemcpy(*dst[m], img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+            free_weights(h);
+            return fail(ITA_ERR_HIP, "uploading the float32 FFN fragment images failed");
+          }
+        }
+      }
     } else {
       expect(NM("ffn%d.w1"), F * E); expect(NM("ffn%d.w2"), E * F); expect(NM("ffn%d.scal"), ITA_F_NSCAL * 4);
       L.w1 = dptr<int8_t>(h, NM("ffn%d.w1"), true, &ok); L.w2 = dptr<int8_t>(h, NM("ffn%d.w2"), true, &ok);

@@ -7,6 +7,8 @@ This is a restatement in torch functional ops of
     models/ITA/layers.py:29-45  ITAFeedForward       (fc1 -> ReLU -> fc2)
     models/ITA_single_layer_upsample_shuffle/model.py:88-140   ITALSTMNetVIT.forward (residual + LayerNorm glue,
                                 PixelShuffle || Upsample -> conv3x3, decoder, cat, 3-layer LSTM, fc)
+and, when decoder.weight is E * 128 wide, the graphs without the fusion tail, whose decoder reads the flattened tokens:
+    models/ITA_upsample_shuffle/model.py:86-113 (E = 128, two layers), models/ITA_single_layer/model.py:79-105 (E = 64)
 taking the parameters as a plain dict under the reference's state_dict names (spectral norm already folded:
 params.fold_spectral_norm).  It is NOT on the product path: bench.py times it on the host cores as the CPU baseline of
 record (kind "torch-f32-eager"), and tests/test_float_twin.py pins it against a fixture produced by the reference's own
@@ -64,12 +66,16 @@ class FloatTwin:
             tp = {"tokens": x}
             for i in range(self.L):
                 x = F.layer_norm(x + self._attention(x, i), (E,), p[f"norms1.{i}.weight"], p[f"norms1.{i}.bias"])
-                tp["x1"] = x
+                tp["x1"] = tp[f"x1_{i}"] = x
                 x = F.layer_norm(x + self._ffn(x, i), (E,), p[f"norms2.{i}.weight"], p[f"norms2.{i}.bias"])
+                tp[f"x2_{i}"] = x
             tp["x2"] = x
-            x2d = x.transpose(1, 2).reshape(B, E, 8, 16)
-            fused = torch.cat([F.pixel_shuffle(x2d, 2), F.interpolate(x2d, size=(16, 32), mode="bilinear", align_corners=True)], 1)
-            feat = F.conv2d(fused, p["down_sample.weight"], p["down_sample.bias"], padding=1).flatten(1)
+            if p["decoder.weight"].shape[1] == E * 128:   # no fusion tail: x.flatten(1), then the decoder
+                feat = x.flatten(1)
+            else:
+                x2d = x.transpose(1, 2).reshape(B, E, 8, 16)
+                fused = torch.cat([F.pixel_shuffle(x2d, 2), F.interpolate(x2d, size=(16, 32), mode="bilinear", align_corners=True)], 1)
+                feat = F.conv2d(fused, p["down_sample.weight"], p["down_sample.bias"], padding=1).flatten(1)
             dec = F.linear(feat, p["decoder.weight"], p["decoder.bias"])
             tp["dec"] = dec
             cat = torch.cat([dec, desvel / 10.0, quat], 1).unsqueeze(0)

@@ -245,14 +245,39 @@ def fold_spectral_norm(sd: dict, name: str):
     return (w / sigma).astype(np.float32)
 
 
+# The reference's model files name the same layers three ways.  models/ITA_single_layer_upsample_shuffle (and its QAT /
+# QAT_only_attn variants): attention_blocks.{i} / ffn_blocks.{i} / norms1.{i} / norms2.{i} -- the names used here.
+# models/ITA_upsample_shuffle (and models/ITA): norm1_layers.{i} / norm2_layers.{i}.  models/ITA_single_layer: one layer as
+# attention_block / ffn_block / norm1 / norm2.
+_LAYER_NAMES = (("norm1_layers.", "norms1."), ("norm2_layers.", "norms2."), ("attention_block.", "attention_blocks.0."),
+                ("ffn_block.", "ffn_blocks.0."), ("norm1.", "norms1.0."), ("norm2.", "norms2.0."))
+
+
+def canonical_state_dict(sd: dict) -> dict:
+    """sd with its layer names mapped to attention_blocks.{i} / ffn_blocks.{i} / norms1.{i} / norms2.{i}"""
+    def ren(k):
+        for a, b in _LAYER_NAMES:
+            if k.startswith(a):
+                return b + k[len(a):]
+        return k
+    return {ren(k): v for k, v in sd.items()}
+
+
 def float_params_from_state_dict(sd: dict, num_layers: int = 1) -> dict:
-    """non-quantised layers under the reference's state_dict names (float or converted checkpoint)"""
+    """non-quantised layers under the reference's state_dict names (float or converted checkpoint).  The decoder's
+    width decides the graph: 4608 reads the fusion tail (down_sample is carried); E * 128 reads the flattened tokens,
+    and a down_sample the model file declares but never calls is dropped."""
+    sd = canonical_state_dict(sd)
     g = lambda k: np.asarray(sd[k].detach().cpu().numpy(), np.float32)
     fp = {k: g(k) for k in ("tokenizer.conv.weight", "tokenizer.conv.bias", "tokenizer.norm.weight",
-                            "tokenizer.norm.bias", "down_sample.weight", "down_sample.bias", "decoder.bias",
-                            "nn_fc2.bias")}
+                            "tokenizer.norm.bias", "decoder.bias", "nn_fc2.bias")}
     fp["decoder.weight"] = fold_spectral_norm(sd, "decoder")
     fp["nn_fc2.weight"] = fold_spectral_norm(sd, "nn_fc2")
+    E, width = fp["tokenizer.conv.weight"].shape[0], fp["decoder.weight"].shape[1]
+    if width == 4608:
+        fp["down_sample.weight"], fp["down_sample.bias"] = g("down_sample.weight"), g("down_sample.bias")
+    elif width != E * 128:
+        raise ValueError(f"decoder reads {width} features: neither the fusion tail (4608) nor the tokens (E * 128 = {E * 128})")
     for i in range(num_layers):
         for nm in (f"norms1.{i}", f"norms2.{i}"):
             fp[nm + ".weight"], fp[nm + ".bias"] = g(nm + ".weight"), g(nm + ".bias")
@@ -271,7 +296,9 @@ def float_params_from_state_dict(sd: dict, num_layers: int = 1) -> dict:
 
 def blob_from_state_dict(sd: dict, num_layers: int = 1) -> bytes:
     """a converted (QAT) checkpoint -> ITAW0001 / ITAW0002; a float checkpoint (training's model_000205.pth: float
-    attention_blocks.{i}.q_proj.weight, no _packed_params) -> ITAW0003"""
+    attention_blocks.{i}.q_proj.weight, no _packed_params) -> ITAW0003.  Every model file's layer names are accepted
+    (canonical_state_dict)."""
+    sd = canonical_state_dict(sd)
     fp = float_params_from_state_dict(sd, num_layers)
     kinds = {_float_attn(sd, i) for i in range(num_layers)}
     if kinds == {True}:

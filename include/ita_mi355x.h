@@ -115,7 +115,7 @@ int ita_ffn_int8_taps(ita_handle h, int layer, const float* x_dev, float* y_dev,
 enum { ITA_FFN_INT8 = 0, ITA_FFN_F32 = 1 };
 int ita_get_ffn_kind(ita_handle h, int layer, int* kind);
 /* the float32 FFN of layer `layer` alone (no residual, no LayerNorm): y = fc2(relu(fc1(x) + b1)) + b2, (B,128,E) f32,
- * bit-identical to two ascending-k fmaf chains per output started from the bias (E = 64) */
+ * bit-identical to two ascending-k fmaf chains per output started from the bias (E = 64, and E = 128 for an ITAW0003 blob) */
 int ita_ffn_f32(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, void* stream);
 /* Attention kind of a loaded layer: ITA_ATTN_INT8 (ITAW0001 / ITAW0002 blob, ita_mha_int8) or ITA_ATTN_F32 (ITAW0003
  * blob: the float graph, models/ITA_single_layer_upsample_shuffle/model.py, nothing quantised).  ita_mha_int8 / _taps,
@@ -125,7 +125,8 @@ enum { ITA_ATTN_INT8 = 0, ITA_ATTN_F32 = 1 };
 int ita_get_attn_kind(ita_handle h, int layer, int* kind);
 /* the float32 attention block of layer `layer` alone (no residual, no LayerNorm), ITASelfAttention.forward
  * (models/ITA/layers.py:67-88): y = out_proj(softmax(Q K^T) V), Q / K / V = x W^T + b, one head, no 1/sqrt(d);
- * (B,128,E) f32, E = 64.  A frame's result does not depend on the batch it runs in. */
+ * (B,128,E) f32, E = 64 or 128 (the E = 128 float graph, models/ITA_upsample_shuffle/model.py, has no fusion tail).  A
+ * frame's result does not depend on the batch it runs in. */
 int ita_mha_f32(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, void* stream);
 /* One encoder layer as the model wires it (QAT/model.py:100-113):
  * y = LN2(x1 + ffn(x1)),  x1 = LN1(x + mha(x)).  x_dev and y_dev may alias.

@@ -18,6 +18,9 @@
  * "ITAW0003": the float ViT+LSTM graph (models/ITA_single_layer_upsample_shuffle/model.py, blocks of
  * models/ITA/layers.py), nothing quantised: the float32 FFN of ITAW0002 and, instead of the int8 attention tensors,
  * attn%d.wqf / wkf / wvf F32 [P][E], attn%d.bqf / bkf / bvf F32 [P], attn%d.wof F32 [E][P], attn%d.bof F32 [E].
+ * E = 64 with the fusion tail, or, with has_tail = 0 and dec.w F32 [512][E * 128], the graphs whose decoder reads the
+ * flattened tokens: E = 128 (models/ITA_upsample_shuffle/model.py) and E = 64 (models/ITA_single_layer/model.py).
+ * ita_load_weights refuses an E = 128 ITAW0003 blob with a fusion tail, and any E = 128 ITAW0002 blob.
  *
  * Layout (little endian):
  *   ita_blob_header | ita_blob_entry[n_tensors] | data (each tensor 64-byte aligned)

@@ -489,6 +489,65 @@ def gen_float_twin(seed, B, out_dir, num_layers=1):
     print("wrote", path, os.path.getsize(path) // 1024, "KiB")
 
 
+def gen_float_no_tail(seed, B, out_dir, E):
+    """The reference's float models WITHOUT the fusion tail, whose decoder reads the flattened tokens (x.flatten(1)):
+    E = 128: ITALSTMNetVIT of models/ITA_upsample_shuffle/model.py:31-113, two layers, decoder 16384 -> 512;
+    E = 64:  ITALSTMNetVIT_single_layer of models/ITA_single_layer/model.py:31-105, one layer, decoder 8192 -> 512.
+    Both declare up_sample / pxShuffle / down_sample and never call them; the synthetic parameters (tail=False) have no
+    down_sample, so the load is strict=False with only down_sample.* missing.  Their layer names differ from the
+    synthetic ones (norm1_layers.i / norm2_layers.i; attention_block / ffn_block / norm1 / norm2).  decoder and nn_fc2
+    are under spectral_norm, removed on the instance as in gen_float_twin.  Two time steps, state carried; taps tok.out,
+    x1_i / x2_i, dec.  Written as floatnt{L}l_E{E}_s{seed}_B{B}.npz (no existing fixture glob matches it)."""
+    if E == 128:
+        from models.ITA_upsample_shuffle.model import ITALSTMNetVIT as Net
+        num_layers = 2
+        ren = lambda k: k.replace("norms1.", "norm1_layers.").replace("norms2.", "norm2_layers.")
+    else:
+        from models.ITA_single_layer.model import ITALSTMNetVIT_single_layer as Net
+        num_layers = 1
+        ren = lambda k: (k.replace("attention_blocks.0.", "attention_block.").replace("ffn_blocks.0.", "ffn_block.")
+                         .replace("norms1.0.", "norm1.").replace("norms2.0.", "norm2."))
+    fp = synth.float_params(seed, E=E, num_layers=num_layers, tail=False)
+    model = Net()
+    for lin in (model.decoder, model.nn_fc2):
+        torch.nn.utils.remove_spectral_norm(lin)
+        lin._load_state_dict_pre_hooks.clear()
+    sd = model.state_dict()
+    for k, v in fp.items():
+        assert ren(k) in sd and tuple(sd[ren(k)].shape) == v.shape, k
+    res = model.load_state_dict({ren(k): torch.from_numpy(v) for k, v in fp.items()}, strict=False)
+    assert not res.unexpected_keys and res.missing_keys and all(k.startswith("down_sample.") for k in res.missing_keys), res
+    model.eval()
+    tap = Tap()
+    tap.add(model.tokenizer, "tok.out")
+    if E == 128:
+        for i in range(num_layers):
+            tap.add(model.norm1_layers[i], f"x1_{i}")
+            tap.add(model.norm2_layers[i], f"x2_{i}")
+    else:
+        tap.add(model.norm1, "x1_0")
+        tap.add(model.norm2, "x2_0")
+    tap.add(model.decoder, "dec")
+    fr0, fr1 = synth.frames(10 * seed + 7, B), synth.frames(10 * seed + 8, B)
+    with torch.no_grad():
+        vel0, (h0, c0) = model(to_X(fr0, None))
+        stage = dict(tap.t)
+        vel1, (h1, c1) = model(to_X(fr1, (h0, c0)))
+    rec = {"meta.seed": np.int64(seed), "meta.B": np.int64(B), "meta.E": np.int64(E), "meta.num_layers": np.int64(num_layers),
+           "meta.params_sha256": np.array(synth.digest(fp)), "meta.torch": np.array(torch.__version__)}
+    for k, v in fr0.items():
+        rec["in0." + k] = v
+    for k, v in fr1.items():
+        rec["in1." + k] = v
+    for k, v in stage.items():
+        rec["s0." + k] = v
+    rec["s0.vel"] = vel0.numpy(); rec["s0.h"] = h0.numpy(); rec["s0.c"] = c0.numpy()
+    rec["s1.vel"] = vel1.numpy(); rec["s1.h"] = h1.numpy(); rec["s1.c"] = c1.numpy()
+    path = os.path.join(out_dir, f"floatnt{num_layers}l_E{E}_s{seed}_B{B}.npz")
+    np.savez_compressed(path, **rec)
+    print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+
+
 def _only_attn_converted(seed, num_layers, calib_seed):
     """models/ITA_single_layer_upsample_shuffle/QAT_only_attn/model.py:25-106 (int8 attention, float32 FFN, residual and
     LayerNorm2) through the same QAT flow as gen_vitlstm, with the qconfig on attention_blocks ONLY: ffn_blocks stay
@@ -611,7 +670,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
     ap.add_argument("--only", default="", help="comma list of: softmax, vitlstm, blocks, tail_large, float_twin, vit2l, vit2l_us, vit1l, "
-                                               "checkpoint, only_attn, only_attn_checkpoint (default: all)")
+                                               "float_no_tail, checkpoint, only_attn, only_attn_checkpoint (default: all)")
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
     only = set(filter(None, a.only.split(",")))
@@ -626,6 +685,9 @@ def main():
         if "float_twin" in only:
             gen_float_twin(0, 2, a.out)
             gen_float_twin(1, 2, a.out, num_layers=2)
+        if "float_no_tail" in only:
+            gen_float_no_tail(1, 2, a.out, E=128)
+            gen_float_no_tail(2, 2, a.out, E=64)
         if "vit2l" in only: gen_vit2l(0, 2, a.out)
         if "vit2l_us" in only: gen_vit2l(1, 2, a.out, upsample_shuffle_file=True)
         if "vit1l" in only: gen_vit1l(0, 2, a.out)
@@ -637,6 +699,8 @@ def main():
         return
     gen_float_twin(0, 2, a.out)
     gen_float_twin(1, 2, a.out, num_layers=2)
+    gen_float_no_tail(1, 2, a.out, E=128)
+    gen_float_no_tail(2, 2, a.out, E=64)
     gen_vit2l(0, 2, a.out)
     gen_vit2l(1, 2, a.out, upsample_shuffle_file=True)
     gen_vit1l(0, 2, a.out)
