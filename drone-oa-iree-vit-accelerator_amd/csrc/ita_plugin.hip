@@ -103,6 +103,11 @@ struct ita_context {
   _Float16 *x2_hi = nullptr, *x2_lo = nullptr, *c1_hi = nullptr, *c1_lo = nullptr,
            *c2_hi = nullptr, *c2_lo = nullptr;
   float* part = nullptr;
+  // the LSTM head's meeting words (ita_lstm_head_kernel): [0] device error word, then one arrival counter per 32-frame
+  // tile every ITA_HEAD_CNT_STRIDE words; zeroed at allocation, re-armed in-kernel by each tile's last workgroup and by
+  // ita_head_status
+  unsigned* head_sync = nullptr;
+  size_t head_sync_bytes = 0;
   // workspace
   int cap = 0;
   bool ws_reserved = false;     // ita_reserve was called: the workspace is pinned (see ensure_workspace)
@@ -202,6 +207,9 @@ void free_workspace(ita_context* c) {
   }
   if (c->part) (void)hipFree(c->part);
   c->part = nullptr;
+  if (c->head_sync) (void)hipFree(c->head_sync);
+  c->head_sync = nullptr;
+  c->head_sync_bytes = 0;
   c->cap = 0;
   for (int& fc : c->front_cap) fc = 0;
 }
@@ -232,6 +240,10 @@ int ensure_workspace(ita_context* c, int B, hipStream_t s = nullptr) {
   HIPCHK(hipMalloc(&c->c2_hi, 2 * (size_t)((B + 31) / 32 * 32) * 256));   // fragment order, whole 32-frame tiles
   HIPCHK(hipMalloc(&c->c2_lo, 2 * (size_t)((B + 31) / 32 * 32) * 256));   // fragment order, whole 32-frame tiles
   HIPCHK(hipMalloc(&c->part, ITA_PART_BUFFERS * sizeof(float) * (size_t)NSPLIT * B * 512));   // ita_vitlstm_front/back
+  c->head_sync_bytes = sizeof(unsigned) * ITA_HEAD_CNT_STRIDE * ((size_t)1 + (B + 31) / 32);
+  HIPCHK(hipMalloc(&c->head_sync, c->head_sync_bytes));
+  HIPCHK(hipMemset(c->head_sync, 0, c->head_sync_bytes));
+  HIPCHK(hipDeviceSynchronize());
   c->cap = B;
   return ITA_OK;
 }
@@ -831,7 +843,7 @@ int build_fold(ita_context* c) {
   }
   (void)hipFree(imp); (void)hipFree(feat); (void)hipFree(mt); (void)hipFree(zero);
   if (rc) return rc;
-  // rows of the GEMM weight in the permuted gate order r' = ut*32 + gate*8 + u (ita_lstm0_kernel)
+  // rows of the GEMM weight in the permuted gate order r' = ut*32 + gate*8 + u (ita_lstm_head_kernel)
   std::vector<float> wf((size_t)512 * LDFOLD, 0.0f);
   for (int rp = 0; rp < 512; ++rp) {
     const int j = ((rp >> 3) & 3) * 128 + (rp >> 5) * 8 + (rp & 7);
@@ -1304,6 +1316,24 @@ int ita_ffn_f32(ita_handle h, int layer, const float* x, float* y, int batch, vo
   return launch_ffn_f32(h, layer, x, y, batch, false, (hipStream_t)stream);
 }
 
+static_assert(ITA_HEAD_ERR_TIMEOUT == ITA_HEAD_TIMEOUT, "one error code, two names");
+int ita_head_status(ita_handle h, int* status) {
+  int rc = check(h, 1, false);
+  if (rc) return rc;
+  if (!status) return fail(ITA_ERR_INVALID_ARG, "null pointer");
+  *status = 0;
+  if (!h->head_sync) return ITA_OK;
+  unsigned v = 0;
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(&v, h->head_sync, sizeof(v), hipMemcpyDeviceToHost));
+  if (v) {   // a timed-out workgroup left its tile's counter short: zero the error word and every counter
+    HIPCHK(hipMemset(h->head_sync, 0, h->head_sync_bytes));
+    HIPCHK(hipDeviceSynchronize());
+  }
+  *status = (int)v;
+  return ITA_OK;
+}
+
 int ita_get_attn_kind(ita_handle h, int layer, int* kind) {
   if (!h || !h->loaded) return fail(ITA_ERR_NO_WEIGHTS, "no weights loaded");
   if (!kind || layer < 0 || layer >= h->hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
@@ -1497,6 +1527,21 @@ int ita_fusion_tail_large(ita_handle h, const float* x, float* out, int batch, i
   }
 }
 
+// the LSTM head behind the folded GEMM: layers 0, 1, 2 and the fc in one launch (ita_lstm_head_kernel), reading the
+// GEMM's split-K partials `part`.  State rows are slots[b] (else b) of (3, rows, 128) arrays with layer stride lstride;
+// h_out / c_out may alias h_in / c_in.
+static int launch_lstm_head(ita_context* h, const float* part, const float* desvel, const float* quat, const float* h_in,
+                            const float* c_in, float* h_out, float* c_out, size_t lstride, float* vel, int B,
+                            const int* slots, hipStream_t s) {
+  ItaLstmHeadArgs p{part, h->fold_inv_scale, h->lw_hi[0], h->lw_lo[0], h->lw_inv_scale[0], h->fold_bias,
+                    h->lw_hi[1], h->lw_lo[1], h->lw_hi[2], h->lw_lo[2], h->lw_inv_scale[1], h->lw_inv_scale[2],
+                    h->bsum[1], h->bsum[2], desvel, quat, h_in, c_in, h_out, c_out, lstride,
+                    h->c1_hi, h->c1_lo, h->c2_hi, h->c2_lo, h->fc_w, h->fc_b, vel, h->head_sync + ITA_HEAD_CNT_STRIDE, h->head_sync, B, slots};
+  hipLaunchKernelGGL(ita_lstm_head_kernel<NSPLIT>, dim3(16 * ((B + 31) / 32)), dim3(256), 0, s, p);
+  HIPCHK(hipGetLastError());
+  return ITA_OK;
+}
+
 // x2_in != null: start behind the encoder from a given (B,128,E) activation (ita_vitlstm_tail); image is then unused
 static int forward_impl(ita_handle h, const void* image, int image_dtype, const float* desvel, const float* quat,
                         const float* h_in, const float* c_in, float* vel, float* h_out, float* c_out, int batch,
@@ -1517,10 +1562,6 @@ static int forward_impl(ita_handle h, const void* image, int image_dtype, const 
   const bool fast = h->tail_mode == 1 && h->folded;
   if (slots && !fast) return fail(ITA_ERR_UNSUPPORTED, "slot-indexed state needs tail mode 1");
   const size_t lstride = (size_t)(slots ? state_rows : batch) * 128;   // layer stride of the (3, rows, 128) state
-  // Layer 0 of the LSTM reads whole rows of h while other workgroups write parts of the same rows when the
-  // state is updated in place (slot-indexed state, or hidden_out_h aliasing hidden_in_h): only then is the
-  // layer-0 h staged by frame index (a side copy inside the encoder kernel).
-  const bool stage_h0 = slots || (h_out < h_in + lstride && h_in < h_out + lstride);
   const int ev_per_fwd = 5 + 2 * h->hdr.num_layers;
   hipEvent_t* ev = nullptr;
   if (h->prof && h->prof_n < h->prof_max && (h->prof_calls++ % h->prof_every) == 0)
@@ -1536,7 +1577,7 @@ static int forward_impl(ita_handle h, const void* image, int image_dtype, const 
 #define MARK() do { if (ev && (h->prof_stage < 0 || evi == m_lo || evi == m_hi)) HIPCHK(hipEventRecord(ev[evi], s)); ++evi; } while (0)
   MARK();
   const bool fused_tok = !x2_in && fuse_tokenizer(h, image_dtype);
-  if (slots && !x2_in) {   // refuse before the first launch: the slot-indexed side copy of h lives in the stream kernel
+  if (slots && !x2_in) {   // refuse before the first launch: the slot-indexed form is served by the stream kernel only
     const Layer& LL = h->layers.back();
     if (!LL.ffn_f32 && !((fused_tok && h->hdr.num_layers == 1) ? LL.simg_tok : LL.simg_enc))
       return fail(ITA_ERR_UNSUPPORTED, "slot-indexed state needs the stream kernel (this blob's accumulator range rules it out)");
@@ -1549,7 +1590,6 @@ static int forward_impl(ita_handle h, const void* image, int image_dtype, const 
                          h->x2_lo, 128 * h->hdr.E, h->ldfold, B);
       HIPCHK(hipGetLastError());
     }
-    if (stage_h0) HIPCHK(hipMemcpyAsync(h->gates, h_in, sizeof(float) * (size_t)B * 128, hipMemcpyDeviceToDevice, s));
   } else if (!fused_tok && (rc = launch_tokenizer(h, image, image_dtype, h->bufA, B, s))) return rc;
   MARK();
   if (!x2_in && !fused_tok && taps && taps->tokens) HIPCHK(hipMemcpyAsync(taps->tokens, h->bufA, tokb, hipMemcpyDeviceToDevice, s));
@@ -1561,8 +1601,8 @@ static int forward_impl(ita_handle h, const void* image, int image_dtype, const 
     const std::function<int()> mid = [&]() -> int { MARK(); marked = true; return ITA_OK; };
     // one encoder layer, in place on bufA
     if ((rc = launch_encoder(h, l, h->bufA, yout, planes ? h->x2_hi : nullptr, planes ? h->x2_lo : nullptr,
-                             (taps && last) ? taps->x1 : nullptr, B, s, nullptr, (planes && stage_h0) ? h_in : nullptr,
-                             (planes && stage_h0) ? h->gates : nullptr, slots, (fused_tok && l == 0) ? image : nullptr,
+                             (taps && last) ? taps->x1 : nullptr, B, s, nullptr, nullptr, nullptr, slots,
+                             (fused_tok && l == 0) ? image : nullptr,
                              (fused_tok && l == 0 && taps) ? taps->tokens : nullptr, &mid))) return rc;
     if (!marked) MARK();
     MARK();
@@ -1575,26 +1615,7 @@ static int forward_impl(ita_handle h, const void* image, int image_dtype, const 
                                                 512, h->kfold, NSPLIT, s, h->foldf_hi, h->foldf_lo))) return rc;
     MARK();
     MARK();
-    _Float16* chi[3] = {nullptr, h->c1_hi, h->c2_hi};
-    _Float16* clo[3] = {nullptr, h->c1_lo, h->c2_lo};
-    {
-      ItaLstm0Args p{h->part, NSPLIT, h->fold_inv_scale, h->lw_hi[0], h->lw_lo[0], h->lw_inv_scale[0], h->fold_bias,
-                     desvel, quat, stage_h0 ? h->gates /* staged by frame */ : h_in, c_in, h_out, c_out, chi[1], clo[1],
-                     h_in + lstride, B, slots};
-      hipLaunchKernelGGL(ita_lstm0_kernel<NSPLIT>, dim3(16, (B + 31) / 32), dim3(64), 0, s, p);
-      HIPCHK(hipGetLastError());
-    }
-    for (int l = 1; l < 3; ++l) {
-      ItaLstmLayerArgs p{chi[l], clo[l], 256, h->lw_hi[l], h->lw_lo[l], 256, h->lw_inv_scale[l], h->bsum[l],
-                         c_in + l * lstride, h_out + l * lstride, c_out + l * lstride,
-                         l < 2 ? chi[l + 1] : nullptr, l < 2 ? clo[l + 1] : nullptr,
-                         l < 2 ? h_in + (l + 1) * lstride : nullptr, B, 256, slots};
-      hipLaunchKernelGGL(ita_lstm_layer_kernel<4>, dim3(16, (B + 31) / 32), dim3(256), 0, s, p);
-      HIPCHK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(ita_fc_kernel, dim3((B * 3 + 63) / 64), dim3(64), 0, s, h_out + 2 * lstride, h->fc_w,
-                       h->fc_b, vel, B, slots);
-    HIPCHK(hipGetLastError());
+    if ((rc = launch_lstm_head(h, h->part, desvel, quat, h_in, c_in, h_out, c_out, lstride, vel, B, slots, s))) return rc;
     MARK();
   } else {
     if (h->hdr.has_tail) {
@@ -1731,29 +1752,8 @@ int ita_vitlstm_back(ita_handle h, const float* desvel, const float* quat, const
   const int B = batch;
   const size_t lstride = (size_t)B * 128;
   const float* part = h->part + (size_t)buf * NSPLIT * h->cap * 512;
-  // layer 0 reads whole rows of h while other workgroups overwrite parts of them when h_out aliases h_in:
-  // only then is its h staged (a copy; ita_vitlstm_forward does this inside the encoder kernel)
-  const bool stage_h0 = h_out < h_in + lstride && h_in < h_out + lstride;
-  if (stage_h0) HIPCHK(hipMemcpyAsync(h->gates, h_in, sizeof(float) * lstride, hipMemcpyDeviceToDevice, s));
-  {
-    ItaLstm0Args p{part, NSPLIT, h->fold_inv_scale, h->lw_hi[0], h->lw_lo[0], h->lw_inv_scale[0], h->fold_bias, desvel, quat,
-                   stage_h0 ? h->gates : h_in, c_in, h_out, c_out, h->c1_hi, h->c1_lo, h_in + lstride, B, nullptr};
-    hipLaunchKernelGGL(ita_lstm0_kernel<NSPLIT>, dim3(16, (B + 31) / 32), dim3(64), 0, s, p);
-    HIPCHK(hipGetLastError());
-  }
-  _Float16* chi[3] = {nullptr, h->c1_hi, h->c2_hi};
-  _Float16* clo[3] = {nullptr, h->c1_lo, h->c2_lo};
-  for (int l = 1; l < 3; ++l) {
-    ItaLstmLayerArgs p{chi[l], clo[l], 256, h->lw_hi[l], h->lw_lo[l], 256, h->lw_inv_scale[l], h->bsum[l],
-                       c_in + l * lstride, h_out + l * lstride, c_out + l * lstride, l < 2 ? chi[l + 1] : nullptr,
-                       l < 2 ? clo[l + 1] : nullptr, l < 2 ? h_in + (l + 1) * lstride : nullptr, B, 256, nullptr};
-    hipLaunchKernelGGL(ita_lstm_layer_kernel<4>, dim3(16, (B + 31) / 32), dim3(256), 0, s, p);
-    HIPCHK(hipGetLastError());
-  }
-  hipLaunchKernelGGL(ita_fc_kernel, dim3((B * 3 + 63) / 64), dim3(64), 0, s, h_out + 2 * lstride, h->fc_w, h->fc_b, vel, B,
-                     (const int*)nullptr);
-  HIPCHK(hipGetLastError());
-  return ITA_OK;
+  // h_out may alias h_in: the head kernel reads all of h_in before any h_out element is written
+  return launch_lstm_head(h, part, desvel, quat, h_in, c_in, h_out, c_out, lstride, vel, B, nullptr, s);
 }
 
 // n consecutive time steps, software-pipelined from the host: front(t+1) on stream_front while back(t) is on stream_back

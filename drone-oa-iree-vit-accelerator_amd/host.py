@@ -28,6 +28,7 @@ IMAGE_F32, IMAGE_U8 = 0, 1
 DISPATCH_F16, DISPATCH_F32 = 0, 1
 FFN_INT8, FFN_F32 = 0, 1
 ATTN_INT8, ATTN_F32 = 0, 1
+HEAD_TIMEOUT = 1
 
 EXPORTED_SYMBOLS = (
     "ita_abi_version", "ita_create", "ita_destroy", "ita_load_weights", "ita_validate_blob", "ita_reserve", "ita_get_dims",
@@ -38,6 +39,7 @@ EXPORTED_SYMBOLS = (
     "ita_fusion_tail_load", "ita_fusion_tail_large",
     "ita_wire_unpack_packet", "ita_wire_postprocess", "ita_vitlstm_forward_slots", "ita_vitlstm_front",
     "ita_vitlstm_back", "ita_vitlstm_pipelined", "ita_vitlstm_front_ev", "ita_vitlstm_encode", "ita_vitlstm_fold", "ita_vitlstm_tail", "ita_debug_softmax_rows",
+    "ita_head_status",
     "ITASelfAttention_workgroup", "ITASelfAttention_workgroup_expanded", "ITAFeedForward_workgroup",
 )
 
@@ -115,6 +117,7 @@ def lib():
         L.ita_get_ffn_kind.argtypes = [vp, i, C.POINTER(i)]
         L.ita_mha_f32.argtypes = [vp, i, vp, vp, i, vp]
         L.ita_get_attn_kind.argtypes = [vp, i, C.POINTER(i)]
+        L.ita_head_status.argtypes = [vp, C.POINTER(i)]
         L.ita_encoder_layer.argtypes = [vp, i, vp, vp, i, vp]
         L.ita_tokenizer.argtypes = [vp, vp, i, vp, i, vp]
         L.ita_fusion_tail.argtypes = [vp, vp, vp, i, vp]
@@ -265,6 +268,13 @@ class Engine:
         k = C.c_int(-1)
         _chk(lib().ita_get_attn_kind(self._h, layer, C.byref(k)))
         return k.value
+
+    def head_status(self) -> int:
+        """device status of the LSTM head since the last query: 0, or HEAD_TIMEOUT (that call's outputs are invalid; the
+        head is re-armed).  Waits for the device."""
+        st = C.c_int(-1)
+        _chk(lib().ita_head_status(self._h, C.byref(st)))
+        return st.value
 
     def mha_f32(self, x, layer: int = 0):
         """ITASelfAttention.forward (float32, softmax(Q K^T) V, no residual / LayerNorm) of a float-attention layer:

@@ -219,6 +219,12 @@ int ita_vitlstm_forward_slots(ita_handle h, const void* image_dev, int image_dty
  * hidden_out_* may alias hidden_in_* in both modes. */
 int ita_set_tail_mode(ita_handle h, int mode);
 
+/* Device status of the LSTM head of tail mode 1, which runs its three layers and the fc in one launch whose workgroups
+ * wait for each other (bounded waits).  *status = 0, or ITA_HEAD_TIMEOUT when a wait timed out since the last query: the
+ * outputs of that call are then invalid.  Waits for the device; a non-zero status is cleared and the head re-armed. */
+#define ITA_HEAD_TIMEOUT 1
+int ita_head_status(ita_handle h, int* status);
+
 /* ---- per-stage timing (bench.py's roofline leg) -------------------------------------------- */
 /* Between ita_profile_begin and ita_profile_end every ita_vitlstm_forward call records HIP
  * events on ITS OWN stream around each stage; ita_profile_end synchronises them and returns

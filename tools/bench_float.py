@@ -59,4 +59,4 @@ else:
 print(json.dumps({"graph": graph, "ms_per_step_1024": round(ms1024, 4),
                   "frames_per_s_1024": round(1024 / ms1024 * 1e3), "ms_per_step_128": round(ms128, 4),
                   "frames_per_s_128": round(128 / ms128 * 1e3), "p50_ms_1frame": round(p50, 4),
-                  "kernels": kernels + ["ita_lstm0_kernel", "ita_lstm_layer_kernel", "ita_fc_kernel"]}))
+                  "kernels": kernels + ["ita_lstm_head_kernel"]}))

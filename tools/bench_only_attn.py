@@ -54,4 +54,4 @@ print(json.dumps({"graph": f"QAT_only_attn E=64 {a.layers} layer(s)", "ms_per_st
                   "frames_per_s_128": round(128 / ms128 * 1e3), "p50_ms_1frame": round(p50, 4),
                   "kernels": ["ita_tok_stream_kernel<64,true>", "ita_stream_kernel<64,false,0,false,false,*> (attention + LN1)",
                               "ita_ffn_f32_kernel (FFN + LN2, f32 MFMA)", "ita_gemm_f16x3_kernel (folded tail+decoder)",
-                              "ita_lstm0_kernel", "ita_lstm_layer_kernel", "ita_fc_kernel"]}))
+                              "ita_lstm_head_kernel"]}))
