@@ -5,6 +5,7 @@
 // (the iree_runtime_plugin.cmake equivalent is plugin/ita_runtime_plugin.cmake).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,6 +20,7 @@
 #include "../../include/ita_weights.h"
 #include "../../include/ita_wire.h"
 #include "ita_f16x3_kernels.h"
+#include "ita_lstm_seq_kernel.h"
 #include "ita_f32_kernels.h"
 #include "ita_int8_kernels.h"
 #include "ita_stream_kernel.h"
@@ -108,6 +110,7 @@ struct ita_context {
   // ita_head_status
   unsigned* head_sync = nullptr;
   size_t head_sync_bytes = 0;
+  char* seq_ho = nullptr;       // ita_lstm_seq_kernel's hand-off buffers: ITA_SEQ_TILE bytes per 32-stream tile
   // workspace
   int cap = 0;
   bool ws_reserved = false;     // ita_reserve was called: the workspace is pinned (see ensure_workspace)
@@ -210,6 +213,8 @@ void free_workspace(ita_context* c) {
   if (c->head_sync) (void)hipFree(c->head_sync);
   c->head_sync = nullptr;
   c->head_sync_bytes = 0;
+  if (c->seq_ho) (void)hipFree(c->seq_ho);
+  c->seq_ho = nullptr;
   c->cap = 0;
   for (int& fc : c->front_cap) fc = 0;
 }
@@ -243,6 +248,7 @@ int ensure_workspace(ita_context* c, int B, hipStream_t s = nullptr) {
   c->head_sync_bytes = sizeof(unsigned) * ITA_HEAD_CNT_STRIDE * ((size_t)1 + (B + 31) / 32);
   HIPCHK(hipMalloc(&c->head_sync, c->head_sync_bytes));
   HIPCHK(hipMemset(c->head_sync, 0, c->head_sync_bytes));
+  HIPCHK(hipMalloc(&c->seq_ho, (size_t)ITA_SEQ_TILE * ((B + 31) / 32)));   // 3 KB per frame, whether or not the sequence form is used
   HIPCHK(hipDeviceSynchronize());
   c->cap = B;
   return ITA_OK;
@@ -1849,6 +1855,39 @@ int ita_vitlstm_pipelined(ita_handle h, const void* const* image, int image_dtyp
   // join: everything is complete in stream_front's order
   HIPCHK(hipEventRecord(h->pipe_ev[2 * ITA_PART_BUFFERS], sb));
   HIPCHK(hipStreamWaitEvent(sf, h->pipe_ev[2 * ITA_PART_BUFFERS], 0));
+  return ITA_OK;
+}
+
+// T time steps of `batch` streams in one call: the image-only part of a chunk of steps runs as ONE batch of Tc * batch
+// frames (time-major rows), the recurrence of those Tc steps as one ita_lstm_seq_kernel launch; the state is carried in
+// state_h / state_c from chunk to chunk.  One stream, no host synchronisation, no allocation once the workspace holds
+// `batch` frames.  (Running the fronts of later chunks ahead on a second stream was built and measured: slower at every
+// shape with more than one chunk, profiles/r05_sequence_overlap_ab.txt.)
+int ita_vitlstm_sequence(ita_handle h, const void* image, int image_dtype, const float* desvel, const float* quat,
+                         float* state_h, float* state_c, const int* lengths, float* vel, int n_steps, int batch, void* stream) {
+  int rc = check(h, batch);
+  if (rc) return rc;
+  if (!image || !desvel || !quat || !state_h || !state_c || !vel) return fail(ITA_ERR_INVALID_ARG, "null pointer");
+  if (n_steps <= 0) return fail(ITA_ERR_INVALID_ARG, "n_steps must be positive");
+  if (image_dtype != ITA_IMAGE_F32 && image_dtype != ITA_IMAGE_U8) return fail(ITA_ERR_INVALID_ARG, "bad image dtype");
+  if (!(h->tail_mode == 1 && h->folded)) return fail(ITA_ERR_UNSUPPORTED, "the sequence form needs tail mode 1 and a full ITAViTLSTM blob");
+  if (h->prof) return fail(ITA_ERR_INVALID_ARG, "ita_vitlstm_sequence cannot run between ita_profile_begin and ita_profile_end");
+  if ((rc = ensure_workspace(h, batch, (hipStream_t)stream))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int B = batch, Tc = h->cap / B;   // >= 1: the workspace holds at least B frames
+  const size_t frame_bytes = (size_t)60 * 90 * (image_dtype == ITA_IMAGE_U8 ? 1 : sizeof(float));
+  for (int t0 = 0; t0 < n_steps; t0 += Tc) {
+    const int n = std::min(Tc, n_steps - t0);
+    const size_t row0 = (size_t)t0 * B;
+    if ((rc = front_impl(h, (const char*)image + row0 * frame_bytes, image_dtype, n * B, 0, stream, nullptr))) return rc;
+    ItaLstmSeqArgs p{h->part, h->fold_inv_scale, h->lw_hi[0], h->lw_lo[0], h->lw_inv_scale[0], h->fold_bias,
+                     h->lw_hi[1], h->lw_lo[1], h->lw_hi[2], h->lw_lo[2], h->lw_inv_scale[1], h->lw_inv_scale[2],
+                     h->bsum[1], h->bsum[2], desvel + row0, quat + row0 * 4, state_h, state_c, lengths, t0, h->seq_ho,
+                     h->fc_w, h->fc_b, vel + row0 * 3, h->head_sync + ITA_HEAD_CNT_STRIDE, h->head_sync, B, n};
+    hipLaunchKernelGGL(ita_lstm_seq_kernel<NSPLIT>, dim3(16 * ((B + 31) / 32)), dim3(256), 0, s, p);
+    HIPCHK(hipGetLastError());
+  }
+  h->front_cap[0] = 0;   // partial buffer 0 holds time-major rows of several steps: not something ita_vitlstm_back may read
   return ITA_OK;
 }
 

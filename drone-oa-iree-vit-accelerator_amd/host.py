@@ -39,7 +39,7 @@ EXPORTED_SYMBOLS = (
     "ita_fusion_tail_load", "ita_fusion_tail_large",
     "ita_wire_unpack_packet", "ita_wire_postprocess", "ita_vitlstm_forward_slots", "ita_vitlstm_front",
     "ita_vitlstm_back", "ita_vitlstm_pipelined", "ita_vitlstm_front_ev", "ita_vitlstm_encode", "ita_vitlstm_fold", "ita_vitlstm_tail", "ita_debug_softmax_rows",
-    "ita_head_status",
+    "ita_head_status", "ita_vitlstm_sequence",
     "ITASelfAttention_workgroup", "ITASelfAttention_workgroup_expanded", "ITAFeedForward_workgroup",
 )
 
@@ -129,6 +129,7 @@ def lib():
         L.ita_vitlstm_fold.argtypes = [vp, i, i, i, vp]
         L.ita_vitlstm_back.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, vp]
         L.ita_vitlstm_pipelined.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, i, i, vp, vp]
+        L.ita_vitlstm_sequence.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, vp, i, i, vp]
         L.ita_mha_q8.argtypes = [vp, i, vp, vp, i, vp]
         L.ita_mha_long_q8.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_vitlstm_tail.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
@@ -390,6 +391,56 @@ class Engine:
         if taps:
             return vel, (h_out, c_out), tp
         return vel, (h_out, c_out)
+
+    def forward_sequence(self, imgs, desvels, quats=None, hidden=None, lengths=None, out=None):
+        """T time steps of B streams in one call (ita_vitlstm_sequence): the image-only part of all T * B frames runs as
+        one batch (in chunks of what the workspace holds: reserve T * B frames to avoid seams), the recurrence as one
+        kernel launch per chunk.  Equal to T calls of forward, bit for bit.
+
+        imgs (T,B,60,90) u8, or f32 (another size is resized as forward does); desvels (T,B); quats (T,B,4), default
+        [1,0,0,0]; hidden (h, c) each (3,B,128), default zero, not modified unless handed back as out; lengths (B) int:
+        stream b takes part in the steps t < lengths[b] only -- behind them its state is kept and its rows of vel are
+        left untouched.  out = (vel (T,B,3), h, c).  Returns (vel, (h, c)), h and c after the last step.  Needs tail mode 1.
+        Measured per step on a 1024-frame workspace (tools/bench_sequence.py): 0.28-0.30 x the best step schedule at 1 and 8
+        streams, 0.35 x at 32, 0.50 x at 128; at 1024 streams (one step per chunk) it LOSES to a loop of forward by 12 %."""
+        torch = _torch()
+        if imgs.dim() != 4:
+            raise ITAError(f"imgs must be (T, B, H, W), got {tuple(imgs.shape)}")
+        T, B = int(imgs.shape[0]), int(imgs.shape[1])
+        img, dt = self._image(imgs)
+        dev = img.device
+        desvels = _dev_f32(desvels).reshape(T, B)
+        if quats is None:
+            quats = torch.zeros((T, B, 4), dtype=torch.float32, device=dev)
+            quats[..., 0] = 1
+        quats = _dev_f32(quats, (T, B, 4))
+        if out is None:
+            vel = torch.empty((T, B, 3), dtype=torch.float32, device=dev)
+            h = torch.empty((3, B, 128), dtype=torch.float32, device=dev)
+            c = torch.empty_like(h)
+        else:
+            vel, h, c = out
+            for t, shp in ((vel, (T, B, 3)), (h, (3, B, 128)), (c, (3, B, 128))):
+                if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shp:
+                    raise ITAError(f"out tensors must be contiguous f32 GPU tensors of shape (T,B,3), (3,B,128), (3,B,128); got {tuple(t.shape)}")
+        if hidden is None:
+            h.zero_()
+            c.zero_()
+        else:
+            h_in, c_in = _dev_f32(hidden[0], (3, B, 128)), _dev_f32(hidden[1], (3, B, 128))
+            if h_in.data_ptr() != h.data_ptr():
+                h.copy_(h_in)
+            if c_in.data_ptr() != c.data_ptr():
+                c.copy_(c_in)
+        lp = None
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).contiguous()
+            if tuple(lengths.shape) != (B,):
+                raise ITAError(f"lengths must have shape ({B},), got {tuple(lengths.shape)}")
+            lp = lengths.data_ptr()
+        _chk(lib().ita_vitlstm_sequence(self._h, img.data_ptr(), dt, desvels.data_ptr(), quats.data_ptr(), h.data_ptr(),
+                                        c.data_ptr(), lp, vel.data_ptr(), T, B, _stream_ptr(self.device)))
+        return vel, (h, c)
 
     def mha_q8(self, x_q, layer: int = 0):
         """attention block on int8 codes: x_q (B,128,E) int8 -> out_q (B,128,E) int8 (ita_mha_q8)"""

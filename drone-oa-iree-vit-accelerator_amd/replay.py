@@ -16,7 +16,7 @@ MI355X counterpart of the reference's training-set replay host
                                                                                             (main.cpp:128-133,155)
   error                              Euclidean distance between the raw model output and the ground truth (:282-287)
 
-What differs is the schedule: the reference walks one trajectory after the other, one frame per graph call.
+What differs is the schedule (the default one, "steps"; "sequence" is described at replay()): the reference walks one trajectory after the other, one frame per graph call.
 Trajectories are independent streams, so here step t runs frame t of EVERY trajectory that still has frames in
 one batched call with slot-indexed state (ita_vitlstm_forward_slots): results per trajectory are the same as
 the sequential walk (a frame's result does not depend on its batch -- tests/test_gpu_parity.py), the GPU sees
@@ -134,11 +134,70 @@ class FrameResult:
     telemetry_found: bool
 
 
-def replay(engine, root: str, max_batch: int = 1024) -> List[FrameResult]:
+SCHEDULES = ("steps", "sequence")
+
+
+def _result(traj: Trajectory, k: int, vel: np.ndarray) -> FrameResult:
+    tel = traj.telemetry[k]
+    gt = np.asarray(tel.ground_truth_velocity, dtype=np.float32)
+    d = vel - gt
+    err = float(math.sqrt(float(d[0]) * float(d[0]) + float(d[1]) * float(d[1]) + float(d[2]) * float(d[2])))
+    return FrameResult(traj.name, os.path.basename(traj.frames[k]), vel.copy(), gt, err, tel.found)
+
+
+def _replay_sequence(engine, trajs: List[Trajectory], max_batch: int) -> List[FrameResult]:
+    """groups of at most max_batch trajectories, each group one Engine.forward_sequence call from zero state: the frames
+    of a trajectory are time steps, the trajectories of a group are streams"""
+    import torch
+    dev = torch.device("cuda", engine.device)
+    out = []
+    for g0 in range(0, len(trajs), max_batch):
+        group = trajs[g0:g0 + max_batch]
+        seqs = []                                        # per trajectory: [(frame index, u8 frame)] of its readable frames
+        for t in group:
+            fr = [(k, read_frame(p)) for k, p in enumerate(t.frames)]
+            seqs.append([(k, im) for k, im in fr if im is not None])   # unreadable frames drop out of the sequence
+        T, B = max(len(q) for q in seqs), len(group)
+        if T == 0:
+            continue
+        imgs = np.zeros((T, B, FRAME_H, FRAME_W), np.uint8)
+        dv = np.zeros((T, B), np.float32)
+        qt = np.zeros((T, B, 4), np.float32)
+        qt[..., 0] = 1.0
+        for b, (t, q) in enumerate(zip(group, seqs)):
+            for step, (k, im) in enumerate(q):
+                imgs[step, b] = im
+                # the same float32 values the step schedule hands over (a Python float divided, then rounded once)
+                dv[step, b] = t.telemetry[k].desired_velocity / 10.0
+                qt[step, b] = t.telemetry[k].quaternion
+        lengths = torch.tensor([len(q) for q in seqs], dtype=torch.int32, device=dev)
+        vel, _ = engine.forward_sequence(torch.from_numpy(imgs).to(dev), torch.from_numpy(dv).to(dev),
+                                         torch.from_numpy(qt).to(dev), None, lengths)
+        vel = vel.cpu().numpy()
+        for b, (t, q) in enumerate(zip(group, seqs)):
+            out.extend(_result(t, k, vel[step, b]) for step, (k, _) in enumerate(q))
+    return out
+
+
+def replay(engine, root: str, max_batch: int = 1024, schedule: str = "steps") -> List[FrameResult]:
     """Runs every trajectory under root through `engine` (host.Engine with a full ITAViTLSTM blob) and returns
-    one FrameResult per readable frame, ordered by (trajectory, frame).  Needs a GPU."""
+    one FrameResult per readable frame, ordered by (trajectory, frame).  Needs a GPU.
+
+    schedule "steps" (default): step t runs frame t of every trajectory that still has frames, one batched call per
+    step.  "sequence": every trajectory is handed over whole (Engine.forward_sequence, padded to the longest of its
+    group, with lengths), so the encoder sees all frames of a group at once and the recurrence runs inside one kernel
+    launch per chunk; the same results bit for bit.  It pays for data sets of a few long trajectories (the step
+    schedule then runs at a handful of frames per call).  The GPU part alone, Engine.forward_sequence against a loop of
+    Engine.forward on frames already in device memory (tools/bench_sequence.py), takes 0.25 x the time per step at up to 8
+    trajectories and 0.43 x at 128, and 12 % MORE at 1024 trajectories per group, which is why "steps" stays the default;
+    replay() itself also decodes the PNGs on the host and has not been timed.  It holds a whole group's frames in memory
+    at once."""
+    if schedule not in SCHEDULES:
+        raise ValueError(f"schedule must be one of {SCHEDULES}, got {schedule!r}")
     import torch
     trajs = scan_root(root)
+    if schedule == "sequence":
+        return _replay_sequence(engine, trajs, max_batch) if trajs else []
     n = len(trajs)
     if n == 0:
         return []
@@ -166,11 +225,7 @@ def replay(engine, root: str, max_batch: int = 1024) -> List[FrameResult]:
         slots = torch.tensor([b[0] for b in batch], dtype=torch.int32, device=dev)
         vel = engine.forward_slots(imgs, dv, qt, state_h, state_c, slots).cpu().numpy()
         for j, (i, k, _) in enumerate(batch):
-            gt = np.asarray(tel[j].ground_truth_velocity, dtype=np.float32)
-            d = vel[j] - gt
-            err = float(math.sqrt(float(d[0]) * float(d[0]) + float(d[1]) * float(d[1]) + float(d[2]) * float(d[2])))
-            results[i].append(FrameResult(trajs[i].name, os.path.basename(trajs[i].frames[k]), vel[j].copy(), gt, err,
-                                          tel[j].found))
+            results[i].append(_result(trajs[i], k, vel[j]))
     return [r for i in range(n) for r in results[i]]
 
 

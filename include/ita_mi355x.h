@@ -201,6 +201,27 @@ int ita_vitlstm_pipelined(ita_handle h, const void* const* image_dev, int image_
                           const float* const* quat_data_dev, float* state_h_dev, float* state_c_dev, float* const* output_dev,
                           int batch, int n_steps, void* stream_front, void* stream_back);
 
+/* Time as a dimension: n_steps consecutive steps of `batch` independent streams whose frames are all known up front
+ * (offline replay), in one call on one stream.  Only the LSTM head depends on the previous step, so the image-only part
+ * (tokenizer, encoder, folded GEMM) of a chunk of steps runs as ONE batch of Tc * batch frames, and the recurrence of
+ * those Tc steps as ONE launch (ita_lstm_seq_kernel: the head kernel with a time loop, weights and cell state resident,
+ * steps handed over between its workgroups in-kernel).  Tc = max(1, workspace frames / batch): ita_reserve(n_steps *
+ * batch) gives one chunk; the result does not depend on the chunking.  Equal to n_steps calls of ita_vitlstm_forward,
+ * bit for bit.  Arrays are time-major:
+ *   image_dev (n_steps, batch, 60, 90) u8 or f32, additional_data_dev (n_steps, batch), quat_data_dev (n_steps, batch, 4),
+ *   output_dev (n_steps, batch, 3);  state_h_dev / state_c_dev (3, batch, 128): in the state before step 0, out the state
+ *   after the last step (updated in place);  lengths_dev (batch) int or NULL = all n_steps: stream b takes part in the
+ *   steps t < lengths[b] only (0 <= lengths[b] <= n_steps) -- behind them its state is kept and its output rows are not
+ *   written.
+ * Stream-ordered, no host synchronisation, no allocation once the workspace holds `batch` frames.  Needs tail mode 1
+ * (ITA_ERR_UNSUPPORTED otherwise, before any launch); refused between ita_profile_begin and ita_profile_end.
+ * ita_head_status reports a timed-out in-kernel wait of this call as it does for the step path.
+ * Uses (overwrites) partial buffer 0 and plane set 0 of the front / back form: an ita_vitlstm_front(buf 0) whose
+ * ita_vitlstm_back has not run yet is lost, and ita_vitlstm_back(buf 0) after this call is refused until a new front. */
+int ita_vitlstm_sequence(ita_handle h, const void* image_dev, int image_dtype, const float* additional_data_dev,
+                         const float* quat_data_dev, float* state_h_dev, float* state_c_dev, const int* lengths_dev,
+                         float* output_dev, int n_steps, int batch, void* stream);
+
 /* Serving form of the same graph: the LSTM state of `num_slots` independent streams lives in two
  * persistent device arrays state_h / state_c of shape (3, num_slots, 128); frame b of the batch belongs to
  * stream slot_idx[b] (device int array, all distinct within one call) and updates that stream's state

@@ -22,6 +22,8 @@ def main():
     ap.add_argument("--synthetic-weights", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--quiet", action="store_true", help="summary only")
+    ap.add_argument("--schedule", choices=("steps", "sequence"), default="steps",
+                    help="steps: one batched call per time step; sequence: whole trajectories per call (Engine.forward_sequence)")
     a = ap.parse_args()
     from drone_oa_iree_vit_accelerator_amd import host, params, replay, synth
     if a.blob:
@@ -32,7 +34,7 @@ def main():
     else:
         raise SystemExit("give --blob or --synthetic-weights")
     eng = host.Engine(blob, device=a.device)
-    res = replay.replay(eng, a.root)
+    res = replay.replay(eng, a.root, schedule=a.schedule)
     if not a.quiet:
         for r in res:
             print(f"{r.trajectory}/{r.frame}  Model Output: [{r.output[0]:.6g}, {r.output[1]:.6g}, {r.output[2]:.6g}]  "
