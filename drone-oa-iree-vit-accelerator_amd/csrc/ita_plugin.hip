@@ -29,6 +29,7 @@
 #include "ita_attn_f32_kernel.h"
 #include "ita_ffn_f32_e128_kernel.h"
 #include "ita_attn_f32_e128_kernel.h"
+#include "ita_ingest_kernel.h"
 
 namespace {
 
@@ -888,6 +889,28 @@ int dispatch_host(const uint16_t* in, uint16_t* out, bool ffn);
 }  // namespace
 
 // =============================================================================== C ABI
+namespace {
+template <typename T>
+int launch_ingest(ita_context* c, const void* src, int H, int W, long long row_stride, long long frame_stride,
+                  float depth_scale, float* frames, int batch, hipStream_t s) {
+  const float scale_y = (float)H / (float)ITA_INGEST_H, scale_x = (float)W / (float)ITA_INGEST_W;   // host IEEE divisions
+  const int row_bytes = W * (int)sizeof(T);
+  if (W >= 2 * ITA_INGEST_W && row_bytes <= ITA_INGEST_ROW_BYTES) {
+    const long long items = (long long)batch * (ITA_INGEST_H / 4);
+    const int grid = (int)std::min<long long>(items, (long long)c->num_cus * 8);
+    hipLaunchKernelGGL(ita_ingest_rows_kernel<T>, dim3(grid), dim3(256), ita_ingest_rows_lds_total(row_bytes), s,
+                       (const T*)src, H, W, row_stride, frame_stride, scale_y, scale_x, depth_scale, frames, batch);
+  } else {
+    const long long blocks = ((long long)batch * ITA_INGEST_H * ITA_INGEST_W + 255) / 256;
+    const int grid = (int)std::min<long long>(blocks, (long long)c->num_cus * 8);
+    hipLaunchKernelGGL(ita_ingest_gather_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)src, H, W, row_stride,
+                       frame_stride, scale_y, scale_x, depth_scale, frames, batch);
+  }
+  HIPCHK(hipGetLastError());
+  return ITA_OK;
+}
+}  // namespace
+
 extern "C" {
 
 int ita_abi_version(void) { return ITA_MI355X_ABI_VERSION; }
@@ -1396,6 +1419,34 @@ int ita_tokenizer(ita_handle h, const void* image, int image_dtype, float* token
   if (!image || !tokens || (image_dtype != ITA_IMAGE_F32 && image_dtype != ITA_IMAGE_U8))
     return fail(ITA_ERR_INVALID_ARG, "bad pointer or image dtype");
   return launch_tokenizer(h, image, image_dtype, tokens, batch, (hipStream_t)stream);
+}
+
+int ita_ingest(ita_handle h, const void* src, int pixel_dtype, int height, int width, long long row_stride,
+               long long frame_stride, float depth_scale, float* frames, int batch, void* stream) {
+  // every argument is judged before the handle is used and before any HIP call
+  if (!h) return fail(ITA_ERR_INVALID_ARG, "null handle");
+  if (!src || !frames) return fail(ITA_ERR_INVALID_ARG, "null pointer");
+  if (pixel_dtype != ITA_PIXEL_U8 && pixel_dtype != ITA_PIXEL_U16 && pixel_dtype != ITA_PIXEL_F32)
+    return fail(ITA_ERR_INVALID_ARG, "pixel_dtype must be ITA_PIXEL_U8, ITA_PIXEL_U16 or ITA_PIXEL_F32");
+  if (height < 1 || height > ITA_INGEST_MAX_DIM || width < 1 || width > ITA_INGEST_MAX_DIM)
+    return fail(ITA_ERR_INVALID_ARG, "height and width must be in [1, 4096]");
+  if (batch < 1) return fail(ITA_ERR_INVALID_ARG, "batch must be positive");
+  if (row_stride < width || frame_stride < (long long)(height - 1) * row_stride + width)
+    return fail(ITA_ERR_INVALID_ARG, "row_stride < width, or frame_stride < (height - 1) * row_stride + width (strides are in pixels)");
+  if (row_stride > (1ll << 40) || frame_stride > (1ll << 40))
+    return fail(ITA_ERR_INVALID_ARG, "stride out of range");
+  const size_t px = pixel_dtype == ITA_PIXEL_U8 ? 1 : pixel_dtype == ITA_PIXEL_U16 ? 2 : 4;
+  if ((uintptr_t)src % px || (uintptr_t)frames % sizeof(float))
+    return fail(ITA_ERR_INVALID_ARG, "src must be aligned to its pixel size, frames to 4 bytes");
+  if (pixel_dtype == ITA_PIXEL_U16 && !(depth_scale > 0.0f && depth_scale <= 3.402823466e38f))
+    return fail(ITA_ERR_INVALID_ARG, "depth_scale must be finite and positive");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = (hipStream_t)stream;
+  switch (pixel_dtype) {
+    case ITA_PIXEL_U8: return launch_ingest<uint8_t>(h, src, height, width, row_stride, frame_stride, depth_scale, frames, batch, s);
+    case ITA_PIXEL_U16: return launch_ingest<uint16_t>(h, src, height, width, row_stride, frame_stride, depth_scale, frames, batch, s);
+    default: return launch_ingest<float>(h, src, height, width, row_stride, frame_stride, depth_scale, frames, batch, s);
+  }
 }
 
 int ita_fusion_tail(ita_handle h, const float* x, float* feat, int batch, void* stream) {

@@ -25,6 +25,8 @@ _REPO = os.path.dirname(_HERE)
 _LIB = None
 
 IMAGE_F32, IMAGE_U8 = 0, 1
+PIXEL_U8, PIXEL_U16, PIXEL_F32 = 0, 1, 2
+INGEST_MAX_DIM = 4096          # ita_ingest: height and width in [1, 4096]
 DISPATCH_F16, DISPATCH_F32 = 0, 1
 FFN_INT8, FFN_F32 = 0, 1
 ATTN_INT8, ATTN_F32 = 0, 1
@@ -39,7 +41,7 @@ EXPORTED_SYMBOLS = (
     "ita_fusion_tail_load", "ita_fusion_tail_large",
     "ita_wire_unpack_packet", "ita_wire_postprocess", "ita_vitlstm_forward_slots", "ita_vitlstm_front",
     "ita_vitlstm_back", "ita_vitlstm_pipelined", "ita_vitlstm_front_ev", "ita_vitlstm_encode", "ita_vitlstm_fold", "ita_vitlstm_tail", "ita_debug_softmax_rows",
-    "ita_head_status", "ita_vitlstm_sequence",
+    "ita_head_status", "ita_vitlstm_sequence", "ita_ingest",
     "ITASelfAttention_workgroup", "ITASelfAttention_workgroup_expanded", "ITAFeedForward_workgroup",
 )
 
@@ -130,6 +132,7 @@ def lib():
         L.ita_vitlstm_back.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, vp]
         L.ita_vitlstm_pipelined.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, i, i, vp, vp]
         L.ita_vitlstm_sequence.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, vp, i, i, vp]
+        L.ita_ingest.argtypes = [vp, vp, i, i, i, C.c_longlong, C.c_longlong, C.c_float, vp, i, vp]
         L.ita_mha_q8.argtypes = [vp, i, vp, vp, i, vp]
         L.ita_mha_long_q8.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_vitlstm_tail.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
@@ -356,6 +359,66 @@ class Engine:
             img = torch.nn.functional.interpolate(img.reshape(-1, 1, *img.shape[-2:]), size=(60, 90),
                                                   mode="bilinear", align_corners=False)
         return img.reshape(-1, 60, 90).contiguous(), IMAGE_F32
+
+    # ---- ingest: camera-resolution frames -> (N,60,90) f32 --------------------------------
+    @staticmethod
+    def _frame_strides(t):
+        """(row_stride, frame_stride) in pixels when the (..., H, W) tensor can be walked as it lies -- last dimension
+        dense, leading dimensions collapsing to one frame stride, frames not overlapping -- else None"""
+        H, W = int(t.shape[-2]), int(t.shape[-1])
+        st = t.stride()
+        if W > 1 and st[-1] != 1:
+            return None
+        rs = int(st[-2]) if H > 1 else W
+        if rs < W:
+            return None
+        extent = (H - 1) * rs + W
+        lead = [(int(d), int(s)) for d, s in zip(t.shape[:-2], st[:-2]) if d != 1]
+        if not lead:
+            return rs, extent
+        for (_, s0), (d1, s1) in zip(lead, lead[1:]):
+            if s0 != s1 * d1:
+                return None
+        return (rs, lead[-1][1]) if lead[-1][1] >= extent else None
+
+    def ingest(self, frames, depth_scale: Optional[float] = None, out=None):
+        """refine_inputs' resize as a stage of its own (ita_ingest): frames (..., H, W) on this engine's GPU, H and W in
+        [1, 4096], uint8 (value code / 255), uint16 or int16 taken as the same bits (value min(code * depth_scale, 1),
+        depth_scale default 1 / 65535) or float32 (as is) -> (N,60,90) f32, bilinear with align_corners=False, equal to
+        ingest_ref.ingest_reference bit for bit.  A view whose last dimension is dense and whose leading dimensions
+        collapse to one frame stride (a cropped camera buffer) is read through its strides without a copy; anything else
+        is made contiguous first.  The result is allocated per call, or written into out ((N,60,90) f32, contiguous); hand
+        it to forward / forward_sequence / forward_slots as f32 frames: eng.forward(eng.ingest(raw), desvel)."""
+        torch = _torch()
+        if not hasattr(frames, "is_cuda") or not frames.is_cuda:
+            raise ITAError("frames must be a GPU tensor (no CPU fallback)")
+        if frames.device.index != self.device:
+            raise ITAError(f"tensor lives on cuda:{frames.device.index}, the engine on cuda:{self.device}")
+        kinds = {torch.uint8: PIXEL_U8, torch.uint16: PIXEL_U16, torch.int16: PIXEL_U16, torch.float32: PIXEL_F32}
+        if frames.dtype not in kinds:
+            raise ITAError(f"ingest takes uint8, uint16, int16 or float32 frames, got {frames.dtype}")
+        if frames.dim() < 2:
+            raise ITAError(f"frames must be (..., H, W), got {tuple(frames.shape)}")
+        H, W = int(frames.shape[-2]), int(frames.shape[-1])
+        if not (1 <= H <= INGEST_MAX_DIM and 1 <= W <= INGEST_MAX_DIM):
+            raise ITAError(f"H and W must be in [1, {INGEST_MAX_DIM}], got {H} x {W}")
+        N = np_prod(frames.shape[:-2])
+        if N < 1:
+            raise ITAError(f"no frames in a tensor of shape {tuple(frames.shape)}")
+        strides = self._frame_strides(frames)
+        if strides is None:
+            frames = frames.contiguous()
+            strides = (W, H * W)
+        if depth_scale is None:
+            depth_scale = 1.0 / 65535.0
+        if out is None:
+            out = torch.empty((N, 60, 90), dtype=torch.float32, device=frames.device)
+        elif not out.is_cuda or out.device.index != self.device or out.dtype != torch.float32 or not out.is_contiguous() \
+                or tuple(out.shape) != (N, 60, 90):
+            raise ITAError(f"out must be a contiguous f32 tensor of shape ({N}, 60, 90) on cuda:{self.device}")
+        _chk(lib().ita_ingest(self._h, frames.data_ptr(), kinds[frames.dtype], H, W, strides[0], strides[1],
+                              float(depth_scale), out.data_ptr(), N, _stream_ptr(self.device)))
+        return out
 
     # ---- whole graph -------------------------------------------------------------------
     def forward(self, img, desvel, quat=None, hidden=None, taps: bool = False, out=None):

@@ -22,9 +22,16 @@ one batched call with slot-indexed state (ita_vitlstm_forward_slots): results pe
 the sequential walk (a frame's result does not depend on its batch -- tests/test_gpu_parity.py), the GPU sees
 batches instead of single frames.
 
-Frames that are not 90 x 60 are resized with PIL's bilinear filter.  The reference uses
-stbir_resize_uint8_linear (stb is vendored there, not part of this path): the two filters are not bit-identical,
-so for resized frames parity with the reference is UNPINNED; 90 x 60 frames go through untouched.
+Frames that are not 90 x 60, in replay() and with replay_frames(..., resize="pil"): resized on the host with PIL's bilinear filter, after a
+conversion to 8 bits.  The reference uses stbir_resize_uint8_linear (stb is vendored there, not part of this path): the
+two filters are not bit-identical, so for resized frames parity with the reference is UNPINNED; 90 x 60 frames go through
+untouched.
+
+With replay_frames(..., resize="gpu") such frames are uploaded at their native size and depth -- 8-bit, or 16-bit ("I;16") depth PNGs with
+their full codes -- and resized by Engine.ingest, then run on the float32 image path.  That resize is the MODEL's own
+(refine_inputs: bilinear, align_corners=False), and it is pinned: ingest_ref.ingest_reference defines it and the kernel
+equals it bit for bit.  Parity with the reference HOST's stb filter stays unpinned in this mode too.  90 x 60 8-bit
+frames stay on the u8 wire path; the other frames of one trajectory must share one size.
 
 The parsing half of this module (scan_root, load_telemetry, read_frame) needs no GPU; replay() does.
 """
@@ -124,6 +131,44 @@ def read_frame(path: str) -> Optional[np.ndarray]:
         return None                      # the reference warns and skips the image (main.cpp:121)
 
 
+def read_frame_native(path: str) -> Optional[np.ndarray]:
+    """the frame at the size and depth of its file: uint16 (H, W) for a 16-bit grey PNG, else uint8 (H, W) luminance"""
+    from PIL import Image
+    try:
+        with Image.open(path) as im:
+            if im.mode in ("I;16", "I;16L", "I;16B", "I;16N"):
+                return np.asarray(im).astype(np.uint16)
+            return np.asarray(im.convert("L"), dtype=np.uint8).copy()
+    except Exception:
+        return None
+
+
+def _is_wire(im: np.ndarray) -> bool:
+    return im.dtype == np.uint8 and im.shape == (FRAME_H, FRAME_W)
+
+
+def _check_one_size(traj: "Trajectory", seen: dict, key, im: np.ndarray):
+    """resize="gpu": the frames of a trajectory that are not u8 90 x 60 share one size"""
+    if _is_wire(im):
+        return
+    if seen.setdefault(key, im.shape) != im.shape:
+        raise ValueError(f"trajectory {traj.name}: frames of {seen[key][1]} x {seen[key][0]} and of {im.shape[1]} x "
+                         f"{im.shape[0]}; with resize='gpu' the frames that are not 90 x 60 must share one size")
+
+
+def _ingest_frames(engine, frames: List[np.ndarray], dev):
+    """host frames of any size / depth -> (n, 60, 90) f32 on the GPU: one Engine.ingest call per (size, dtype)"""
+    import torch
+    out = torch.empty((len(frames), FRAME_H, FRAME_W), dtype=torch.float32, device=dev)
+    groups = {}
+    for j, im in enumerate(frames):
+        groups.setdefault((im.shape, im.dtype.str), []).append(j)
+    for idx in groups.values():
+        raw = torch.from_numpy(np.stack([frames[j] for j in idx])).to(dev)
+        out[torch.tensor(idx, device=dev)] = engine.ingest(raw)
+    return out
+
+
 @dataclass
 class FrameResult:
     trajectory: str
@@ -135,6 +180,7 @@ class FrameResult:
 
 
 SCHEDULES = ("steps", "sequence")
+RESIZES = ("pil", "gpu")
 
 
 def _result(traj: Trajectory, k: int, vel: np.ndarray) -> FrameResult:
@@ -145,41 +191,93 @@ def _result(traj: Trajectory, k: int, vel: np.ndarray) -> FrameResult:
     return FrameResult(traj.name, os.path.basename(traj.frames[k]), vel.copy(), gt, err, tel.found)
 
 
-def _replay_sequence(engine, trajs: List[Trajectory], max_batch: int) -> List[FrameResult]:
+def _sequence_call(engine, dev, streams, hidden=None):
+    """one Engine.forward_sequence call: streams = per stream [(Telemetry, frame)], the frames of the call either all u8
+    90 x 60 (the u8 wire path) or none of them (Engine.ingest, the float32 path) -> (vel (T,B,3) numpy, (h, c))"""
+    import torch
+    T, B = max(len(q) for q in streams), len(streams)
+    native = not _is_wire(next(im for q in streams for _, im in q))
+    imgs = None if native else np.zeros((T, B, FRAME_H, FRAME_W), np.uint8)
+    cells, raws = [], []                             # native: flat (step * B + b) cell of every frame handed to ingest
+    dv = np.zeros((T, B), np.float32)
+    qt = np.zeros((T, B, 4), np.float32)
+    qt[..., 0] = 1.0
+    for b, q in enumerate(streams):
+        for step, (tel, im) in enumerate(q):
+            if native:
+                cells.append(step * B + b)
+                raws.append(im)
+            else:
+                imgs[step, b] = im
+            # the same float32 values the step schedule hands over (a Python float divided, then rounded once)
+            dv[step, b] = tel.desired_velocity / 10.0
+            qt[step, b] = tel.quaternion
+    lengths = torch.tensor([len(q) for q in streams], dtype=torch.int32, device=dev)
+    if native:
+        imgs_dev = torch.zeros((T * B, FRAME_H, FRAME_W), dtype=torch.float32, device=dev)
+        imgs_dev[torch.tensor(cells, device=dev)] = _ingest_frames(engine, raws, dev)
+        imgs_dev = imgs_dev.reshape(T, B, FRAME_H, FRAME_W)
+    else:
+        imgs_dev = torch.from_numpy(imgs).to(dev)
+    vel, hidden = engine.forward_sequence(imgs_dev, torch.from_numpy(dv).to(dev), torch.from_numpy(qt).to(dev), hidden, lengths)
+    return vel.cpu().numpy(), hidden
+
+
+def _replay_sequence(engine, trajs: List[Trajectory], max_batch: int, resize: str = "pil") -> List[FrameResult]:
     """groups of at most max_batch trajectories, each group one Engine.forward_sequence call from zero state: the frames
-    of a trajectory are time steps, the trajectories of a group are streams"""
+    of a trajectory are time steps, the trajectories of a group are streams.  resize="gpu": a call takes one image type,
+    so a group is cut by what its trajectories hold -- those of u8 90 x 60 frames only run as one call on the u8 wire
+    path (as every group does with resize="pil"), those without any such frame as one call through Engine.ingest, and a
+    trajectory that mixes the two runs alone, one call per run of consecutive frames of a kind with its state carried
+    from call to call (equal to one call: forward_sequence does not depend on how the steps are cut).  A frame's result
+    does not depend on the streams beside it, so the cut changes no result."""
     import torch
     dev = torch.device("cuda", engine.device)
+    reader = read_frame_native if resize == "gpu" else read_frame
     out = []
     for g0 in range(0, len(trajs), max_batch):
         group = trajs[g0:g0 + max_batch]
-        seqs = []                                        # per trajectory: [(frame index, u8 frame)] of its readable frames
+        seqs = []                                        # per trajectory: [(frame index, frame)] of its readable frames
         for t in group:
-            fr = [(k, read_frame(p)) for k, p in enumerate(t.frames)]
+            fr = [(k, reader(p)) for k, p in enumerate(t.frames)]
             seqs.append([(k, im) for k, im in fr if im is not None])   # unreadable frames drop out of the sequence
-        T, B = max(len(q) for q in seqs), len(group)
-        if T == 0:
+            seen = {}
+            for _, im in seqs[-1]:
+                _check_one_size(t, seen, 0, im)
+        if max(len(q) for q in seqs) == 0:
             continue
-        imgs = np.zeros((T, B, FRAME_H, FRAME_W), np.uint8)
-        dv = np.zeros((T, B), np.float32)
-        qt = np.zeros((T, B, 4), np.float32)
-        qt[..., 0] = 1.0
+        vels = [None] * len(group)                       # per trajectory: (steps, 3)
+        kinds = [{_is_wire(im) for _, im in q} for q in seqs]
+        for want in ({True}, {False}):                   # an empty trajectory rides with the wire ones, as it always did
+            part = [b for b, kd in enumerate(kinds) if kd == want or (not kd and want == {True})]
+            if not any(seqs[b] for b in part):
+                continue
+            vel, _ = _sequence_call(engine, dev, [[(group[b].telemetry[k], im) for k, im in seqs[b]] for b in part])
+            for j, b in enumerate(part):
+                vels[b] = vel[:len(seqs[b]), j]
+        for b, kd in enumerate(kinds):
+            if len(kd) < 2:
+                continue
+            hidden, rows, q = None, [], seqs[b]
+            start = 0
+            for i in range(1, len(q) + 1):               # runs of consecutive frames of one kind
+                if i == len(q) or _is_wire(q[i][1]) != _is_wire(q[start][1]):
+                    vel, hidden = _sequence_call(engine, dev, [[(group[b].telemetry[k], im) for k, im in q[start:i]]], hidden)
+                    rows.append(vel[:, 0])
+                    start = i
+            vels[b] = np.concatenate(rows)
         for b, (t, q) in enumerate(zip(group, seqs)):
-            for step, (k, im) in enumerate(q):
-                imgs[step, b] = im
-                # the same float32 values the step schedule hands over (a Python float divided, then rounded once)
-                dv[step, b] = t.telemetry[k].desired_velocity / 10.0
-                qt[step, b] = t.telemetry[k].quaternion
-        lengths = torch.tensor([len(q) for q in seqs], dtype=torch.int32, device=dev)
-        vel, _ = engine.forward_sequence(torch.from_numpy(imgs).to(dev), torch.from_numpy(dv).to(dev),
-                                         torch.from_numpy(qt).to(dev), None, lengths)
-        vel = vel.cpu().numpy()
-        for b, (t, q) in enumerate(zip(group, seqs)):
-            out.extend(_result(t, k, vel[step, b]) for step, (k, _) in enumerate(q))
+            out.extend(_result(t, k, vels[b][step]) for step, (k, _) in enumerate(q))
     return out
 
 
 def replay(engine, root: str, max_batch: int = 1024, schedule: str = "steps") -> List[FrameResult]:
+    """replay_frames with the host resize (resize="pil"): frames that are not 90 x 60 are resized by PIL as 8 bits.  This
+    entry keeps its signature; the choice of the resize is replay_frames' own argument."""
+    return replay_frames(engine, root, max_batch, schedule, "pil")
+
+
+def replay_frames(engine, root: str, max_batch: int = 1024, schedule: str = "steps", resize: str = "pil") -> List[FrameResult]:
     """Runs every trajectory under root through `engine` (host.Engine with a full ITAViTLSTM blob) and returns
     one FrameResult per readable frame, ordered by (trajectory, frame).  Needs a GPU.
 
@@ -190,14 +288,25 @@ def replay(engine, root: str, max_batch: int = 1024, schedule: str = "steps") ->
     schedule then runs at a handful of frames per call).  The GPU part alone, Engine.forward_sequence against a loop of
     Engine.forward on frames already in device memory (tools/bench_sequence.py), takes 0.25 x the time per step at up to 8
     trajectories and 0.43 x at 128, and 12 % MORE at 1024 trajectories per group, which is why "steps" stays the default;
-    replay() itself also decodes the PNGs on the host and has not been timed.  It holds a whole group's frames in memory
-    at once."""
+    This function itself also decodes the PNGs on the host and has not been timed.  It holds a whole group's frames in memory
+    at once.
+
+    resize "pil" (default): frames that are not 90 x 60 are resized on the host (read_frame).  "gpu": they are uploaded
+    at native size and depth (u8, or 16-bit depth PNGs) and resized by Engine.ingest -- the model's own refine_inputs
+    resize, pinned by ingest_ref.ingest_reference -- then run as float32 frames; 90 x 60 u8 frames stay on the u8 wire
+    path in both schedules ("steps": a call of their own beside the float32 frames of the same step; "sequence": see
+    _replay_sequence), so their results are those of replay().  The frames of one
+    trajectory that are not 90 x 60 must share one size (ValueError otherwise)."""
     if schedule not in SCHEDULES:
         raise ValueError(f"schedule must be one of {SCHEDULES}, got {schedule!r}")
+    if resize not in RESIZES:
+        raise ValueError(f"resize must be one of {RESIZES}, got {resize!r}")
     import torch
     trajs = scan_root(root)
     if schedule == "sequence":
-        return _replay_sequence(engine, trajs, max_batch) if trajs else []
+        return _replay_sequence(engine, trajs, max_batch, resize) if trajs else []
+    reader = read_frame_native if resize == "gpu" else read_frame
+    seen = {}
     n = len(trajs)
     if n == 0:
         return []
@@ -212,20 +321,29 @@ def replay(engine, root: str, max_batch: int = 1024, schedule: str = "steps") ->
             while cursor[i] < len(t.frames) and len(batch) < max_batch:
                 k = cursor[i]
                 cursor[i] += 1
-                img = read_frame(t.frames[k])
+                img = reader(t.frames[k])
                 if img is not None:                      # unreadable frames are skipped, state untouched
+                    _check_one_size(t, seen, i, img)
                     batch.append((i, k, img))
                     break
         if not batch:
             break
-        imgs = torch.from_numpy(np.stack([b[2] for b in batch])).to(dev)
-        tel = [trajs[i].telemetry[k] for i, k, _ in batch]
-        dv = torch.tensor([t.desired_velocity / 10.0 for t in tel], dtype=torch.float32, device=dev)
-        qt = torch.tensor([t.quaternion for t in tel], dtype=torch.float32, device=dev)
-        slots = torch.tensor([b[0] for b in batch], dtype=torch.int32, device=dev)
-        vel = engine.forward_slots(imgs, dv, qt, state_h, state_c, slots).cpu().numpy()
-        for j, (i, k, _) in enumerate(batch):
-            results[i].append(_result(trajs[i], k, vel[j]))
+        # the u8 wire frames of the step, then (resize="gpu" only) its native frames through ingest: two calls on
+        # disjoint slots, and a frame's result does not depend on the batch it runs in
+        for part in ([b for b in batch if _is_wire(b[2])], [b for b in batch if not _is_wire(b[2])]):
+            if not part:
+                continue
+            if _is_wire(part[0][2]):
+                imgs = torch.from_numpy(np.stack([b[2] for b in part])).to(dev)
+            else:
+                imgs = _ingest_frames(engine, [b[2] for b in part], dev)
+            tel = [trajs[i].telemetry[k] for i, k, _ in part]
+            dv = torch.tensor([t.desired_velocity / 10.0 for t in tel], dtype=torch.float32, device=dev)
+            qt = torch.tensor([t.quaternion for t in tel], dtype=torch.float32, device=dev)
+            slots = torch.tensor([b[0] for b in part], dtype=torch.int32, device=dev)
+            vel = engine.forward_slots(imgs, dv, qt, state_h, state_c, slots).cpu().numpy()
+            for j, (i, k, _) in enumerate(part):
+                results[i].append(_result(trajs[i], k, vel[j]))
     return [r for i in range(n) for r in results[i]]
 
 

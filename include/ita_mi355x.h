@@ -141,6 +141,22 @@ int ita_encoder_layer(ita_handle h, int layer, const float* x_dev, float* y_dev,
  * of the two forms agree to ~1e-6, not bit for bit (oracle/ita_oracle.c: ita_oracle_tokenizer_u8 / ita_oracle_tokenizer). */
 int ita_tokenizer(ita_handle h, const void* image_dev, int image_dtype, float* tokens_dev, int batch, void* stream);
 
+/* refine_inputs' resize (QAT/model.py:29-30: F.interpolate(..., mode='bilinear', align_corners=False)) as a stage of its
+ * own, for frames as a camera or a data set delivers them: `batch` frames of height x width pixels of pixel_dtype, row r
+ * of frame b at src_dev + (b * frame_stride + r * row_stride) PIXELS (a cropped view of a larger buffer is passed as it
+ * is) -> frames_dev (batch,60,90) f32, contiguous, ready for ITA_IMAGE_F32.  Pixel value before blending: u8
+ * f32(code) / 255.0f (main.cpp:118,125), u16 min(f32(code) * depth_scale, 1.0f), f32 as is.  The result equals
+ * ingest_ref.py: ingest_reference bit for bit (every operation a separately rounded float32 operation).
+ * Reads only the pixels [base, base + (height-1) * row_stride + width) of each frame, whatever the alignment of base;
+ * writes only the batch * 5400 floats.  Stream-ordered, no allocation, no host synchronisation; needs no weights.
+ * ITA_ERR_INVALID_ARG before any launch: a null pointer, a bad dtype, height or width outside [1, 4096], row_stride <
+ * width, frame_stride < (height-1) * row_stride + width, a stride above 2^40 pixels, batch < 1, src_dev not aligned to
+ * its pixel size, frames_dev not aligned to 4 bytes, and for u16 a depth_scale that is not finite and positive (it is
+ * ignored for u8 and f32). */
+typedef enum ita_pixel_dtype { ITA_PIXEL_U8 = 0, ITA_PIXEL_U16 = 1, ITA_PIXEL_F32 = 2 } ita_pixel_dtype;
+int ita_ingest(ita_handle h, const void* src_dev, int pixel_dtype, int height, int width, long long row_stride,
+               long long frame_stride, float depth_scale, float* frames_dev, int batch, void* stream);
+
 /* Fusion tail (QAT/model.py:116-121): x (B,128,E) -> (B,9,16,32) flattened, row stride 4608. */
 int ita_fusion_tail(ita_handle h, const float* x_dev, float* feat_dev, int batch, void* stream);
 

@@ -24,6 +24,9 @@ def main():
     ap.add_argument("--quiet", action="store_true", help="summary only")
     ap.add_argument("--schedule", choices=("steps", "sequence"), default="steps",
                     help="steps: one batched call per time step; sequence: whole trajectories per call (Engine.forward_sequence)")
+    ap.add_argument("--resize", choices=("pil", "gpu"), default="pil",
+                    help="frames that are not 90 x 60 -- pil: resized on the host as 8 bits; gpu: uploaded at native size and depth "
+                         "(u8 or 16-bit) and resized by Engine.ingest, the model's own refine_inputs resize")
     a = ap.parse_args()
     from drone_oa_iree_vit_accelerator_amd import host, params, replay, synth
     if a.blob:
@@ -34,7 +37,7 @@ def main():
     else:
         raise SystemExit("give --blob or --synthetic-weights")
     eng = host.Engine(blob, device=a.device)
-    res = replay.replay(eng, a.root, schedule=a.schedule)
+    res = replay.replay_frames(eng, a.root, schedule=a.schedule, resize=a.resize)
     if not a.quiet:
         for r in res:
             print(f"{r.trajectory}/{r.frame}  Model Output: [{r.output[0]:.6g}, {r.output[1]:.6g}, {r.output[2]:.6g}]  "
