@@ -495,3 +495,29 @@ __device__ __forceinline__ void layernorm_lanes(float (&r)[E / 4], const WP& w, 
 #pragma unroll
   for (int i = 0; i < EC; ++i) r[i] = fmaf((r[i] - mean) * rstd, w[c0 + i], b[c0 + i]);
 }
+
+// Row epilogue of a finished block: r[EC] consecutive channels as f32 to yrow (if non-null) and, if planes are asked for,
+// as f16 hi/lo planes for the folded decoder GEMM: hi = (f16)v, lo = (f16)(v - (float)hi), 8 channels per store.
+template <int EC>
+__device__ __forceinline__ void store_row_planes(const float (&r)[EC], float* __restrict__ yrow,
+                                                 _Float16* __restrict__ hi_row, _Float16* __restrict__ lo_row) {
+  if (yrow) {
+#pragma unroll
+    for (int i = 0; i < EC; i += 4) *(f32x4*)(yrow + i) = (f32x4){r[i], r[i + 1], r[i + 2], r[i + 3]};
+  }
+  if (hi_row) {
+    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+#pragma unroll
+    for (int i = 0; i < EC; i += 8) {
+      h8 vh, vl;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const _Float16 hh = (_Float16)r[i + j];
+        vh[j] = hh;
+        vl[j] = (_Float16)(r[i + j] - (float)hh);
+      }
+      *(h8*)(hi_row + i) = vh;
+      *(h8*)(lo_row + i) = vl;
+    }
+  }
+}

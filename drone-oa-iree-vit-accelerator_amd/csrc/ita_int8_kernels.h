@@ -118,28 +118,7 @@ __device__ __forceinline__ void finish_tokens(const char* lds_outq, float so, co
     for (int i = 0; i < EC; ++i) r[i] = xr[i] + r[i];
     layernorm_lanes<E>(r, ln_w, ln_b, qtr * EC);
   }
-  if (yrow) {
-#pragma unroll
-    for (int i = 0; i < EC; i += 4) {
-      f32x4 v = {r[i], r[i + 1], r[i + 2], r[i + 3]};
-      *(f32x4*)(yrow + i) = v;
-    }
-  }
-  if (hi_row) {
-    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-#pragma unroll
-    for (int i = 0; i < EC; i += 8) {
-      h8 vh, vl;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const _Float16 hh = (_Float16)r[i + j];
-        vh[j] = hh;
-        vl[j] = (_Float16)(r[i + j] - (float)hh);
-      }
-      *(h8*)(hi_row + i) = vh;
-      *(h8*)(lo_row + i) = vl;
-    }
-  }
+  store_row_planes(r, yrow, hi_row, lo_row);
 }
 
 // 32x32 output tile, weights as the A operand (rows = output features) read from global memory,

@@ -27,8 +27,6 @@
 #include "ita_long_attn_kernel.h"
 #include "ita_ffn_f32_kernel.h"
 #include "ita_attn_f32_kernel.h"
-#include "ita_ffn_f32_e128_kernel.h"
-#include "ita_attn_f32_e128_kernel.h"
 #include "ita_ingest_kernel.h"
 
 namespace {
@@ -345,12 +343,12 @@ int launch_ffn_f32(ita_context* c, int layer, const float* x, float* y, int B, b
   a.h0_src = h0_src; a.h0_dst = h0_dst; a.slots = slots;
   const int cap = 2 * c->num_cus;
   if (c->hdr.E == 64) {
-    const int ntile = B * (128 / ItaFfnF32Lds::TT);
-    hipLaunchKernelGGL(ita_ffn_f32_kernel, dim3(ntile < cap ? ntile : cap), dim3(256), ItaFfnF32Lds::TOTAL, s, a);
+    const int ntile = B * (128 / ItaFfnF32Lds<64>::TT);
+    hipLaunchKernelGGL(ita_ffn_f32_kernel<64>, dim3(ntile < cap ? ntile : cap), dim3(256), ItaFfnF32Lds<64>::TOTAL, s, a);
   } else {   // E = 128: the weights stream as fragment images (66 KB of LDS: two workgroups per CU)
     a.w1 = L.w1p; a.w2 = L.w2p;
-    const int ntile = B * (128 / ItaFfnF32E128Lds::TT);
-    hipLaunchKernelGGL(ita_ffn_f32_e128_kernel, dim3(ntile < cap ? ntile : cap), dim3(256), ItaFfnF32E128Lds::TOTAL, s, a);
+    const int ntile = B * (128 / ItaFfnF32Lds<128>::TT);
+    hipLaunchKernelGGL(ita_ffn_f32_kernel<128>, dim3(ntile < cap ? ntile : cap), dim3(256), ItaFfnF32Lds<128>::TOTAL, s, a);
   }
   HIPCHK(hipGetLastError());
   return ITA_OK;
@@ -367,9 +365,9 @@ int launch_attn_f32(ita_context* c, int layer, const float* x, float* y, int B, 
   a.ln_w = L.n1w; a.ln_b = L.n1b; a.B = B; a.fuse_ln = fuse ? 1 : 0;
   // 130 KB (E = 64) / 96 KB (E = 128) of LDS: one workgroup per CU, frames in a grid stride
   if (c->hdr.E == 64)
-    hipLaunchKernelGGL(ita_attn_f32_kernel, dim3(B < c->num_cus ? B : c->num_cus), dim3(512), ItaAttnF32Lds::TOTAL, s, a);
+    hipLaunchKernelGGL(ita_attn_f32_kernel<64>, dim3(B < c->num_cus ? B : c->num_cus), dim3(512), ItaAttnF32Lds<64>::TOTAL, s, a);
   else
-    hipLaunchKernelGGL(ita_attn_f32_e128_kernel, dim3(B < c->num_cus ? B : c->num_cus), dim3(512), ItaAttnF32E128Lds::TOTAL, s, a);
+    hipLaunchKernelGGL(ita_attn_f32_kernel<128>, dim3(B < c->num_cus ? B : c->num_cus), dim3(512), ItaAttnF32Lds<128>::TOTAL, s, a);
   HIPCHK(hipGetLastError());
   return ITA_OK;
 }
@@ -932,9 +930,9 @@ int ita_create(ita_handle* out, int device_ordinal) {
   c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   int rc = ITA_OK;
   if ((rc = set_lds(ita_mha_kernel<64>, ItaMhaLds<64>::TOTAL))) { delete c; return rc; }
-  if ((rc = set_lds(ita_attn_f32_kernel, ItaAttnF32Lds::TOTAL))) { delete c; return rc; }
-  if ((rc = set_lds(ita_attn_f32_e128_kernel, ItaAttnF32E128Lds::TOTAL))) { delete c; return rc; }
-  if ((rc = set_lds(ita_ffn_f32_e128_kernel, ItaFfnF32E128Lds::TOTAL))) { delete c; return rc; }
+  if ((rc = set_lds(ita_attn_f32_kernel<64>, ItaAttnF32Lds<64>::TOTAL))) { delete c; return rc; }
+  if ((rc = set_lds(ita_attn_f32_kernel<128>, ItaAttnF32Lds<128>::TOTAL))) { delete c; return rc; }
+  if ((rc = set_lds(ita_ffn_f32_kernel<128>, ItaFfnF32Lds<128>::TOTAL))) { delete c; return rc; }
   if ((rc = set_lds(ita_mha_kernel<128>, ItaMhaLds<128>::TOTAL))) { delete c; return rc; }
   if ((rc = set_lds(ita_ffn_kernel<64>, ItaFfnLds<64>::TOTAL))) { delete c; return rc; }
   if ((rc = set_lds(ita_ffn_kernel<128>, ItaFfnLds<128>::TOTAL))) { delete c; return rc; }
@@ -1067,7 +1065,7 @@ int ita_load_weights(ita_handle h, const void* blob, size_t nbytes) {
       L.w1f = dptr<float>(h, NM("ffn%d.w1f"), true, &ok); L.b1f = dptr<float>(h, NM("ffn%d.b1f"), true, &ok);
       L.w2f = dptr<float>(h, NM("ffn%d.w2f"), true, &ok); L.b2f = dptr<float>(h, NM("ffn%d.b2f"), true, &ok);
       const float *w1 = hptr<float>(h, NM("ffn%d.w1f")), *w2 = hptr<float>(h, NM("ffn%d.w2f"));
-      if (E == 128 && w1 && w2) {   // ita_ffn_f32_e128_kernel streams W1 / W2 as B-fragment images
+      if (E == 128 && w1 && w2) {   // ita_ffn_f32_kernel<128> streams W1 / W2 as B-fragment images
         std::vector<float> img(F * E);
         float** dst[2] = {&L.w1p, &L.w2p};
         for (int m = 0; m < 2; ++m) {

@@ -1,5 +1,5 @@
 """The float graphs without the fusion tail on the MI355X: E = 128 (models/ITA_upsample_shuffle/model.py, two layers,
-ita_attn_f32_e128_kernel + ita_ffn_f32_e128_kernel) and E = 64 (models/ITA_single_layer/model.py, one layer).
+ita_attn_f32_kernel<128> + ita_ffn_f32_kernel<128>) and E = 64 (models/ITA_single_layer/model.py, one layer).
 ita_mha_f32 against float64, ita_ffn_f32 and whole layers bit-equal to the oracle composition, the forward against the
 reference fixtures (tests/golden/floatnt*) and FloatTwin in both tail modes, the serving forms against the eager
 forward, and the refusals that remain at E = 128."""

@@ -2,7 +2,7 @@
 """Step time of the attention-only QAT graph (models/ITA_single_layer_upsample_shuffle/QAT_only_attn/model.py: int8
 attention, float32 FFN + residual + LayerNorm2; an ITAW0002 blob) on the GPU box.  Prints one JSON line: ms per step
 and frames/s at 1024 and at 128 frames, the single-frame p50 latency, and the kernel labels.  For the kernel time of
-ita_ffn_f32_kernel run it under rocprofv3 --kernel-trace --stats (a run of its own).
+ita_ffn_f32_kernel<64> run it under rocprofv3 --kernel-trace --stats (a run of its own).
 usage: python tools/bench_only_attn.py [--layers 1|2] [--steps K]"""
 import argparse, glob, json, os, sys, time
 import numpy as np
@@ -53,5 +53,5 @@ print(json.dumps({"graph": f"QAT_only_attn E=64 {a.layers} layer(s)", "ms_per_st
                   "frames_per_s_1024": round(1024 / ms1024 * 1e3), "ms_per_step_128": round(ms128, 4),
                   "frames_per_s_128": round(128 / ms128 * 1e3), "p50_ms_1frame": round(p50, 4),
                   "kernels": ["ita_tok_stream_kernel<64,true>", "ita_stream_kernel<64,false,0,false,false,*> (attention + LN1)",
-                              "ita_ffn_f32_kernel (FFN + LN2, f32 MFMA)", "ita_gemm_f16x3_kernel (folded tail+decoder)",
+                              "ita_ffn_f32_kernel<64> (FFN + LN2, f32 MFMA)", "ita_gemm_f16x3_kernel (folded tail+decoder)",
                               "ita_lstm_head_kernel"]}))
