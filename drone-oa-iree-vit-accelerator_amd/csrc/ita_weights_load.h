@@ -1,0 +1,615 @@
+// ita_weights_load.h -- the load-time half of ita_plugin.hip: what one ita_load_weights call builds (Weights) and the
+// steps that build it from a blob, in the order the loader runs them.
+//
+// A part of ita_plugin.hip, its only includer, and not a stand-alone header: ita_plugin.hip defines fail(), HIPCHK,
+// DevBuf, K0P / K0S and the two exact-f32 launch helpers the fold uses (launch_tail, launch_gemm) ahead of the #include.
+#pragma once
+
+namespace {
+
+struct Layer {
+  const int8_t *wq, *wk, *wv, *wo, *w1, *w2;
+  const int32_t *bq, *bk, *bv, *bo, *b1, *b2;
+  float ascal[ITA_A_NSCAL], fscal[ITA_F_NSCAL];
+  const float *n1w, *n1b, *n2w, *n2b;
+  // float32 FFN of an ITAW0002 blob (the attention-only graph), device pointers; the int8 FFN fields are then null
+  bool ffn_f32 = false;
+  const float *w1f = nullptr, *b1f = nullptr, *w2f = nullptr, *b2f = nullptr;
+  DevBuf<float> w1p, w2p;   // E = 128: B-fragment images of W1 / W2 (ita_ffn_f32_frag_image)
+  // float32 attention of an ITAW0003 blob (the float graph), device pointers; the int8 attention fields are then null
+  bool attn_f32 = false;
+  const float *wqf = nullptr, *wkf = nullptr, *wvf = nullptr, *bqf = nullptr, *bkf = nullptr, *bvf = nullptr,
+              *wof = nullptr, *bof = nullptr;
+  // LDS images of the stream kernels (ita_stream_kernel.h), device copies: whole layer, whole layer with the
+  // tokenizer in front (layer 0 of the E = 64 model), attention block only
+  DevBuf<char> simg_enc, simg_tok, simg_mha;
+  unsigned fast_sites = 0;   // ITA_SITE_* bits: requantisation sites proven equal under single rounding (fast_site_ok)
+};
+
+// Everything one ita_load_weights call produces.  Raw pointers point into dblob; every DevBuf is a buffer derived from
+// it.  `w = Weights{}` releases the lot and leaves the handle unloaded.
+struct Weights {
+  bool loaded = false;
+  ita_blob_header hdr{};
+  std::vector<char> hblob;
+  DevBuf<char> dblob;
+  std::vector<Layer> layers;
+  // float layers (device pointers into dblob)
+  const float *tail_b = nullptr, *dec_w = nullptr, *dec_b = nullptr, *fc_w = nullptr, *fc_b = nullptr;
+  // derived device buffers
+  DevBuf<float> tail_wT;
+  DevBuf<char> tok_simg;                   // LDS images of ita_tok_stream_kernel: [u8 frames (conv weights x 1/65280) | f32 frames]
+  size_t tok_simg_bytes = 0;               // size of one of the two
+  DevBuf<float> wcat[3], bsum[3];
+  // split-precision (f16 hi/lo) tail: folded tail+decoder matrix and LSTM weights, pre-scaled
+  int kfold = 8192, ldfold = 8192 + 64;    // K and plane row stride of the folded GEMM (see the constants at the top of ita_plugin.hip)
+  bool folded = false;
+  DevBuf<_Float16> foldf_hi, foldf_lo;     // G0 once more as B... MFMA fragments [16][K/16][64][8], for batches of <= 32 frames
+  DevBuf<_Float16> fold_hi, fold_lo;       // [512][LDFOLD]: G0 = W_ih0[:, :512] . Wfold, rows in permuted gate order
+  DevBuf<float> fold_bias;                 // [512] gate-major: W_ih0[:, :512] . dec(tail(0)) + b_ih0 + b_hh0
+  float fold_inv_scale = 1.0f;
+  DevBuf<_Float16> lw_hi[3], lw_lo[3];     // [512][K0S | 256 | 256]
+  float lw_inv_scale[3] = {1.0f, 1.0f, 1.0f};
+};
+
+template <typename T>
+const T* dptr(const Weights& w, const char* name, bool required, bool* ok) {
+  const ita_blob_entry* e = ita_blob_find(w.hblob.data(), w.hblob.size(), name);
+  if (!e) {
+    if (required) *ok = false;
+    return nullptr;
+  }
+  return (const T*)(w.dblob + e->offset);
+}
+template <typename T>
+const T* hptr(const Weights& w, const char* name) {
+  const ita_blob_entry* e = ita_blob_find(w.hblob.data(), w.hblob.size(), name);
+  return e ? (const T*)(w.hblob.data() + e->offset) : nullptr;
+}
+
+// ---- IEEE binary16 <-> binary32 on the host (also used by the host-buffer drop-in symbols)
+float half_to_float(uint16_t hbits) {
+  const uint32_t sign = (uint32_t)(hbits & 0x8000u) << 16;
+  uint32_t exp = (hbits >> 10) & 0x1fu, man = hbits & 0x3ffu, out;
+  if (exp == 0) {
+    if (man == 0) out = sign;
+    else {
+      exp = 127 - 15 + 1;
+      while (!(man & 0x400u)) { man <<= 1; --exp; }
+      out = sign | (exp << 23) | ((man & 0x3ffu) << 13);
+    }
+  } else if (exp == 31) out = sign | 0x7f800000u | (man << 13);
+  else out = sign | ((exp + 127 - 15) << 23) | (man << 13);
+  float f;
+  memcpy(&f, &out, 4);
+  return f;
+}
+uint16_t float_to_half(float f) {   // round to nearest even
+  uint32_t x;
+  memcpy(&x, &f, 4);
+  const uint16_t sign = (uint16_t)((x >> 16) & 0x8000u);
+  const uint32_t absx = x & 0x7fffffffu;
+  if (absx >= 0x7f800000u) return (uint16_t)(sign | 0x7c00u | (absx > 0x7f800000u ? 0x200u : 0));
+  if (absx >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);            // overflow -> inf
+  if (absx < 0x33000001u) return sign;                                    // underflow -> 0
+  int exp = (int)(absx >> 23) - 127 + 15;
+  uint32_t man = (absx & 0x7fffffu) | 0x800000u;
+  int shift = 13;
+  if (exp <= 0) { shift += 1 - exp; exp = 0; }
+  uint32_t hm = man >> shift;
+  const uint32_t rem = man & ((1u << shift) - 1), halfway = 1u << (shift - 1);
+  if (rem > halfway || (rem == halfway && (hm & 1))) ++hm;
+  uint32_t outv = exp > 0 ? (((uint32_t)exp << 10) + (hm - 0x400u)) : hm;   // mantissa carry bumps the exponent
+  return (uint16_t)(sign | outv);
+}
+
+// ---- split precision: a weight tensor travels as two f16 planes of w * 2^e, e chosen so that max|w| * 2^e lies in
+// [512, 1024), which keeps the lo halves normal in f16
+int split_scale_exp(float max_abs) {
+  if (!(max_abs > 0.0f)) return 0;
+  int ex;
+  (void)frexpf(max_abs, &ex);   // max_abs = m * 2^ex, m in [0.5, 1)
+  return 10 - ex;
+}
+void split_half(float v, uint16_t* hi, uint16_t* lo) {   // v already scaled: hi = half(v), lo = half(v - hi)
+  *hi = float_to_half(v);
+  *lo = float_to_half(v - half_to_float(*hi));
+}
+float max_abs_of(const float* w, size_t n) {
+  float mx = 0.0f;
+  for (size_t i = 0; i < n; ++i) mx = fabsf(w[i]) > mx ? fabsf(w[i]) : mx;
+  return mx;
+}
+int split_upload(const std::vector<float>& w, DevBuf<_Float16>& d_hi, DevBuf<_Float16>& d_lo, float* inv_scale) {
+  const int e = split_scale_exp(max_abs_of(w.data(), w.size()));
+  const float sc = ldexpf(1.0f, e);
+  *inv_scale = ldexpf(1.0f, -e);
+  std::vector<uint16_t> hi(w.size()), lo(w.size());
+  for (size_t i = 0; i < w.size(); ++i) split_half(w[i] * sc, &hi[i], &lo[i]);
+  HIPCHK(d_hi.upload((const _Float16*)hi.data(), hi.size()));
+  HIPCHK(d_lo.upload((const _Float16*)lo.data(), lo.size()));
+  return ITA_OK;
+}
+
+// ---- stream kernels (ita_stream_kernel.h): the LDS image a workgroup copies verbatim at start-up.
+// Natural-k matrices (Wq, Wk, Wv, W1) are chunk-major [k/16][row][16].  The block output projections (Wo, fc2)
+// consume activations that were packed four 16-feature tiles at a time straight from MFMA accumulators:
+// fragment ks of lane (token, kq) holds, at byte 4j+i, feature 16(4ks+j) + 4kq + i -- so chunk 4ks+kq of their
+// image holds those input features, and image row 16et + rho is output channel (E/4)(rho>>2) + 4et + (rho&3),
+// which hands lane (token, kq) its own channels (E/4)kq + 4et + i.
+struct StreamHostParams {
+  const int8_t *wq, *wk, *wv, *wo, *w1, *w2;
+  const int32_t *bq, *bk, *bv, *bo, *b1, *b2;
+  const float *n1w, *n1b, *n2w, *n2b, *tlw, *tlb, *conv_w, *conv_b;
+};
+
+// The integer conv tables of the u8 tokenizer (ita_stream_kernel.h: ItaTokTab; definition: oracle/ita_oracle.c
+// ita_oracle_tok_quant_weights / ita_oracle_tokenizer_u8): per channel 23-bit fixed-point weights Wq = rne(w * 2^e), e = 22 -
+// exponent(max |w|), split into balanced bytes w0, w1 and the remainder w2, laid out as int8 MFMA A fragments.
+template <int E>
+void build_tok_tab(const float* conv_w, const float* conv_b, char* tab) {
+  using T = ItaTokTab<E>;
+  int32_t* ti = (int32_t*)(tab + T::TI);
+  float* ts = (float*)(tab + T::TS);
+  std::vector<int8_t> dig((size_t)E * 49 * 3);
+  for (int c = 0; c < E; ++c) {
+    float mx = 0.0f;
+    for (int k = 0; k < 49; ++k) mx = fmaxf(mx, fabsf(conv_w[(size_t)c * 49 + k]));
+    int e = 0;
+    if (mx > 0.0f) {
+      int ex;
+      (void)frexpf(mx, &ex);
+      e = 22 - ex;
+    }
+    long long s0 = 0, s1 = 0, s2 = 0;
+    for (int k = 0; k < 49; ++k) {
+      const int32_t W = (int32_t)rintf(ldexpf(conv_w[(size_t)c * 49 + k], e));
+      const int32_t w0 = ((W + 128) & 255) - 128, W1r = (W - w0) >> 8;
+      const int32_t w1 = ((W1r + 128) & 255) - 128, w2 = (W1r - w1) >> 8;
+      dig[((size_t)c * 49 + k) * 3 + 0] = (int8_t)w0; dig[((size_t)c * 49 + k) * 3 + 1] = (int8_t)w1; dig[((size_t)c * 49 + k) * 3 + 2] = (int8_t)w2;
+      s0 += w0; s1 += w1; s2 += w2;
+    }
+    // the kernel feeds a ^ 0x80 = a - 128: S0 = S0' + 128 sum w0, S1 = S1' + 128 (sum w1 + sum w0), ... (L = S0 + 256 S1, H = S2 + 256 S3)
+    ti[c] = (int32_t)(128 * s0 + 256 * 128 * (s1 + s0));
+    ti[E + c] = (int32_t)(128 * (s2 + s1) + 256 * 128 * s2);
+    const float sc = ldexpf(1.0f, -e) / 65280.0f;
+    ts[c] = sc; ts[E + c] = 65536.0f * sc; ts[2 * E + c] = conv_b[c];
+  }
+  for (int ct = 0; ct < T::NCT; ++ct)
+    for (int j = 0; j < 3; ++j)
+      for (int lane = 0; lane < 64; ++lane) {
+        const int rho = lane & 15, kq = lane >> 4, ch = (E / 4) * (rho >> 2) + 4 * ct + (rho & 3);
+        for (int b = 0; b < 16; ++b) {
+          const int t = 4 * b + kq;        // slot b of k-group kq <-> tap 4 b + kq (the lane that blends it); taps >= 49: zero
+          tab[T::TW + ((ct * 3 + j) * 64 + lane) * 16 + b] = t < 49 ? (char)dig[((size_t)ch * 49 + t) * 3 + j] : 0;
+        }
+      }
+}
+
+template <int E, bool FFN, bool TOK>
+int build_stream_image(const StreamHostParams& p, DevBuf<char>& out) {
+  using L = ItaStreamLds<E, FFN, TOK>;
+  constexpr int P = 192, F = 256;
+  std::vector<char> im(L::GIMAGE, 0);   // (E = 128 with FFN: fc1 / fc2 weights lie behind the LDS part)
+  auto natural = [&](int off, const int8_t* w, int rows, int kb) {
+    for (int r = 0; r < rows; ++r)
+      for (int k = 0; k < kb; ++k) im[off + (((k >> 4) * rows + r) << 4) + (k & 15)] = (char)w[(size_t)r * kb + k];
+  };
+  auto fragment = [&](int off, const int8_t* w, int nks, int kb) {   // w: [E][kb], kb = 64 * nks
+    for (int ks = 0; ks < nks; ++ks)
+      for (int kq = 0; kq < 4; ++kq)
+        for (int et = 0; et < E / 16; ++et)
+          for (int rho = 0; rho < 16; ++rho) {
+            const int ch = (E / 4) * (rho >> 2) + 4 * et + (rho & 3);
+            for (int j = 0; j < 4; ++j)
+              for (int i = 0; i < 4; ++i)
+                im[off + (((4 * ks + kq) * E + et * 16 + rho) << 4) + 4 * j + i] =
+                    (char)w[(size_t)ch * kb + (4 * ks + j) * 16 + 4 * kq + i];
+          }
+  };
+  natural(L::WQ, p.wq, P, E); natural(L::WK, p.wk, P, E); natural(L::WV, p.wv, P, E);
+  fragment(L::WO, p.wo, 3, P);
+  int32_t* bias = (int32_t*)(im.data() + L::BIAS);
+  memcpy(bias, p.bq, P * 4); memcpy(bias + P, p.bk, P * 4); memcpy(bias + 2 * P, p.bv, P * 4);
+  memcpy(bias + 3 * P, p.bo, E * 4);
+  float* ln = (float*)(im.data() + L::LNP);
+  if (p.n1w && p.n1b) { memcpy(ln, p.n1w, E * 4); memcpy(ln + E, p.n1b, E * 4); }
+  auto bias_accumulators = [&]() {   // accumulators start at ITA_ACC_BIAS + bias (ita_device.h: scale_clamp_b)
+    for (int i = 0; i < L::NBIAS; ++i) bias[i] = (int32_t)((uint32_t)bias[i] + (uint32_t)ITA_ACC_BIAS);
+  };
+  if constexpr (FFN) {
+    natural(L::W12G ? L::GW1 : L::W1, p.w1, F, E);
+    fragment(L::W12G ? L::GW2 : L::W2, p.w2, 4, F);
+    memcpy(bias + 3 * P + E, p.b1, F * 4); memcpy(bias + 3 * P + E + F, p.b2, E * 4);
+    memcpy(ln + 2 * E, p.n2w, E * 4); memcpy(ln + 3 * E, p.n2b, E * 4);
+  }
+  if constexpr (TOK) {
+    memcpy(ln + 4 * E, p.tlw, E * 4); memcpy(ln + 5 * E, p.tlb, E * 4);
+    build_tok_tab<E>(p.conv_w, p.conv_b, im.data() + L::CW);
+    int32_t* tap = (int32_t*)(im.data() + L::TAP);
+    for (int t = 0; t < 52; ++t) tap[t] = t < 49 ? (t / 7) * 96 + (t % 7) : 0;
+  }
+  bias_accumulators();
+  {
+    int32_t* vb4 = (int32_t*)(im.data() + L::VB4);
+    for (int d = 0; d < P; ++d)
+      for (int i = 0; i < 4; ++i) vb4[4 * d + i] = bias[2 * P + d];
+  }
+  HIPCHK(out.upload(im.data(), im.size()));
+  return ITA_OK;
+}
+
+// The stream kernels read an int32 accumulator as the float 1.5 * 2^23 + sum, which is exact while |sum| < 2^22.
+// Worst case of a Linear row: sum_k |w| * 128 + |bias| (inputs are int8 codes).  QK^T (192 * 128 * 128) and A.V
+// (<= 255 * 128) are inside the range by construction.  A blob outside it runs on the block kernels instead.
+bool stream_range_ok(const StreamHostParams& p, int E, bool ffn, const float* ascal, const float* fscal) {
+  // ... and the requantised value travels as a 16-bit integer between the rounding and the u8 saturation
+  // (ita_device.h: rq_pack16_v3), so |acc * mult| + 128 has to stay below 2^15 as well: same worst case times the multiplier.
+  auto rows_ok = [](const int8_t* w, const int32_t* b, int rows, int k, float mult) {
+    if (!(mult > 0.0f)) return false;
+    for (int r = 0; r < rows; ++r) {
+      long long sum = 0;
+      for (int i = 0; i < k; ++i) sum += w[(size_t)r * k + i] < 0 ? -(long long)w[(size_t)r * k + i] : w[(size_t)r * k + i];
+      const long long bb = b[r] < 0 ? -(long long)b[r] : b[r];
+      if (sum * 128 + bb >= (1ll << 22)) return false;
+      if ((double)(sum * 128 + bb) * (double)mult >= 32000.0) return false;
+    }
+    return true;
+  };
+  if (!(ascal[ITA_A_ML] > 0.0f) || 192.0 * 128 * 128 * (double)ascal[ITA_A_ML] >= 32000.0) return false;   // Q K^T
+  // A V: the integer softmax's probabilities sum to at most 255 per row (each is floor(num * 255 / sum(num))), so |sum p v| <= 255 * 128
+  if (!(ascal[ITA_A_MC] > 0.0f) || 255.0 * 128 * (double)ascal[ITA_A_MC] >= 32000.0) return false;
+  return rows_ok(p.wq, p.bq, 192, E, ascal[ITA_A_MQ]) && rows_ok(p.wk, p.bk, 192, E, ascal[ITA_A_MK]) &&
+         rows_ok(p.wv, p.bv, 192, E, ascal[ITA_A_MV]) && rows_ok(p.wo, p.bo, E, 192, ascal[ITA_A_MO]) &&
+         (!ffn || (rows_ok(p.w1, p.b1, 256, E, fscal[ITA_F_M1]) && rows_ok(p.w2, p.b2, E, 256, fscal[ITA_F_M2])));
+}
+
+// Single-rounding permission of one requantisation site.  The reference computes rne(fl(acc * m)) -- two roundings; the
+// fast form of the stream kernels computes fl(acc * m + magic) in one fused multiply-add -- one rounding.  They can differ
+// only for an accumulator value whose exact product lies within half an ulp of a rounding tie without being one.  The set of
+// accumulator values that matter is small (|acc * m| below the clamp range: a few hundred thousand integers), so it is
+// simply enumerated, on the host, in the arithmetic the GPU instructions perform (IEEE f32 multiply, add and fma; this file
+// is compiled with -ffp-contract=off): a site is fast only if no value differs after the clamp.
+bool fast_site_ok(float m) {
+  if (!(m > 0.0f) || !(m < 1.0f)) return false;
+  const double lim = 130.0 / (double)m;
+  if (lim > 4.0e6) return false;   // outside the biased-float accumulator range: not a stream-kernel blob anyway
+  const long long A = (long long)lim + 2;
+  auto code = [](float t) {        // low 16 bits of the pattern = r + 128 (two's complement), then the u8 saturation
+    unsigned u;
+    memcpy(&u, &t, 4);
+    const int v = (int)(int16_t)(u & 0xffffu);
+    return v < 0 ? 0 : v > 255 ? 255 : v;
+  };
+  for (long long a = -A; a <= A; ++a) {
+    const float x = (float)a;
+    const float y = x * m;
+    if (code(y + ITA_MAGIC128_F) != code(fmaf(x, m, ITA_MAGIC128_F))) return false;
+  }
+  return true;
+}
+unsigned fast_sites_of(const float* ascal) {
+  unsigned mask = 0;
+  const int idx[6] = {ITA_A_MQ, ITA_A_MK, ITA_A_MV, ITA_A_ML, ITA_A_MC, ITA_A_MO};
+  for (int i = 0; i < 6; ++i)
+    if (fast_site_ok(ascal[idx[i]])) mask |= 1u << i;   // bit order = ITA_SITE_Q, _K, _V, _L, _C, _O
+  return mask;
+}
+
+// ---- the steps of ita_load_weights, in the order the loader runs them; each returns an ITA_* code, and the loader
+// resets the Weights on any failure, so none of them cleans up after itself
+struct BlobKinds { int ffn, attn; };   // ita_blob_ffn_kind / ita_blob_attn_kind: 0 = int8, 1 = float32
+
+#define NM(fmt) (snprintf(nm, sizeof nm, fmt, i), nm)   // tensor name of layer i, in the local buffer nm
+
+// step 1: the header and the tensor table, before anything of the handle is touched
+int check_blob(const void* blob, size_t nbytes, ita_blob_header* hdr_out, BlobKinds* kinds) {
+  const int ffn_kind = nbytes < sizeof(ita_blob_header) ? -1 : ita_blob_ffn_kind(blob, nbytes);
+  const int attn_kind = nbytes < sizeof(ita_blob_header) ? -1 : ita_blob_attn_kind(blob, nbytes);
+  if (ffn_kind < 0 || attn_kind < 0) return fail(ITA_ERR_BAD_BLOB, "not an ITAW0001 / ITAW0002 / ITAW0003 blob");
+  ita_blob_header hdr;
+  memcpy(&hdr, blob, sizeof hdr);
+  if (hdr.n_tensors < 0 || sizeof(hdr) + (size_t)hdr.n_tensors * sizeof(ita_blob_entry) > nbytes)
+    return fail(ITA_ERR_BAD_BLOB, "tensor table exceeds the blob");
+  if ((hdr.E != 64 && hdr.E != 128) || hdr.S != 128 || hdr.P != 192 || hdr.F != 256 || hdr.H != 1 ||
+      hdr.num_layers < 1 || hdr.num_layers > 16)
+    return fail(ITA_ERR_UNSUPPORTED, "kernels are built for E in {64,128}, S=128, P=192, F=256, H=1");
+  // the float graph (ITAW0003) runs at E = 64 with its fusion tail, and at E = 128 without one (ITA_upsample_shuffle)
+  if (attn_kind == 1 && hdr.E != 64 && hdr.has_tail)
+    return fail(ITA_ERR_UNSUPPORTED, "the float32 graph's fusion tail (ITAW0003) is built for E = 64; at E = 128 it runs without one");
+  if (attn_kind == 0 && ffn_kind == 1 && hdr.E != 64) return fail(ITA_ERR_UNSUPPORTED, "the float32 FFN (ITAW0002) is built for E = 64");
+  const ita_blob_entry* e = (const ita_blob_entry*)((const char*)blob + sizeof(hdr));
+  for (int i = 0; i < hdr.n_tensors; ++i)
+    if (e[i].offset < 0 || e[i].nbytes < 0 || (size_t)e[i].offset + (size_t)e[i].nbytes > nbytes || (e[i].offset & 15))
+      return fail(ITA_ERR_BAD_BLOB, "tensor out of bounds or misaligned");
+  char bad[32];
+  const int v = ita_blob_validate(blob, nbytes, bad);
+  if (v) return fail(ITA_ERR_BAD_BLOB, std::string(v == -2 ? "required tensor missing: " : v == -3 ? "tensor has the wrong dtype or size: " : "malformed blob ") + bad);
+  *hdr_out = hdr;
+  *kinds = BlobKinds{ffn_kind, attn_kind};
+  return ITA_OK;
+}
+
+// step 2: the layers' and the float tail's pointers into the uploaded blob (w.hdr, w.hblob and w.dblob are in place)
+int bind_layers(Weights& w, BlobKinds kinds) {
+  const ita_blob_header& hdr = w.hdr;
+  bool ok = true;
+  w.layers = std::vector<Layer>(hdr.num_layers);
+  char nm[40];
+  auto expect = [&](const char* name, size_t bytes) {
+    const ita_blob_entry* e = ita_blob_find(w.hblob.data(), w.hblob.size(), name);
+    if (e && (size_t)e->nbytes != bytes) ok = false;
+  };
+  const size_t E = hdr.E, P = hdr.P, F = hdr.F;
+  for (int i = 0; i < hdr.num_layers; ++i) {
+    Layer& L = w.layers[i];
+    if (kinds.attn == 1) {   // float32 attention (sizes checked by ita_blob_validate)
+      L.attn_f32 = true;
+      L.wqf = dptr<float>(w, NM("attn%d.wqf"), true, &ok); L.wkf = dptr<float>(w, NM("attn%d.wkf"), true, &ok);
+      L.wvf = dptr<float>(w, NM("attn%d.wvf"), true, &ok); L.bqf = dptr<float>(w, NM("attn%d.bqf"), true, &ok);
+      L.bkf = dptr<float>(w, NM("attn%d.bkf"), true, &ok); L.bvf = dptr<float>(w, NM("attn%d.bvf"), true, &ok);
+      L.wof = dptr<float>(w, NM("attn%d.wof"), true, &ok); L.bof = dptr<float>(w, NM("attn%d.bof"), true, &ok);
+    } else {
+      expect(NM("attn%d.wq"), P * E); expect(NM("attn%d.wo"), E * P); expect(NM("attn%d.bq"), P * 4);
+      expect(NM("attn%d.bo"), E * 4); expect(NM("attn%d.scal"), ITA_A_NSCAL * 4);
+      L.wq = dptr<int8_t>(w, NM("attn%d.wq"), true, &ok); L.wk = dptr<int8_t>(w, NM("attn%d.wk"), true, &ok);
+      L.wv = dptr<int8_t>(w, NM("attn%d.wv"), true, &ok); L.wo = dptr<int8_t>(w, NM("attn%d.wo"), true, &ok);
+      L.bq = dptr<int32_t>(w, NM("attn%d.bq"), true, &ok); L.bk = dptr<int32_t>(w, NM("attn%d.bk"), true, &ok);
+      L.bv = dptr<int32_t>(w, NM("attn%d.bv"), true, &ok); L.bo = dptr<int32_t>(w, NM("attn%d.bo"), true, &ok);
+      const float* as = hptr<float>(w, NM("attn%d.scal"));
+      if (!as) { ok = false; break; }
+      memcpy(L.ascal, as, sizeof L.ascal);
+    }
+    if (kinds.ffn == 1) {   // float32 FFN (sizes checked by ita_blob_validate)
+      L.ffn_f32 = true;
+      L.w1f = dptr<float>(w, NM("ffn%d.w1f"), true, &ok); L.b1f = dptr<float>(w, NM("ffn%d.b1f"), true, &ok);
+      L.w2f = dptr<float>(w, NM("ffn%d.w2f"), true, &ok); L.b2f = dptr<float>(w, NM("ffn%d.b2f"), true, &ok);
+      const float *w1 = hptr<float>(w, NM("ffn%d.w1f")), *w2 = hptr<float>(w, NM("ffn%d.w2f"));
+      if (E == 128 && w1 && w2) {   // ita_ffn_f32_kernel<128> streams W1 / W2 as B-fragment images
+        std::vector<float> img(F * E);
+        ita_ffn_f32_frag_image(w1, (int)F, (int)E, img.data());
+        const bool up1 = L.w1p.upload(img.data(), img.size()) == hipSuccess;
+        ita_ffn_f32_frag_image(w2, (int)E, (int)F, img.data());
+        if (!up1 || L.w2p.upload(img.data(), img.size()) != hipSuccess)
+          return fail(ITA_ERR_HIP, "uploading the float32 FFN fragment images failed");
+      }
+    } else {
+      expect(NM("ffn%d.w1"), F * E); expect(NM("ffn%d.w2"), E * F); expect(NM("ffn%d.scal"), ITA_F_NSCAL * 4);
+      L.w1 = dptr<int8_t>(w, NM("ffn%d.w1"), true, &ok); L.w2 = dptr<int8_t>(w, NM("ffn%d.w2"), true, &ok);
+      L.b1 = dptr<int32_t>(w, NM("ffn%d.b1"), true, &ok); L.b2 = dptr<int32_t>(w, NM("ffn%d.b2"), true, &ok);
+      const float* fs = hptr<float>(w, NM("ffn%d.scal"));
+      if (!fs) { ok = false; break; }
+      memcpy(L.fscal, fs, sizeof L.fscal);
+    }
+    L.n1w = dptr<float>(w, NM("norm1_%d.w"), false, &ok); L.n1b = dptr<float>(w, NM("norm1_%d.b"), false, &ok);
+    L.n2w = dptr<float>(w, NM("norm2_%d.w"), false, &ok); L.n2b = dptr<float>(w, NM("norm2_%d.b"), false, &ok);
+  }
+  if (!ok) return fail(ITA_ERR_BAD_BLOB, "a required block tensor is missing or mis-sized");
+  w.tail_b = dptr<float>(w, "tail.conv_b", false, &ok);
+  w.dec_w = dptr<float>(w, "dec.w", false, &ok); w.dec_b = dptr<float>(w, "dec.b", false, &ok);
+  w.fc_w = dptr<float>(w, "fc.w", false, &ok); w.fc_b = dptr<float>(w, "fc.b", false, &ok);
+  return ITA_OK;
+}
+
+// step 3: the LDS images of the stream kernels, for every int8-attention layer whose accumulators stay in range
+int build_stream_images(Weights& w) {
+  const ita_blob_header& hdr = w.hdr;
+  char nm[40];
+  for (int i = 0; i < hdr.num_layers; ++i) {
+    Layer& L = w.layers[i];
+    if (L.attn_f32) continue;   // no int8 attention: no stream images (ita_attn_f32_kernel + ita_ffn_f32_kernel)
+    StreamHostParams sp{};
+    sp.wq = hptr<int8_t>(w, NM("attn%d.wq")); sp.wk = hptr<int8_t>(w, NM("attn%d.wk")); sp.wv = hptr<int8_t>(w, NM("attn%d.wv"));
+    sp.wo = hptr<int8_t>(w, NM("attn%d.wo")); sp.w1 = hptr<int8_t>(w, NM("ffn%d.w1")); sp.w2 = hptr<int8_t>(w, NM("ffn%d.w2"));
+    sp.bq = hptr<int32_t>(w, NM("attn%d.bq")); sp.bk = hptr<int32_t>(w, NM("attn%d.bk")); sp.bv = hptr<int32_t>(w, NM("attn%d.bv"));
+    sp.bo = hptr<int32_t>(w, NM("attn%d.bo")); sp.b1 = hptr<int32_t>(w, NM("ffn%d.b1")); sp.b2 = hptr<int32_t>(w, NM("ffn%d.b2"));
+    sp.n1w = hptr<float>(w, NM("norm1_%d.w")); sp.n1b = hptr<float>(w, NM("norm1_%d.b"));
+    sp.n2w = hptr<float>(w, NM("norm2_%d.w")); sp.n2b = hptr<float>(w, NM("norm2_%d.b"));
+    sp.tlw = hptr<float>(w, "tok.ln_w"); sp.tlb = hptr<float>(w, "tok.ln_b");
+    sp.conv_w = hptr<float>(w, "tok.conv_w"); sp.conv_b = hptr<float>(w, "tok.conv_b");
+    int rc = ITA_OK;
+    // a float-FFN layer gets the attention image only: its FFN is ita_ffn_f32_kernel (no simg_enc / simg_tok)
+    const bool lns = !L.ffn_f32 && sp.n1w && sp.n1b && sp.n2w && sp.n2b && stream_range_ok(sp, hdr.E, true, L.ascal, L.fscal);
+    if (!stream_range_ok(sp, hdr.E, false, L.ascal, L.fscal)) continue;   // no images: this layer runs on the block kernels
+    L.fast_sites = fast_sites_of(L.ascal);
+    if (hdr.E == 64) {
+      rc = build_stream_image<64, false, false>(sp, L.simg_mha);
+      if (!rc && lns) rc = build_stream_image<64, true, false>(sp, L.simg_enc);
+      if (!rc && lns && i == 0 && sp.tlw && sp.tlb && sp.conv_w && sp.conv_b) rc = build_stream_image<64, true, true>(sp, L.simg_tok);
+    } else {
+      rc = build_stream_image<128, false, false>(sp, L.simg_mha);
+      if (!rc && lns) rc = build_stream_image<128, true, false>(sp, L.simg_enc);
+    }
+    if (rc) return rc;
+  }
+  return ITA_OK;
+}
+#undef NM
+
+// step 4: the LDS images of ita_tok_stream_kernel<E, U8>, when the blob has the conv weights, the bias and the LayerNorm
+int build_tokenizer_images(Weights& w) {
+  const int Ei = w.hdr.E;
+  const float *cw = hptr<float>(w, "tok.conv_w"), *cb = hptr<float>(w, "tok.conv_b"), *lw = hptr<float>(w, "tok.ln_w"),
+              *lb = hptr<float>(w, "tok.ln_b");
+  if (!cw || !cb || !lw || !lb) return ITA_OK;
+  // [0]: u8 frames (integer conv tables), [1]: f32 frames (f32 MFMA A fragments); each padded to the larger of the two
+  const int nct = Ei / 16;
+  const size_t one8 = Ei == 64 ? (size_t)ItaTokStreamLds<64, true>::IMAGE : (size_t)ItaTokStreamLds<128, true>::IMAGE;
+  const size_t onef = Ei == 64 ? (size_t)ItaTokStreamLds<64, false>::IMAGE : (size_t)ItaTokStreamLds<128, false>::IMAGE;
+  const size_t one = ((one8 > onef ? one8 : onef) + 15) & ~(size_t)15;
+  std::vector<char> im(2 * one, 0);
+  {
+    char* b0 = im.data();
+    memcpy(b0, lw, Ei * 4); memcpy(b0 + Ei * 4, lb, Ei * 4);
+    int off_tap;
+    if (Ei == 64) { build_tok_tab<64>(cw, cb, b0 + ItaTokStreamLds<64, true>::CW); off_tap = ItaTokStreamLds<64, true>::TAP; }
+    else { build_tok_tab<128>(cw, cb, b0 + ItaTokStreamLds<128, true>::CW); off_tap = ItaTokStreamLds<128, true>::TAP; }
+    int32_t* tap = (int32_t*)(b0 + off_tap);
+    for (int t = 0; t < 52; ++t) tap[t] = t < 49 ? (t / 7) * 96 + (t % 7) : 0;
+  }
+  {
+    char* b0 = im.data() + one;
+    const int off_cw = 2 * Ei * 4, off_cb = off_cw + 13 * nct * 64 * 4, off_tap = off_cb + Ei * 4;
+    memcpy(b0, lw, Ei * 4); memcpy(b0 + Ei * 4, lb, Ei * 4);
+    float* cwf = (float*)(b0 + off_cw);
+    for (int st = 0; st < 13; ++st)
+      for (int ct = 0; ct < nct; ++ct)
+        for (int lane = 0; lane < 64; ++lane) {
+          const int t = 4 * st + (lane >> 4), rho = lane & 15, ch = (Ei / 4) * (rho >> 2) + 4 * ct + (rho & 3);
+          cwf[(st * nct + ct) * 64 + lane] = t < 49 ? cw[(size_t)ch * 49 + t] : 0.0f;
+        }
+    memcpy(b0 + off_cb, cb, Ei * 4);
+    int32_t* tap = (int32_t*)(b0 + off_tap);
+    for (int t = 0; t < 52; ++t) tap[t] = t < 49 ? (t / 7) * 96 + (t % 7) : 0;
+  }
+  w.tok_simg_bytes = one;
+  HIPCHK(w.tok_simg.upload(im.data(), im.size()));
+  return ITA_OK;
+}
+
+// step 5: the exact-f32 fusion tail's conv3x3 weights re-laid [c][ky][kx][o -> 12], so one tap's 9 output weights are contiguous
+int build_tail_weights(Weights& w) {
+  const float* cw = hptr<float>(w, "tail.conv_w");
+  if (!cw) return ITA_OK;
+  const int cin = w.hdr.E / 4 + w.hdr.E;
+  std::vector<float> wT((size_t)cin * 9 * 12, 0.0f);
+  for (int o = 0; o < 9; ++o)
+    for (int c = 0; c < cin; ++c)
+      for (int k = 0; k < 9; ++k) wT[((size_t)c * 9 + k) * 12 + o] = cw[((size_t)o * cin + c) * 9 + k];
+  HIPCHK(w.tail_wT.upload(wT.data(), wT.size()));
+  return ITA_OK;
+}
+
+// step 6: LSTM [W_ih | W_hh] concatenated along k (layer 0 zero padded to K0P) and b_ih + b_hh for the exact-f32 path,
+// and the split-precision A fragments of the LSTM kernels
+int build_lstm_weights(Weights& w) {
+  if (!hptr<float>(w, "lstm.w_ih0")) return ITA_OK;
+  for (int l = 0; l < 3; ++l) {
+    char a[32], b[32], ci[32], d[32];
+    snprintf(a, sizeof a, "lstm.w_ih%d", l); snprintf(b, sizeof b, "lstm.w_hh%d", l);
+    snprintf(ci, sizeof ci, "lstm.b_ih%d", l); snprintf(d, sizeof d, "lstm.b_hh%d", l);
+    const float *wih = hptr<float>(w, a), *whh = hptr<float>(w, b), *bih = hptr<float>(w, ci), *bhh = hptr<float>(w, d);
+    if (!wih || !whh || !bih || !bhh) return fail(ITA_ERR_BAD_BLOB, "incomplete LSTM parameters");
+    const int in = l == 0 ? 517 : 128, kp = l == 0 ? K0P : 256;
+    std::vector<float> wc((size_t)512 * kp, 0.0f), bs(512);
+    for (int j = 0; j < 512; ++j) {
+      memcpy(&wc[(size_t)j * kp], wih + (size_t)j * in, sizeof(float) * in);
+      memcpy(&wc[(size_t)j * kp + in], whh + (size_t)j * 128, sizeof(float) * 128);
+      bs[j] = bih[j] + bhh[j];
+    }
+    HIPCHK(w.wcat[l].upload(wc.data(), wc.size()));
+    HIPCHK(w.bsum[l].upload(bs.data(), bs.size()));
+    // split-precision planes, rows permuted to r' = ut*32 + gate*8 + u so that one MFMA tile holds
+    // i,f,g,o of 8 units.  Layers 1, 2: the concatenated [W_ih | W_hh].  Layer 0: only what the folded
+    // GEMM does not cover, [W_hh0 (128) | W_ih0[:,512] (desvel) | W_ih0[:,513:517] (quat) | 0] (K0S wide).
+    const int kf = l == 0 ? K0S : 256;
+    std::vector<float> wf((size_t)512 * kf, 0.0f);
+    for (int rp = 0; rp < 512; ++rp) {
+      const int j = ((rp >> 3) & 3) * 128 + (rp >> 5) * 8 + (rp & 7);
+      if (l == 0) {
+        memcpy(&wf[(size_t)rp * kf], whh + (size_t)j * 128, sizeof(float) * 128);
+        memcpy(&wf[(size_t)rp * kf + 128], wih + (size_t)j * 517 + 512, sizeof(float) * 5);
+      } else {
+        memcpy(&wf[(size_t)rp * kf], &wc[(size_t)j * kp], sizeof(float) * 256);
+      }
+    }
+    // ... and stored as the A fragments the LSTM kernels load: [ut][k-range][k-step][lane (row r, k half h)][8]
+    const int nsw = l == 0 ? 1 : 4, nss = l == 0 ? kf / 16 : 4;   // k-ranges (one per wave) x k-steps of 16
+    std::vector<float> wfrag(wf.size());
+    for (int ut = 0; ut < 16; ++ut)
+      for (int kw = 0; kw < nsw; ++kw)
+        for (int st = 0; st < nss; ++st)
+          for (int lane = 0; lane < 64; ++lane)
+            for (int j = 0; j < 8; ++j)
+              wfrag[((((size_t)ut * nsw + kw) * nss + st) * 64 + lane) * 8 + j] =
+                  wf[(size_t)(ut * 32 + (lane & 31)) * kf + (kw * nss + st) * 16 + 8 * (lane >> 5) + j];
+    const int rc = split_upload(wfrag, w.lw_hi[l], w.lw_lo[l], &w.lw_inv_scale[l]);
+    if (rc) return rc;
+  }
+  return ITA_OK;
+}
+
+// step 7, device part: Wfold^T [K][512] (K = 128 E) in hmt and the folded bias in hb.  With a fusion tail, unit impulses
+// go through the exact f32 kernels, bias-free (PixelShuffle/Upsample/concat/conv3x3, then the decoder Linear), and
+// dec(tail(0)) is the bias; without one (models/ITA/QAT/model.py:80-81: the decoder reads the flattened tokens) Wfold is
+// the decoder matrix itself.  Then one fold further, since the decoder output feeds only LSTM layer 0:
+//   G0^T[k][j] = sum_n Wfold^T[k][n] * W_ih0[j][n]        (wcat[0] holds W_ih0 in its first 517 columns)
+int fold_matrix(const Weights& w, int num_cus, std::vector<float>& hmt, std::vector<float>& hb) {
+  const int CH = 1024, KFOLD = w.kfold;
+  const bool has_tail = w.hdr.has_tail != 0;
+  DevBuf<float> imp, feat, mt, zero;
+  HIPCHK(imp.alloc((size_t)(has_tail ? CH : 512) * KFOLD));
+  HIPCHK(feat.alloc((size_t)CH * 4608));
+  HIPCHK(mt.alloc((size_t)KFOLD * 512));
+  HIPCHK(zero.alloc(16));
+  HIPCHK(hipMemset(zero, 0, sizeof(float) * 16));
+  int rc = ITA_OK;
+  if (has_tail) {
+    auto tail = [&](const float* bias, int B) { return launch_tail(num_cus, w.hdr.E, w.tail_wT, bias, imp, feat, 4608, B, nullptr); };
+    for (int c0 = 0; c0 < KFOLD; c0 += CH) {   // bias-free pass: column i of Wfold = dec_nobias(tail_nobias(e_i))
+      const size_t n = (size_t)CH * KFOLD;
+      hipLaunchKernelGGL(ita_impulse_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, imp, CH, KFOLD, c0);
+      if ((rc = tail(zero, CH))) return rc;
+      if ((rc = launch_gemm(feat, 4608, w.dec_w, 4608, nullptr, mt + (size_t)c0 * 512, 512, CH, 512, 4608, nullptr))) return rc;
+    }
+    // bias' = dec(tail(0)) with the real biases
+    HIPCHK(hipMemset(imp, 0, sizeof(float) * KFOLD));
+    if ((rc = tail(w.tail_b, 1))) return rc;
+    if ((rc = launch_gemm(feat, 4608, w.dec_w, 4608, w.dec_b, imp, 512, 1, 512, 4608, nullptr))) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(hb.data(), imp, 512 * sizeof(float), hipMemcpyDeviceToHost));
+  } else {
+    // Wfold^T[k][n] = dec_w[n][k]: transposed on the host (once, at load time); bias' = the decoder bias
+    const float *dw = hptr<float>(w, "dec.w"), *db = hptr<float>(w, "dec.b");
+    for (int n = 0; n < 512; ++n)
+      for (int k = 0; k < KFOLD; ++k) hmt[(size_t)k * 512 + n] = dw[(size_t)n * KFOLD + k];
+    HIPCHK(hipMemcpy(mt, hmt.data(), hmt.size() * sizeof(float), hipMemcpyHostToDevice));
+    memcpy(hb.data(), db, 512 * sizeof(float));
+  }
+  // computed with the exact f32 GEMM; the buffer that held the impulses is reused for the result
+  if ((rc = launch_gemm(mt, 512, w.wcat[0], K0P, nullptr, imp, 512, KFOLD, 512, 512, nullptr))) return rc;
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(hmt.data(), imp, hmt.size() * sizeof(float), hipMemcpyDeviceToHost));
+  return ITA_OK;
+}
+
+// step 7: the folded tail + decoder + W_ih0 matrix as split-precision planes, and its bias
+int build_fold(Weights& w, int num_cus) {
+  const int KFOLD = w.kfold, LDFOLD = w.ldfold;
+  std::vector<float> hmt((size_t)KFOLD * 512), hb(512);
+  int rc = fold_matrix(w, num_cus, hmt, hb);   // (its device temporaries are gone before the planes are allocated)
+  if (rc) return rc;
+  // rows of the GEMM weight in the permuted gate order r' = ut*32 + gate*8 + u (ita_lstm_head_kernel)
+  std::vector<float> wf((size_t)512 * LDFOLD, 0.0f);
+  for (int rp = 0; rp < 512; ++rp) {
+    const int j = ((rp >> 3) & 3) * 128 + (rp >> 5) * 8 + (rp & 7);
+    for (int k = 0; k < KFOLD; ++k) wf[(size_t)rp * LDFOLD + k] = hmt[(size_t)k * 512 + j];
+  }
+  if ((rc = split_upload(wf, w.fold_hi, w.fold_lo, &w.fold_inv_scale))) return rc;
+  {
+    // the same values in fragment order for ita_gemm_f16x3_tiny_kernel (same scale: max |w| is the same)
+    std::vector<float> wfr((size_t)512 * KFOLD);
+    for (int nt = 0; nt < 16; ++nt)
+      for (int st = 0; st < KFOLD / 16; ++st)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int j = 0; j < 8; ++j)
+            wfr[(((size_t)nt * (KFOLD / 16) + st) * 64 + lane) * 8 + j] =
+                wf[(size_t)(nt * 32 + (lane & 31)) * LDFOLD + st * 16 + 8 * (lane >> 5) + j];
+    float inv2 = 0.0f;
+    if ((rc = split_upload(wfr, w.foldf_hi, w.foldf_lo, &inv2))) return rc;
+    if (inv2 != w.fold_inv_scale) return fail(ITA_ERR_UNSUPPORTED, "fragment copy of the folded weights got a different scale");
+  }
+  // bias'' = W_ih0[:, :512] . bias' + b_ih0 + b_hh0   (gate-major order)
+  const float *wih0 = hptr<float>(w, "lstm.w_ih0"), *bih0 = hptr<float>(w, "lstm.b_ih0"), *bhh0 = hptr<float>(w, "lstm.b_hh0");
+  std::vector<float> b2(512);
+  for (int j = 0; j < 512; ++j) {
+    double acc = (double)bih0[j] + (double)bhh0[j];
+    for (int n = 0; n < 512; ++n) acc += (double)wih0[(size_t)j * 517 + n] * (double)hb[n];
+    b2[j] = (float)acc;
+  }
+  HIPCHK(w.fold_bias.upload(b2.data(), b2.size()));
+  w.folded = true;
+  return ITA_OK;
+}
+
+}  // namespace
