@@ -1,11 +1,12 @@
 // ita_lstm_seq_kernel.h -- the LSTM head with a time loop: T steps of layers 0, 1, 2 and the fc in one launch.
 //
-// ita_lstm_head_kernel (ita_f16x3_kernels.h) advances the recurrence by one step per launch.  When the frames of a stream
+// ita_lstm_head_kernel (ita_lstm_head_kernel.h) advances the recurrence by one step per launch.  When the frames of a stream
 // are known in advance, the image-only part of T steps x B streams (tokenizer, encoder, folded GEMM) runs as ONE batch of
 // T * B frames, time-major, and only the recurrence is serial: this kernel walks it inside one launch.
 //
-// Same decomposition as the head kernel: workgroup = 4 waves = one unit tile ut (8 hidden units) x one tile ft of 32 STREAMS,
-// for all three layers; 1-D grid of 16 * ceil(B / 32), id = 16 ft + ut.  What stays in the workgroup across the steps
+// The decomposition (workgroup = one unit tile ut x one tile ft of 32 STREAMS, id = 16 ft + ut), the meeting protocol and
+// the arithmetic are the head kernel's: both kernels are built from the device functions of ita_lstm_head_kernel.h, which
+// is why T steps here equal T launches of the head kernel bit for bit.  What stays in the workgroup across the steps
 // instead of being reloaded: the weight fragments of all three layers (layer 0's 9 k-steps x hi / lo in LDS, 18 KB;
 // layers 1, 2: 4 + 4 k-steps x hi / lo per wave in registers), the biases, the fc weights (LDS), and h and c of the
 // (stream, unit) pairs the workgroup owns -- c never leaves its owner until the last step.  Per step a workgroup reads
@@ -24,10 +25,7 @@
 // pairs is the same arithmetic.  The initial state takes the same road: before the first step every owner publishes its
 // units of h_in into the parity-1 buffers ("step -1") and the tile meets once, so every step of the loop is alike.
 //
-// Meetings: the head kernel's protocol, unchanged (payload stored sc1 -> every wave drains vmcnt(0) -> workgroup barrier ->
-// one relaxed agent-scope add; one lane polls with s_sleep, bounded by ITA_HEAD_SPIN_TICKS; every load of handed-off bytes
-// an sc1 buffer load; no release / acquire fence; nothing written with a scalar-memory instruction).  One counter per
-// stream tile counts up through the launch.  With nt steps a workgroup arrives 2 nt + 2 times:
+// Meetings.  One counter per stream tile counts up through the launch.  With nt steps a workgroup arrives 2 nt + 2 times:
 //   M0        after publishing the initial h                              (polled for 16)
 //   M1(t)     after layer 0 of step t has published h0(t)                 (polled for 16 (2t + 2))
 //   M2(t)     after layer 1 of step t has published h1(t)                 (polled for 16 (2t + 3))
@@ -38,8 +36,7 @@
 //     polled.  L1(t) needs h0(t): M1(t); and h1(t-1): M2(t-1), polled earlier.  L2(t) needs h1(t): M2(t); and h2(t-1): every
 //     workgroup stored it in L2(t-1) and drained the stores before arriving at M1(t), which precedes M2(t).
 //   * fc(t) runs on workgroup ut = t % 16 behind M1(t+1): every workgroup's h2(t) stores were drained before that arrival.
-// On a timeout the polling workgroup sets the device error word (ITA_HEAD_TIMEOUT of ita_head_status) and returns from the
-// kernel at once, so a stuck tile costs one timeout, not one per step.
+// On a timeout the polling workgroup returns from the kernel at once, so a stuck tile costs one timeout, not one per step.
 //
 // Why two copies by step parity are enough (and one is not).  A buffer written in step t+1 is the one that held step t-1.
 //   P1: the writer, L0(t+1), follows the writer's poll of M2(t) and so of M1(t); every workgroup arrived at M1(t) after its
@@ -53,22 +50,16 @@
 // State aliasing: the state is updated in place.  A workgroup reads only the state of its own (stream, unit) pairs, before
 // its first arrival, and writes the same elements once, after the last step.
 //
-// Progress, for any grid size: as for the head kernel.  A stream tile waits for nothing outside itself; ids are dealt
-// round-robin over the eight XCDs and every XCD dispatches its share in id order, so the members of the lowest unfinished
-// tile are dispatched before any workgroup of a later tile on the same XCD, and that tile completes and frees its slots as
-// long as an XCD can hold two of these workgroups.  The compiler gives this kernel 256 VGPRs + 60 AGPRs (no scratch; with a
-// budget of 256 it spills 48), so a CU holds one workgroup and an XCD 32: at more than 512 streams the tiles run in rounds.
+// Progress: the head kernel's argument, with one difference.  The compiler gives this kernel 256 VGPRs + 60 AGPRs (no
+// scratch; with a budget of 256 it spills 48), so a CU holds one workgroup and an XCD 32: at more than 512 streams the
+// tiles run in rounds.
 //
 // Lengths (optional): stream b takes part in the steps t < lengths[b] of the whole sequence (this launch starts at step
 // t0).  Behind its length a stream's h and c keep their values (the owner re-publishes the old h) and its velocity row is
 // not written.  A tile runs  min(nsteps, max over its streams of lengths - t0)  steps: the bound is tile-uniform, so its
 // sixteen workgroups agree on the number of meetings.
-//
-// The arithmetic of every output is the head kernel's: partials summed in z order, the K = 144 remainder on one wave's MFMA
-// chain, layers 1, 2 ((p0 + p1) + p2) + p3, fast sigmoid / tanh, the fc's fmaf chain from the bias -- T steps here equal T
-// launches of the head kernel bit for bit.
 #pragma once
-#include "ita_f16x3_kernels.h"
+#include "ita_lstm_head_kernel.h"
 
 constexpr int ITA_SEQ_PLANE = 2 * 4 * 64 * 16;                    // one f16 plane, k < 128, of one stream tile: 8 KB
 constexpr int ITA_SEQ_P1 = 0, ITA_SEQ_P2 = 2 * ITA_SEQ_PLANE;     // [hi | lo] each
@@ -77,12 +68,7 @@ constexpr int ITA_SEQ_PARITY = ITA_SEQ_H2 + 32 * 128 * 4;         // bytes per p
 constexpr int ITA_SEQ_TILE = 2 * ITA_SEQ_PARITY;                  // bytes of hand-off buffers per stream tile
 
 struct ItaLstmSeqArgs {
-  const float* part; float inv_fold_scale;            // [NSPLIT][nsteps * B][512] raw split-K accumulators, row t * B + b
-  const _Float16 *w0_hi, *w0_lo; float inv_wscale0;   // as ItaLstmHeadArgs
-  const float* bias0;
-  const _Float16 *w1_hi, *w1_lo, *w2_hi, *w2_lo;
-  float inv_wscale1, inv_wscale2;
-  const float *bsum1, *bsum2;
+  ItaLstmModelArgs m;                                 // part: [NSPLIT][nsteps * B][512], row t * B + b
   const float *desvel, *quat;                         // (nsteps, B), (nsteps, B, 4): this launch's steps
   float *state_h, *state_c;                           // (3, B, 128): in the state before the first step, out after the last
   const int* lengths; int t0;                         // optional (B), in steps of the whole sequence; this launch starts at t0
@@ -91,6 +77,7 @@ struct ItaLstmSeqArgs {
   unsigned *cnt, *err;                                // the head kernel's arrival counters (0 between launches) and error word
   int B, nsteps;
 };
+static_assert(offsetof(ItaLstmSeqArgs, desvel) == 104, "kernel-argument layout");
 
 // byte offset within a plane of the 8-element group holding k (k % 8 == 0 or 4: + 2 (k & 7)) of stream r of the tile
 __device__ __forceinline__ int ita_seq_plane_off(int r, int k) {
@@ -129,8 +116,8 @@ __global__ __launch_bounds__(256, 1) void ita_lstm_seq_kernel(const ItaLstmSeqAr
   f32x4 c0 = {0.0f, 0.0f, 0.0f, 0.0f}, h0 = {0.0f, 0.0f, 0.0f, 0.0f}, bz[4];
   int len0 = 0;
   if (wave == 0) {
-    const _Float16* wfr_hi = a.w0_hi + ((size_t)ut * 9 * 64 + lane) * 8;
-    const _Float16* wfr_lo = a.w0_lo + ((size_t)ut * 9 * 64 + lane) * 8;
+    const _Float16* wfr_hi = a.m.w0_hi + ((size_t)ut * 9 * 64 + lane) * 8;
+    const _Float16* wfr_lo = a.m.w0_lo + ((size_t)ut * 9 * 64 + lane) * 8;
 #pragma unroll
     for (int s = 0; s < 9; ++s) {
       w0s[0][s][lane] = *(const f16x8*)(wfr_hi + s * 512);
@@ -139,7 +126,7 @@ __global__ __launch_bounds__(256, 1) void ita_lstm_seq_kernel(const ItaLstmSeqAr
     c0 = *(const f32x4*)(a.state_c + (size_t)bc0 * 128 + u0);
     h0 = *(const f32x4*)(a.state_h + (size_t)bc0 * 128 + u0);
 #pragma unroll
-    for (int gt = 0; gt < 4; ++gt) bz[gt] = *(const f32x4*)(a.bias0 + gt * 128 + u0);
+    for (int gt = 0; gt < 4; ++gt) bz[gt] = *(const f32x4*)(a.m.bias0 + gt * 128 + u0);
     len0 = b0 < B ? (a.lengths ? a.lengths[b0] - a.t0 : a.nsteps) : 0;
   }
   // layers 1, 2: this wave's k-range of the weights; thread t finishes (stream t / 8, unit t % 8)
@@ -147,10 +134,10 @@ __global__ __launch_bounds__(256, 1) void ita_lstm_seq_kernel(const ItaLstmSeqAr
   f16x8 w1h[4], w1l[4], w2h[4], w2l[4];
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
-    w1h[s] = *(const f16x8*)(a.w1_hi + wo + 512 * s);
-    w1l[s] = *(const f16x8*)(a.w1_lo + wo + 512 * s);
-    w2h[s] = *(const f16x8*)(a.w2_hi + wo + 512 * s);
-    w2l[s] = *(const f16x8*)(a.w2_lo + wo + 512 * s);
+    w1h[s] = *(const f16x8*)(a.m.w1_hi + wo + 512 * s);
+    w1l[s] = *(const f16x8*)(a.m.w1_lo + wo + 512 * s);
+    w2h[s] = *(const f16x8*)(a.m.w2_hi + wo + 512 * s);
+    w2l[s] = *(const f16x8*)(a.m.w2_lo + wo + 512 * s);
   }
   const int ef = tid >> 3, eu = tid & 7, eb = f0 + ef, un = ut * 8 + eu, ebc = min(eb, B - 1);
   const size_t lstride = (size_t)B * 128;
@@ -160,8 +147,8 @@ __global__ __launch_bounds__(256, 1) void ita_lstm_seq_kernel(const ItaLstmSeqAr
   float bs1[4], bs2[4];
 #pragma unroll
   for (int gt = 0; gt < 4; ++gt) {
-    bs1[gt] = a.bsum1[gt * 128 + un];
-    bs2[gt] = a.bsum2[gt * 128 + un];
+    bs1[gt] = a.m.bsum1[gt * 128 + un];
+    bs2[gt] = a.m.bsum2[gt * 128 + un];
   }
   if (tid < 96) *(f32x4*)&fw[tid >> 5][4 * (tid & 31)] = *(const f32x4*)(a.fc_w + 4 * tid);
   // step 0's partials (wave w covers streams 8w .. 8w+7, lane (stream 8w + lane / 8, columns 4 (lane % 8) ..)), desvel, quat
@@ -171,10 +158,8 @@ __global__ __launch_bounds__(256, 1) void ita_lstm_seq_kernel(const ItaLstmSeqAr
   {
     f32x4 pz[NS];
 #pragma unroll
-    for (int z = 0; z < NS; ++z) pz[z] = *(const f32x4*)(a.part + z * zstride + prow);
-    ps = pz[0];
-#pragma unroll
-    for (int z = 1; z < NS; ++z) ps += pz[z];
+    for (int z = 0; z < NS; ++z) pz[z] = *(const f32x4*)(a.m.part + z * zstride + prow);
+    ps = sum_partials(pz);
   }
   f32x4 q = {0.0f, 0.0f, 0.0f, 0.0f};
   float dv = 0.0f;
@@ -186,58 +171,32 @@ __global__ __launch_bounds__(256, 1) void ita_lstm_seq_kernel(const ItaLstmSeqAr
   // publishing the h this workgroup owns into the buffers of parity `par`
   auto publish_h0 = [&](int par) {   // wave 0: 8-byte sc1 stores
     f16x4 x_hi, x_lo;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      _Float16 x, y;
-      split_f16(h0[i], x, y); x_hi[i] = x; x_lo[i] = y;
-    }
+    split_f16x4(h0, x_hi, x_lo);
     const int o = par * ITA_SEQ_PARITY + ITA_SEQ_P1 + ita_seq_plane_off(r, u0);
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, x_hi), ho, o, 0, ITA_SC1);
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, x_lo), ho, o + ITA_SEQ_PLANE, 0, ITA_SC1);
+    ita_store_sc1_f16x4(x_hi, ho, o);
+    ita_store_sc1_f16x4(x_lo, ho, o + ITA_SEQ_PLANE);
   };
   auto publish_h1 = [&](int par) {   // every thread; gathered in LDS into one 16-byte sc1 store per stream and plane
-    _Float16 x, y;
-    split_f16(h1, x, y);
-    pub[0][ef][eu] = x;
-    pub[1][ef][eu] = y;
-    __syncthreads();
+    ita_gather_h8(h1, pub, ef, eu);
     if (wave == 0 && h == 0) {
       const int o = par * ITA_SEQ_PARITY + ITA_SEQ_P2 + ita_seq_plane_off(r, ut * 8);
-      const f16x8 vh = *(const f16x8*)&pub[0][r][0], vl = *(const f16x8*)&pub[1][r][0];
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, vh), ho, o, 0, ITA_SC1);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, vl), ho, o + ITA_SEQ_PLANE, 0, ITA_SC1);
+      ita_publish_h8(pub, r, ho, o, ho, o + ITA_SEQ_PLANE);
     }
   };
   auto publish_h2 = [&](int par) {   // every thread: 4-byte sc1 stores
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, h2), ho, par * ITA_SEQ_PARITY + ITA_SEQ_H2 + (ef * 128 + un) * 4,
                                           0, ITA_SC1);
   };
-  // arrival: every wave's payload stores (and every earlier load) have completed
-  auto arrive = [&]() -> unsigned {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    unsigned prev = 0;
-    if (tid == 0) prev = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return prev;
-  };
   // the fc of one step from the H2 buffer of parity `par`: vel rows of step t (all threads of the workgroup)
   auto fc_step = [&](int par, int t) {
     f32x4 hr[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      hr[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                            ho, par * ITA_SEQ_PARITY + ITA_SEQ_H2 + (((i * 256 + tid) >> 5) * 128 + 4 * (tid & 31)) * 4, 0, ITA_SC1));
+      hr[i] = ita_load_sc1_f32x4(ho, par * ITA_SEQ_PARITY + ITA_SEQ_H2 + (((i * 256 + tid) >> 5) * 128 + 4 * (tid & 31)) * 4);
 #pragma unroll
     for (int i = 0; i < 4; ++i) *(f32x4*)&hs[(i * 256 + tid) >> 5][4 * (tid & 31)] = hr[i];
     __syncthreads();
-    if (tid < 96) {
-      const int fr = tid / 3, o = tid - 3 * fr, b = f0 + fr;
-      if (b < B && (!a.lengths || a.t0 + t < a.lengths[b])) {
-        float acc = a.fc_b[o];
-        for (int k = 0; k < 128; ++k) acc = fmaf(hs[fr][k], fw[o][k], acc);
-        a.vel[((size_t)t * B + b) * 3 + o] = acc;
-      }
-    }
+    lstm_fc_rows(hs, fw, a.fc_b, a.vel, (size_t)t * B, f0, B, tid, [&](int b) { return !a.lengths || a.t0 + t < a.lengths[b]; });
     __syncthreads();   // hs is the accumulators' storage of the next layer
   };
 
@@ -245,7 +204,7 @@ __global__ __launch_bounds__(256, 1) void ita_lstm_seq_kernel(const ItaLstmSeqAr
   if (wave == 0) publish_h0(1);
   publish_h1(1);
   publish_h2(1);
-  (void)arrive();
+  (void)ita_head_arrive(a.cnt, ft, tid);
   if (tid == 0) flag = ita_head_poll(cnt, 16u, a.err) ? 1u : 0u;
   __syncthreads();
   if (!flag) return;
@@ -258,30 +217,19 @@ __global__ __launch_bounds__(256, 1) void ita_lstm_seq_kernel(const ItaLstmSeqAr
     if (wave == 0) {
 #pragma unroll
       for (int s = 0; s < 8; ++s) {
-        xh[s] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(ho, prv * ITA_SEQ_PARITY + ITA_SEQ_P1 + (s * 64 + lane) * 16, 0, ITA_SC1));
-        xl[s] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(ho, prv * ITA_SEQ_PARITY + ITA_SEQ_P1 + ITA_SEQ_PLANE + (s * 64 + lane) * 16, 0, ITA_SC1));
+        xh[s] = ita_load_sc1_f16x8(ho, prv * ITA_SEQ_PARITY + ITA_SEQ_P1 + (s * 64 + lane) * 16);
+        xl[s] = ita_load_sc1_f16x8(ho, prv * ITA_SEQ_PARITY + ITA_SEQ_P1 + ITA_SEQ_PLANE + (s * 64 + lane) * 16);
       }
     }
     __syncthreads();
     if (wave == 0) {
-      f32x16 acc;
+      f32x16 acc = {};
 #pragma unroll
-      for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
-#pragma unroll
-      for (int s = 0; s < 8; ++s) {
-        const f16x8 wh = w0s[0][s][lane], wl = w0s[1][s][lane];
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh[s], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl[s], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh[s], acc, 0, 0, 0);
-      }
+      for (int s = 0; s < 8; ++s) acc = mfma_f16x3(acc, w0s[0][s][lane], w0s[1][s][lane], xh[s], xl[s]);
       {   // k = 128 .. 132: [desvel / 10 | quat]
-        f32x4 x0 = {0.0f, 0.0f, 0.0f, 0.0f};
-        float x1 = 0.0f;
-        if (h == 0) {
-          x0 = (f32x4){dv / 10.0f, q.x, q.y, q.z};
-          x1 = q.w;
-        }
-        f16x8 yh, yl;
+        float x1;
+        const f32x4 x0 = lstm_l0_extra(dv, q, h, x1);
+        f16x8 yh, yl;   // eight f32 -> hi, lo (not shared)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const float x = j < 4 ? x0[j & 3] : (j == 4 ? x1 : 0.0f);
@@ -289,21 +237,17 @@ __global__ __launch_bounds__(256, 1) void ita_lstm_seq_kernel(const ItaLstmSeqAr
           yh[j] = hi;
           yl[j] = (_Float16)(x - (float)hi);
         }
-        const f16x8 wh = w0s[0][8][lane], wl = w0s[1][8][lane];
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, yh, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, yl, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, yh, acc, 0, 0, 0);
+        acc = mfma_f16x3(acc, w0s[0][8][lane], w0s[1][8][lane], yh, yl);
       }
       const bool on = t < len0;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        float g[4];
+        float g[4];   // the pre-activation is not shared
 #pragma unroll
         for (int gt = 0; gt < 4; ++gt)
-          g[gt] = (pt[r][gt * 8 + 4 * h + i] * a.inv_fold_scale + acc[4 * gt + i] * a.inv_wscale0) + bz[gt][i];
-        const float ig = lstm_sigmoid_fast(g[0]), fg = lstm_sigmoid_fast(g[1]), cg = lstm_tanh_fast(g[2]), og = lstm_sigmoid_fast(g[3]);
-        const float c = fmaf(fg, c0[i], ig * cg);
-        const float hn = og * lstm_tanh_fast(c);
+          g[gt] = (pt[r][gt * 8 + 4 * h + i] * a.m.inv_fold_scale + acc[4 * gt + i] * a.m.inv_wscale0) + bz[gt][i];
+        float c, hn;
+        lstm_cell_fast(g[0], g[1], g[2], g[3], c0[i], c, hn);
         if (on) {
           c0[i] = c;
           h0[i] = hn;
@@ -311,14 +255,14 @@ __global__ __launch_bounds__(256, 1) void ita_lstm_seq_kernel(const ItaLstmSeqAr
       }
       publish_h0(par);
     }
-    (void)arrive();   // M1(t)
+    (void)ita_head_arrive(a.cnt, ft, tid);   // M1(t)
     // the next step's partials, desvel and quat: in flight while the meeting waits
     f32x4 pz[NS];
     const bool more = t + 1 < nt;
     if (more) {
       const size_t step = (size_t)(t + 1) * B;
 #pragma unroll
-      for (int z = 0; z < NS; ++z) pz[z] = *(const f32x4*)(a.part + z * zstride + step * 512 + prow);
+      for (int z = 0; z < NS; ++z) pz[z] = *(const f32x4*)(a.m.part + z * zstride + step * 512 + prow);
       if (wave == 0) {
         q = *(const f32x4*)(a.quat + (step + bc0) * 4);
         dv = a.desvel[step + bc0];
@@ -331,7 +275,7 @@ __global__ __launch_bounds__(256, 1) void ita_lstm_seq_kernel(const ItaLstmSeqAr
       if (tid == 0) flag = ita_head_poll(cnt, 16u * (2u * t + 1u + l), a.err) ? 1u : 0u;
       __syncthreads();
       if (!flag) return;
-      if (l == 1 && more) {   // the prefetched partials have arrived while the meeting waited
+      if (l == 1 && more) {   // the prefetched partials have arrived while the meeting waited (not sum_partials: not shared)
         ps = pz[0];
 #pragma unroll
         for (int z = 1; z < NS; ++z) ps += pz[z];
@@ -344,8 +288,8 @@ __global__ __launch_bounds__(256, 1) void ita_lstm_seq_kernel(const ItaLstmSeqAr
                          (((wave & 1) * 4) * 64 + lane) * 16;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-          fah[s] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(ho, base + 1024 * s, 0, ITA_SC1));
-          fal[s] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(ho, base + ITA_SEQ_PLANE + 1024 * s, 0, ITA_SC1));
+          fah[s] = ita_load_sc1_f16x8(ho, base + 1024 * s);
+          fal[s] = ita_load_sc1_f16x8(ho, base + ITA_SEQ_PLANE + 1024 * s);
         }
       } else {
         // waves 2, 3 of layer 2: h2 of the previous step, f32 rows split here (lane (r, h): k = 64 (wave - 2) + 16 s + 8 h ..)
@@ -353,11 +297,11 @@ __global__ __launch_bounds__(256, 1) void ita_lstm_seq_kernel(const ItaLstmSeqAr
         const int base = prv * ITA_SEQ_PARITY + ITA_SEQ_H2 + (r * 128 + 64 * (wave - 2) + 8 * h) * 4;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-          hx[s][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ho, base + 64 * s, 0, ITA_SC1));
-          hx[s][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ho, base + 64 * s + 16, 0, ITA_SC1));
+          hx[s][0] = ita_load_sc1_f32x4(ho, base + 64 * s);
+          hx[s][1] = ita_load_sc1_f32x4(ho, base + 64 * s + 16);
         }
 #pragma unroll
-        for (int s = 0; s < 4; ++s)
+        for (int s = 0; s < 4; ++s)   // eight f32 -> hi, lo (not shared)
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
             _Float16 hi, lo;
@@ -366,40 +310,29 @@ __global__ __launch_bounds__(256, 1) void ita_lstm_seq_kernel(const ItaLstmSeqAr
             fal[s][j] = lo;
           }
       }
-      f32x16 acc;
+      f32x16 acc = {};
 #pragma unroll
-      for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const f16x8 fwh = l == 1 ? w1h[s] : w2h[s], fwl = l == 1 ? w1l[s] : w2l[s];
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fwl, fah[s], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fwh, fal[s], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fwh, fah[s], acc, 0, 0, 0);
-      }
+      for (int s = 0; s < 4; ++s) acc = mfma_f16x3(acc, l == 1 ? w1h[s] : w2h[s], l == 1 ? w1l[s] : w2l[s], fah[s], fal[s]);
+      // the four waves' accumulators through LDS to thread (stream ef, unit eu)'s four gates (not shared beyond lstm_sum4)
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc4[wave][e][lane] = acc[e];
       __syncthreads();
-      // C layout of a tile: accumulator e of lane (r, h) = gate e / 4 of unit (e % 4) + 4 h, stream r
       float gsum[4];
       const int pl = ef + 32 * (eu >> 2);
 #pragma unroll
-      for (int gte = 0; gte < 4; ++gte) {
-        const int e = 4 * gte + (eu & 3);
-        gsum[gte] = ((acc4[0][e][pl] + acc4[1][e][pl]) + acc4[2][e][pl]) + acc4[3][e][pl];
-      }
-      const float iws = l == 1 ? a.inv_wscale1 : a.inv_wscale2;
+      for (int gte = 0; gte < 4; ++gte) gsum[gte] = lstm_sum4(acc4, 4 * gte + (eu & 3), pl);
+      const float iws = l == 1 ? a.m.inv_wscale1 : a.m.inv_wscale2;
       const float* bs = l == 1 ? bs1 : bs2;
       const float gi = gsum[0] * iws + bs[0], gf = gsum[1] * iws + bs[1], gg = gsum[2] * iws + bs[2], go = gsum[3] * iws + bs[3];
-      const float ig = lstm_sigmoid_fast(gi), fg = lstm_sigmoid_fast(gf), cg = lstm_tanh_fast(gg), og = lstm_sigmoid_fast(go);
-      const float c = fmaf(fg, l == 1 ? c1 : c2, ig * cg);
-      const float hn = og * lstm_tanh_fast(c);
+      float c, hn;
+      lstm_cell_fast(gi, gf, gg, go, l == 1 ? c1 : c2, c, hn);
       if (t < lenE) {
         if (l == 1) { c1 = c; h1 = hn; }
         else        { c2 = c; h2 = hn; }
       }
       if (l == 1) {
         publish_h1(par);
-        (void)arrive();   // M2(t)
+        (void)ita_head_arrive(a.cnt, ft, tid);   // M2(t)
       } else {
         publish_h2(par);   // drained by the next arrival: M1(t+1) or the end
       }
@@ -416,7 +349,7 @@ __global__ __launch_bounds__(256, 1) void ita_lstm_seq_kernel(const ItaLstmSeqAr
     a.state_c[so1] = c1; a.state_h[so1] = h1;
     a.state_c[so2] = c2; a.state_h[so2] = h2;
   }
-  const unsigned prev = arrive();
+  const unsigned prev = ita_head_arrive(a.cnt, ft, tid);
   if (tid == 0) flag = prev == 16u * (2u * nt + 2u) - 1u ? 1u : 0u;
   __syncthreads();
   if (!flag) return;

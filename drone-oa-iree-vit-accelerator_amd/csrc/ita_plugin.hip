@@ -21,6 +21,7 @@
 #include "../../include/ita_weights.h"
 #include "../../include/ita_wire.h"
 #include "ita_f16x3_kernels.h"
+#include "ita_lstm_head_kernel.h"
 #include "ita_lstm_seq_kernel.h"
 #include "ita_f32_kernels.h"
 #include "ita_int8_kernels.h"
@@ -1023,17 +1024,41 @@ int ita_fusion_tail_large(ita_handle h, const float* x, float* out, int batch, i
   }
 }
 
+// what the LSTM head and its sequence form read of the model, and the GEMM's split-K partials `part`
+static ItaLstmModelArgs lstm_model_args(const ita_context* h, const float* part) {
+  const auto& w = h->w;
+  ItaLstmModelArgs m;
+  m.part = part;          m.inv_fold_scale = w.fold_inv_scale;
+  m.w0_hi = w.lw_hi[0];   m.w0_lo = w.lw_lo[0];   m.inv_wscale0 = w.lw_inv_scale[0];
+  m.bias0 = w.fold_bias;
+  m.w1_hi = w.lw_hi[1];   m.w1_lo = w.lw_lo[1];   m.inv_wscale1 = w.lw_inv_scale[1];
+  m.w2_hi = w.lw_hi[2];   m.w2_lo = w.lw_lo[2];   m.inv_wscale2 = w.lw_inv_scale[2];
+  m.bsum1 = w.bsum[1];    m.bsum2 = w.bsum[2];
+  return m;
+}
+// both kernels' grid: sixteen workgroups (unit tiles) per tile of 32 frames / streams
+static dim3 lstm_grid(int B) { return dim3(16 * ((B + 31) / 32)); }
+
 // the LSTM head behind the folded GEMM: layers 0, 1, 2 and the fc in one launch (ita_lstm_head_kernel), reading the
 // GEMM's split-K partials `part`.  State rows are slots[b] (else b) of (3, rows, 128) arrays with layer stride lstride;
 // h_out / c_out may alias h_in / c_in.
 static int launch_lstm_head(ita_context* h, const float* part, const float* desvel, const float* quat, const float* h_in,
                             const float* c_in, float* h_out, float* c_out, size_t lstride, float* vel, int B,
                             const int* slots, hipStream_t s) {
-  ItaLstmHeadArgs p{part, h->w.fold_inv_scale, h->w.lw_hi[0], h->w.lw_lo[0], h->w.lw_inv_scale[0], h->w.fold_bias,
-                    h->w.lw_hi[1], h->w.lw_lo[1], h->w.lw_hi[2], h->w.lw_lo[2], h->w.lw_inv_scale[1], h->w.lw_inv_scale[2],
-                    h->w.bsum[1], h->w.bsum[2], desvel, quat, h_in, c_in, h_out, c_out, lstride,
+  ItaLstmHeadArgs p{lstm_model_args(h, part), desvel, quat, h_in, c_in, h_out, c_out, lstride,
                     h->ws.c1_hi, h->ws.c1_lo, h->ws.c2_hi, h->ws.c2_lo, h->w.fc_w, h->w.fc_b, vel, h->ws.head_sync + ITA_HEAD_CNT_STRIDE, h->ws.head_sync, B, slots};
-  hipLaunchKernelGGL(ita_lstm_head_kernel<NSPLIT>, dim3(16 * ((B + 31) / 32)), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(ita_lstm_head_kernel<NSPLIT>, lstm_grid(B), dim3(256), 0, s, p);
+  HIPCHK(hipGetLastError());
+  return ITA_OK;
+}
+
+// its sequence form (ita_lstm_seq_kernel): n steps of B streams from partial buffer 0, whose row t * B + b is stream b's
+// frame of step t; desvel, quat and vel point at the first of these steps, which is step t0 of the sequence `lengths` counts
+static int launch_lstm_seq(ita_context* h, const float* desvel, const float* quat, float* state_h, float* state_c,
+                           const int* lengths, int t0, float* vel, int B, int n, hipStream_t s) {
+  ItaLstmSeqArgs p{lstm_model_args(h, h->ws.part), desvel, quat, state_h, state_c, lengths, t0, h->ws.seq_ho,
+                   h->w.fc_w, h->w.fc_b, vel, h->ws.head_sync + ITA_HEAD_CNT_STRIDE, h->ws.head_sync, B, n};
+  hipLaunchKernelGGL(ita_lstm_seq_kernel<NSPLIT>, lstm_grid(B), dim3(256), 0, s, p);
   HIPCHK(hipGetLastError());
   return ITA_OK;
 }
@@ -1368,12 +1393,7 @@ int ita_vitlstm_sequence(ita_handle h, const void* image, int image_dtype, const
     const int n = std::min(Tc, n_steps - t0);
     const size_t row0 = (size_t)t0 * B;
     if ((rc = front_impl(h, (const char*)image + row0 * frame_bytes, image_dtype, n * B, 0, stream, nullptr))) return rc;
-    ItaLstmSeqArgs p{h->ws.part, h->w.fold_inv_scale, h->w.lw_hi[0], h->w.lw_lo[0], h->w.lw_inv_scale[0], h->w.fold_bias,
-                     h->w.lw_hi[1], h->w.lw_lo[1], h->w.lw_hi[2], h->w.lw_lo[2], h->w.lw_inv_scale[1], h->w.lw_inv_scale[2],
-                     h->w.bsum[1], h->w.bsum[2], desvel + row0, quat + row0 * 4, state_h, state_c, lengths, t0, h->ws.seq_ho,
-                     h->w.fc_w, h->w.fc_b, vel + row0 * 3, h->ws.head_sync + ITA_HEAD_CNT_STRIDE, h->ws.head_sync, B, n};
-    hipLaunchKernelGGL(ita_lstm_seq_kernel<NSPLIT>, dim3(16 * ((B + 31) / 32)), dim3(256), 0, s, p);
-    HIPCHK(hipGetLastError());
+    if ((rc = launch_lstm_seq(h, desvel + row0, quat + row0 * 4, state_h, state_c, lengths, t0, vel + row0 * 3, B, n, s))) return rc;
   }
   h->ws.front_cap[0] = 0;   // partial buffer 0 holds time-major rows of several steps: not something ita_vitlstm_back may read
   return ITA_OK;

@@ -579,7 +579,7 @@ int build_fold(Weights& w, int num_cus) {
   std::vector<float> hmt((size_t)KFOLD * 512), hb(512);
   int rc = fold_matrix(w, num_cus, hmt, hb);   // (its device temporaries are gone before the planes are allocated)
   if (rc) return rc;
-  // rows of the GEMM weight in the permuted gate order r' = ut*32 + gate*8 + u (ita_lstm_head_kernel)
+  // rows of the GEMM weight in the permuted gate order r' = ut*32 + gate*8 + u (ita_lstm_head_kernel.h)
   std::vector<float> wf((size_t)512 * LDFOLD, 0.0f);
   for (int rp = 0; rp < 512; ++rp) {
     const int j = ((rp >> 3) & 3) * 128 + (rp >> 5) * 8 + (rp & 7);

@@ -1,4 +1,4 @@
-// Cost of the LSTM head's in-launch meetings (ita_lstm_head_kernel) against the same phases as separate launches, on the
+// Cost of the LSTM head's in-launch meetings (ita_lstm_head_kernel, csrc/ita_lstm_head_kernel.h) against the same phases as separate launches, on the
 // head's geometry: 256-thread workgroups in groups of 16 consecutive ids, 4 and 32 groups (128 and 1024 frames).  Per
 // workgroup and edge a 1 KB payload stored write-through (sc1), then every member reads its group's 16 KB with sc1 loads.
 // Meeting = every wave s_waitcnt vmcnt(0) (asm) -> barrier -> one lane's relaxed agent-scope atomic add -> one lane polls
