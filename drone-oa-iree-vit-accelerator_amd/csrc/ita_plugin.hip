@@ -30,6 +30,7 @@
 #include "ita_ffn_f32_kernel.h"
 #include "ita_attn_f32_kernel.h"
 #include "ita_ingest_kernel.h"
+#include "ita_ingest_wire_kernel.h"
 
 namespace {
 
@@ -137,6 +138,16 @@ struct TailLarge {
   int E = 0, CO = 0, nt = 0, nchunk = 0;
 };
 
+// The device tables of one source size of ita_ingest_wire (ita_ingest_wire_prepare)
+struct WireSize {
+  int H = 0, W = 0;                // 0: the slot is free
+  DevBuf<int> idx;                 // n0y[60] | cnty[60] | n0x[90] | cntx[90]
+  DevBuf<float> coeff;             // wy[60][ldy] | wx transposed [ldx][90]
+  ItaWireTables dev{};
+  int span[3] = {};                // source rows the widest band of 4 / 8 / 12 output rows needs (the staged kernel's LDS)
+};
+constexpr int ITA_WIRE_SIZES = 8;
+
 }  // namespace
 
 // Device memory is grouped by lifetime: `w` per ita_load_weights, `ws` per workspace capacity, `tl` per
@@ -163,6 +174,9 @@ struct ita_context {
   // staging for the host-buffer drop-in symbols
   DevBuf<float> dsp_in, dsp_out;
   std::vector<float> dsp_host;
+  // ita_ingest_wire: the last ITA_WIRE_SIZES source sizes prepared; a new one beyond that replaces the oldest
+  WireSize wire[ITA_WIRE_SIZES];
+  int wire_next = 0;
 };
 
 namespace {
@@ -545,6 +559,65 @@ int launch_ingest(ita_context* c, const void* src, int H, int W, long long row_s
   return ITA_OK;
 }
 
+WireSize* find_wire(ita_context* c, int H, int W) {
+  for (WireSize& w : c->wire)
+    if (w.H == H && w.W == W) return &w;
+  return nullptr;
+}
+
+// Builds and uploads the two tables of a source size.  Allocates and copies synchronously: not for a captured stream.
+int prepare_wire(ita_context* c, int H, int W, WireSize** out) {
+  if (WireSize* w = find_wire(c, H, W)) {
+    if (out) *out = w;
+    return ITA_OK;
+  }
+  ItaResizeAxis ay, ax;
+  if (!ita_resize_axis(H, ITA_WIRE_H, ay) || !ita_resize_axis(W, ITA_WIRE_W, ax))
+    return fail(ITA_ERR_INVALID_ARG, "no resize table for this source size");
+  WireSize* slot = nullptr;
+  for (WireSize& w : c->wire)
+    if (!slot && w.H == 0) slot = &w;
+  if (!slot) {
+    slot = &c->wire[c->wire_next];
+    c->wire_next = (c->wire_next + 1) % ITA_WIRE_SIZES;
+    HIPCHK(hipDeviceSynchronize());   // a launch still in flight may read the tables that go
+  }
+  *slot = WireSize{};
+  std::vector<int> idx;
+  for (const std::vector<int>* v : {&ay.n0, &ay.count, &ax.n0, &ax.count}) idx.insert(idx.end(), v->begin(), v->end());
+  std::vector<float> coeff(ay.coeff);
+  coeff.resize(ay.coeff.size() + ax.coeff.size());   // wx transposed: [ldx][90]
+  for (int ox = 0; ox < ITA_WIRE_W; ++ox)
+    for (int j = 0; j < ax.width; ++j) coeff[ay.coeff.size() + (size_t)j * ITA_WIRE_W + ox] = ax.coeff[(size_t)ox * ax.width + j];
+  WireSize w;
+  HIPCHK(w.idx.upload(idx.data(), idx.size()));
+  HIPCHK(w.coeff.upload(coeff.data(), coeff.size()));
+  w.dev.n0y = w.idx;
+  w.dev.cnty = w.idx + ITA_WIRE_H;
+  w.dev.n0x = w.idx + 2 * ITA_WIRE_H;
+  w.dev.cntx = w.idx + 2 * ITA_WIRE_H + ITA_WIRE_W;
+  w.dev.wy = w.coeff;
+  w.dev.wx = w.coeff + ay.coeff.size();
+  w.dev.ldy = ay.width;
+  w.dev.ldx = ax.width;
+  for (int b = 0; b < 3; ++b)
+    for (int oy0 = 0, rows = 4 * (b + 1); oy0 < ITA_WIRE_H; oy0 += rows) {
+      int first = H, end = 0;
+      for (int oy = oy0; oy < std::min(oy0 + rows, ITA_WIRE_H); ++oy) {
+        first = std::min(first, ay.n0[oy]);
+        end = std::max(end, ay.n0[oy] + ay.count[oy]);
+      }
+      w.span[b] = std::max(w.span[b], end - first);
+    }
+  int rc = set_lds((const void*)ita_ingest_wire_kernel<true, true>, ITA_WIRE_STAGED_LDS_MAX);
+  if (rc) return rc;
+  w.H = H;
+  w.W = W;
+  *slot = std::move(w);
+  if (out) *out = slot;
+  return ITA_OK;
+}
+
 // event indices of a profiling stage's first and last mark among the 5 + 2 L events of one recorded forward
 struct StageMarks { int lo, hi; };
 StageMarks stage_marks(int num_layers, int stage) {
@@ -915,6 +988,75 @@ int ita_ingest(ita_handle h, const void* src, int pixel_dtype, int height, int w
     case ITA_PIXEL_U16: return launch_ingest<uint16_t>(h, src, height, width, row_stride, frame_stride, depth_scale, frames, batch, s);
     default: return launch_ingest<float>(h, src, height, width, row_stride, frame_stride, depth_scale, frames, batch, s);
   }
+}
+
+int ita_resize_table(int n_in, int n_out, int* n0, int* count, float* coeff, int coeff_width, int* width_out) {
+  if (!n0 || !count || !coeff || !width_out || coeff_width < 1) return fail(ITA_ERR_INVALID_ARG, "null pointer or coeff_width < 1");
+  ItaResizeAxis t;
+  if (!ita_resize_axis(n_in, n_out, t)) return fail(ITA_ERR_INVALID_ARG, "n_in must be in [1, 4096], n_out in [1, 4096]");
+  *width_out = t.width;
+  if (t.width > coeff_width) return fail(ITA_ERR_INVALID_ARG, "coeff_width is smaller than the table's width (see width_out)");
+  for (int o = 0; o < n_out; ++o) {
+    n0[o] = t.n0[o];
+    count[o] = t.count[o];
+    for (int j = 0; j < coeff_width; ++j) coeff[(size_t)o * coeff_width + j] = j < t.width ? t.coeff[(size_t)o * t.width + j] : 0.0f;
+  }
+  return ITA_OK;
+}
+
+int ita_ingest_wire_prepare(ita_handle h, int height, int width) {
+  if (!h) return fail(ITA_ERR_INVALID_ARG, "null handle");
+  if (height < 1 || height > ITA_WIRE_MAX_DIM || width < 1 || width > ITA_WIRE_MAX_DIM)
+    return fail(ITA_ERR_INVALID_ARG, "height and width must be in [1, 4096]");
+  HIPCHK(hipSetDevice(h->device));
+  return prepare_wire(h, height, width, nullptr);
+}
+
+int ita_ingest_wire(ita_handle h, const uint8_t* src, int height, int width, long long row_stride, long long frame_stride,
+                    uint8_t* wire, int batch, void* stream) {
+  // every argument is judged before the handle is used and before any HIP call
+  if (!h) return fail(ITA_ERR_INVALID_ARG, "null handle");
+  if (!src || !wire) return fail(ITA_ERR_INVALID_ARG, "null pointer");
+  if (height < 1 || height > ITA_WIRE_MAX_DIM || width < 1 || width > ITA_WIRE_MAX_DIM)
+    return fail(ITA_ERR_INVALID_ARG, "height and width must be in [1, 4096]");
+  if (batch < 1) return fail(ITA_ERR_INVALID_ARG, "batch must be positive");
+  if (row_stride < width || frame_stride < (long long)(height - 1) * row_stride + width)
+    return fail(ITA_ERR_INVALID_ARG, "row_stride < width, or frame_stride < (height - 1) * row_stride + width");
+  if (row_stride > (1ll << 40) || frame_stride > (1ll << 40))
+    return fail(ITA_ERR_INVALID_ARG, "stride out of range");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = (hipStream_t)stream;
+  WireSize* w = find_wire(h, height, width);
+  if (!w) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+      return fail(ITA_ERR_INVALID_ARG, "this source size has no tables yet and they cannot be built inside a stream capture; call ita_ingest_wire_prepare first");
+    const int rc = prepare_wire(h, height, width, &w);
+    if (rc) return rc;
+  }
+  // bands of 12, 8 or 4 output rows with their source rows staged in LDS, the tallest that fits; else bands of 4 read
+  // from global memory
+  int rows = 4, span = 0;
+  if (row_stride % 4 == 0)
+    for (int b = 2; b >= 0 && !span; --b)
+      if (ita_wire_lds_bytes(width, w->span[b]) <= ITA_WIRE_STAGED_LDS_MAX) {
+        rows = 4 * (b + 1);
+        span = w->span[b];
+      }
+  const long long items = (long long)batch * ((ITA_WIRE_H + rows - 1) / rows);
+  const int grid = (int)std::min<long long>(items, (long long)h->num_cus * 8);
+  const int lds = ita_wire_lds_bytes(width, span);
+  if (span)
+    hipLaunchKernelGGL((ita_ingest_wire_kernel<true, true>), dim3(grid), dim3(256), lds, s, src, height, width, row_stride,
+                       frame_stride, w->dev, wire, batch, rows, span);
+  else if (row_stride % 4 == 0)
+    hipLaunchKernelGGL((ita_ingest_wire_kernel<true, false>), dim3(grid), dim3(256), lds, s, src, height, width, row_stride,
+                       frame_stride, w->dev, wire, batch, rows, span);
+  else
+    hipLaunchKernelGGL((ita_ingest_wire_kernel<false, false>), dim3(grid), dim3(256), lds, s, src, height, width, row_stride,
+                       frame_stride, w->dev, wire, batch, rows, span);
+  HIPCHK(hipGetLastError());
+  return ITA_OK;
 }
 
 int ita_fusion_tail(ita_handle h, const float* x, float* feat, int batch, void* stream) {

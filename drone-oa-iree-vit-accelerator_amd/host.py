@@ -41,7 +41,7 @@ EXPORTED_SYMBOLS = (
     "ita_fusion_tail_load", "ita_fusion_tail_large",
     "ita_wire_unpack_packet", "ita_wire_postprocess", "ita_vitlstm_forward_slots", "ita_vitlstm_front",
     "ita_vitlstm_back", "ita_vitlstm_pipelined", "ita_vitlstm_front_ev", "ita_vitlstm_encode", "ita_vitlstm_fold", "ita_vitlstm_tail", "ita_debug_softmax_rows",
-    "ita_head_status", "ita_vitlstm_sequence", "ita_ingest",
+    "ita_head_status", "ita_vitlstm_sequence", "ita_ingest", "ita_ingest_wire", "ita_ingest_wire_prepare", "ita_resize_table",
     "ITASelfAttention_workgroup", "ITASelfAttention_workgroup_expanded", "ITAFeedForward_workgroup",
 )
 
@@ -133,6 +133,9 @@ def lib():
         L.ita_vitlstm_pipelined.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, i, i, vp, vp]
         L.ita_vitlstm_sequence.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, vp, i, i, vp]
         L.ita_ingest.argtypes = [vp, vp, i, i, i, C.c_longlong, C.c_longlong, C.c_float, vp, i, vp]
+        L.ita_ingest_wire.argtypes = [vp, vp, i, i, C.c_longlong, C.c_longlong, vp, i, vp]
+        L.ita_ingest_wire_prepare.argtypes = [vp, i, i]
+        L.ita_resize_table.argtypes = [i, i, vp, vp, vp, i, C.POINTER(i)]
         L.ita_mha_q8.argtypes = [vp, i, vp, vp, i, vp]
         L.ita_mha_long_q8.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_vitlstm_tail.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
@@ -192,6 +195,18 @@ def _dev_f32(t, shape=None):
     if shape is not None and tuple(t.shape) != tuple(shape):
         raise ITAError(f"expected shape {tuple(shape)}, got {tuple(t.shape)}")
     return t
+
+
+def resize_table(n_in: int, n_out: int):
+    """ita_resize_table: one axis of the wire ingest's filter tables, built on the host (no GPU, no handle) ->
+    (n0[n_out] int32, count[n_out] int32, coeff[n_out, width] float32), as ingest_wire_ref.resize_tables returns them"""
+    import numpy as np
+    cap = 4 * INGEST_MAX_DIM + 8                          # wider than any table of a source of at most 4096 pixels
+    n0, count = np.zeros(n_out, np.int32), np.zeros(n_out, np.int32)
+    coeff = np.zeros((max(n_out, 1), cap), np.float32)
+    width = C.c_int(0)
+    _chk(lib().ita_resize_table(n_in, n_out, n0.ctypes.data, count.ctypes.data, coeff.ctypes.data, cap, C.byref(width)))
+    return n0, count, coeff[:, :width.value].copy()
 
 
 class Engine:
@@ -418,6 +433,47 @@ class Engine:
             raise ITAError(f"out must be a contiguous f32 tensor of shape ({N}, 60, 90) on cuda:{self.device}")
         _chk(lib().ita_ingest(self._h, frames.data_ptr(), kinds[frames.dtype], H, W, strides[0], strides[1],
                               float(depth_scale), out.data_ptr(), N, _stream_ptr(self.device)))
+        return out
+
+    # ---- wire ingest: camera-resolution u8 frames -> (N,60,90) u8 wire frames --------------
+    def prepare_ingest_wire(self, H: int, W: int):
+        """ita_ingest_wire_prepare: builds and uploads the filter tables of an H x W source, so that ingest_wire on that
+        size allocates nothing (a CUDA-graph capture needs this first).  The engine keeps the last eight sizes."""
+        _chk(lib().ita_ingest_wire_prepare(self._h, int(H), int(W)))
+
+    def ingest_wire(self, frames, out=None):
+        """The reference host's resize (ita_ingest_wire): frames (..., H, W) uint8 on this engine's GPU, H and W in
+        [1, 4096] -> (N,60,90) uint8 wire frames: stb_image_resize2's default filters (Mitchell down, Catmull-Rom up, edge
+        clamp), equal to ingest_wire_ref.ingest_wire_reference bit for bit and within 1 code of stb itself.  Strided
+        views are read as Engine.ingest reads them.  The result is allocated per call, or written into out ((N,60,90)
+        uint8, contiguous); hand it to forward / forward_sequence / forward_slots, which run it on the u8 wire path:
+        eng.forward(eng.ingest_wire(raw), desvel)."""
+        torch = _torch()
+        if not hasattr(frames, "is_cuda") or not frames.is_cuda:
+            raise ITAError("frames must be a GPU tensor (no CPU fallback)")
+        if frames.device.index != self.device:
+            raise ITAError(f"tensor lives on cuda:{frames.device.index}, the engine on cuda:{self.device}")
+        if frames.dtype != torch.uint8:
+            raise ITAError(f"ingest_wire takes uint8 frames, got {frames.dtype}")
+        if frames.dim() < 2:
+            raise ITAError(f"frames must be (..., H, W), got {tuple(frames.shape)}")
+        H, W = int(frames.shape[-2]), int(frames.shape[-1])
+        if not (1 <= H <= INGEST_MAX_DIM and 1 <= W <= INGEST_MAX_DIM):
+            raise ITAError(f"H and W must be in [1, {INGEST_MAX_DIM}], got {H} x {W}")
+        N = np_prod(frames.shape[:-2])
+        if N < 1:
+            raise ITAError(f"no frames in a tensor of shape {tuple(frames.shape)}")
+        strides = self._frame_strides(frames)
+        if strides is None:
+            frames = frames.contiguous()
+            strides = (W, H * W)
+        if out is None:
+            out = torch.empty((N, 60, 90), dtype=torch.uint8, device=frames.device)
+        elif not out.is_cuda or out.device.index != self.device or out.dtype != torch.uint8 or not out.is_contiguous() \
+                or tuple(out.shape) != (N, 60, 90):
+            raise ITAError(f"out must be a contiguous uint8 tensor of shape ({N}, 60, 90) on cuda:{self.device}")
+        _chk(lib().ita_ingest_wire(self._h, frames.data_ptr(), H, W, strides[0], strides[1], out.data_ptr(), N,
+                                   _stream_ptr(self.device)))
         return out
 
     # ---- whole graph -------------------------------------------------------------------

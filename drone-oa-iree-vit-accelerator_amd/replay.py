@@ -24,13 +24,21 @@ batches instead of single frames.
 
 Frames that are not 90 x 60, in replay() and with replay_frames(..., resize="pil"): resized on the host with PIL's bilinear filter, after a
 conversion to 8 bits.  The reference uses stbir_resize_uint8_linear (stb is vendored there, not part of this path): the
-two filters are not bit-identical, so for resized frames parity with the reference is UNPINNED; 90 x 60 frames go through
-untouched.
+two filters are not bit-identical, so in this mode parity with the reference for resized frames is UNPINNED; 90 x 60
+frames go through untouched.
+
+With replay_frames(..., resize="stb") the reference host's resize IS reproduced, and pinned: 8-bit frames (16-bit PNGs
+converted to 8 bits first, as stbi_load(..., 1) does) that are not 90 x 60 are uploaded at native size and resized by
+Engine.ingest_wire -- stb_image_resize2's default filters, Mitchell down and Catmull-Rom up, edge clamp -- to u8 wire
+frames, and every frame runs on the u8 wire path.  How it is pinned: ingest_wire_ref.ingest_wire_reference restates the
+filter from its formulas, the kernel equals it bit for bit, and it is held to stb's own output on recorded fixtures
+(tests/golden/resize_stb_*.npz): every code within 1 of stb's, a differing code only where the value before truncation
+lies within 1e-3 of an integer (stb sums its taps in SIMD order; at most one such code per 5400 was seen).
 
 With replay_frames(..., resize="gpu") such frames are uploaded at their native size and depth -- 8-bit, or 16-bit ("I;16") depth PNGs with
 their full codes -- and resized by Engine.ingest, then run on the float32 image path.  That resize is the MODEL's own
 (refine_inputs: bilinear, align_corners=False), and it is pinned: ingest_ref.ingest_reference defines it and the kernel
-equals it bit for bit.  Parity with the reference HOST's stb filter stays unpinned in this mode too.  90 x 60 8-bit
+equals it bit for bit.  It is not the reference HOST's stb filter (that is resize="stb").  90 x 60 8-bit
 frames stay on the u8 wire path; the other frames of one trajectory must share one size.
 
 The parsing half of this module (scan_root, load_telemetry, read_frame) needs no GPU; replay() does.
@@ -143,6 +151,15 @@ def read_frame_native(path: str) -> Optional[np.ndarray]:
         return None
 
 
+def read_frame_u8(path: str) -> Optional[np.ndarray]:
+    """the frame at the size of its file as 8 bits, the way stbi_load(..., 1) hands it to the reference host: a 16-bit
+    grey PNG keeps the high byte of every code, anything else is its luminance"""
+    im = read_frame_native(path)
+    if im is not None and im.dtype == np.uint16:
+        im = (im >> 8).astype(np.uint8)
+    return im
+
+
 def _is_wire(im: np.ndarray) -> bool:
     return im.dtype == np.uint8 and im.shape == (FRAME_H, FRAME_W)
 
@@ -169,6 +186,20 @@ def _ingest_frames(engine, frames: List[np.ndarray], dev):
     return out
 
 
+def _wire_frames(engine, frames: List[np.ndarray], dev):
+    """resize="stb": host u8 frames of any size -> (n, 60, 90) u8 wire frames on the GPU: 90 x 60 frames as they are, the
+    others through one Engine.ingest_wire call per size"""
+    import torch
+    out = torch.empty((len(frames), FRAME_H, FRAME_W), dtype=torch.uint8, device=dev)
+    groups = {}
+    for j, im in enumerate(frames):
+        groups.setdefault(im.shape, []).append(j)
+    for shape, idx in groups.items():
+        raw = torch.from_numpy(np.stack([frames[j] for j in idx])).to(dev)
+        out[torch.tensor(idx, device=dev)] = raw if shape == (FRAME_H, FRAME_W) else engine.ingest_wire(raw)
+    return out
+
+
 @dataclass
 class FrameResult:
     trajectory: str
@@ -180,7 +211,7 @@ class FrameResult:
 
 
 SCHEDULES = ("steps", "sequence")
-RESIZES = ("pil", "gpu")
+RESIZES = ("pil", "gpu", "stb")
 
 
 def _result(traj: Trajectory, k: int, vel: np.ndarray) -> FrameResult:
@@ -191,12 +222,13 @@ def _result(traj: Trajectory, k: int, vel: np.ndarray) -> FrameResult:
     return FrameResult(traj.name, os.path.basename(traj.frames[k]), vel.copy(), gt, err, tel.found)
 
 
-def _sequence_call(engine, dev, streams, hidden=None):
+def _sequence_call(engine, dev, streams, hidden=None, to_wire=False):
     """one Engine.forward_sequence call: streams = per stream [(Telemetry, frame)], the frames of the call either all u8
-    90 x 60 (the u8 wire path) or none of them (Engine.ingest, the float32 path) -> (vel (T,B,3) numpy, (h, c))"""
+    90 x 60 (the u8 wire path) or none of them (Engine.ingest, the float32 path), or with to_wire u8 frames of any size
+    (Engine.ingest_wire, the u8 wire path) -> (vel (T,B,3) numpy, (h, c))"""
     import torch
     T, B = max(len(q) for q in streams), len(streams)
-    native = not _is_wire(next(im for q in streams for _, im in q))
+    native = to_wire or not _is_wire(next(im for q in streams for _, im in q))
     imgs = None if native else np.zeros((T, B, FRAME_H, FRAME_W), np.uint8)
     cells, raws = [], []                             # native: flat (step * B + b) cell of every frame handed to ingest
     dv = np.zeros((T, B), np.float32)
@@ -214,8 +246,8 @@ def _sequence_call(engine, dev, streams, hidden=None):
             qt[step, b] = tel.quaternion
     lengths = torch.tensor([len(q) for q in streams], dtype=torch.int32, device=dev)
     if native:
-        imgs_dev = torch.zeros((T * B, FRAME_H, FRAME_W), dtype=torch.float32, device=dev)
-        imgs_dev[torch.tensor(cells, device=dev)] = _ingest_frames(engine, raws, dev)
+        imgs_dev = torch.zeros((T * B, FRAME_H, FRAME_W), dtype=torch.uint8 if to_wire else torch.float32, device=dev)
+        imgs_dev[torch.tensor(cells, device=dev)] = (_wire_frames if to_wire else _ingest_frames)(engine, raws, dev)
         imgs_dev = imgs_dev.reshape(T, B, FRAME_H, FRAME_W)
     else:
         imgs_dev = torch.from_numpy(imgs).to(dev)
@@ -230,10 +262,13 @@ def _replay_sequence(engine, trajs: List[Trajectory], max_batch: int, resize: st
     path (as every group does with resize="pil"), those without any such frame as one call through Engine.ingest, and a
     trajectory that mixes the two runs alone, one call per run of consecutive frames of a kind with its state carried
     from call to call (equal to one call: forward_sequence does not depend on how the steps are cut).  A frame's result
-    does not depend on the streams beside it, so the cut changes no result."""
+    does not depend on the streams beside it, so the cut changes no result.  resize="stb": every frame becomes a u8 wire
+    frame (Engine.ingest_wire), so a group is one call again."""
     import torch
     dev = torch.device("cuda", engine.device)
-    reader = read_frame_native if resize == "gpu" else read_frame
+    to_wire = resize == "stb"
+    reader = {"pil": read_frame, "gpu": read_frame_native, "stb": read_frame_u8}[resize]
+    is_wire = (lambda im: True) if to_wire else _is_wire
     out = []
     for g0 in range(0, len(trajs), max_batch):
         group = trajs[g0:g0 + max_batch]
@@ -243,16 +278,18 @@ def _replay_sequence(engine, trajs: List[Trajectory], max_batch: int, resize: st
             seqs.append([(k, im) for k, im in fr if im is not None])   # unreadable frames drop out of the sequence
             seen = {}
             for _, im in seqs[-1]:
-                _check_one_size(t, seen, 0, im)
+                if not to_wire:
+                    _check_one_size(t, seen, 0, im)
         if max(len(q) for q in seqs) == 0:
             continue
         vels = [None] * len(group)                       # per trajectory: (steps, 3)
-        kinds = [{_is_wire(im) for _, im in q} for q in seqs]
+        kinds = [{is_wire(im) for _, im in q} for q in seqs]
         for want in ({True}, {False}):                   # an empty trajectory rides with the wire ones, as it always did
             part = [b for b, kd in enumerate(kinds) if kd == want or (not kd and want == {True})]
             if not any(seqs[b] for b in part):
                 continue
-            vel, _ = _sequence_call(engine, dev, [[(group[b].telemetry[k], im) for k, im in seqs[b]] for b in part])
+            vel, _ = _sequence_call(engine, dev, [[(group[b].telemetry[k], im) for k, im in seqs[b]] for b in part],
+                                    to_wire=to_wire)
             for j, b in enumerate(part):
                 vels[b] = vel[:len(seqs[b]), j]
         for b, kd in enumerate(kinds):
@@ -296,16 +333,24 @@ def replay_frames(engine, root: str, max_batch: int = 1024, schedule: str = "ste
     resize, pinned by ingest_ref.ingest_reference -- then run as float32 frames; 90 x 60 u8 frames stay on the u8 wire
     path in both schedules ("steps": a call of their own beside the float32 frames of the same step; "sequence": see
     _replay_sequence), so their results are those of replay().  The frames of one
-    trajectory that are not 90 x 60 must share one size (ValueError otherwise)."""
+    trajectory that are not 90 x 60 must share one size (ValueError otherwise).  "stb": the reference host's own resize
+    -- frames are read as 8 bits at native size (16-bit PNGs converted first), those that are not 90 x 60 resized by
+    Engine.ingest_wire (stb's default filters, pinned by ingest_wire_ref.ingest_wire_reference), and ALL frames run as u8
+    wire frames: one call per step or per group, any mix of sizes."""
     if schedule not in SCHEDULES:
         raise ValueError(f"schedule must be one of {SCHEDULES}, got {schedule!r}")
     if resize not in RESIZES:
         raise ValueError(f"resize must be one of {RESIZES}, got {resize!r}")
+    if resize == "stb" and not callable(getattr(type(engine), "ingest_wire", None)):
+        # judged with the other arguments, before the root is read or the engine used: an engine-like object without the
+        # wire ingest (a stand-in, an engine of an older build) cannot run this mode, and there is no host fallback for it
+        raise ValueError(f"resize='stb' needs an engine with ingest_wire (host.Engine), got {type(engine).__name__}")
     import torch
     trajs = scan_root(root)
     if schedule == "sequence":
         return _replay_sequence(engine, trajs, max_batch, resize) if trajs else []
-    reader = read_frame_native if resize == "gpu" else read_frame
+    reader = {"pil": read_frame, "gpu": read_frame_native, "stb": read_frame_u8}[resize]
+    to_wire = resize == "stb"
     seen = {}
     n = len(trajs)
     if n == 0:
@@ -323,17 +368,21 @@ def replay_frames(engine, root: str, max_batch: int = 1024, schedule: str = "ste
                 cursor[i] += 1
                 img = reader(t.frames[k])
                 if img is not None:                      # unreadable frames are skipped, state untouched
-                    _check_one_size(t, seen, i, img)
+                    if not to_wire:
+                        _check_one_size(t, seen, i, img)
                     batch.append((i, k, img))
                     break
         if not batch:
             break
         # the u8 wire frames of the step, then (resize="gpu" only) its native frames through ingest: two calls on
         # disjoint slots, and a frame's result does not depend on the batch it runs in
-        for part in ([b for b in batch if _is_wire(b[2])], [b for b in batch if not _is_wire(b[2])]):
+        # (resize="stb": every frame of the step becomes a u8 wire frame, one call)
+        for part in ([b for b in batch if to_wire or _is_wire(b[2])], [b for b in batch if not (to_wire or _is_wire(b[2]))]):
             if not part:
                 continue
-            if _is_wire(part[0][2]):
+            if to_wire:
+                imgs = _wire_frames(engine, [b[2] for b in part], dev)
+            elif _is_wire(part[0][2]):
                 imgs = torch.from_numpy(np.stack([b[2] for b in part])).to(dev)
             else:
                 imgs = _ingest_frames(engine, [b[2] for b in part], dev)

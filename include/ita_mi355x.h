@@ -157,6 +157,31 @@ typedef enum ita_pixel_dtype { ITA_PIXEL_U8 = 0, ITA_PIXEL_U16 = 1, ITA_PIXEL_F3
 int ita_ingest(ita_handle h, const void* src_dev, int pixel_dtype, int height, int width, long long row_stride,
                long long frame_stride, float depth_scale, float* frames_dev, int batch, void* stream);
 
+/* The reference HOST's resize as a stage in front of the graph, for hosts that decode camera frames: `batch` u8 frames of
+ * height x width, row r of frame b at src_dev + b * frame_stride + r * row_stride (strides in pixels = bytes; a cropped
+ * view of a larger buffer is passed as it is) -> wire_dev (batch,60,90) u8, contiguous: the wire frames ITA_IMAGE_U8
+ * takes.  It is what stbir_resize_uint8_linear(src, width, height, 0, dst, 90, 60, 0, 1 channel) computes in the reference's
+ * replay host (samples/inference_trainingset_custom_dispatch/main.cpp:117-128): stb_image_resize2's default filters --
+ * Mitchell on an axis that shrinks, Catmull-Rom on one that grows or keeps its size -- edge clamp, pixel f32(code) *
+ * 3.9215689e-03f, code = trunc(clamp(y * 255 + 0.5)).  The result equals ingest_wire_ref.py: ingest_wire_reference bit
+ * for bit; that definition is within 1 code of stb's own output, and differs from it only where y * 255 + 0.5 lies
+ * within 1e-3 of an integer (tests/golden/resize_stb_*.npz).  A 60 x 90 source comes out unchanged.
+ * ita_ingest_wire_prepare builds and uploads the two filter tables of a source size; the handle keeps the last eight
+ * sizes.  ita_ingest_wire on a prepared size is stream-ordered, allocates nothing and does not synchronise; on another
+ * size it prepares first (allocation, synchronous copies), which is refused with ITA_ERR_INVALID_ARG on a stream that is
+ * being captured.  Reads only [base, base + (height-1) * row_stride + width) of each frame, whatever the alignment of
+ * base; writes only the batch * 5400 bytes.  Needs no weights.
+ * ITA_ERR_INVALID_ARG before any launch: a null pointer, height or width outside [1, 4096], row_stride < width,
+ * frame_stride < (height-1) * row_stride + width, a stride above 2^40, batch < 1.
+ * ita_resize_table: one axis of those tables on the host (no GPU, no handle): n0[n_out], count[n_out] and
+ * coeff[n_out][coeff_width] (zero padded), output o = sum_j coeff[o][j] * source[n0[o] + j]; *width_out = the widest
+ * count (ITA_ERR_INVALID_ARG, with *width_out set, if coeff_width is smaller).  Equals ingest_wire_ref.py: resize_tables
+ * bit for bit. */
+int ita_ingest_wire_prepare(ita_handle h, int height, int width);
+int ita_ingest_wire(ita_handle h, const uint8_t* src_dev, int height, int width, long long row_stride,
+                    long long frame_stride, uint8_t* wire_dev, int batch, void* stream);
+int ita_resize_table(int n_in, int n_out, int* n0, int* count, float* coeff, int coeff_width, int* width_out);
+
 /* Fusion tail (QAT/model.py:116-121): x (B,128,E) -> (B,9,16,32) flattened, row stride 4608. */
 int ita_fusion_tail(ita_handle h, const float* x_dev, float* feat_dev, int batch, void* stream);
 

@@ -24,9 +24,10 @@ def main():
     ap.add_argument("--quiet", action="store_true", help="summary only")
     ap.add_argument("--schedule", choices=("steps", "sequence"), default="steps",
                     help="steps: one batched call per time step; sequence: whole trajectories per call (Engine.forward_sequence)")
-    ap.add_argument("--resize", choices=("pil", "gpu"), default="pil",
+    ap.add_argument("--resize", choices=("pil", "gpu", "stb"), default="pil",
                     help="frames that are not 90 x 60 -- pil: resized on the host as 8 bits; gpu: uploaded at native size and depth "
-                         "(u8 or 16-bit) and resized by Engine.ingest, the model's own refine_inputs resize")
+                         "(u8 or 16-bit) and resized by Engine.ingest, the model's own refine_inputs resize; stb: read as 8 bits, resized "
+                         "by Engine.ingest_wire with the reference host's stb filters, run as u8 wire frames")
     a = ap.parse_args()
     from drone_oa_iree_vit_accelerator_amd import host, params, replay, synth
     if a.blob:
