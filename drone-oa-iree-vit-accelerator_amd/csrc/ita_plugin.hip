@@ -12,9 +12,9 @@
 #include <mutex>
 #include <string>
 #include <atomic>
-#include <functional>
 #include <thread>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ita_mi355x.h"
@@ -48,6 +48,45 @@ int fail(int code, const std::string& msg) {
     if (e_ != hipSuccess)                                                                         \
       return fail(ITA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                \
   } while (0)
+
+// Every kernel launch of the plugin goes through launch / launch_lds.  Bytes is the kernel's dynamic LDS: what launch
+// starts it with, and the most launch_lds may start it with.  Instantiating a launch with Bytes > 0 puts {kernel, Bytes}
+// on a process-wide list during static initialisation, and ita_create raises the dynamic-LDS limit of every listed kernel
+// on its device: a kernel that can be launched is registered by construction, on every device that has a handle, before
+// its first launch (which may sit inside a stream capture).
+struct LdsKernel { const void* kernel; int bytes; };
+std::vector<LdsKernel>& lds_kernels() {
+  static std::vector<LdsKernel> list;
+  return list;
+}
+template <auto Kernel, int Bytes>
+struct LdsListed {
+  static inline const bool yes = (lds_kernels().push_back({reinterpret_cast<const void*>(Kernel), Bytes}), true);
+};
+
+constexpr int LDS_PER_CU = 160 * 1024;   // gfx950
+
+template <auto Kernel, int Bytes, typename... Args>
+int launch_lds(dim3 grid, dim3 block, int lds_bytes, hipStream_t s, const Args&... args) {
+  // An instantiation that asks for more than the device has (ita_tail_big_kernel<4, 8, 9>, 166752 bytes: more than 48
+  // output channels on 16-row tiles) is not listed: hipFuncSetAttribute refuses it, and ita_create would fail for every
+  // caller.  HIP refuses its launch instead, with the same ITA_ERR_HIP.
+  if constexpr (Bytes > 0 && Bytes <= LDS_PER_CU)
+    (void)LdsListed<Kernel, Bytes>::yes;   // the ODR-use that instantiates the member, nothing at run time
+  hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, s, args...);
+  HIPCHK(hipGetLastError());
+  return ITA_OK;
+}
+template <auto Kernel, int Bytes = 0, typename... Args>
+int launch(dim3 grid, dim3 block, hipStream_t s, const Args&... args) {
+  return launch_lds<Kernel, Bytes>(grid, block, Bytes, s, args...);
+}
+
+// f(std::integral_constant<int, 64 or 128>): the compile-time split over the two embedding widths
+template <typename F>
+int with_E(int E, F&& f) {
+  return E == 64 ? f(std::integral_constant<int, 64>{}) : f(std::integral_constant<int, 128>{});
+}
 
 constexpr int K0P = 672;    // exact-f32 path: LSTM layer-0 concat width 517 + 128 = 645, padded to a multiple of 32
 constexpr int K0S = 144;    // f16x3 path, LSTM layer 0 remainder: [h_in0 (128) | desvel | quat (4) | 0 pad]
@@ -92,18 +131,14 @@ int launch_tail(int num_cus, int E, const float* wT, const float* bias, const fl
   if (E != 64) return fail(ITA_ERR_UNSUPPORTED, "fusion tail is built for E = 64 (ITAViTLSTM)");
   ItaTailArgs a{x, wT, bias, feat, ld, B};
   const int grid = B < 2 * num_cus ? B : 2 * num_cus;
-  hipLaunchKernelGGL(ita_tail_kernel<64>, dim3(grid), dim3(256), ita_tail_lds_bytes<64>(), s, a);
-  HIPCHK(hipGetLastError());
-  return ITA_OK;
+  return launch<ita_tail_kernel<64>, ita_tail_lds_bytes<64>()>(dim3(grid), dim3(256), s, a);
 }
 
 int launch_gemm(const float* A, int lda, const float* W, int ldw, const float* bias, float* C, int ldc, int M, int N,
                 int K, hipStream_t s) {
   if (N % 64 || K % 32) return fail(ITA_ERR_UNSUPPORTED, "gemm needs N % 64 == 0 and K % 32 == 0");
   ItaGemmArgs g{A, lda, W, ldw, bias, C, ldc, M, N, K};
-  hipLaunchKernelGGL(ita_gemm_f32_kernel, dim3(N / 64, (M + 31) / 32), dim3(256), 0, s, g);
-  HIPCHK(hipGetLastError());
-  return ITA_OK;
+  return launch<ita_gemm_f32_kernel>(dim3(N / 64, (M + 31) / 32), dim3(256), s, g);
 }
 
 }  // namespace
@@ -186,16 +221,13 @@ ita_handle g_bound = nullptr;
 int g_bound_layer = 0;
 int g_bound_dtype = ITA_DISPATCH_F16;
 
-// Growth frees and reallocates every buffer, so it is only allowed while nothing can still reference the old ones:
-// never after an explicit ita_reserve (HIP graphs and front/back pairs keep raw pointers into the workspace), and never
-// on a stream that is being captured.
-int ensure_workspace(ita_context* c, int B, hipStream_t s = nullptr) {
-  if (B <= c->ws.cap) return ITA_OK;
-  if (c->ws_reserved)
-    return fail(ITA_ERR_INVALID_ARG, "batch exceeds the workspace pinned by ita_reserve; call ita_reserve(max_batch) again while idle");
+bool capturing(hipStream_t s) {
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-    return fail(ITA_ERR_INVALID_ARG, "the workspace cannot grow inside a stream capture; call ita_reserve first");
+  return hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+
+// Frees and reallocates every buffer of the workspace, for B frames
+int grow_workspace(ita_context* c, int B) {
   c->ws = Workspace{};
   Workspace& ws = c->ws;
   const size_t E = (size_t)c->w.hdr.E, nb = (size_t)B, ntile = (nb + 31) / 32;
@@ -220,9 +252,15 @@ int ensure_workspace(ita_context* c, int B, hipStream_t s = nullptr) {
   return ITA_OK;
 }
 
-int set_lds(const void* kernel, int bytes) {
-  HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  return ITA_OK;
+// Growth is only allowed while nothing can still reference the old buffers: never after an explicit ita_reserve (HIP
+// graphs and front/back pairs keep raw pointers into the workspace), and never on a stream that is being captured.
+int ensure_workspace(ita_context* c, int B, hipStream_t s) {
+  if (B <= c->ws.cap) return ITA_OK;
+  if (c->ws_reserved)
+    return fail(ITA_ERR_INVALID_ARG, "batch exceeds the workspace pinned by ita_reserve; call ita_reserve(max_batch) again while idle");
+  if (capturing(s))
+    return fail(ITA_ERR_INVALID_ARG, "the workspace cannot grow inside a stream capture; call ita_reserve first");
+  return grow_workspace(c, B);
 }
 
 int check(ita_handle h, int batch, bool need_weights = true) {
@@ -230,6 +268,13 @@ int check(ita_handle h, int batch, bool need_weights = true) {
   if (batch <= 0) return fail(ITA_ERR_INVALID_ARG, "batch must be positive");
   if (need_weights && !h->w.loaded) return fail(ITA_ERR_NO_WEIGHTS, "ita_load_weights has not been called");
   HIPCHK(hipSetDevice(h->device));
+  return ITA_OK;
+}
+
+// check(), then what every per-layer entry point asks of its activation pointers and layer index
+int check_layer_io(ita_handle h, int layer, const void* x, const void* y, int batch) {
+  if (int rc = check(h, batch)) return rc;
+  if (!x || !y || layer < 0 || layer >= h->w.hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
   return ITA_OK;
 }
 
@@ -250,6 +295,54 @@ ItaMhaArgs mha_args(ita_context* c, int layer, const float* x, float* y, int B, 
   return a;
 }
 
+// event indices of a profiling stage's first and last mark among the events of one recorded forward
+struct StageMarks { int lo, hi; };
+StageMarks stage_marks(int num_layers, int stage) {
+  const int L2 = 2 * num_layers;
+  const int lo[ITA_NUM_STAGES] = {0, 1, 1, 1 + L2, 2 + L2, 3 + L2}, hi[ITA_NUM_STAGES] = {1, 1 + L2, 1 + L2, 2 + L2, 3 + L2, 4 + L2};
+  return {lo[stage], hi[stage]};
+}
+
+// The profiling marks of one call between ita_profile_begin and ita_profile_end: the call's slice of prof_ev (null when
+// the call is not sampled), the selected stage and the index of the next mark.  An event in the stream costs a pipeline
+// bubble of ~5 us (the next kernel cannot be launched under the tail of the previous one), so in single-stage mode only
+// that stage's two marks are recorded.
+struct StageRecorder {
+  ita_context* h;
+  hipStream_t s;
+  hipEvent_t* ev = nullptr;
+  int stage, lo, hi;     // the marks that close the count: the selected stage's two, or (all stages) the first and the last
+  int next = 0;          // mark(): a whole forward numbers its marks as it goes
+  unsigned seen = 0;     // bit 0: lo was recorded, bit 1: hi
+  // events of one recorded forward: forward start, tokenizer end, two per layer, tail, decoder, LSTM + fc
+  static int events_per_forward(const ita_context* h) { return 5 + 2 * h->w.hdr.num_layers; }
+
+  // all_stages_too: the call runs every stage (a front half is sampled in single-stage mode only)
+  StageRecorder(ita_context* h_, hipStream_t s_, bool all_stages_too) : h(h_), s(s_), stage(h_->prof_stage) {
+    const int per = events_per_forward(h);
+    const StageMarks m = stage >= 0 ? stage_marks(h->w.hdr.num_layers, stage) : StageMarks{0, per - 1};
+    lo = m.lo;
+    hi = m.hi;
+    if (h->prof && (all_stages_too || stage >= 0) && h->prof_n < h->prof_max && (h->prof_calls++ % h->prof_every) == 0)
+      ev = &h->prof_ev[(size_t)h->prof_n * per];
+  }
+  int record(int i) {
+    HIPCHK(hipEventRecord(ev[i], s));
+    seen |= (i == lo ? 1u : 0u) | (i == hi ? 2u : 0u);
+    return ITA_OK;
+  }
+  int mark() {   // the next mark of a whole forward
+    const int i = next++;
+    return ev && (stage < 0 || i == lo || i == hi) ? record(i) : ITA_OK;
+  }
+  int mark(int st, bool end) {   // a front half: the start or end mark of stage st, when that is the selected stage
+    return ev && stage == st ? record(end ? hi : lo) : ITA_OK;
+  }
+  // the slot counts as a forward only when both closing marks were recorded in this call
+  void finish() { if (ev && seen == 3u) ++h->prof_n; }
+};
+
+// What one encoder layer (launch_encoder) or one stream-kernel launch (launch_stream) reads and writes
 struct StreamIo {
   const int8_t* xq = nullptr;   // int8 in / int8 out attention block (mode 2)
   int8_t* yq = nullptr;
@@ -263,7 +356,16 @@ struct StreamIo {
   const int* slots = nullptr;
   const void* img = nullptr;   // u8 wire frames: tokenizer fused in front (x unused)
   float* tok_tap = nullptr;
+  StageRecorder* mid = nullptr;   // launch_encoder: marks the attention / FFN boundary of a layer that runs as two launches
 };
+
+// the stream kernel's instantiations without stamps; `fast` picks the single-rounding one (all six sites proven: fast_site_ok)
+template <int E, bool FFN, int TOK, bool IO8>
+int launch_stream_kernel(bool fast, dim3 grid, hipStream_t s, const ItaStreamArgs& a) {
+  constexpr int lds = ItaStreamLds<E, FFN, TOK != 0>::TOTAL;
+  return fast ? launch<ita_stream_kernel<E, FFN, TOK, false, IO8, true>, lds>(grid, dim3(512), s, a)
+              : launch<ita_stream_kernel<E, FFN, TOK, false, IO8, false>, lds>(grid, dim3(512), s, a);
+}
 
 // mode 0: whole encoder layer; 1: attention block only (fuse_ln: + residual + LayerNorm1)
 int launch_stream(ita_context* c, int layer, int mode, bool fuse_ln, const StreamIo& io, int B, hipStream_t s) {
@@ -278,43 +380,33 @@ int launch_stream(ita_context* c, int layer, int mode, bool fuse_ln, const Strea
   a.stamps = io.stamps; a.h0_src = io.h0_src; a.h0_dst = io.h0_dst; a.slots = io.slots;
   a.img = io.img; a.tok_tap = io.tok_tap; a.xq = io.xq; a.yq = io.yq;
   a.fast_sites = L.fast_sites;
-  const int grid = B < c->num_cus ? B : c->num_cus;
-  const bool fast = L.fast_sites == ITA_SITES_ALL;   // the single-rounding instantiation: all six sites proven (fast_site_ok)
-#define ITA_LAUNCH_STREAM(E_, FFN_, TOK_, IO8_)                                                                                   \
-  do {                                                                                                                            \
-    if (fast) hipLaunchKernelGGL((ita_stream_kernel<E_, FFN_, TOK_, false, IO8_, true>), dim3(grid), dim3(512),                     \
-                                 (ItaStreamLds<E_, FFN_, (TOK_) != 0>::TOTAL), s, a);                                              \
-    else hipLaunchKernelGGL((ita_stream_kernel<E_, FFN_, TOK_, false, IO8_, false>), dim3(grid), dim3(512),                         \
-                            (ItaStreamLds<E_, FFN_, (TOK_) != 0>::TOTAL), s, a);                                                   \
-  } while (0)
+  const dim3 grid(B < c->num_cus ? B : c->num_cus), block(512);
+  const bool fast = L.fast_sites == ITA_SITES_ALL;
   if (mode == 2) {
     if (!L.simg_mha) return fail(ITA_ERR_UNSUPPORTED, "this layer has no attention image (accumulator range)");
     a.image = L.simg_mha;
-    if (c->w.hdr.E == 64) ITA_LAUNCH_STREAM(64, false, 0, true);
-    else ITA_LAUNCH_STREAM(128, false, 0, true);
-  } else if (mode == 1) {
+    return with_E(c->w.hdr.E, [&](auto e) { return launch_stream_kernel<decltype(e)::value, false, 0, true>(fast, grid, s, a); });
+  }
+  if (mode == 1) {
     if (!L.simg_mha) return fail(ITA_ERR_BAD_BLOB, "attention image missing");
     if (fuse_ln && !L.n1w) return fail(ITA_ERR_BAD_BLOB, "norm1 parameters missing from the blob");
     a.image = L.simg_mha;
-    if (c->w.hdr.E == 64) ITA_LAUNCH_STREAM(64, false, 0, false);
-    else ITA_LAUNCH_STREAM(128, false, 0, false);
-  } else if (io.img) {
+    return with_E(c->w.hdr.E, [&](auto e) { return launch_stream_kernel<decltype(e)::value, false, 0, false>(fast, grid, s, a); });
+  }
+  if (io.img) {
     if (!L.simg_tok) return fail(ITA_ERR_BAD_BLOB, "tokenizer / LayerNorm parameters missing from the blob");
     a.image = L.simg_tok;
-    if (io.stamps) hipLaunchKernelGGL((ita_stream_kernel<64, true, 1, true>), dim3(grid), dim3(512), (ItaStreamLds<64, true, true>::TOTAL), s, a);
-    else ITA_LAUNCH_STREAM(64, true, 1, false);
-  } else {
-    if (!L.simg_enc) return fail(ITA_ERR_BAD_BLOB, "LayerNorm parameters missing from the blob");
-    a.image = L.simg_enc;
-    if (c->w.hdr.E == 128) {   // attention + FFN of an E = 128 layer in one launch; fc1 / fc2 weights are read from the global image
-      if (io.stamps) return fail(ITA_ERR_UNSUPPORTED, "phase stamps are built for the E = 64 encoder");
-      ITA_LAUNCH_STREAM(128, true, 0, false);
-    } else if (io.stamps) hipLaunchKernelGGL((ita_stream_kernel<64, true, 0, true>), dim3(grid), dim3(512), (ItaStreamLds<64, true, false>::TOTAL), s, a);
-    else ITA_LAUNCH_STREAM(64, true, 0, false);
+    if (io.stamps) return launch<ita_stream_kernel<64, true, 1, true>, ItaStreamLds<64, true, true>::TOTAL>(grid, block, s, a);
+    return launch_stream_kernel<64, true, 1, false>(fast, grid, s, a);
   }
-#undef ITA_LAUNCH_STREAM
-  HIPCHK(hipGetLastError());
-  return ITA_OK;
+  if (!L.simg_enc) return fail(ITA_ERR_BAD_BLOB, "LayerNorm parameters missing from the blob");
+  a.image = L.simg_enc;
+  if (c->w.hdr.E == 128) {   // attention + FFN of an E = 128 layer in one launch; fc1 / fc2 weights are read from the global image
+    if (io.stamps) return fail(ITA_ERR_UNSUPPORTED, "phase stamps are built for the E = 64 encoder");
+    return launch_stream_kernel<128, true, 0, false>(fast, grid, s, a);
+  }
+  if (io.stamps) return launch<ita_stream_kernel<64, true, 0, true>, ItaStreamLds<64, true, false>::TOTAL>(grid, block, s, a);
+  return launch_stream_kernel<64, true, 0, false>(fast, grid, s, a);
 }
 
 int launch_mha_stream(ita_context* c, int layer, const float* x, float* y, int B, bool fuse, hipStream_t s) {
@@ -333,13 +425,10 @@ int launch_mha(ita_context* c, int layer, const float* x, float* y, int B, bool 
   if (!t && c->w.layers[layer].simg_mha) return launch_mha_stream(c, layer, x, y, B, fuse, s);
   const ItaMhaArgs a = mha_args(c, layer, x, y, B, fuse, t);
   const int grid = B < c->num_cus ? B : c->num_cus;
-  if (c->w.hdr.E == 64) {
-    hipLaunchKernelGGL(ita_mha_kernel<64>, dim3(grid), dim3(512), ItaMhaLds<64>::TOTAL, s, a);
-  } else {
-    hipLaunchKernelGGL(ita_mha_kernel<128>, dim3(grid), dim3(512), ItaMhaLds<128>::TOTAL, s, a);
-  }
-  HIPCHK(hipGetLastError());
-  return ITA_OK;
+  return with_E(c->w.hdr.E, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    return launch<ita_mha_kernel<E>, ItaMhaLds<E>::TOTAL>(dim3(grid), dim3(512), s, a);
+  });
 }
 
 int launch_ffn(ita_context* c, int layer, const float* x, float* y, int B, bool fuse, const ita_ffn_taps* t,
@@ -354,13 +443,10 @@ int launch_ffn(ita_context* c, int layer, const float* x, float* y, int B, bool 
   if (t) { a.t_xq = t->x_q; a.t_h = t->h; a.t_out = t->out_q; }
   a.y_hi = y_hi; a.y_lo = y_lo; a.ld_planes = c->w.ldfold;
   const int grid = B < 2 * c->num_cus ? B : 2 * c->num_cus;
-  if (c->w.hdr.E == 64) {
-    hipLaunchKernelGGL(ita_ffn_kernel<64>, dim3(grid), dim3(512), ItaFfnLds<64>::TOTAL, s, a);
-  } else {
-    hipLaunchKernelGGL(ita_ffn_kernel<128>, dim3(grid), dim3(512), ItaFfnLds<128>::TOTAL, s, a);
-  }
-  HIPCHK(hipGetLastError());
-  return ITA_OK;
+  return with_E(c->w.hdr.E, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    return launch<ita_ffn_kernel<E>, ItaFfnLds<E>::TOTAL>(dim3(grid), dim3(512), s, a);
+  });
 }
 
 // the float32 FFN (ita_ffn_f32_kernel.h) of an ITAW0002 layer, fuse: + residual + LayerNorm2
@@ -376,17 +462,13 @@ int launch_ffn_f32(ita_context* c, int layer, const float* x, float* y, int B, b
   a.B = B; a.fuse_ln = fuse ? 1 : 0;
   a.y_hi = y_hi; a.y_lo = y_lo; a.ld_planes = c->w.ldfold;
   a.h0_src = h0_src; a.h0_dst = h0_dst; a.slots = slots;
+  if (c->w.hdr.E != 64) { a.w1 = L.w1p; a.w2 = L.w2p; }   // E = 128: the weights stream as fragment images (66 KB of LDS: two workgroups per CU)
   const int cap = 2 * c->num_cus;
-  if (c->w.hdr.E == 64) {
-    const int ntile = B * (128 / ItaFfnF32Lds<64>::TT);
-    hipLaunchKernelGGL(ita_ffn_f32_kernel<64>, dim3(ntile < cap ? ntile : cap), dim3(256), ItaFfnF32Lds<64>::TOTAL, s, a);
-  } else {   // E = 128: the weights stream as fragment images (66 KB of LDS: two workgroups per CU)
-    a.w1 = L.w1p; a.w2 = L.w2p;
-    const int ntile = B * (128 / ItaFfnF32Lds<128>::TT);
-    hipLaunchKernelGGL(ita_ffn_f32_kernel<128>, dim3(ntile < cap ? ntile : cap), dim3(256), ItaFfnF32Lds<128>::TOTAL, s, a);
-  }
-  HIPCHK(hipGetLastError());
-  return ITA_OK;
+  return with_E(c->w.hdr.E, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    const int ntile = B * (128 / ItaFfnF32Lds<E>::TT);
+    return launch<ita_ffn_f32_kernel<E>, ItaFfnF32Lds<E>::TOTAL>(dim3(ntile < cap ? ntile : cap), dim3(256), s, a);
+  });
 }
 
 // the float32 attention block (ita_attn_f32_kernel.h) of an ITAW0003 layer, fuse: + residual + LayerNorm1
@@ -399,53 +481,44 @@ int launch_attn_f32(ita_context* c, int layer, const float* x, float* y, int B, 
   a.wq = L.wqf; a.wk = L.wkf; a.wv = L.wvf; a.bq = L.bqf; a.bk = L.bkf; a.bv = L.bvf; a.wo = L.wof; a.bo = L.bof;
   a.ln_w = L.n1w; a.ln_b = L.n1b; a.B = B; a.fuse_ln = fuse ? 1 : 0;
   // 130 KB (E = 64) / 96 KB (E = 128) of LDS: one workgroup per CU, frames in a grid stride
-  if (c->w.hdr.E == 64)
-    hipLaunchKernelGGL(ita_attn_f32_kernel<64>, dim3(B < c->num_cus ? B : c->num_cus), dim3(512), ItaAttnF32Lds<64>::TOTAL, s, a);
-  else
-    hipLaunchKernelGGL(ita_attn_f32_kernel<128>, dim3(B < c->num_cus ? B : c->num_cus), dim3(512), ItaAttnF32Lds<128>::TOTAL, s, a);
-  HIPCHK(hipGetLastError());
-  return ITA_OK;
+  return with_E(c->w.hdr.E, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    return launch<ita_attn_f32_kernel<E>, ItaAttnF32Lds<E>::TOTAL>(dim3(B < c->num_cus ? B : c->num_cus), dim3(512), s, a);
+  });
 }
 
 // One encoder layer: the stream kernel (ita_stream_kernel.h) when the layer has an LDS image -- E = 64 and every
 // accumulator provably inside the biased-float range (stream_range_ok) -- else the two block kernels through bufB.
 // A float-FFN layer (ITAW0002) is always two launches: the attention block with the fused residual + LayerNorm1 into bufB
-// (stream kernel mode 1, or ita_mha_kernel for a layer without an attention image), then ita_ffn_f32_kernel; `mid`, when
-// given, runs between the two (the profiler's stage-2 mark).  A float layer (ITAW0003) is the same two launches with
-// ita_attn_f32_kernel as the first.
-int launch_encoder(ita_context* c, int layer, const float* x, float* y, _Float16* y_hi, _Float16* y_lo, float* x1_tap,
-                   int B, hipStream_t s, unsigned long long* stamps = nullptr, const float* h0_src = nullptr,
-                   float* h0_dst = nullptr, const int* slots = nullptr, const void* img = nullptr,
-                   float* tok_tap = nullptr, const std::function<int()>* mid = nullptr) {
+// (stream kernel mode 1, or ita_mha_kernel for a layer without an attention image), then ita_ffn_f32_kernel; io.mid,
+// when given, takes its next mark between the two (the profiler's stage-2 mark).  A float layer (ITAW0003) is the same
+// two launches with ita_attn_f32_kernel as the first.
+int launch_encoder(ita_context* c, int layer, const StreamIo& io, int B, hipStream_t s) {
   const Layer& L = c->w.layers[layer];
   if (!L.n1w || !L.n2w) return fail(ITA_ERR_BAD_BLOB, "LayerNorm parameters missing from the blob");
+  const size_t x1_bytes = sizeof(float) * (size_t)B * 128 * c->w.hdr.E;
   if (L.ffn_f32) {
-    if (img || stamps) return fail(ITA_ERR_UNSUPPORTED, "a float-FFN layer runs behind the stand-alone tokenizer, without stamps");
+    if (io.img || io.stamps) return fail(ITA_ERR_UNSUPPORTED, "a float-FFN layer runs behind the stand-alone tokenizer, without stamps");
     if (c->w.hdr.E != 64 && !L.w1p) return fail(ITA_ERR_UNSUPPORTED, "the float32 FFN of an ITAW0002 blob is built for E = 64");
     int rc = ensure_workspace(c, B, s);
     if (rc) return rc;
-    if ((rc = L.attn_f32 ? launch_attn_f32(c, layer, x, c->ws.bufB, B, true, s)
-                         : launch_mha(c, layer, x, c->ws.bufB, B, true, nullptr, s))) return rc;
-    if (x1_tap) HIPCHK(hipMemcpyAsync(x1_tap, c->ws.bufB, sizeof(float) * (size_t)B * 128 * c->w.hdr.E, hipMemcpyDeviceToDevice, s));
-    if (mid && (rc = (*mid)())) return rc;
-    return launch_ffn_f32(c, layer, c->ws.bufB, y, B, true, s, y_hi, y_lo, h0_src, h0_dst, slots);
+    if ((rc = L.attn_f32 ? launch_attn_f32(c, layer, io.x, c->ws.bufB, B, true, s)
+                         : launch_mha(c, layer, io.x, c->ws.bufB, B, true, nullptr, s))) return rc;
+    if (io.x1_tap) HIPCHK(hipMemcpyAsync(io.x1_tap, c->ws.bufB, x1_bytes, hipMemcpyDeviceToDevice, s));
+    if (io.mid && (rc = io.mid->mark())) return rc;
+    return launch_ffn_f32(c, layer, c->ws.bufB, io.y, B, true, s, io.y_hi, io.y_lo, io.h0_src, io.h0_dst, io.slots);
   }
-  if (img ? L.simg_tok != nullptr : L.simg_enc != nullptr) {
-    StreamIo io;
-    io.x = x; io.y = y; io.y_hi = y_hi; io.y_lo = y_lo; io.x1_tap = x1_tap; io.stamps = stamps;
-    io.h0_src = h0_src; io.h0_dst = h0_dst; io.slots = slots; io.img = img; io.tok_tap = tok_tap;
-    return launch_stream(c, layer, 0, false, io, B, s);
-  }
-  if (img) return fail(ITA_ERR_INVALID_ARG, "launch_encoder: frames need the tokenizer image");
+  if (io.img ? L.simg_tok != nullptr : L.simg_enc != nullptr) return launch_stream(c, layer, 0, false, io, B, s);
+  if (io.img) return fail(ITA_ERR_INVALID_ARG, "launch_encoder: frames need the tokenizer image");
   // (everything that can refuse is checked before the first launch: no partial work is left behind an error)
-  if (h0_dst && slots) return fail(ITA_ERR_UNSUPPORTED, "slot-indexed state needs the stream kernel (this blob's accumulator range rules it out)");
+  if (io.h0_dst && io.slots) return fail(ITA_ERR_UNSUPPORTED, "slot-indexed state needs the stream kernel (this blob's accumulator range rules it out)");
   int rc = ensure_workspace(c, B, s);
   if (rc) return rc;
-  if ((rc = launch_mha(c, layer, x, c->ws.bufB, B, true, nullptr, s))) return rc;
-  if (x1_tap) HIPCHK(hipMemcpyAsync(x1_tap, c->ws.bufB, sizeof(float) * (size_t)B * 128 * c->w.hdr.E, hipMemcpyDeviceToDevice, s));
-  if (h0_dst)   // the side copy the stream kernel makes for the LSTM
-    HIPCHK(hipMemcpyAsync(h0_dst, h0_src, sizeof(float) * (size_t)B * 128, hipMemcpyDeviceToDevice, s));
-  return launch_ffn(c, layer, c->ws.bufB, y, B, true, nullptr, s, y_hi, y_lo);
+  if ((rc = launch_mha(c, layer, io.x, c->ws.bufB, B, true, nullptr, s))) return rc;
+  if (io.x1_tap) HIPCHK(hipMemcpyAsync(io.x1_tap, c->ws.bufB, x1_bytes, hipMemcpyDeviceToDevice, s));
+  if (io.h0_dst)   // the side copy the stream kernel makes for the LSTM
+    HIPCHK(hipMemcpyAsync(io.h0_dst, io.h0_src, sizeof(float) * (size_t)B * 128, hipMemcpyDeviceToDevice, s));
+  return launch_ffn(c, layer, c->ws.bufB, io.y, B, true, nullptr, s, io.y_hi, io.y_lo);
 }
 
 // frames into the E = 64 model: the tokenizer runs inside the first encoder layer's kernel
@@ -462,38 +535,17 @@ int launch_tokenizer(ita_context* c, const void* img, int dtype, float* tokens, 
   const bool u8 = dtype == ITA_IMAGE_U8;
   ItaTokStreamArgs ta{c->w.tok_simg + (u8 ? 0 : c->w.tok_simg_bytes), img, tokens, B};
   const int g = B < 2 * c->num_cus ? B : 2 * c->num_cus;   // 35 KB of LDS, <= 128 registers: two workgroups per CU
-  if (c->w.hdr.E == 64) {
-    if (u8) hipLaunchKernelGGL((ita_tok_stream_kernel<64, true>), dim3(g), dim3(512), (ItaTokStreamLds<64, true>::TOTAL), s, ta);
-    else hipLaunchKernelGGL((ita_tok_stream_kernel<64, false>), dim3(g), dim3(512), (ItaTokStreamLds<64, false>::TOTAL), s, ta);
-  } else {
-    if (u8) hipLaunchKernelGGL((ita_tok_stream_kernel<128, true>), dim3(g), dim3(512), (ItaTokStreamLds<128, true>::TOTAL), s, ta);
-    else hipLaunchKernelGGL((ita_tok_stream_kernel<128, false>), dim3(g), dim3(512), (ItaTokStreamLds<128, false>::TOTAL), s, ta);
-  }
-  HIPCHK(hipGetLastError());
-  return ITA_OK;
+  return with_E(c->w.hdr.E, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    return u8 ? launch<ita_tok_stream_kernel<E, true>, ItaTokStreamLds<E, true>::TOTAL>(dim3(g), dim3(512), s, ta)
+              : launch<ita_tok_stream_kernel<E, false>, ItaTokStreamLds<E, false>::TOTAL>(dim3(g), dim3(512), s, ta);
+  });
 }
 
 template <int NT, int WAVES, int TPS>
 int launch_tail_big_w(const ItaTailBigArgs& a, hipStream_t s) {
-  // the attribute is per DEVICE: one bit per ordinal (a process-wide flag left the second GPU's context without it).
-  // Lock-free on the launch path: the mutex is only taken by the first launch on a device.
-  static std::mutex mu;
-  static std::atomic<uint64_t> attr_set{0};
-  auto kern = ita_tail_big_kernel<NT, WAVES, TPS>;
-  constexpr int lds_bytes = ItaTailBigLds<NT, WAVES, TPS>::TOTAL;
-  {
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-      std::lock_guard<std::mutex> g(mu);
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-      attr_set.fetch_or(bit, std::memory_order_release);
-    }
-  }
-  hipLaunchKernelGGL(kern, dim3(2 * a.TW / 32, 2 * a.TH / (2 * WAVES), a.B), dim3(64 * WAVES), lds_bytes, s, a);
-  HIPCHK(hipGetLastError());
-  return ITA_OK;
+  return launch<ita_tail_big_kernel<NT, WAVES, TPS>, ItaTailBigLds<NT, WAVES, TPS>::TOTAL>(
+      dim3(2 * a.TW / 32, 2 * a.TH / (2 * WAVES), a.B), dim3(64 * WAVES), s, a);
 }
 // 16-row tiles on 8 waves with a whole chunk's weights resident when the map height allows (measured best:
 // 0.61 ms for 32 frames of BASELINE config 5); else 8-row tiles on 4 waves with a third of the chunk's taps
@@ -511,11 +563,8 @@ int launch_gemm_split(const _Float16* a_hi, const _Float16* a_lo, int lda, const
   if (N % BN || K % (64 * nsplit)) return fail(ITA_ERR_UNSUPPORTED, "split gemm shape");
   static const int dbg = getenv("ITA_GEMM_DBG") ? atoi(getenv("ITA_GEMM_DBG")) : 0;
   ItaGemmSplitArgs g{a_hi, a_lo, lda, w_hi, w_lo, ldw, out, M, N, K, nsplit, dbg, wf_hi, wf_lo};
-  if (M <= 32 && N % 32 == 0 && wf_hi && wf_lo) {   // one M tile: one wave per 32 x 32 tile and K slice
-    hipLaunchKernelGGL(ita_gemm_f16x3_tiny_kernel, dim3(N / 32, 1, nsplit), dim3(64), 0, s, g);
-    HIPCHK(hipGetLastError());
-    return ITA_OK;
-  }
+  if (M <= 32 && N % 32 == 0 && wf_hi && wf_lo)   // one M tile: one wave per 32 x 32 tile and K slice
+    return launch<ita_gemm_f16x3_tiny_kernel>(dim3(N / 32, 1, nsplit), dim3(64), s, g);
   if (M <= 256 && N % 32 == 0) {   // a few M tiles: four-wave workgroups share the staging, same arithmetic
     // M tiles per workgroup: up to four (128 frames: 128 workgroups).  Fewer tiles per workgroup fill the chip -- MT = ceil(M / 64)
     // gives 256 workgroups from 64 frames on and the kernel alone gets 1.4-2.9 us faster (64 / 128 frames, one stream) -- but in
@@ -524,19 +573,14 @@ int launch_gemm_split(const _Float16* a_hi, const _Float16* a_lo, int lda, const
     const int mt = M >= 128 ? 4 : (M + 31) / 32;
     const dim3 grid((N / 32) * nsplit, (M + 32 * mt - 1) / (32 * mt));
     switch (mt) {
-      case 1: hipLaunchKernelGGL(ita_gemm_f16x3_small_kernel<1>, grid, dim3(256), ita_gemm_small_lds(1), s, g); break;
-      case 2: hipLaunchKernelGGL(ita_gemm_f16x3_small_kernel<2>, grid, dim3(256), ita_gemm_small_lds(2), s, g); break;
-      case 3: hipLaunchKernelGGL(ita_gemm_f16x3_small_kernel<3>, grid, dim3(256), ita_gemm_small_lds(3), s, g); break;
-      default: hipLaunchKernelGGL(ita_gemm_f16x3_small_kernel<4>, grid, dim3(256), ita_gemm_small_lds(4), s, g); break;
+      case 1: return launch<ita_gemm_f16x3_small_kernel<1>, ita_gemm_small_lds(1)>(grid, dim3(256), s, g);
+      case 2: return launch<ita_gemm_f16x3_small_kernel<2>, ita_gemm_small_lds(2)>(grid, dim3(256), s, g);
+      case 3: return launch<ita_gemm_f16x3_small_kernel<3>, ita_gemm_small_lds(3)>(grid, dim3(256), s, g);
+      default: return launch<ita_gemm_f16x3_small_kernel<4>, ita_gemm_small_lds(4)>(grid, dim3(256), s, g);
     }
-    HIPCHK(hipGetLastError());
-    return ITA_OK;
   }
-  constexpr int lds_bytes = ItaGemmSplitLds<BM, BN>::TOTAL;
-  auto kern = ita_gemm_f16x3_kernel<BM, BN, WM, WN>;
-  hipLaunchKernelGGL(kern, dim3((N / BN) * ((M + BM - 1) / BM) * nsplit), dim3(64 * WM * WN), lds_bytes, s, g);
-  HIPCHK(hipGetLastError());
-  return ITA_OK;
+  return launch<ita_gemm_f16x3_kernel<BM, BN, WM, WN>, ItaGemmSplitLds<BM, BN>::TOTAL>(
+      dim3((N / BN) * ((M + BM - 1) / BM) * nsplit), dim3(64 * WM * WN), s, g);
 }
 
 template <typename T>
@@ -547,15 +591,24 @@ int launch_ingest(ita_context* c, const void* src, int H, int W, long long row_s
   if (W >= 2 * ITA_INGEST_W && row_bytes <= ITA_INGEST_ROW_BYTES) {
     const long long items = (long long)batch * (ITA_INGEST_H / 4);
     const int grid = (int)std::min<long long>(items, (long long)c->num_cus * 8);
-    hipLaunchKernelGGL(ita_ingest_rows_kernel<T>, dim3(grid), dim3(256), ita_ingest_rows_lds_total(row_bytes), s,
-                       (const T*)src, H, W, row_stride, frame_stride, scale_y, scale_x, depth_scale, frames, batch);
-  } else {
-    const long long blocks = ((long long)batch * ITA_INGEST_H * ITA_INGEST_W + 255) / 256;
-    const int grid = (int)std::min<long long>(blocks, (long long)c->num_cus * 8);
-    hipLaunchKernelGGL(ita_ingest_gather_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)src, H, W, row_stride,
-                       frame_stride, scale_y, scale_x, depth_scale, frames, batch);
+    // (at most ITA_INGEST_ROW_BYTES a row: within the LDS any kernel may ask for, nothing to register)
+    return launch_lds<ita_ingest_rows_kernel<T>, 0>(dim3(grid), dim3(256), ita_ingest_rows_lds_total(row_bytes), s, (const T*)src, H, W,
+                                                    row_stride, frame_stride, scale_y, scale_x, depth_scale, frames, batch);
   }
-  HIPCHK(hipGetLastError());
+  const long long blocks = ((long long)batch * ITA_INGEST_H * ITA_INGEST_W + 255) / 256;
+  const int grid = (int)std::min<long long>(blocks, (long long)c->num_cus * 8);
+  return launch<ita_ingest_gather_kernel<T>>(dim3(grid), dim3(256), s, (const T*)src, H, W, row_stride, frame_stride, scale_y, scale_x,
+                                             depth_scale, frames, batch);
+}
+
+// the source frames ita_ingest and ita_ingest_wire accept; no handle and no HIP call is involved
+static_assert(ITA_INGEST_MAX_DIM == 4096 && ITA_WIRE_MAX_DIM == 4096, "one size rule, one message");
+int check_frames(int height, int width, long long row_stride, long long frame_stride, int batch) {
+  if (height < 1 || height > 4096 || width < 1 || width > 4096) return fail(ITA_ERR_INVALID_ARG, "height and width must be in [1, 4096]");
+  if (batch < 1) return fail(ITA_ERR_INVALID_ARG, "batch must be positive");
+  if (row_stride < width || frame_stride < (long long)(height - 1) * row_stride + width)
+    return fail(ITA_ERR_INVALID_ARG, "row_stride < width, or frame_stride < (height - 1) * row_stride + width (strides are in pixels)");
+  if (row_stride > (1ll << 40) || frame_stride > (1ll << 40)) return fail(ITA_ERR_INVALID_ARG, "stride out of range");
   return ITA_OK;
 }
 
@@ -609,21 +662,11 @@ int prepare_wire(ita_context* c, int H, int W, WireSize** out) {
       }
       w.span[b] = std::max(w.span[b], end - first);
     }
-  int rc = set_lds((const void*)ita_ingest_wire_kernel<true, true>, ITA_WIRE_STAGED_LDS_MAX);
-  if (rc) return rc;
   w.H = H;
   w.W = W;
   *slot = std::move(w);
   if (out) *out = slot;
   return ITA_OK;
-}
-
-// event indices of a profiling stage's first and last mark among the 5 + 2 L events of one recorded forward
-struct StageMarks { int lo, hi; };
-StageMarks stage_marks(int num_layers, int stage) {
-  const int L2 = 2 * num_layers;
-  const int lo[ITA_NUM_STAGES] = {0, 1, 1, 1 + L2, 2 + L2, 3 + L2}, hi[ITA_NUM_STAGES] = {1, 1 + L2, 1 + L2, 2 + L2, 3 + L2, 4 + L2};
-  return {lo[stage], hi[stage]};
 }
 
 // ita_load_weights without its cleanup: any non-zero return leaves h->w half built
@@ -703,51 +746,8 @@ int ita_create(ita_handle* out, int device_ordinal) {
   std::unique_ptr<ita_context> c(new ita_context());
   c->device = dev;
   c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  // the kernels whose dynamic LDS size is registered when a handle is created, with their byte counts
-#define KFN(...) reinterpret_cast<const void*>(&__VA_ARGS__)
-  const struct { const void* kernel; int bytes; } lds[] = {
-      {KFN(ita_mha_kernel<64>), ItaMhaLds<64>::TOTAL},
-      {KFN(ita_attn_f32_kernel<64>), ItaAttnF32Lds<64>::TOTAL},
-      {KFN(ita_attn_f32_kernel<128>), ItaAttnF32Lds<128>::TOTAL},
-      {KFN(ita_ffn_f32_kernel<128>), ItaFfnF32Lds<128>::TOTAL},
-      {KFN(ita_mha_kernel<128>), ItaMhaLds<128>::TOTAL},
-      {KFN(ita_ffn_kernel<64>), ItaFfnLds<64>::TOTAL},
-      {KFN(ita_ffn_kernel<128>), ItaFfnLds<128>::TOTAL},
-      {KFN(ita_tok_stream_kernel<64, true>), ItaTokStreamLds<64, true>::TOTAL},
-      {KFN(ita_tok_stream_kernel<128, true>), ItaTokStreamLds<128, true>::TOTAL},
-      {KFN(ita_tok_stream_kernel<64, false>), ItaTokStreamLds<64, false>::TOTAL},
-      {KFN(ita_tok_stream_kernel<128, false>), ItaTokStreamLds<128, false>::TOTAL},
-      {KFN(ita_tail_kernel<64>), ita_tail_lds_bytes<64>()},
-      {KFN(ita_tail_up_kernel), ItaTailUpLds::TOTAL},
-      {KFN(ita_long_proj_kernel<false>), ItaStreamLds<128, false, false>::TOTAL},
-      {KFN(ita_long_proj_kernel<true>), ItaStreamLds<128, false, false>::TOTAL},
-      {KFN(ita_long_attn_kernel<false>), ItaLongLds::TOTAL},
-      {KFN(ita_long_attn_kernel<true>), ItaLongLds::TOTAL},
-      {KFN(ita_stream_kernel<64, true, 1, false, false, true>), ItaStreamLds<64, true, true>::TOTAL},
-      {KFN(ita_stream_kernel<64, true, 0, false, false, true>), ItaStreamLds<64, true, false>::TOTAL},
-      {KFN(ita_stream_kernel<64, false, 0, false, false, true>), ItaStreamLds<64, false, false>::TOTAL},
-      {KFN(ita_stream_kernel<128, false, 0, false, false, true>), ItaStreamLds<128, false, false>::TOTAL},
-      {KFN(ita_stream_kernel<128, true, 0, false, false, true>), ItaStreamLds<128, true, false>::TOTAL},
-      {KFN(ita_stream_kernel<64, false, 0, false, true, true>), ItaStreamLds<64, false, false>::TOTAL},
-      {KFN(ita_stream_kernel<128, false, 0, false, true, true>), ItaStreamLds<128, false, false>::TOTAL},
-      {KFN(ita_stream_kernel<64, true, 1>), ItaStreamLds<64, true, true>::TOTAL},
-      {KFN(ita_stream_kernel<64, true, 0>), ItaStreamLds<64, true, false>::TOTAL},
-      {KFN(ita_stream_kernel<64, true, 1, true>), ItaStreamLds<64, true, true>::TOTAL},
-      {KFN(ita_stream_kernel<64, true, 0, true>), ItaStreamLds<64, true, false>::TOTAL},
-      {KFN(ita_stream_kernel<64, false, 0>), ItaStreamLds<64, false, false>::TOTAL},
-      {KFN(ita_stream_kernel<128, false, 0>), ItaStreamLds<128, false, false>::TOTAL},
-      {KFN(ita_stream_kernel<128, true, 0>), ItaStreamLds<128, true, false>::TOTAL},
-      {KFN(ita_stream_kernel<64, false, 0, false, true>), ItaStreamLds<64, false, false>::TOTAL},
-      {KFN(ita_stream_kernel<128, false, 0, false, true>), ItaStreamLds<128, false, false>::TOTAL},
-      {KFN(ita_gemm_f16x3_kernel<128, 128, 2, 4>), ItaGemmSplitLds<128, 128>::TOTAL},
-      {KFN(ita_gemm_f16x3_small_kernel<1>), ita_gemm_small_lds(1)},
-      {KFN(ita_gemm_f16x3_small_kernel<2>), ita_gemm_small_lds(2)},
-      {KFN(ita_gemm_f16x3_small_kernel<3>), ita_gemm_small_lds(3)},
-      {KFN(ita_gemm_f16x3_small_kernel<4>), ita_gemm_small_lds(4)},
-  };
-#undef KFN
-  for (const auto& k : lds)
-    if (int rc = set_lds(k.kernel, k.bytes)) return rc;
+  for (const LdsKernel& k : lds_kernels())   // every kernel a launch can start with dynamic LDS, on this device
+    HIPCHK(hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes));
   *out = c.release();
   return ITA_OK;
 }
@@ -783,8 +783,10 @@ int ita_reserve(ita_handle h, int max_batch) {
   int rc = check(h, max_batch);
   if (rc) return rc;
   h->ws_reserved = false;          // an explicit reserve may move the workspace: the caller vouches that nothing is in flight
-  if (max_batch > h->ws.cap) HIPCHK(hipDeviceSynchronize());
-  rc = ensure_workspace(h, max_batch);
+  if (max_batch > h->ws.cap) {
+    HIPCHK(hipDeviceSynchronize());
+    rc = grow_workspace(h, max_batch);
+  }
   h->ws_reserved = rc == ITA_OK;
   return rc;
 }
@@ -802,9 +804,7 @@ int ita_get_dims(ita_handle h, int* E, int* S, int* P, int* F, int* H, int* num_
 
 int ita_mha_int8_taps(ita_handle h, int layer, const float* x, float* y, int batch, const ita_mha_taps* taps,
                       void* stream) {
-  int rc = check(h, batch);
-  if (rc) return rc;
-  if (!x || !y || layer < 0 || layer >= h->w.hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
+  if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
   return launch_mha(h, layer, x, y, batch, false, taps, (hipStream_t)stream);
 }
 int ita_mha_int8(ita_handle h, int layer, const float* x, float* y, int batch, void* stream) {
@@ -812,9 +812,7 @@ int ita_mha_int8(ita_handle h, int layer, const float* x, float* y, int batch, v
 }
 
 int ita_mha_long_q8(ita_handle h, int layer, const int8_t* x_q, int8_t* out_q, int batch, int seq_len, void* stream) {
-  int rc = check(h, batch);
-  if (rc) return rc;
-  if (!x_q || !out_q || layer < 0 || layer >= h->w.hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
+  if (int rc = check_layer_io(h, layer, x_q, out_q, batch)) return rc;
   if (h->w.layers[layer].attn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's attention is float32 (ITAW0003 blob): no int8 long attention");
   if (h->w.hdr.E != 128) return fail(ITA_ERR_UNSUPPORTED, "long-sequence attention is built for E = 128 (models/ITA, models/ITA_upsample_shuffle)");
   if (seq_len < 128 || seq_len % 128 || seq_len > 65536 || batch > 65535)
@@ -826,8 +824,7 @@ int ita_mha_long_q8(ita_handle h, int layer, const int8_t* x_q, int8_t* out_q, i
   const size_t ntile = (size_t)batch * (seq_len / 128);
   const size_t need = ntile * (3 * 24576 + 192 * 4);
   if (need > h->long_ws_bytes) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    if (capturing(s))
       return fail(ITA_ERR_INVALID_ARG, "the long-attention workspace cannot grow inside a stream capture; run one call first");
     HIPCHK(hipDeviceSynchronize());
     h->long_ws_bytes = 0;
@@ -843,19 +840,16 @@ int ita_mha_long_q8(ita_handle h, int layer, const int8_t* x_q, int8_t* out_q, i
   a.B = batch; a.S = seq_len;
   const bool fast = L.fast_sites == ITA_SITES_ALL;
   const int pg = ntile < (size_t)h->num_cus ? (int)ntile : h->num_cus;
-  if (fast) hipLaunchKernelGGL(ita_long_proj_kernel<true>, dim3(pg), dim3(512), (ItaStreamLds<128, false, false>::TOTAL), s, a);
-  else hipLaunchKernelGGL(ita_long_proj_kernel<false>, dim3(pg), dim3(512), (ItaStreamLds<128, false, false>::TOTAL), s, a);
-  HIPCHK(hipGetLastError());
-  if (fast) hipLaunchKernelGGL(ita_long_attn_kernel<true>, dim3(seq_len / 128, batch), dim3(512), ItaLongLds::TOTAL, s, a);
-  else hipLaunchKernelGGL(ita_long_attn_kernel<false>, dim3(seq_len / 128, batch), dim3(512), ItaLongLds::TOTAL, s, a);
-  HIPCHK(hipGetLastError());
-  return ITA_OK;
+  constexpr int proj_lds = ItaStreamLds<128, false, false>::TOTAL;
+  const dim3 attn_grid(seq_len / 128, batch);
+  if (int rc = fast ? launch<ita_long_proj_kernel<true>, proj_lds>(dim3(pg), dim3(512), s, a)
+                    : launch<ita_long_proj_kernel<false>, proj_lds>(dim3(pg), dim3(512), s, a)) return rc;
+  return fast ? launch<ita_long_attn_kernel<true>, ItaLongLds::TOTAL>(attn_grid, dim3(512), s, a)
+              : launch<ita_long_attn_kernel<false>, ItaLongLds::TOTAL>(attn_grid, dim3(512), s, a);
 }
 
 int ita_mha_q8(ita_handle h, int layer, const int8_t* x_q, int8_t* out_q, int batch, void* stream) {
-  int rc = check(h, batch);
-  if (rc) return rc;
-  if (!x_q || !out_q || layer < 0 || layer >= h->w.hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
+  if (int rc = check_layer_io(h, layer, x_q, out_q, batch)) return rc;
   StreamIo io;
   io.xq = x_q; io.yq = out_q;
   return launch_stream(h, layer, 2, false, io, batch, (hipStream_t)stream);
@@ -863,9 +857,7 @@ int ita_mha_q8(ita_handle h, int layer, const int8_t* x_q, int8_t* out_q, int ba
 
 int ita_ffn_int8_taps(ita_handle h, int layer, const float* x, float* y, int batch, const ita_ffn_taps* taps,
                       void* stream) {
-  int rc = check(h, batch);
-  if (rc) return rc;
-  if (!x || !y || layer < 0 || layer >= h->w.hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
+  if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
   return launch_ffn(h, layer, x, y, batch, false, taps, (hipStream_t)stream);
 }
 int ita_ffn_int8(ita_handle h, int layer, const float* x, float* y, int batch, void* stream) {
@@ -880,9 +872,7 @@ int ita_get_ffn_kind(ita_handle h, int layer, int* kind) {
 }
 
 int ita_ffn_f32(ita_handle h, int layer, const float* x, float* y, int batch, void* stream) {
-  int rc = check(h, batch);
-  if (rc) return rc;
-  if (!x || !y || layer < 0 || layer >= h->w.hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
+  if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
   return launch_ffn_f32(h, layer, x, y, batch, false, (hipStream_t)stream);
 }
 
@@ -912,17 +902,15 @@ int ita_get_attn_kind(ita_handle h, int layer, int* kind) {
 }
 
 int ita_mha_f32(ita_handle h, int layer, const float* x, float* y, int batch, void* stream) {
-  int rc = check(h, batch);
-  if (rc) return rc;
-  if (!x || !y || layer < 0 || layer >= h->w.hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
+  if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
   return launch_attn_f32(h, layer, x, y, batch, false, (hipStream_t)stream);
 }
 
 int ita_encoder_layer(ita_handle h, int layer, const float* x, float* y, int batch, void* stream) {
-  int rc = check(h, batch);
-  if (rc) return rc;
-  if (!x || !y || layer < 0 || layer >= h->w.hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
-  return launch_encoder(h, layer, x, y, nullptr, nullptr, nullptr, batch, (hipStream_t)stream);
+  if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
+  StreamIo io;
+  io.x = x; io.y = y;
+  return launch_encoder(h, layer, io, batch, (hipStream_t)stream);
 }
 
 int ita_debug_encoder_stamps(ita_handle h, int layer, const float* x, const void* image_u8, float* y, int batch,
@@ -934,8 +922,9 @@ int ita_debug_encoder_stamps(ita_handle h, int layer, const float* x, const void
   if (h->w.layers[layer].attn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's attention is float32 (ITAW0003 blob): no stream kernel, no stamps");
   if (image_u8 ? !h->w.layers[layer].simg_tok : !h->w.layers[layer].simg_enc)
     return fail(ITA_ERR_UNSUPPORTED, "this layer does not run on the stream kernel");
-  return launch_encoder(h, layer, x, y, nullptr, nullptr, nullptr, batch, (hipStream_t)stream, stamps, nullptr, nullptr,
-                        nullptr, image_u8);
+  StreamIo io;
+  io.x = x; io.y = y; io.stamps = stamps; io.img = image_u8;
+  return launch_encoder(h, layer, io, batch, (hipStream_t)stream);
 }
 
 #ifdef ITA_UP_STAMP
@@ -949,9 +938,7 @@ int ita_debug_softmax_rows(ita_handle h, const int8_t* logits, uint8_t* probs, i
   int rc = check(h, rows, false);
   if (rc) return rc;
   if (!logits || !probs) return fail(ITA_ERR_INVALID_ARG, "null pointer");
-  hipLaunchKernelGGL(ita_softmax_rows_kernel, dim3((rows + 15) / 16), dim3(64), 0, (hipStream_t)stream, logits, probs, rows);
-  HIPCHK(hipGetLastError());
-  return ITA_OK;
+  return launch<ita_softmax_rows_kernel>(dim3((rows + 15) / 16), dim3(64), (hipStream_t)stream, logits, probs, rows);
 }
 
 int ita_tokenizer(ita_handle h, const void* image, int image_dtype, float* tokens, int batch, void* stream) {
@@ -969,13 +956,7 @@ int ita_ingest(ita_handle h, const void* src, int pixel_dtype, int height, int w
   if (!src || !frames) return fail(ITA_ERR_INVALID_ARG, "null pointer");
   if (pixel_dtype != ITA_PIXEL_U8 && pixel_dtype != ITA_PIXEL_U16 && pixel_dtype != ITA_PIXEL_F32)
     return fail(ITA_ERR_INVALID_ARG, "pixel_dtype must be ITA_PIXEL_U8, ITA_PIXEL_U16 or ITA_PIXEL_F32");
-  if (height < 1 || height > ITA_INGEST_MAX_DIM || width < 1 || width > ITA_INGEST_MAX_DIM)
-    return fail(ITA_ERR_INVALID_ARG, "height and width must be in [1, 4096]");
-  if (batch < 1) return fail(ITA_ERR_INVALID_ARG, "batch must be positive");
-  if (row_stride < width || frame_stride < (long long)(height - 1) * row_stride + width)
-    return fail(ITA_ERR_INVALID_ARG, "row_stride < width, or frame_stride < (height - 1) * row_stride + width (strides are in pixels)");
-  if (row_stride > (1ll << 40) || frame_stride > (1ll << 40))
-    return fail(ITA_ERR_INVALID_ARG, "stride out of range");
+  if (int rc = check_frames(height, width, row_stride, frame_stride, batch)) return rc;
   const size_t px = pixel_dtype == ITA_PIXEL_U8 ? 1 : pixel_dtype == ITA_PIXEL_U16 ? 2 : 4;
   if ((uintptr_t)src % px || (uintptr_t)frames % sizeof(float))
     return fail(ITA_ERR_INVALID_ARG, "src must be aligned to its pixel size, frames to 4 bytes");
@@ -1017,19 +998,12 @@ int ita_ingest_wire(ita_handle h, const uint8_t* src, int height, int width, lon
   // every argument is judged before the handle is used and before any HIP call
   if (!h) return fail(ITA_ERR_INVALID_ARG, "null handle");
   if (!src || !wire) return fail(ITA_ERR_INVALID_ARG, "null pointer");
-  if (height < 1 || height > ITA_WIRE_MAX_DIM || width < 1 || width > ITA_WIRE_MAX_DIM)
-    return fail(ITA_ERR_INVALID_ARG, "height and width must be in [1, 4096]");
-  if (batch < 1) return fail(ITA_ERR_INVALID_ARG, "batch must be positive");
-  if (row_stride < width || frame_stride < (long long)(height - 1) * row_stride + width)
-    return fail(ITA_ERR_INVALID_ARG, "row_stride < width, or frame_stride < (height - 1) * row_stride + width");
-  if (row_stride > (1ll << 40) || frame_stride > (1ll << 40))
-    return fail(ITA_ERR_INVALID_ARG, "stride out of range");
+  if (int rc = check_frames(height, width, row_stride, frame_stride, batch)) return rc;
   HIPCHK(hipSetDevice(h->device));
   hipStream_t s = (hipStream_t)stream;
   WireSize* w = find_wire(h, height, width);
   if (!w) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    if (capturing(s))
       return fail(ITA_ERR_INVALID_ARG, "this source size has no tables yet and they cannot be built inside a stream capture; call ita_ingest_wire_prepare first");
     const int rc = prepare_wire(h, height, width, &w);
     if (rc) return rc;
@@ -1046,17 +1020,15 @@ int ita_ingest_wire(ita_handle h, const uint8_t* src, int height, int width, lon
   const long long items = (long long)batch * ((ITA_WIRE_H + rows - 1) / rows);
   const int grid = (int)std::min<long long>(items, (long long)h->num_cus * 8);
   const int lds = ita_wire_lds_bytes(width, span);
-  if (span)
-    hipLaunchKernelGGL((ita_ingest_wire_kernel<true, true>), dim3(grid), dim3(256), lds, s, src, height, width, row_stride,
-                       frame_stride, w->dev, wire, batch, rows, span);
-  else if (row_stride % 4 == 0)
-    hipLaunchKernelGGL((ita_ingest_wire_kernel<true, false>), dim3(grid), dim3(256), lds, s, src, height, width, row_stride,
-                       frame_stride, w->dev, wire, batch, rows, span);
-  else
-    hipLaunchKernelGGL((ita_ingest_wire_kernel<false, false>), dim3(grid), dim3(256), lds, s, src, height, width, row_stride,
-                       frame_stride, w->dev, wire, batch, rows, span);
-  HIPCHK(hipGetLastError());
-  return ITA_OK;
+  // (the unstaged forms hold four W-float rows: within the LDS any kernel may ask for, nothing to register)
+  auto run = [&](auto dwords, auto staged) {
+    constexpr bool DWORDS = decltype(dwords)::value, STAGED = decltype(staged)::value;
+    return launch_lds<ita_ingest_wire_kernel<DWORDS, STAGED>, STAGED ? ITA_WIRE_STAGED_LDS_MAX : 0>(
+        dim3(grid), dim3(256), lds, s, src, height, width, row_stride, frame_stride, w->dev, wire, batch, rows, span);
+  };
+  if (span) return run(std::true_type{}, std::true_type{});
+  if (row_stride % 4 == 0) return run(std::true_type{}, std::false_type{});
+  return run(std::false_type{}, std::false_type{});
 }
 
 int ita_fusion_tail(ita_handle h, const float* x, float* feat, int batch, void* stream) {
@@ -1153,9 +1125,7 @@ int ita_fusion_tail_large(ita_handle h, const float* x, float* out, int batch, i
     if (span_ok(tok_h, OH, 16, ItaTailUpLds::RH) && span_ok(tok_w, OW, 32, ItaTailUpLds::RW)) {
       ItaTailUpArgs u{x, h->tl.up_hi, h->tl.up_lo, h->tl.ps_hi, h->tl.ps_lo, h->tl.bias, h->tl.inv_scale, out, batch, tok_h, tok_w, h->tl.CO};
       const long ntiles = (long)(OW / 32) * (OH / 16) * batch;      // persistent: one workgroup per CU, tiles dealt round robin
-      hipLaunchKernelGGL(ita_tail_up_kernel, dim3((unsigned)(ntiles < h->num_cus ? ntiles : h->num_cus)), dim3(512), ItaTailUpLds::TOTAL, s, u);
-      HIPCHK(hipGetLastError());
-      return ITA_OK;
+      return launch<ita_tail_up_kernel, ItaTailUpLds::TOTAL>(dim3((unsigned)(ntiles < h->num_cus ? ntiles : h->num_cus)), dim3(512), s, u);
     }
   }
   switch (h->tl.nt) {
@@ -1189,9 +1159,7 @@ static int launch_lstm_head(ita_context* h, const float* part, const float* desv
                             const int* slots, hipStream_t s) {
   ItaLstmHeadArgs p{lstm_model_args(h, part), desvel, quat, h_in, c_in, h_out, c_out, lstride,
                     h->ws.c1_hi, h->ws.c1_lo, h->ws.c2_hi, h->ws.c2_lo, h->w.fc_w, h->w.fc_b, vel, h->ws.head_sync + ITA_HEAD_CNT_STRIDE, h->ws.head_sync, B, slots};
-  hipLaunchKernelGGL(ita_lstm_head_kernel<NSPLIT>, lstm_grid(B), dim3(256), 0, s, p);
-  HIPCHK(hipGetLastError());
-  return ITA_OK;
+  return launch<ita_lstm_head_kernel<NSPLIT>>(lstm_grid(B), dim3(256), s, p);
 }
 
 // its sequence form (ita_lstm_seq_kernel): n steps of B streams from partial buffer 0, whose row t * B + b is stream b's
@@ -1200,9 +1168,7 @@ static int launch_lstm_seq(ita_context* h, const float* desvel, const float* qua
                            const int* lengths, int t0, float* vel, int B, int n, hipStream_t s) {
   ItaLstmSeqArgs p{lstm_model_args(h, h->ws.part), desvel, quat, state_h, state_c, lengths, t0, h->ws.seq_ho,
                    h->w.fc_w, h->w.fc_b, vel, h->ws.head_sync + ITA_HEAD_CNT_STRIDE, h->ws.head_sync, B, n};
-  hipLaunchKernelGGL(ita_lstm_seq_kernel<NSPLIT>, lstm_grid(B), dim3(256), 0, s, p);
-  HIPCHK(hipGetLastError());
-  return ITA_OK;
+  return launch<ita_lstm_seq_kernel<NSPLIT>>(lstm_grid(B), dim3(256), s, p);
 }
 
 // x2_in != null: start behind the encoder from a given (B,128,E) activation (ita_vitlstm_tail); image is then unused
@@ -1225,19 +1191,8 @@ static int forward_impl(ita_handle h, const void* image, int image_dtype, const 
   const bool fast = h->tail_mode == 1 && h->w.folded;
   if (slots && !fast) return fail(ITA_ERR_UNSUPPORTED, "slot-indexed state needs tail mode 1");
   const size_t lstride = (size_t)(slots ? state_rows : batch) * 128;   // layer stride of the (3, rows, 128) state
-  const int ev_per_fwd = 5 + 2 * h->w.hdr.num_layers;
-  hipEvent_t* ev = nullptr;
-  if (h->prof && h->prof_n < h->prof_max && (h->prof_calls++ % h->prof_every) == 0)
-    ev = &h->prof_ev[(size_t)h->prof_n * ev_per_fwd];
-  // an event in the stream costs a pipeline bubble of ~5 us (the next kernel cannot be launched
-  // under the tail of the previous one), so in single-stage mode only that stage's two marks are recorded
-  int evi = 0, m_lo = 0, m_hi = ev_per_fwd - 1;
-  if (h->prof_stage >= 0) {
-    const StageMarks m = stage_marks(h->w.hdr.num_layers, h->prof_stage);
-    m_lo = m.lo; m_hi = m.hi;
-  }
-#define MARK() do { if (ev && (h->prof_stage < 0 || evi == m_lo || evi == m_hi)) HIPCHK(hipEventRecord(ev[evi], s)); ++evi; } while (0)
-  MARK();
+  StageRecorder rec(h, s, true);
+  if ((rc = rec.mark())) return rc;
   const bool fused_tok = !x2_in && fuse_tokenizer(h, image_dtype);
   if (slots && !x2_in) {   // refuse before the first launch: the slot-indexed form is served by the stream kernel only
     const Layer& LL = h->w.layers.back();
@@ -1248,74 +1203,68 @@ static int forward_impl(ita_handle h, const void* image, int image_dtype, const 
     HIPCHK(hipMemcpyAsync(h->ws.bufA, x2_in, tokb, hipMemcpyDeviceToDevice, s));
     if (fast) {
       const size_t n = (size_t)B * 128 * h->w.hdr.E;
-      hipLaunchKernelGGL(ita_split_planes_kernel, dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0, s, h->ws.bufA, h->ws.x2_hi,
-                         h->ws.x2_lo, 128 * h->w.hdr.E, h->w.ldfold, B);
-      HIPCHK(hipGetLastError());
+      if ((rc = launch<ita_split_planes_kernel>(dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), s, h->ws.bufA, h->ws.x2_hi,
+                                                h->ws.x2_lo, 128 * h->w.hdr.E, h->w.ldfold, B))) return rc;
     }
   } else if (!fused_tok && (rc = launch_tokenizer(h, image, image_dtype, h->ws.bufA, B, s))) return rc;
-  MARK();
+  if ((rc = rec.mark())) return rc;
   if (!x2_in && !fused_tok && taps && taps->tokens) HIPCHK(hipMemcpyAsync(taps->tokens, h->ws.bufA, tokb, hipMemcpyDeviceToDevice, s));
   for (int l = 0; l < (x2_in ? 0 : h->w.hdr.num_layers); ++l) {
     const bool last = l == h->w.hdr.num_layers - 1;
     const bool planes = fast && last;
-    float* yout = (planes && !(taps && taps->x2)) ? nullptr : h->ws.bufA;
-    bool marked = false;   // a float-FFN layer records the attention / FFN boundary between its two launches
-    const std::function<int()> mid = [&]() -> int { MARK(); marked = true; return ITA_OK; };
-    // one encoder layer, in place on bufA
-    if ((rc = launch_encoder(h, l, h->ws.bufA, yout, planes ? h->ws.x2_hi : nullptr, planes ? h->ws.x2_lo : nullptr,
-                             (taps && last) ? taps->x1 : nullptr, B, s, nullptr, nullptr, nullptr, slots,
-                             (fused_tok && l == 0) ? image : nullptr,
-                             (fused_tok && l == 0 && taps) ? taps->tokens : nullptr, &mid))) return rc;
-    if (!marked) MARK();
-    MARK();
+    StreamIo io;   // one encoder layer, in place on bufA
+    io.x = h->ws.bufA;
+    io.y = (planes && !(taps && taps->x2)) ? nullptr : h->ws.bufA;
+    if (planes) { io.y_hi = h->ws.x2_hi; io.y_lo = h->ws.x2_lo; }
+    if (taps && last) io.x1_tap = taps->x1;
+    io.slots = slots;
+    if (fused_tok && l == 0) { io.img = image; io.tok_tap = taps ? taps->tokens : nullptr; }
+    io.mid = &rec;   // a layer of two launches records the attention / FFN boundary between them
+    const int mid_mark = rec.next;
+    if ((rc = launch_encoder(h, l, io, B, s))) return rc;
+    if (rec.next == mid_mark && (rc = rec.mark())) return rc;
+    if ((rc = rec.mark())) return rc;
   }
-  if (x2_in) { MARK(); MARK(); }
+  if (x2_in && ((rc = rec.mark()) || (rc = rec.mark()))) return rc;
   if (taps && taps->x2) HIPCHK(hipMemcpyAsync(taps->x2, h->ws.bufA, tokb, hipMemcpyDeviceToDevice, s));
   if (fast) {
     // folded tail+decoder: dec = x2 . Wfold^T + bias'   (x2 planes were written by the last FFN)
     if ((rc = launch_gemm_split<128, 128, 2, 4>(h->ws.x2_hi, h->ws.x2_lo, h->w.ldfold, h->w.fold_hi, h->w.fold_lo, h->w.ldfold, h->ws.part, B,
                                                 512, h->w.kfold, NSPLIT, s, h->w.foldf_hi, h->w.foldf_lo))) return rc;
-    MARK();
-    MARK();
+    if ((rc = rec.mark()) || (rc = rec.mark())) return rc;
     if ((rc = launch_lstm_head(h, h->ws.part, desvel, quat, h_in, c_in, h_out, c_out, lstride, vel, B, slots, s))) return rc;
-    MARK();
+    if ((rc = rec.mark())) return rc;
   } else {
     if (h->w.hdr.has_tail) {
       if ((rc = launch_tail(h->num_cus, h->w.hdr.E, h->w.tail_wT, h->w.tail_b, h->ws.bufA, h->ws.feat, 4608, B, s))) return rc;
-      MARK();
+      if ((rc = rec.mark())) return rc;
       if (taps && taps->feat)
         HIPCHK(hipMemcpyAsync(taps->feat, h->ws.feat, sizeof(float) * (size_t)B * 4608, hipMemcpyDeviceToDevice, s));
       // decoder writes straight into the LSTM layer-0 concat buffer (columns 0..511)
       if ((rc = launch_gemm(h->ws.feat, 4608, h->w.dec_w, 4608, h->w.dec_b, h->ws.cat0, K0P, B, 512, 4608, s))) return rc;
     } else {   // no fusion tail: the decoder reads the flattened tokens, (B,128,E) as it stands in bufA
-      MARK();
+      if ((rc = rec.mark())) return rc;
       if ((rc = launch_gemm(h->ws.bufA, h->w.kfold, h->w.dec_w, h->w.kfold, h->w.dec_b, h->ws.cat0, K0P, B, 512, h->w.kfold, s))) return rc;
     }
-    MARK();
+    if ((rc = rec.mark())) return rc;
     if (taps && taps->dec)
       HIPCHK(hipMemcpy2DAsync(taps->dec, 512 * sizeof(float), h->ws.cat0, K0P * sizeof(float), 512 * sizeof(float), B,
                               hipMemcpyDeviceToDevice, s));
-    {
-      ItaLstmPrepArgs p{desvel, quat, h_in, h->ws.cat0, h->ws.cat1, h->ws.cat2, K0P, B};
-      hipLaunchKernelGGL(ita_lstm_prep_kernel, dim3(B), dim3(256), 0, s, p);
-      HIPCHK(hipGetLastError());
-    }
+    ItaLstmPrepArgs prep{desvel, quat, h_in, h->ws.cat0, h->ws.cat1, h->ws.cat2, K0P, B};
+    if ((rc = launch<ita_lstm_prep_kernel>(dim3(B), dim3(256), s, prep))) return rc;
     float* cats[3] = {h->ws.cat0, h->ws.cat1, h->ws.cat2};
     const int kp[3] = {K0P, 256, 256};
     for (int l = 0; l < 3; ++l) {
       if ((rc = launch_gemm(cats[l], kp[l], h->w.wcat[l], kp[l], h->w.bsum[l], h->ws.gates, 512, B, 512, kp[l], s))) return rc;
       ItaLstmPointArgs p{h->ws.gates, c_in + (size_t)l * B * 128, h_out + (size_t)l * B * 128, c_out + (size_t)l * B * 128,
                          l < 2 ? cats[l + 1] : nullptr, 256, B};
-      hipLaunchKernelGGL(ita_lstm_point_kernel, dim3((B * 128 + 255) / 256), dim3(256), 0, s, p);
-      HIPCHK(hipGetLastError());
+      if ((rc = launch<ita_lstm_point_kernel>(dim3((B * 128 + 255) / 256), dim3(256), s, p))) return rc;
     }
-    hipLaunchKernelGGL(ita_fc_kernel, dim3((B * 3 + 63) / 64), dim3(64), 0, s, h_out + (size_t)2 * B * 128, h->w.fc_w,
-                       h->w.fc_b, vel, B);
-    HIPCHK(hipGetLastError());
-    MARK();
+    if ((rc = launch<ita_fc_kernel>(dim3((B * 3 + 63) / 64), dim3(64), s, h_out + (size_t)2 * B * 128, h->w.fc_w, h->w.fc_b, vel, B,
+                                    (const int*)nullptr))) return rc;   // (rows in order: no slots)
+    if ((rc = rec.mark())) return rc;
   }
-#undef MARK
-  if (ev) ++h->prof_n;
+  rec.finish();
   return ITA_OK;
 }
 
@@ -1348,39 +1297,31 @@ static int front_impl(ita_handle h, const void* image, int image_dtype, int batc
   _Float16* const xh = h->ws.x2_hi + (size_t)xbuf * h->ws.cap * h->w.ldfold;
   _Float16* const xl = h->ws.x2_lo + (size_t)xbuf * h->ws.cap * h->w.ldfold;
   // sampled single-stage profiling (ita_profile_begin_sampled with only_stage 0, 1 or 3) also works here
-  const int per = 5 + 2 * h->w.hdr.num_layers;
-  hipEvent_t* ev = nullptr;
-  if (h->prof && h->prof_stage >= 0 && h->prof_n < h->prof_max && (h->prof_calls++ % h->prof_every) == 0)
-    ev = &h->prof_ev[(size_t)h->prof_n * per];
-  auto mark = [&](int stage, bool end) -> int {
-    if (ev && h->prof_stage == stage) {
-      const StageMarks m = stage_marks(h->w.hdr.num_layers, stage);
-      HIPCHK(hipEventRecord(ev[end ? m.hi : m.lo], s));
-    }
-    return ITA_OK;
-  };
+  StageRecorder rec(h, s, false);
   if (parts & 1) {
-    if ((rc = mark(0, false))) return rc;
+    if ((rc = rec.mark(0, false))) return rc;
     const bool fused_tok = fuse_tokenizer(h, image_dtype);
     if (!fused_tok && (rc = launch_tokenizer(h, image, image_dtype, h->ws.bufA, batch, s))) return rc;
-    if ((rc = mark(0, true)) || (rc = mark(1, false))) return rc;
+    if ((rc = rec.mark(0, true)) || (rc = rec.mark(1, false))) return rc;
     for (int l = 0; l < h->w.hdr.num_layers; ++l) {
       const bool last = l == h->w.hdr.num_layers - 1;
-      if ((rc = launch_encoder(h, l, h->ws.bufA, last ? nullptr : h->ws.bufA, last ? xh : nullptr, last ? xl : nullptr,
-                               nullptr, batch, s, nullptr, nullptr, nullptr, nullptr, (fused_tok && l == 0) ? image : nullptr,
-                               nullptr))) return rc;
+      StreamIo io;
+      io.x = h->ws.bufA;
+      if (last) { io.y_hi = xh; io.y_lo = xl; } else io.y = h->ws.bufA;
+      if (fused_tok && l == 0) io.img = image;
+      if ((rc = launch_encoder(h, l, io, batch, s))) return rc;
     }
-    if ((rc = mark(1, true))) return rc;
+    if ((rc = rec.mark(1, true))) return rc;
     if (encoder_done_event) HIPCHK(hipEventRecord((hipEvent_t)encoder_done_event, s));
   }
   if (parts & 2) {
-    if ((rc = mark(3, false))) return rc;
+    if ((rc = rec.mark(3, false))) return rc;
     float* part = h->ws.part + (size_t)buf * NSPLIT * h->ws.cap * 512;
     if ((rc = launch_gemm_split<128, 128, 2, 4>(xh, xl, h->w.ldfold, h->w.fold_hi, h->w.fold_lo, h->w.ldfold, part, batch, 512,
                                                 h->w.kfold, NSPLIT, s, h->w.foldf_hi, h->w.foldf_lo))) return rc;
-    if ((rc = mark(3, true))) return rc;
+    if ((rc = rec.mark(3, true))) return rc;
   }
-  if (ev && (h->prof_stage == 0 || h->prof_stage == 1 || h->prof_stage == 3)) ++h->prof_n;
+  rec.finish();
   return ITA_OK;
 }
 
@@ -1559,7 +1500,7 @@ int ita_profile_begin_sampled(ita_handle h, int max_forwards, int every_n, int o
   h->prof_every = every_n;
   h->prof_stage = only_stage;
   h->prof_calls = 0;
-  const size_t need = (size_t)max_forwards * (5 + 2 * h->w.hdr.num_layers);
+  const size_t need = (size_t)max_forwards * StageRecorder::events_per_forward(h);
   while (h->prof_ev.size() < need) {
     hipEvent_t e;
     HIPCHK(hipEventCreate(&e));
@@ -1575,7 +1516,7 @@ int ita_profile_end(ita_handle h, double* stage_ms, int* n_forwards) {
   if (!h || !stage_ms || !n_forwards) return fail(ITA_ERR_INVALID_ARG, "null argument");
   HIPCHK(hipSetDevice(h->device));
   h->prof = false;
-  const int L = h->w.hdr.num_layers, per = 5 + 2 * L;
+  const int L = h->w.hdr.num_layers, per = StageRecorder::events_per_forward(h);
   for (int i = 0; i < ITA_NUM_STAGES; ++i) stage_ms[i] = 0.0;
   for (int f = 0; f < h->prof_n; ++f) {
     hipEvent_t* ev = &h->prof_ev[(size_t)f * per];

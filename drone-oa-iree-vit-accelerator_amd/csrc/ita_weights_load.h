@@ -2,7 +2,8 @@
 // steps that build it from a blob, in the order the loader runs them.
 //
 // A part of ita_plugin.hip, its only includer, and not a stand-alone header: ita_plugin.hip defines fail(), HIPCHK,
-// DevBuf, K0P / K0S and the two exact-f32 launch helpers the fold uses (launch_tail, launch_gemm) ahead of the #include.
+// DevBuf, K0P / K0S, launch and the two exact-f32 launch helpers the fold uses (launch_tail, launch_gemm) ahead of the
+// #include.
 #pragma once
 
 namespace {
@@ -548,7 +549,7 @@ int fold_matrix(const Weights& w, int num_cus, std::vector<float>& hmt, std::vec
     auto tail = [&](const float* bias, int B) { return launch_tail(num_cus, w.hdr.E, w.tail_wT, bias, imp, feat, 4608, B, nullptr); };
     for (int c0 = 0; c0 < KFOLD; c0 += CH) {   // bias-free pass: column i of Wfold = dec_nobias(tail_nobias(e_i))
       const size_t n = (size_t)CH * KFOLD;
-      hipLaunchKernelGGL(ita_impulse_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, imp, CH, KFOLD, c0);
+      if ((rc = launch<ita_impulse_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), nullptr, imp, CH, KFOLD, c0))) return rc;
       if ((rc = tail(zero, CH))) return rc;
       if ((rc = launch_gemm(feat, 4608, w.dec_w, 4608, nullptr, mt + (size_t)c0 * 512, 512, CH, 512, 4608, nullptr))) return rc;
     }
