@@ -1,6 +1,6 @@
 // ita_int8_kernels.h -- the ITA int8 blocks on gfx950 int8 MFMA.
 //
-//   ita_mha_kernel<E>  : ITASelfAttention_QAT.forward   (reference models/ITA/QAT/layers.py:101-127)
+//   ita_mha_kernel<E, H> : ITASelfAttention_QAT.forward with H heads (reference models/ITA/QAT/layers.py:101-127)
 //                        + optional fused residual add + LayerNorm
 //                        (models/ITA_single_layer_upsample_shuffle/QAT/model.py:102-106)
 //   ita_ffn_kernel<E>  : ITAFeedForward_QAT.forward     (layers.py:61-75) + residual + LayerNorm
@@ -29,7 +29,7 @@ struct ItaMhaArgs {
   int B;
   int fuse_ln;
   // optional per-stage taps for parity tests (all may be null)
-  int8_t *t_xq, *t_Q, *t_K, *t_V, *t_logits;
+  int8_t *t_xq, *t_Q, *t_K, *t_V, *t_logits;   // logits and probs: (B, H, 128, 128)
   uint8_t* t_probs;
   int8_t *t_ctx, *t_out;
 };
@@ -164,8 +164,9 @@ __device__ __forceinline__ void store_tile_fx(const i32x16& acc, float mult, flo
 }
 
 // ======================================================================================
-template <int E>
+template <int E, int H = 1>   // H heads of 192 / H features: 1, 2, 3, 4 or 6
 __global__ __launch_bounds__(512) void ita_mha_kernel(const ItaMhaArgs a) {
+  static_assert(H >= 1 && 192 % (16 * H) == 0, "a head is a whole number of 16-feature chunks");
   using L = ItaMhaLds<E>;
   constexpr int S = 128, P = 192, EC = E / 4;
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -231,7 +232,10 @@ __global__ __launch_bounds__(512) void ita_mha_kernel(const ItaMhaArgs a) {
     __syncthreads();
 
     // ---------------- phase A: per wave 16 queries: QK^T -> integer softmax -> A.V, in registers
-    {
+    // (The one-head branch is the kernel's earlier phase A, kept verbatim: its instruction stream is the measured one.
+    //  Sharing the logits tap / softmax / A.V code with the head loop through forceinline helpers -- by value, by
+    //  reference, with lazily formed tap offsets, either helper alone -- moved its schedule and registers every time.)
+    if constexpr (H == 1) {
       const int q0 = wave * 16, qi = lane & 15, kq = lane >> 4;
       i32x4 qf[3];
 #pragma unroll
@@ -303,6 +307,97 @@ __global__ __launch_bounds__(512) void ita_mha_kernel(const ItaMhaArgs a) {
                                   rq_bits(acc[3], a.mc));
         *(unsigned*)(lds + L::Q + cm_off(q0 + qi, dt * 16 + 4 * kq, 128)) = c4;
         if (a.t_ctx) *(unsigned*)(a.t_ctx + ((size_t)b * S + q0 + qi) * P + dt * 16 + 4 * kq) = c4;
+      }
+    } else {
+      // Head by head.  Head hd owns the NC 16-feature chunks [hd*NC, (hd+1)*NC) of Q, K and the context; logits and
+      // context keep one multiplier (ml, mc) across the heads, as the reference's matmul1 / matmul2 keep one scale.
+      constexpr int NC = P / (16 * H), KS = (NC + 3) / 4;   // chunks per head; 16x16x64 steps per head (4 chunks each)
+      const int q0 = wave * 16, qi = lane & 15, kq = lane >> 4;
+#pragma unroll
+      for (int hd = 0; hd < H; ++hd) {
+        // Step ks takes the head's chunk 4*ks + kq from lane group kq.  A and B agree on that assignment, which is all
+        // the dot product needs, so a head need not start on a 64-byte boundary.  Past the head's last chunk the Q
+        // fragment is zero and the K fragment rereads the head's first chunk: the product adds nothing.
+        i32x4 qf[KS];
+        int kb0[KS];   // first feature (K byte) of this lane's chunk
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+          const bool in = NC % 4 == 0 || 4 * ks + kq < NC;
+          kb0[ks] = 16 * hd * NC + (in ? 64 * ks + 16 * kq : 0);
+          const i32x4 f = lds_frag(lds + L::Q, cm_off(q0 + qi, kb0[ks], 128));
+          qf[ks] = in ? f : i32x4{0, 0, 0, 0};
+        }
+        // S^T tiles: rows = keys, cols = queries: v[4*kt + i] <-> key kt*16 + 4*kq + i, query q0 + qi
+        int v[32];
+#pragma unroll
+        for (int kt = 0; kt < 8; ++kt) {
+          i32x4 acc = {0, 0, 0, 0};
+#pragma unroll
+          for (int ks = 0; ks < KS; ++ks) {
+            const i32x4 kf = lds_frag(lds + L::K, cm_off(kt * 16 + qi, kb0[ks], 128));
+            acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(kf, qf[ks], acc, 0, 0, 0);
+          }
+#pragma unroll
+          for (int i = 0; i < 4; ++i) v[4 * kt + i] = bits_to_int(rq_bits(acc[i], a.ml));
+        }
+        const size_t row = (((size_t)b * H + hd) * S + q0 + qi) * S + 4 * kq;   // logits / probs taps: (B, H, 128, 128)
+        if (a.t_logits) {
+          int8_t* tl = a.t_logits + row;
+#pragma unroll
+          for (int kt = 0; kt < 8; ++kt)
+            *(unsigned*)(tl + 16 * kt) = pack4(v[4 * kt], v[4 * kt + 1], v[4 * kt + 2], v[4 * kt + 3]);
+        }
+        // integer softmax (models/ITA/QAT/ITA_softmax.py:51-61): shift = max - x,
+        // num = 256 >> shift, inv = floor(255*2^16 / sum), y = (num * inv) >> 16 = (inv >> 8) >> shift
+        int m = v[0];
+#pragma unroll
+        for (int j = 1; j < 32; ++j) m = max(m, v[j]);
+        m = max(m, __shfl_xor(m, 16));
+        m = max(m, __shfl_xor(m, 32));
+        int sum = 0;
+#pragma unroll
+        for (int j = 0; j < 32; ++j) {
+          v[j] = min(m - v[j], 23);
+          sum += 256 >> v[j];
+        }
+        sum += __shfl_xor(sum, 16);
+        sum += __shfl_xor(sum, 32);
+        sum = max(sum, 1);
+        const int inv = (int)floorf((1.0f / (float)sum) * 16711680.0f);
+        const int inv_hi = inv >> 8;
+        unsigned pk[8];
+#pragma unroll
+        for (int kt = 0; kt < 8; ++kt)
+          pk[kt] = pack4(inv_hi >> v[4 * kt], inv_hi >> v[4 * kt + 1], inv_hi >> v[4 * kt + 2],
+                         inv_hi >> v[4 * kt + 3]);
+        if (a.t_probs) {
+          uint8_t* tp = a.t_probs + row;
+#pragma unroll
+          for (int kt = 0; kt < 8; ++kt) *(unsigned*)(tp + 16 * kt) = pk[kt];
+        }
+        // A.V with uint8 probabilities on a signed MFMA: (p - 128) * v summed + 128 * colsum(v).  A 16-feature tile
+        // lies inside one head (16 divides every head width), so the head's tiles take the head's probabilities.
+        i32x4 pf[2];
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+          for (int t = 0; t < 4; ++t) pf[kb][t] = (int)(pk[4 * kb + t] ^ 0x80808080u);
+#pragma unroll
+        for (int dt = hd * NC; dt < (hd + 1) * NC; ++dt) {
+          i32x4 acc = *(const i32x4*)(colsum + dt * 16 + 4 * kq);
+          acc = acc << 7;
+#pragma unroll
+          for (int kb = 0; kb < 2; ++kb) {
+            const i32x4 vf = lds_frag(lds + L::VT, ((((kb * 4 + kq) * P) + dt * 16 + qi) << 4));
+            acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(vf, pf[kb], acc, 0, 0, 0);
+          }
+          // acc[i] <-> feature dt*16 + 4*kq + i, query q0 + qi; the context overwrites this wave's own Q rows, in the
+          // chunks of the head whose Q fragments are already in registers
+          const unsigned c4 = pack4(rq_bits(acc[0], a.mc), rq_bits(acc[1], a.mc), rq_bits(acc[2], a.mc),
+                                    rq_bits(acc[3], a.mc));
+          *(unsigned*)(lds + L::Q + cm_off(q0 + qi, dt * 16 + 4 * kq, 128)) = c4;
+          if (a.t_ctx) *(unsigned*)(a.t_ctx + ((size_t)b * S + q0 + qi) * P + dt * 16 + 4 * kq) = c4;
+        }
       }
     }
     __syncthreads();

@@ -383,7 +383,7 @@ int launch_stream(ita_context* c, int layer, int mode, bool fuse_ln, const Strea
   const dim3 grid(B < c->num_cus ? B : c->num_cus), block(512);
   const bool fast = L.fast_sites == ITA_SITES_ALL;
   if (mode == 2) {
-    if (!L.simg_mha) return fail(ITA_ERR_UNSUPPORTED, "this layer has no attention image (accumulator range)");
+    if (!L.simg_mha) return fail(ITA_ERR_UNSUPPORTED, "this layer has no attention image (accumulator range, or more than one head)");
     a.image = L.simg_mha;
     return with_E(c->w.hdr.E, [&](auto e) { return launch_stream_kernel<decltype(e)::value, false, 0, true>(fast, grid, s, a); });
   }
@@ -416,7 +416,8 @@ int launch_mha_stream(ita_context* c, int layer, const float* x, float* y, int B
 }
 
 // the attention block: without taps on the stream kernel (weights resident in LDS, activations chained through
-// registers); with taps, or for a layer without an LDS image, on the tile-phased kernel that can expose every tensor
+// registers); with taps, or for a layer without an LDS image (accumulator range, or H > 1 heads), on the tile-phased
+// kernel that can expose every tensor and is instantiated per head count
 int launch_mha(ita_context* c, int layer, const float* x, float* y, int B, bool fuse, const ita_mha_taps* t,
                hipStream_t s) {
   if (c->w.layers[layer].attn_f32)
@@ -427,7 +428,14 @@ int launch_mha(ita_context* c, int layer, const float* x, float* y, int B, bool 
   const int grid = B < c->num_cus ? B : c->num_cus;
   return with_E(c->w.hdr.E, [&](auto e) {
     constexpr int E = decltype(e)::value;
-    return launch<ita_mha_kernel<E>, ItaMhaLds<E>::TOTAL>(dim3(grid), dim3(512), s, a);
+    switch (c->w.hdr.H) {   // (check_blob admits these five)
+      case 1: return launch<ita_mha_kernel<E, 1>, ItaMhaLds<E>::TOTAL>(dim3(grid), dim3(512), s, a);
+      case 2: return launch<ita_mha_kernel<E, 2>, ItaMhaLds<E>::TOTAL>(dim3(grid), dim3(512), s, a);
+      case 3: return launch<ita_mha_kernel<E, 3>, ItaMhaLds<E>::TOTAL>(dim3(grid), dim3(512), s, a);
+      case 4: return launch<ita_mha_kernel<E, 4>, ItaMhaLds<E>::TOTAL>(dim3(grid), dim3(512), s, a);
+      case 6: return launch<ita_mha_kernel<E, 6>, ItaMhaLds<E>::TOTAL>(dim3(grid), dim3(512), s, a);
+    }
+    return fail(ITA_ERR_UNSUPPORTED, "the attention kernel is built for H in {1,2,3,4,6}");
   });
 }
 
@@ -487,7 +495,7 @@ int launch_attn_f32(ita_context* c, int layer, const float* x, float* y, int B, 
   });
 }
 
-// One encoder layer: the stream kernel (ita_stream_kernel.h) when the layer has an LDS image -- E = 64 and every
+// One encoder layer: the stream kernel (ita_stream_kernel.h) when the layer has an LDS image -- one head and every
 // accumulator provably inside the biased-float range (stream_range_ok) -- else the two block kernels through bufB.
 // A float-FFN layer (ITAW0002) is always two launches: the attention block with the fused residual + LayerNorm1 into bufB
 // (stream kernel mode 1, or ita_mha_kernel for a layer without an attention image), then ita_ffn_f32_kernel; io.mid,
@@ -511,7 +519,7 @@ int launch_encoder(ita_context* c, int layer, const StreamIo& io, int B, hipStre
   if (io.img ? L.simg_tok != nullptr : L.simg_enc != nullptr) return launch_stream(c, layer, 0, false, io, B, s);
   if (io.img) return fail(ITA_ERR_INVALID_ARG, "launch_encoder: frames need the tokenizer image");
   // (everything that can refuse is checked before the first launch: no partial work is left behind an error)
-  if (io.h0_dst && io.slots) return fail(ITA_ERR_UNSUPPORTED, "slot-indexed state needs the stream kernel (this blob's accumulator range rules it out)");
+  if (io.h0_dst && io.slots) return fail(ITA_ERR_UNSUPPORTED, "slot-indexed state needs the stream kernel (this blob's accumulator range or head count rules it out)");
   int rc = ensure_workspace(c, B, s);
   if (rc) return rc;
   if ((rc = launch_mha(c, layer, io.x, c->ws.bufB, B, true, nullptr, s))) return rc;
@@ -818,7 +826,7 @@ int ita_mha_long_q8(ita_handle h, int layer, const int8_t* x_q, int8_t* out_q, i
   if (seq_len < 128 || seq_len % 128 || seq_len > 65536 || batch > 65535)
     return fail(ITA_ERR_UNSUPPORTED, "seq_len must be a multiple of 128 in [128, 65536], batch <= 65535");
   const Layer& L = h->w.layers[layer];
-  if (!L.simg_mha) return fail(ITA_ERR_UNSUPPORTED, "this layer has no attention image (accumulator range)");
+  if (!L.simg_mha) return fail(ITA_ERR_UNSUPPORTED, "this layer has no attention image (accumulator range, or more than one head)");
   // the logits of a long row still fit the 16-bit travel format: same bound as stream_range_ok (per key, not per row)
   hipStream_t s = (hipStream_t)stream;
   const size_t ntile = (size_t)batch * (seq_len / 128);
@@ -1197,7 +1205,7 @@ static int forward_impl(ita_handle h, const void* image, int image_dtype, const 
   if (slots && !x2_in) {   // refuse before the first launch: the slot-indexed form is served by the stream kernel only
     const Layer& LL = h->w.layers.back();
     if (!LL.ffn_f32 && !((fused_tok && h->w.hdr.num_layers == 1) ? LL.simg_tok : LL.simg_enc))
-      return fail(ITA_ERR_UNSUPPORTED, "slot-indexed state needs the stream kernel (this blob's accumulator range rules it out)");
+      return fail(ITA_ERR_UNSUPPORTED, "slot-indexed state needs the stream kernel (this blob's accumulator range or head count rules it out)");
   }
   if (x2_in) {
     HIPCHK(hipMemcpyAsync(h->ws.bufA, x2_in, tokb, hipMemcpyDeviceToDevice, s));

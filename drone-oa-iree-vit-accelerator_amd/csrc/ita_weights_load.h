@@ -4,6 +4,12 @@
 // A part of ita_plugin.hip, its only includer, and not a stand-alone header: ita_plugin.hip defines fail(), HIPCHK,
 // DevBuf, K0P / K0S, launch and the two exact-f32 launch helpers the fold uses (launch_tail, launch_gemm) ahead of the
 // #include.
+//
+// Head counts (header field H): an ITAW0001 blob (int8 attention, int8 FFN) loads with H in {1, 2, 3, 4, 6}; its layers
+// then get no stream-kernel images at H > 1 and run on ita_mha_kernel<E, H> + ita_ffn_kernel<E>.  Two refusals stay, both
+// ITA_ERR_UNSUPPORTED in check_blob: an ITAW0003 blob (float attention, one head by construction of its kernel) with
+// H > 1, and an ITAW0002 blob (int8 attention, float FFN) with H > 1 -- launch_mha would run it, but no fixture of the
+// reference pins that graph, so it is not offered.
 #pragma once
 
 namespace {
@@ -312,9 +318,14 @@ int check_blob(const void* blob, size_t nbytes, ita_blob_header* hdr_out, BlobKi
   memcpy(&hdr, blob, sizeof hdr);
   if (hdr.n_tensors < 0 || sizeof(hdr) + (size_t)hdr.n_tensors * sizeof(ita_blob_entry) > nbytes)
     return fail(ITA_ERR_BAD_BLOB, "tensor table exceeds the blob");
-  if ((hdr.E != 64 && hdr.E != 128) || hdr.S != 128 || hdr.P != 192 || hdr.F != 256 || hdr.H != 1 ||
+  const bool heads_ok = hdr.H == 1 || hdr.H == 2 || hdr.H == 3 || hdr.H == 4 || hdr.H == 6;
+  if ((hdr.E != 64 && hdr.E != 128) || hdr.S != 128 || hdr.P != 192 || hdr.F != 256 || !heads_ok ||
       hdr.num_layers < 1 || hdr.num_layers > 16)
-    return fail(ITA_ERR_UNSUPPORTED, "kernels are built for E in {64,128}, S=128, P=192, F=256, H=1");
+    return fail(ITA_ERR_UNSUPPORTED, "kernels are built for E in {64,128}, S=128, P=192, F=256, H in {1,2,3,4,6}");
+  // heads run on the int8 block attention kernel of an all-int8 blob only: the float attention kernel (ITAW0003) has
+  // one head, and the attention-only graph (ITAW0002) is not tested with more
+  if (hdr.H != 1 && (attn_kind != 0 || ffn_kind != 0))
+    return fail(ITA_ERR_UNSUPPORTED, "H > 1 needs an ITAW0001 blob (int8 attention and int8 FFN)");
   // the float graph (ITAW0003) runs at E = 64 with its fusion tail, and at E = 128 without one (ITA_upsample_shuffle)
   if (attn_kind == 1 && hdr.E != 64 && hdr.has_tail)
     return fail(ITA_ERR_UNSUPPORTED, "the float32 graph's fusion tail (ITAW0003) is built for E = 64; at E = 128 it runs without one");
@@ -399,6 +410,7 @@ int build_stream_images(Weights& w) {
   for (int i = 0; i < hdr.num_layers; ++i) {
     Layer& L = w.layers[i];
     if (L.attn_f32) continue;   // no int8 attention: no stream images (ita_attn_f32_kernel + ita_ffn_f32_kernel)
+    if (hdr.H != 1) continue;   // the stream kernels have one head: a multi-head layer runs on the block kernels
     StreamHostParams sp{};
     sp.wq = hptr<int8_t>(w, NM("attn%d.wq")); sp.wk = hptr<int8_t>(w, NM("attn%d.wk")); sp.wv = hptr<int8_t>(w, NM("attn%d.wv"));
     sp.wo = hptr<int8_t>(w, NM("attn%d.wo")); sp.w1 = hptr<int8_t>(w, NM("ffn%d.w1")); sp.w2 = hptr<int8_t>(w, NM("ffn%d.w2"));

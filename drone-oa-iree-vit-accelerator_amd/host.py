@@ -219,15 +219,20 @@ class Engine:
         self.device = torch.cuda.current_device() if device is None else int(device)
         self._h = C.c_void_p()
         _chk(lib().ita_create(C.byref(self._h), self.device))
+        self.load_weights(blob)
+        self._reserved = 0          # frames the workspace is pinned for (ita_reserve); grows only
+        self._graphs = []           # weakrefs of live captured graphs: they hold raw workspace pointers
+        if reserve:
+            self.reserve(reserve)
+
+    def load_weights(self, blob: bytes):
+        """(Re)load a blob into this handle (ita_load_weights) and read its dims.  A refused blob raises and leaves the
+        handle without weights: load another one."""
         buf = C.create_string_buffer(blob, len(blob))
         _chk(lib().ita_load_weights(self._h, buf, len(blob)))
         d = [C.c_int() for _ in range(6)]
         _chk(lib().ita_get_dims(self._h, *[C.byref(x) for x in d]))
         self.E, self.S, self.P, self.F, self.H, self.num_layers = [x.value for x in d]
-        self._reserved = 0          # frames the workspace is pinned for (ita_reserve); grows only
-        self._graphs = []           # weakrefs of live captured graphs: they hold raw workspace pointers
-        if reserve:
-            self.reserve(reserve)
 
     def reserve(self, batch: int):
         """Size and pin the workspace for `batch` frames (ita_reserve).  Growing it frees and reallocates every internal
@@ -262,7 +267,8 @@ class Engine:
     # ---- int8 blocks -------------------------------------------------------------------
     def mha(self, x, layer: int = 0, taps: bool = False):
         """the layer's attention block without residual / LayerNorm: ITASelfAttention_QAT.forward, (B,128,E) f32 ->
-        (B,128,E) f32 [, dict of int tensors], or, on an ITAW0003 blob, the float32 ITASelfAttention (no taps)"""
+        (B,128,E) f32 [, dict of int tensors], or, on an ITAW0003 blob, the float32 ITASelfAttention (no taps).  The
+        logits and probs taps are (B,128,128) at one head and (B,H,128,128) at H > 1."""
         torch = _torch()
         if self.attn_kind(layer) == ATTN_F32:
             if taps:
@@ -275,8 +281,9 @@ class Engine:
             _chk(lib().ita_mha_int8(self._h, layer, x.data_ptr(), y.data_ptr(), B, _stream_ptr(self.device)))
             return y
         mk = lambda *s, dt=torch.int8: torch.empty(s, dtype=dt, device=x.device)
+        lp = (B, 128, 128) if self.H == 1 else (B, self.H, 128, 128)
         t = dict(x_q=mk(B, 128, self.E), Q=mk(B, 128, self.P), K=mk(B, 128, self.P), V=mk(B, 128, self.P),
-                 logits=mk(B, 128, 128), probs=mk(B, 128, 128, dt=torch.uint8), ctx=mk(B, 128, self.P),
+                 logits=mk(*lp), probs=mk(*lp, dt=torch.uint8), ctx=mk(B, 128, self.P),
                  out_q=mk(B, 128, self.E))
         st = _MhaTaps(**{k: v.data_ptr() for k, v in t.items()})
         _chk(lib().ita_mha_int8_taps(self._h, layer, x.data_ptr(), y.data_ptr(), B, C.byref(st), _stream_ptr(self.device)))

@@ -124,9 +124,10 @@ def pack_blob(tensors: Dict[str, np.ndarray], E: int, S: int = 128, P: int = 192
     return hdr + b"".join(entries) + b"".join(chunks)
 
 
-def blob_from_record(rec: dict, float_params: dict | None, E: int, num_layers: int = 1) -> bytes:
+def blob_from_record(rec: dict, float_params: dict | None, E: int, num_layers: int = 1, H: int = 1) -> bytes:
     """A record without the int8 FFN (no ``ffn0.fc1.w_q``) is the attention-only graph: its FFN comes from
-    float_params (``ffn_blocks.{i}.fc1.weight`` ...) and the blob is an ITAW0002 one."""
+    float_params (``ffn_blocks.{i}.fc1.weight`` ...) and the blob is an ITAW0002 one.  H: the attention's head count
+    (the tensors do not depend on it; the engine runs H in {1, 2, 3, 4, 6} of an ITAW0001 blob)."""
     ffn_f32 = "ffn0.fc1.w_q" not in rec
     if ffn_f32 and (float_params is None or "ffn_blocks.0.fc1.weight" not in float_params):
         raise KeyError("the record has no int8 FFN and float_params no ffn_blocks.{i}.fc1.weight")
@@ -142,7 +143,7 @@ def blob_from_record(rec: dict, float_params: dict | None, E: int, num_layers: i
             ft = {k: v for k, v in ft.items() if not (k.startswith("ffn") and k[-1] == "f")}
         t.update(ft)
         has_tail = "tail.conv_w" in t     # without it the decoder reads the flattened tokens (models/ITA/QAT/model.py:80-81)
-    return pack_blob(t, E=E, num_layers=num_layers, has_tail=has_tail, ffn_f32=ffn_f32)
+    return pack_blob(t, E=E, H=H, num_layers=num_layers, has_tail=has_tail, ffn_f32=ffn_f32)
 
 
 def float_attention_tensors(fp: dict, i: int) -> Dict[str, np.ndarray]:
@@ -294,16 +295,18 @@ def float_params_from_state_dict(sd: dict, num_layers: int = 1) -> dict:
     return fp
 
 
-def blob_from_state_dict(sd: dict, num_layers: int = 1) -> bytes:
+def blob_from_state_dict(sd: dict, num_layers: int = 1, H: int = 1) -> bytes:
     """a converted (QAT) checkpoint -> ITAW0001 / ITAW0002; a float checkpoint (training's model_000205.pth: float
     attention_blocks.{i}.q_proj.weight, no _packed_params) -> ITAW0003.  Every model file's layer names are accepted
-    (canonical_state_dict)."""
+    (canonical_state_dict).  H: the head count the checkpoint was trained with (a state dict does not hold it)."""
     sd = canonical_state_dict(sd)
     fp = float_params_from_state_dict(sd, num_layers)
     kinds = {_float_attn(sd, i) for i in range(num_layers)}
     if kinds == {True}:
+        if H != 1:
+            raise ValueError("the float graph (ITAW0003) runs with one head")
         return blob_from_float_params(fp, num_layers)
     if len(kinds) > 1:
         raise ValueError("a checkpoint mixing float and converted attention layers has no blob format")
     E = fp["tokenizer.conv.weight"].shape[0]
-    return blob_from_record(record_from_state_dict(sd, num_layers), fp, E=E, num_layers=num_layers)
+    return blob_from_record(record_from_state_dict(sd, num_layers), fp, E=E, num_layers=num_layers, H=H)

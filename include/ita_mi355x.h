@@ -33,7 +33,7 @@ typedef enum ita_status {
   ITA_ERR_INVALID_ARG = -1,
   ITA_ERR_BAD_BLOB = -2,      /* magic / bounds / missing tensor */
   ITA_ERR_NO_WEIGHTS = -3,    /* compute call before ita_load_weights */
-  ITA_ERR_UNSUPPORTED = -4,   /* dims the kernels are not built for */
+  ITA_ERR_UNSUPPORTED = -4,   /* dims or a head count the kernels, or this entry point, are not built for */
   ITA_ERR_HIP = -5,           /* a HIP runtime call failed; see ita_error_string */
   ITA_ERR_NO_DEVICE = -6,
   ITA_ERR_NOT_BOUND = -7      /* drop-in symbol called without ita_bind_dispatch */
@@ -48,6 +48,11 @@ int ita_abi_version(void);
 int ita_create(ita_handle* out, int device_ordinal);
 int ita_destroy(ita_handle h);
 /* Uploads an "ITAW0001" blob (ita_weights.h) from host memory; replaces any earlier weights.
+ * Dims: E in {64, 128}, S = 128, P = 192, F = 256, H (attention heads) in {1, 2, 3, 4, 6}; H > 1 for an all-int8
+ * (ITAW0001) blob only -- ITAW0002 and ITAW0003 blobs run with one head.  Anything else: ITA_ERR_UNSUPPORTED.
+ * A layer with H > 1 runs on the block kernels (ita_mha_kernel<E, H>, then the FFN block) behind the stand-alone tokenizer;
+ * every entry point below serves it except those that need the one-head stream kernel, which return
+ * ITA_ERR_UNSUPPORTED before any launch: ita_mha_q8, ita_mha_long_q8, ita_debug_encoder_stamps, ita_vitlstm_forward_slots.
  * The reference pre-loads weights into the accelerator out of band
  * (docs/HOW-TO-run-the-full-project-workflow.md:55); this is that step. */
 int ita_load_weights(ita_handle h, const void* blob, size_t nbytes);
@@ -74,12 +79,12 @@ const char* ita_error_string(void);       /* human readable detail for ita_last_
 /* ---- hot path: device pointers, asynchronous on `stream` ---------------------------------- */
 
 /* ITASelfAttention_QAT.forward (models/ITA/QAT/layers.py:101-127): x (B,128,E) f32 -> y (B,128,E)
- * f32 = dequantised out_proj.  layer < num_layers. */
+ * f32 = dequantised out_proj, with the blob's H heads of P / H features.  layer < num_layers. */
 int ita_mha_int8(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, void* stream);
 
 /* As above, also writing the per-stage integer tensors (any pointer may be NULL):
- * x_q (B,128,E) s8, Q/K/V (B,128,P) s8, logits (B,128,128) s8, probs (B,128,128) u8,
- * ctx (B,128,P) s8, out_q (B,128,E) s8.  Used by the parity tests
+ * x_q (B,128,E) s8, Q/K/V (B,128,P) s8, logits (B,H,128,128) s8, probs (B,H,128,128) u8 (H from ita_get_dims: one
+ * 128 x 128 map per head, (B,128,128) at H = 1), ctx (B,128,P) s8 (heads concatenated), out_q (B,128,E) s8.  Used by the parity tests
  * (the reference hooks the same tensors: tests/export_and_validation_W_B.py:25-102). */
 typedef struct ita_mha_taps {
   int8_t *x_q, *Q, *K, *V, *logits;

@@ -62,7 +62,9 @@ enum ita_dtype { ITA_F32 = 0, ITA_I8 = 1, ITA_I32 = 2, ITA_U8 = 3, ITA_F16 = 4 }
 typedef struct ita_blob_header {
   char magic[8];
   int32_t n_tensors;
-  int32_t E, S, P, F, H; /* models/ITA_single_layer_upsample_shuffle/QAT/model.py:38 */
+  int32_t E, S, P, F, H; /* models/ITA_single_layer_upsample_shuffle/QAT/model.py:38.  H: attention heads of P / H
+                          * features each (whole 16-feature chunks).  No tensor depends on it.  ita_load_weights takes
+                          * H in {1, 2, 3, 4, 6} for an ITAW0001 blob and H = 1 for ITAW0002 / ITAW0003. */
   int32_t num_layers;
   int32_t has_tail;   /* 1: pixel-shuffle/upsample fusion tail + 4608-wide decoder (ITAViTLSTM) */
   int32_t reserved[6];
@@ -126,7 +128,7 @@ static inline int ita_blob_validate(const void* blob, size_t nbytes, char* bad_n
   const int kind = ita_blob_ffn_kind(blob, nbytes), akind = ita_blob_attn_kind(blob, nbytes);
   if (kind < 0 || akind < 0) return -1;
   if (h->n_tensors < 0 || sizeof(ita_blob_header) + (size_t)h->n_tensors * sizeof(ita_blob_entry) > nbytes) return -1;
-  if (h->E <= 0 || h->E % 64 || h->E > 1024 || h->S != 128 || h->P <= 0 || h->P % 64 || h->F <= 0 || h->F % 64 || h->H != 1 ||
+  if (h->E <= 0 || h->E % 64 || h->E > 1024 || h->S != 128 || h->P <= 0 || h->P % 64 || h->F <= 0 || h->F % 64 || h->H < 1 || h->H > h->P / 16 || (h->P / 16) % h->H ||
       h->num_layers < 1 || h->num_layers > 16)
     return -1;
   const ita_blob_entry* e = (const ita_blob_entry*)((const char*)blob + sizeof(ita_blob_header));
