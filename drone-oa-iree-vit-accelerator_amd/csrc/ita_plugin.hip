@@ -68,10 +68,10 @@ constexpr int LDS_PER_CU = 160 * 1024;   // gfx950
 
 template <auto Kernel, int Bytes, typename... Args>
 int launch_lds(dim3 grid, dim3 block, int lds_bytes, hipStream_t s, const Args&... args) {
-  // An instantiation that asks for more than the device has (ita_tail_big_kernel<4, 8, 9>, 166752 bytes: more than 48
-  // output channels on 16-row tiles) is not listed: hipFuncSetAttribute refuses it, and ita_create would fail for every
-  // caller.  HIP refuses its launch instead, with the same ITA_ERR_HIP.
-  if constexpr (Bytes > 0 && Bytes <= LDS_PER_CU)
+  // An instantiation that asks for more than a CU has could never launch (hipFuncSetAttribute refuses it, and ita_create
+  // would fail for every caller): it fails the build here instead of a user's call.
+  static_assert(Bytes <= LDS_PER_CU, "this kernel instantiation asks for more LDS than a gfx950 CU has");
+  if constexpr (Bytes > 0)
     (void)LdsListed<Kernel, Bytes>::yes;   // the ODR-use that instantiates the member, nothing at run time
   hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, s, args...);
   HIPCHK(hipGetLastError());
@@ -557,11 +557,14 @@ int launch_tail_big_w(const ItaTailBigArgs& a, hipStream_t s) {
 }
 // 16-row tiles on 8 waves with a whole chunk's weights resident when the map height allows (measured best:
 // 0.61 ms for 32 frames of BASELINE config 5); else 8-row tiles on 4 waves with a third of the chunk's taps
-// resident (70 KB of LDS, two workgroups per CU: 0.66 ms).
+// resident (70 KB of LDS, two workgroups per CU: 0.66 ms).  More than 48 output channels (NT = 4) always take the
+// 8-row form (76256 bytes, still two workgroups per CU; the map height is a multiple of 8 by ita_fusion_tail_large's
+// own check): <4, 8, 9> would need 166752 bytes, more than a CU has.
 template <int NT>
 int launch_tail_big(const ItaTailBigArgs& a, hipStream_t s) {
-  if ((2 * a.TH) % 16 != 0) return launch_tail_big_w<NT, 4, 3>(a, s);
-  return launch_tail_big_w<NT, 8, 9>(a, s);
+  if constexpr (NT < 4)
+    if ((2 * a.TH) % 16 == 0) return launch_tail_big_w<NT, 8, 9>(a, s);
+  return launch_tail_big_w<NT, 4, 3>(a, s);
 }
 
 template <int BM, int BN, int WM, int WN>

@@ -909,15 +909,21 @@ class FusionTailLarge:
         if not torch.cuda.is_available():
             raise ITAError("no GPU visible: the ITA engine has no CPU path")
         self.device = torch.cuda.current_device() if device is None else int(device)
-        w = np.ascontiguousarray(conv_w, dtype=np.float32)
-        b = np.ascontiguousarray(conv_b, dtype=np.float32)
-        self.CO, cin = w.shape[0], w.shape[1]
-        self.E = cin * 4 // 5
-        if w.shape[2:] != (3, 3) or self.E // 4 + self.E != cin or b.shape != (self.CO,):
-            raise ITAError("conv_w must be (CO, 5E/4, 3, 3) and conv_b (CO,)")
         self._h = C.c_void_p()
         _chk(lib().ita_create(C.byref(self._h), self.device))
-        _chk(lib().ita_fusion_tail_load(self._h, w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), self.E, self.CO))
+        self.reload(conv_w, conv_b)
+
+    def reload(self, conv_w, conv_b):
+        """ita_fusion_tail_load on the same handle: replaces the weights, E and CO included"""
+        import numpy as np
+        w = np.ascontiguousarray(conv_w, dtype=np.float32)
+        b = np.ascontiguousarray(conv_b, dtype=np.float32)
+        CO, cin = w.shape[0], w.shape[1]
+        E = cin * 4 // 5
+        if w.shape[2:] != (3, 3) or E // 4 + E != cin or b.shape != (CO,):
+            raise ITAError("conv_w must be (CO, 5E/4, 3, 3) and conv_b (CO,)")
+        _chk(lib().ita_fusion_tail_load(self._h, w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), E, CO))
+        self.E, self.CO = E, CO
 
     def __call__(self, x, tok_h: int, tok_w: int, out=None):
         """x (B, tok_h*tok_w, E) f32 on the GPU -> (B, CO, 2 tok_h, 2 tok_w) f32"""

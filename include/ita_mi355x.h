@@ -313,8 +313,19 @@ int ita_profile_end(ita_handle h, double* stage_ms, int* n_forwards);
  * tok_h x tok_w token grid (models/ITA_upsample_shuffle/model.py:70-79 declares them with E = 128 and
  * 48 outputs):  x_dev (B, tok_h*tok_w, E) f32 -> out_dev (B, out_ch, 2 tok_h, 2 tok_w) f32.
  * ita_fusion_tail_load takes HOST pointers (conv weight (out_ch, 5E/4, 3, 3), bias (out_ch)), once;
- * it is independent of ita_load_weights.  Split-precision f16 MFMA, result within 1e-5 relative of
- * the f32 oracle.  Needs E % 16 == 0, out_ch <= 64, tok_h % 4 == 0, tok_w % 16 == 0. */
+ * it is independent of ita_load_weights; a later call on the same handle replaces the weights, E
+ * and out_ch included.  Needs E % 16 == 0, out_ch <= 64, tok_h % 4 == 0, tok_w % 16 == 0,
+ * batch <= 65535 (ITA_ERR_UNSUPPORTED otherwise; a refused load leaves the loaded tail in place).
+ * Split-precision f16 MFMA: the weights are scaled by a power of two before their f16 hi / lo split
+ * (any weight magnitude, exactly), the tokens are split AS THEY COME.  The accuracy claim -- within
+ * 2e-5 of the largest output magnitude of the f32 oracle and of a float64 evaluation -- therefore
+ * holds for a window of token magnitudes, tested at tokens ~ N(0,1) * 2^p for p = -6 ... +12:
+ *   above it, a token or bilinear blend with |value| > 65504 overflows the f16 hi plane (inf, then
+ *   NaN, in the output; N(0,1) * 2^14 does);
+ *   below it, the lo plane sinks into the f16 subnormals and loses bits: the result stays finite
+ *   and the error grows as the tokens shrink -- measured (zero bias, relative to the largest
+ *   output) 1.2e-6 at p = -6, 1.9e-5 to 2.3e-5 at p = -10, 7.2e-5 to 7.9e-5 at p = -12, as an
+ *   emulation that keeps f16 subnormals predicts: the MFMA does not flush them. */
 int ita_fusion_tail_load(ita_handle h, const float* conv_w_host, const float* conv_b_host, int E, int out_ch);
 int ita_fusion_tail_large(ita_handle h, const float* x_dev, float* out_dev, int batch, int tok_h, int tok_w,
                           void* stream);

@@ -2,14 +2,17 @@
 
 CPU: the generalised oracle (oracle/ita_oracle.c:ita_oracle_tail_general) against outputs of the torch layers the
 reference declares (tests/golden/tail_large_*.npz, tools/gen_golden.py:gen_tail_large): <= 2e-5 absolute (PyTorch's
-conv summation order is not the oracle's), and its sampled form against the full form (equality).
+conv summation order is not the oracle's), and its sampled form against the full form (equality); both, and the torch
+outputs, against a float64 definition written from the layers alone (tail_common.tail_f64).
 GPU (-m gpu): ita_fusion_tail_large through the C ABI against the oracle.  The kernel runs the convolution on
 split-precision f16 MFMA (three products, f32 accumulate): tolerance 2e-5 relative to the largest output magnitude,
-stated at the assertion (the task's bound for this tail is 1e-4).
+stated at the assertion (the task's bound for this tail is 1e-4).  Every kernel instantiation behind the call, the exact
+cases, token magnitudes, refusals and reloads: test_gpu_tail_matrix.py.
 """
 import numpy as np
 import pytest
 
+import tail_common as tc
 from conftest import golden_files
 from drone_oa_iree_vit_accelerator_amd import host, params, synth
 
@@ -54,6 +57,51 @@ def test_oracle_sampled_equals_full(oracle):
     assert np.array_equal(vals, full[pts[:, 0], pts[:, 1], pts[:, 2], pts[:, 3]])
 
 
+@pytest.mark.parametrize("path", FIX, ids=[p.split("/")[-1][:-4] for p in FIX])
+def test_f64_definition_vs_torch_layers(path):
+    """the float64 definition against what torch's own layers gave (f32: same bound as the oracle's comparison)"""
+    meta, c, want = _case(path)
+    got = tc.tail_f64(c["x"], meta["tok_h"], meta["tok_w"], c["conv_w"], c["conv_b"])
+    assert got.shape == want.shape
+    assert np.abs(got - want).max() <= 2e-5
+
+
+@pytest.mark.parametrize("shape", [(64, 4, 16, 9), (48, 8, 16, 33)], ids=tc.case_id)
+def test_oracle_general_vs_f64_definition(oracle, shape):
+    """The C oracle is one f32 fmaf chain of K = 9 * 5E/4 terms per output, over inputs that carry at most a few f32
+    roundings of their own (the bilinear blend): its distance from the float64 definition is bounded by K 2^-24
+    max|out| (the first-order bound of recursive f32 summation with a unit roundoff of 2^-24, in units of the largest
+    output; derived, not tuned)."""
+    E, th, tw, co = shape
+    c = tc.case(shape)
+    got = oracle.tail_general(c["x"], th, tw, c["conv_w"], c["conv_b"])
+    want = tc.want_f64(shape)
+    K = 9 * (5 * E // 4)
+    err, bound = np.abs(got - want).max(), K * 2.0 ** -24 * np.abs(want).max()
+    print(f"\n{tc.case_id(shape)}: max|oracle - f64| = {err:.3e}, bound {bound:.3e}")
+    assert got.shape == want.shape and err <= bound
+
+
+def test_matrix_reaches_every_kernel_variant():
+    """tail_common.variant restates the dispatch of ita_fusion_tail_large; the GPU matrix and the exact cases name all nine"""
+    assert {tc.variant(*s) for s in tc.MATRIX} == set(tc.VARIANTS)
+    assert {tc.variant(*s) for s in tc.EXACT} == set(tc.VARIANTS)
+
+
+@pytest.mark.parametrize("shape", tc.EXACT, ids=tc.case_id)
+def test_integer_case_expectation_is_exact(shape):
+    """the float64 result of the integer cases is integral and below 2^24: exactly representable in f32, and every
+    partial sum of any summation order with it, so it is a zero-tolerance expectation for the kernels"""
+    E, th, tw, co = shape
+    c = tc.integer_case(shape, B=2)
+    want = tc.tail_f64(c["x"], th, tw, c["conv_w"], c["conv_b"])
+    assert np.array_equal(want, np.rint(want))
+    # the largest partial sum any order can reach: sum |w| |x| + |b|, scaled as the loader scales the weights (max|w| = 4 -> 2^7)
+    worst = 9 * (E // 4) * 4 * 8 * 128 + 16
+    assert worst < 2 ** 24 and np.abs(want).max() <= worst
+    assert np.all(c["conv_w"][:, E // 4:] == 0) and np.abs(c["conv_w"]).max() == 4 and np.abs(c["x"]).max() <= 8
+
+
 # ------------------------------------------------------------------------------------------ GPU
 def _run(torch, c, th, tw):
     eng = host.FusionTailLarge(c["conv_w"], c["conv_b"], device=0)
@@ -66,9 +114,10 @@ def _run(torch, c, th, tw):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", [(128, 4, 16, 48, 2), (64, 8, 16, 9, 3), (128, 8, 32, 16, 1), (64, 4, 16, 33, 2),
-                                   (128, 24, 48, 48, 1), (128, 16, 16, 20, 2)],
+                                   (128, 24, 48, 48, 1), (128, 16, 16, 20, 2), (64, 8, 16, 64, 2), (128, 8, 16, 64, 2)],
                          ids=["E128_4x16_co48", "E64_8x16_co9", "E128_8x32_co16", "E64_4x16_co33",
-                              "E128_24x48_co48_interior_tiles", "E128_16x16_co20_one_tile_wide"])
+                              "E128_24x48_co48_interior_tiles", "E128_16x16_co20_one_tile_wide",
+                              "E64_8x16_co64_16row_grid", "E128_8x16_co64_16row_grid"])
 def test_gpu_tail_large_vs_oracle(oracle, shape):
     import torch
     E, th, tw, co, B = shape
