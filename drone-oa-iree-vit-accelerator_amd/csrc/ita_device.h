@@ -521,3 +521,110 @@ __device__ __forceinline__ void store_row_planes(const float (&r)[EC], float* __
     }
   }
 }
+
+// ---- one token per four lanes 16 and 32 apart: lane (qi = lane & 15, kq = lane >> 4) holds channels (E/4) kq .. + E/4 - 1 of
+// token qi -- the C layout of the 16x16 MFMAs, shared by the encoder stream kernel (ita_stream_kernel.h) and the tokenizer
+// (ita_tokenizer_kernel.h).
+// ITA_ABLATE: diagnostic builds of those kernels (results are wrong; the bits are listed in ita_stream_kernel.h)
+#ifndef ITA_ABLATE
+#define ITA_ABLATE 0
+#endif
+// sums / maxima over the four lanes (kq = 0..3) that share a token: lane ^ 16, lane ^ 32.  With both
+// operands the same register the swap leaves {row pairs duplicated} in the two results, so the
+// commutative combine needs no select.
+__device__ __forceinline__ float sum16_f(float v) {
+  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+__device__ __forceinline__ float sum32_f(float v) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+__device__ __forceinline__ int sum1632_i(int v) {
+  auto r = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
+  v = (int)r[0] + (int)r[1];
+  r = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
+  return (int)r[0] + (int)r[1];
+}
+__device__ __forceinline__ int max1632_i(int v) {
+  auto r = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
+  v = max((int)r[0], (int)r[1]);
+  r = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
+  return max((int)r[0], (int)r[1]);
+}
+
+// LayerNorm over E channels held E/4 per lane by the four lanes qi, qi+16, qi+32, qi+48, in the oracle's
+// summation order: the quarter sums p_kq sequentially over consecutive channels, combined (p0+p1)+(p2+p3)
+// -- layernorm_lanes<E> (above) with the lane exchange 16 / 32 apart instead of 1 / 2.
+template <int E>
+__device__ __forceinline__ void layernorm_q16(float (&r)[E / 4], const float* w, const float* b, int c0) {
+  constexpr int EC = E / 4;
+  if constexpr (ITA_ABLATE & 16) return;
+  const float inv_e = 1.0f / (float)E;
+  float p = 0.0f;
+#pragma unroll
+  for (int i = 0; i < EC; ++i) p = p + r[i];
+  float tot = sum32_f(sum16_f(p));
+  const float mean = tot * inv_e;
+  p = 0.0f;
+#pragma unroll
+  for (int i = 0; i < EC; ++i) { float d = r[i] - mean; p = fmaf(d, d, p); }
+  tot = sum32_f(sum16_f(p));
+  const float var = tot * inv_e;
+  const float rstd = 1.0f / sqrtf(var + 1e-5f);
+#pragma unroll
+  for (int i = 0; i < EC; i += 4) {
+    const f32x4 w4 = *(const f32x4*)(w + c0 + i), b4 = *(const f32x4*)(b + c0 + i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r[i + j] = fmaf((r[i + j] - mean) * rstd, w4[j], b4[j]);
+  }
+}
+
+// ---- f32 token rows in and out.  Lane (qi, kq) owns the quarter [E/4 kq, E/4 (kq+1)) of token qi's row.  Loaded or stored
+// quarter by quarter, a wave-instruction touches 64 different cache lines for 16 bytes each -- the shape one CU moves at a
+// fifth of its contiguous rate (tools/microbench/cu_fill_rows.hip).  Instead the four lanes of a token move 64 CONTIGUOUS
+// bytes per instruction (16 rows x 64 B per wave-instruction) and a 4 x 4 transpose of 16-byte items across those lanes
+// (lanes 16 and 32 apart: two rounds of v_permlane32_swap / v_permlane16_swap, 16 instructions) sorts the quarters out.
+// raw[16 jj + 4 i + c]: item i of transpose jj = floats 4 p .. 4 p + 3 of the row, p = (E/16) i + 4 jj + kq.
+template <int E>
+__device__ __forceinline__ void ld_tok_items(const float* row, int kq, float (&raw)[E / 4]) {
+  constexpr int PQ = E / 16, NJ = E / 64;
+#pragma unroll
+  for (int jj = 0; jj < NJ; ++jj)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const f32x4 v = *(const f32x4*)(row + 4 * (PQ * i + 4 * jj + kq));
+      raw[16 * jj + 4 * i] = v.x; raw[16 * jj + 4 * i + 1] = v.y; raw[16 * jj + 4 * i + 2] = v.z; raw[16 * jj + 4 * i + 3] = v.w;
+    }
+}
+// in place: items (as loaded / as they will be stored) <-> this lane's quarter in channel order; its own inverse
+template <int E>
+__device__ __forceinline__ void tok_items_transpose(float (&x)[E / 4]) {
+  constexpr int NJ = E / 64;
+#pragma unroll
+  for (int jj = 0; jj < NJ; ++jj)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      unsigned i0 = __float_as_uint(x[16 * jj + c]), i1 = __float_as_uint(x[16 * jj + 4 + c]);
+      unsigned i2 = __float_as_uint(x[16 * jj + 8 + c]), i3 = __float_as_uint(x[16 * jj + 12 + c]);
+      const auto a02 = __builtin_amdgcn_permlane32_swap(i0, i2, false, false);
+      const auto a13 = __builtin_amdgcn_permlane32_swap(i1, i3, false, false);
+      const auto b01 = __builtin_amdgcn_permlane16_swap(a02[0], a13[0], false, false);
+      const auto b23 = __builtin_amdgcn_permlane16_swap(a02[1], a13[1], false, false);
+      x[16 * jj + c] = __uint_as_float(b01[0]); x[16 * jj + 4 + c] = __uint_as_float(b01[1]);
+      x[16 * jj + 8 + c] = __uint_as_float(b23[0]); x[16 * jj + 12 + c] = __uint_as_float(b23[1]);
+    }
+}
+template <int E>
+__device__ __forceinline__ void st_tok_quarter(float* row, int kq, const float (&y)[E / 4]) {
+  constexpr int PQ = E / 16, NJ = E / 64;
+  float t[E / 4];
+#pragma unroll
+  for (int i = 0; i < E / 4; ++i) t[i] = y[i];
+  tok_items_transpose<E>(t);
+#pragma unroll
+  for (int jj = 0; jj < NJ; ++jj)
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      *(f32x4*)(row + 4 * (PQ * i + 4 * jj + kq)) = (f32x4){t[16 * jj + 4 * i], t[16 * jj + 4 * i + 1], t[16 * jj + 4 * i + 2], t[16 * jj + 4 * i + 3]};
+}

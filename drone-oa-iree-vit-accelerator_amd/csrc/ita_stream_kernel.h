@@ -25,9 +25,7 @@
 // frame = 161 744 B of the CU's 160 KB (163 840).  E = 128 (no tokenizer; fc1 / fc2 weights stay in global memory): 158 464 B.
 #pragma once
 #include "ita_int8_kernels.h"
-#ifndef ITA_ABLATE
-#define ITA_ABLATE 0
-#endif
+#include "ita_tokenizer_kernel.h"
 
 struct ItaStreamArgs {
   const char* image;      // device copy of the LDS image (ItaStreamLds<...>::IMAGE bytes, built at load time)
@@ -63,75 +61,6 @@ enum { ITA_SITE_Q = 1, ITA_SITE_K = 2, ITA_SITE_V = 4, ITA_SITE_L = 8, ITA_SITE_
 
 #define ITA_SCHED_BARRIER() __builtin_amdgcn_sched_barrier(0)
 
-// ---- the conv7x7 of the u8 tokenizer as int8 MFMA (oracle/ita_oracle.c: ita_oracle_tokenizer_u8).  The blended tap is the
-// exact integer B256 = 256 a1 + a0 <= 65280, the conv weight of a channel 23-bit fixed point Wq = 65536 w2 + 256 w1 + w0 with
-// balanced digits, and the 49-tap sum splits into byte products that int8 MFMAs accumulate exactly:
-//     S0 = sum a0 w0,  S1 = sum (a0 w1 + a1 w0),  S2 = sum (a0 w2 + a1 w1),  S3 = sum a1 w2,   L = S0 + 256 S1,  H = S2 + 256 S3
-//     pre = fma((float)H, 65536 s, fma((float)L, s, bias))
-// The unsigned bytes a0, a1 ride the signed MFMA as a ^ 0x80 = a - 128; the 128 * sum(w) terms sit in the accumulators'
-// initial values (I0 for S0 -- it also carries 256 x the term of S1 --, I2 for S2 / S3).  K = 64 slots of the 16x16x64 MFMA:
-// lane (token qi, k-group kq) holds its own 13 taps 4 j + kq in bytes j = 0..12 of its B fragment (the weight image has
-// the same slot -> tap mapping, zero weights in the three pad slots).  Six MFMAs per 16-channel tile instead of thirteen
-// v_mfma_f32_16x16x4_f32, which run at the f32 vector rate and hold the SIMD's VALU meanwhile (-5 us per 1024-frame launch).
-template <int E>
-struct ItaTokTab {
-  static constexpr int NCT = E / 16;
-  static constexpr int TW = 0;                          // int8 [NCT][3 byte planes][64 lanes][16]: A fragments, row rho <-> channel (E/4)(rho>>2) + 4 ct + (rho&3)
-  static constexpr int TI = TW + NCT * 3 * 1024;        // int32 [2][E]: I0 | I2
-  static constexpr int TS = TI + 2 * E * 4;             // f32 [3][E]: s | 65536 s | conv bias
-  static constexpr int BYTES = TS + 3 * E * 4;
-};
-// thirteen blended taps (exact integers) -> the two B fragments (low bytes, high bytes; both ^ 0x80)
-__device__ __forceinline__ void tok_u8_fragments(const unsigned (&pb)[13], i32x4& a0, i32x4& a1) {
-  unsigned p16[8];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) p16[k] = __builtin_amdgcn_perm(pb[2 * k + 1], pb[2 * k], 0x05040100u) ^ 0x80808080u;
-  p16[6] = (pb[12] & 0xffffu) ^ 0x80808080u;
-  p16[7] = 0;                                           // pad slots: their weights are zero
-#pragma unroll
-  for (int d = 0; d < 4; ++d) {
-    a0[d] = (int)__builtin_amdgcn_perm(p16[2 * d + 1], p16[2 * d], 0x06040200u);
-    a1[d] = (int)__builtin_amdgcn_perm(p16[2 * d + 1], p16[2 * d], 0x07050301u);
-  }
-}
-// one 16-channel tile: out[i] = pre-LayerNorm conv output of channel (E/4) kq + 4 ct + i of this lane's token
-template <int E>
-__device__ __forceinline__ void tok_u8_tile(const char* tab, int ct, int lane, int kq, const i32x4& a0, const i32x4& a1, float (&out)[4]) {
-  using T = ItaTokTab<E>;
-  const int c0 = (E / 4) * kq + 4 * ct;
-  // (one weight fragment live at a time, the sums combined in place: the tile runs where the encoder kernel has no register to spare)
-  const i32x4 z = {0, 0, 0, 0};
-  i32x4 s0 = *(const i32x4*)(tab + T::TI + c0 * 4), s1, s2 = *(const i32x4*)(tab + T::TI + (E + c0) * 4), s3;
-  {
-    const i32x4 w0 = *(const i32x4*)(tab + T::TW + ((ct * 3 + 0) * 64 + lane) * 16);
-    s0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(w0, a0, s0, 0, 0, 0);
-    s1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(w0, a1, z, 0, 0, 0);
-  }
-  {
-    const i32x4 w1 = *(const i32x4*)(tab + T::TW + ((ct * 3 + 1) * 64 + lane) * 16);
-    s2 = __builtin_amdgcn_mfma_i32_16x16x64_i8(w1, a1, s2, 0, 0, 0);
-    s1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(w1, a0, s1, 0, 0, 0);
-  }
-  {
-    const i32x4 w2 = *(const i32x4*)(tab + T::TW + ((ct * 3 + 2) * 64 + lane) * 16);
-    s3 = __builtin_amdgcn_mfma_i32_16x16x64_i8(w2, a1, z, 0, 0, 0);
-    s2 = __builtin_amdgcn_mfma_i32_16x16x64_i8(w2, a0, s2, 0, 0, 0);
-  }
-  float lf[4], hf[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { lf[i] = (float)(s0[i] + (s1[i] << 8)); hf[i] = (float)(s2[i] + (s3[i] << 8)); }
-  {
-    const f32x4 sc = *(const f32x4*)(tab + T::TS + c0 * 4), cb = *(const f32x4*)(tab + T::TS + (2 * E + c0) * 4);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) lf[i] = fmaf(lf[i], sc[i], cb[i]);
-  }
-  {
-    const f32x4 sc16 = *(const f32x4*)(tab + T::TS + (E + c0) * 4);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) out[i] = fmaf(hf[i], sc16[i], lf[i]);
-  }
-}
-
 template <int E, bool FFN, bool TOK>
 struct ItaStreamLds {
   static constexpr int S = 128, P = 192, F = 256;
@@ -160,14 +89,16 @@ struct ItaStreamLds {
   static constexpr int VT = K + S * P;               // int8 [8][192][16]   V^T, keys permuted (ita_int8_kernels.h)
   static constexpr int COLSUM = VT + P * S;          // int32 [2][192]: 128 * column sums of V, per frame parity
   static constexpr int IMG = COLSUM + 2 * P * 4;     // u8 [8 waves][9][96]: rows 2*y0-3 .. 2*y0+5 of the next frame, 3 zero columns each side
-  static constexpr int IMG_WAVE = 9 * 96;
+  static constexpr int IMG_WAVE = ITA_TOK_U8_WIN;
   static constexpr int TOTAL = IMG + (TOK ? 8 * IMG_WAVE : 0);
   static_assert(IMAGE % 16 == 0 && K % 16 == 0 && IMG % 16 == 0, "16-byte alignment");
   static_assert(TOTAL <= 160 * 1024, "LDS budget");
 };
 
 // ITA_ABLATE (diagnostic builds only, results are wrong): 1 no requantisation VALU, 2 no int8 MFMA, 4 no tokenizer,
-// 8 no LDS operand reads, 16 no LayerNorm, 32 no softmax, 64 no barriers, 128 no h0 copy / output stores -- what remains is timed against the full kernel to see what a frame's time is made of
+// 8 no LDS operand reads, 16 no LayerNorm, 32 no softmax, 64 no barriers, 128 no h0 copy / output stores, 256 one plane store,
+// 512 no window reads in the tokenizer's blend, 1024 no conv tiles -- what remains is timed against the full kernel to see what
+// a frame's time is made of.  (The default, 0, is set in ita_device.h: layernorm_q16 there and the blend in ita_tokenizer_kernel.h have hooks.)
 __device__ __forceinline__ i32x4 mfma16(i32x4 a, i32x4 b, i32x4 c) {
   if constexpr (ITA_ABLATE & 2) return c;   // (operand loads become dead code too)
   return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0);
@@ -175,56 +106,6 @@ __device__ __forceinline__ i32x4 mfma16(i32x4 a, i32x4 b, i32x4 c) {
 __device__ __forceinline__ i32x4 sfrag(const char* lds, int off) {
   if constexpr (ITA_ABLATE & 8) return (i32x4){off, off, off, off};
   return *(const i32x4*)(lds + off);
-}
-// sums / maxima over the four lanes (kq = 0..3) that share a token: lane ^ 16, lane ^ 32.  With both
-// operands the same register the swap leaves {row pairs duplicated} in the two results, so the
-// commutative combine needs no select.
-__device__ __forceinline__ float sum16_f(float v) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float sum32_f(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ int sum1632_i(int v) {
-  auto r = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
-  v = (int)r[0] + (int)r[1];
-  r = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
-  return (int)r[0] + (int)r[1];
-}
-__device__ __forceinline__ int max1632_i(int v) {
-  auto r = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
-  v = max((int)r[0], (int)r[1]);
-  r = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
-  return max((int)r[0], (int)r[1]);
-}
-
-// LayerNorm over E channels held E/4 per lane by the four lanes qi, qi+16, qi+32, qi+48, in the oracle's
-// summation order: the quarter sums p_kq sequentially over consecutive channels, combined (p0+p1)+(p2+p3)
-// -- layernorm_lanes<E> (ita_device.h) with the lane exchange 16 / 32 apart instead of 1 / 2.
-template <int E>
-__device__ __forceinline__ void layernorm_q16(float (&r)[E / 4], const float* w, const float* b, int c0) {
-  constexpr int EC = E / 4;
-  if constexpr (ITA_ABLATE & 16) return;
-  const float inv_e = 1.0f / (float)E;
-  float p = 0.0f;
-#pragma unroll
-  for (int i = 0; i < EC; ++i) p = p + r[i];
-  float tot = sum32_f(sum16_f(p));
-  const float mean = tot * inv_e;
-  p = 0.0f;
-#pragma unroll
-  for (int i = 0; i < EC; ++i) { float d = r[i] - mean; p = fmaf(d, d, p); }
-  tot = sum32_f(sum16_f(p));
-  const float var = tot * inv_e;
-  const float rstd = 1.0f / sqrtf(var + 1e-5f);
-#pragma unroll
-  for (int i = 0; i < EC; i += 4) {
-    const f32x4 w4 = *(const f32x4*)(w + c0 + i), b4 = *(const f32x4*)(b + c0 + i);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) r[i + j] = fmaf((r[i + j] - mean) * rstd, w4[j], b4[j]);
-  }
 }
 
 // Integer softmax (models/ITA/QAT/ITA_softmax.py:51-61) of the 16 rows a wave holds as packed signed 16-bit logit pairs
@@ -371,55 +252,6 @@ __device__ __forceinline__ void dq_group(const i32x4 (&acc)[4], float mult, floa
   dq16_b(acc, mult, scale, d);
 }
 
-// ---- f32 token rows in and out.  Lane (qi, kq) owns the quarter [E/4 kq, E/4 (kq+1)) of token qi's row.  Loaded or stored
-// quarter by quarter, a wave-instruction touches 64 different cache lines for 16 bytes each -- the shape one CU moves at a
-// fifth of its contiguous rate (tools/microbench/cu_fill_rows.hip).  Instead the four lanes of a token move 64 CONTIGUOUS
-// bytes per instruction (16 rows x 64 B per wave-instruction) and a 4 x 4 transpose of 16-byte items across those lanes
-// (lanes 16 and 32 apart: two rounds of v_permlane32_swap / v_permlane16_swap, 16 instructions) sorts the quarters out.
-// raw[16 jj + 4 i + c]: item i of transpose jj = floats 4 p .. 4 p + 3 of the row, p = (E/16) i + 4 jj + kq.
-template <int E>
-__device__ __forceinline__ void ld_tok_items(const float* row, int kq, float (&raw)[E / 4]) {
-  constexpr int PQ = E / 16, NJ = E / 64;
-#pragma unroll
-  for (int jj = 0; jj < NJ; ++jj)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const f32x4 v = *(const f32x4*)(row + 4 * (PQ * i + 4 * jj + kq));
-      raw[16 * jj + 4 * i] = v.x; raw[16 * jj + 4 * i + 1] = v.y; raw[16 * jj + 4 * i + 2] = v.z; raw[16 * jj + 4 * i + 3] = v.w;
-    }
-}
-// in place: items (as loaded / as they will be stored) <-> this lane's quarter in channel order; its own inverse
-template <int E>
-__device__ __forceinline__ void tok_items_transpose(float (&x)[E / 4]) {
-  constexpr int NJ = E / 64;
-#pragma unroll
-  for (int jj = 0; jj < NJ; ++jj)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      unsigned i0 = __float_as_uint(x[16 * jj + c]), i1 = __float_as_uint(x[16 * jj + 4 + c]);
-      unsigned i2 = __float_as_uint(x[16 * jj + 8 + c]), i3 = __float_as_uint(x[16 * jj + 12 + c]);
-      const auto a02 = __builtin_amdgcn_permlane32_swap(i0, i2, false, false);
-      const auto a13 = __builtin_amdgcn_permlane32_swap(i1, i3, false, false);
-      const auto b01 = __builtin_amdgcn_permlane16_swap(a02[0], a13[0], false, false);
-      const auto b23 = __builtin_amdgcn_permlane16_swap(a02[1], a13[1], false, false);
-      x[16 * jj + c] = __uint_as_float(b01[0]); x[16 * jj + 4 + c] = __uint_as_float(b01[1]);
-      x[16 * jj + 8 + c] = __uint_as_float(b23[0]); x[16 * jj + 12 + c] = __uint_as_float(b23[1]);
-    }
-}
-template <int E>
-__device__ __forceinline__ void st_tok_quarter(float* row, int kq, const float (&y)[E / 4]) {
-  constexpr int PQ = E / 16, NJ = E / 64;
-  float t[E / 4];
-#pragma unroll
-  for (int i = 0; i < E / 4; ++i) t[i] = y[i];
-  tok_items_transpose<E>(t);
-#pragma unroll
-  for (int jj = 0; jj < NJ; ++jj)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      *(f32x4*)(row + 4 * (PQ * i + 4 * jj + kq)) = (f32x4){t[16 * jj + 4 * i], t[16 * jj + 4 * i + 1], t[16 * jj + 4 * i + 2], t[16 * jj + 4 * i + 3]};
-}
-
 // (amdgpu_waves_per_eu(2, 2): the workgroup owns the CU's LDS, so two waves per SIMD is all there will ever be -- without
 // it the scheduler trades instruction-level parallelism for registers it has no use for: the LDS size is dynamic)
 // FAST: every requantisation site of this layer passed the load-time single-rounding proof (ita_plugin.hip: fast_site_ok).
@@ -466,80 +298,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       a.stamps[(((size_t)blockIdx.x * 8 + fi) * 2 + (wave >> 2)) * 16 + (ph)] = __builtin_amdgcn_s_memtime(); \
   } while (0)
 
-  // ---- fused tokenizer (OverlapPatchMerging, reference models/ITA/QAT/layers.py:39-45; same arithmetic and
-  // operation order as the oracle's ita_oracle_tokenizer_u8).  Conv7x7/s2 and the bilinear 30x45 -> 8x16 resize are both linear,
-  // so the 7x7 patch is blended first and convolved once per token.  Wave w = token row w needs image rows
-  // 2*y0-3 .. 2*y0+5 only (y0 = source row of the resize), a private 9 x 96 byte window with a zero border:
-  //   fetch  : five dwords per lane of the next frame (issued a phase early, consumed by fill)
-  //   fill   : funnel-shift to the window's 16-byte pieces, mask the border, one ds_write_b128 per lane
-  //   compute: lane (qi, kq) blends taps 4s+kq (s = 0..12) of token qi -- exactly the B operand
-  //            (column = token, k = kq) of v_mfma_f32_16x16x4_f32, on gfx950 an exact ascending-k fmaf chain;
-  //            the A operand is the conv weight fragment image.  C = lane (token qi, channels 16kq+4ct+i):
-  //            the layout the encoder keeps x in.  No patch, no pre-LayerNorm token ever reaches LDS.
-  // Everything per-lane below is derived from an OPAQUE copy of the lane id taken once per frame: otherwise the compiler
-  // hoists ~60 registers of loop-invariant geometry and LDS addresses out of the frame loop, and the kernel (which
-  // lives at the 256-register limit of two waves per SIMD) spills.
+  // ---- fused tokenizer: the u8 window and conv functions of ita_tokenizer_kernel.h, placed between the phases of the int8
+  // blocks by the frame loop: fetch a phase early, fill after B2, blend + the four tiles + LayerNorm after the output stores.
+  // Everything per-lane in them is derived from an OPAQUE copy of the lane id taken once per frame (ol), see there.
   unsigned tk_d[5] = {0, 0, 0, 0, 0};
-  struct TokGeo { int y0, x0, rr, pc, row, o; float h1, w1; };
-  auto tok_geo = [&](int ol) {
-    TokGeo g;
-    int yp, xp;
-    bilinear_src_dev(wave, 30.0f / 8.0f, 30, g.y0, yp, g.h1);        // y0 <= 27 < 29 and x0 <= 43 < 44: the second
-    bilinear_src_dev(ol & 15, 45.0f / 16.0f, 45, g.x0, xp, g.w1);    // neighbour is always one row / column on
-    g.rr = ol / 6; g.pc = ol - 6 * g.rr;                             // window piece of this lane (lane < 54)
-    g.row = 2 * g.y0 - 3 + g.rr;                                     // image row (-1 for the top row of wave 0)
-    g.o = g.row * 90 + 16 * g.pc - 3;                                // frame byte of the piece's first window byte
-    return g;
-  };
-  auto tok_fetch = [&](int fb, int ol) {
-    const TokGeo g = tok_geo(ol);
-    const uint8_t* src = (const uint8_t*)a.img + (size_t)fb * 5400;
-    const int a0 = g.o & ~3;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      const int aj = a0 + 4 * j;
-      tk_d[j] = 0;
-      if (ol < 54 && g.row >= 0 && aj >= 0 && aj < 5400) tk_d[j] = *(const unsigned*)(src + aj);
-    }
-  };
-  auto tok_fill = [&](int ol) {
-    const TokGeo g = tok_geo(ol);
-    const int sh = g.o & 3;
-    unsigned o4[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o4[j] = __builtin_amdgcn_alignbyte(tk_d[j + 1], tk_d[j], sh);
-    if (g.pc == 0) o4[0] &= 0xff000000u;        // window columns 0..2  = image columns -3..-1
-    if (g.pc == 5) o4[3] &= 0x000000ffu;        // window columns 93..95 = image columns 90..92
-    if (ol < 54)
-      *(i32x4*)(lds + L::IMG + wave * L::IMG_WAVE + g.rr * 96 + 16 * g.pc) =
-          (i32x4){(int)o4[0], (int)o4[1], (int)o4[2], (int)o4[3]};
-  };
-  // blend: this lane's 13 taps of its token as exact integers, packed into the two B fragments of the int8 conv
   i32x4 tk_a0, tk_a1;
   float tk_out[16];
-  auto tok_blend = [&](int ol) {
-    const TokGeo g = tok_geo(ol);
-    const int kq = ol >> 4;
-    const uint8_t* win = (const uint8_t*)(lds + L::IMG + wave * L::IMG_WAVE) + 2 * g.x0;
-    const int* tap = (const int*)(lds + L::TAP);
-    // The weights of this fixed resize are dyadic, h = H / 8 and w = W / 32 with 0 < H1 < 8, 0 < W1 < 32 for every
-    // token, so the blend of a tap is the exact integer  256 * 255 * value = H0 W0 a + H0 W1 b + H1 W0 c + H1 W1 d
-    // on the pixel CODES (each product weight <= 7 * 31 fits a byte); 1 / 65280 is folded into the conv scales
-    // (oracle/ita_oracle.c ita_oracle_tokenizer_u8).  No k / 255 table, no float blend.
-    const unsigned H1 = (unsigned)(8.0f * g.h1) & 7u, W1 = (unsigned)(32.0f * g.w1) & 31u, H0 = 8u - H1, W0 = 32u - W1;
-    const unsigned w00 = (H0 * W0) & 255u, w01 = (H0 * W1) & 255u, w10 = (H1 * W0) & 255u, w11 = (H1 * W1) & 255u;
-    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the window is private to this wave
-    __builtin_amdgcn_wave_barrier();
-    unsigned pb[13];
-#pragma unroll
-    for (int s = 0; s < 13; ++s) {
-      if constexpr (ITA_ABLATE & 512) { pb[s] = w00 * s; continue; }
-      const int off = tap[4 * s + kq];    // ky * 96 + kx of tap 4s + kq (0 for the pad taps 49..51: their weights are 0)
-      pb[s] = (unsigned)win[off] * w00 + (unsigned)win[off + 2] * w01 + (unsigned)win[off + 192] * w10 +
-              (unsigned)win[off + 194] * w11;
-    }
-    tok_u8_fragments(pb, tk_a0, tk_a1);
-  };
+  auto tok_fetch = [&](int fb, int ol) { tok_u8_fetch(a.img, fb, wave, ol, tk_d); };
+  auto tok_fill = [&](int ol) { tok_u8_fill(lds + L::IMG, wave, ol, tk_d); };
+  auto tok_blend = [&](int ol) { tok_u8_blend(lds + L::IMG, (const int*)(lds + L::TAP), wave, ol, tk_a0, tk_a1); };
   // one 16-channel tile of the conv: six int8 MFMAs + the float recombination, placed between the phases of the int8
   // blocks by the caller
   auto tok_step = [&](int ct, int ol) {
@@ -959,148 +726,4 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #undef fl
 #undef fc
 #undef fo
-}
-
-// ------------------------------------------------------------------ the tokenizer on its own
-// OverlapPatchMerging (reference models/ITA/QAT/layers.py:39-45) with the structure of the fused tokenizer above -- per-wave
-// 9-row pixel windows, the blended taps as the lane's own MFMA B operand, conv weights as v_mfma_f32_16x16x4_f32 A fragments,
-// LayerNorm in registers -- for the cases the fused form does not cover: E = 128 (its encoder kernel has no LDS left for
-// the 27 KB of conv fragments), f32 frames (module.main_graph's own input type: four times the window bytes) and callers of
-// ita_tokenizer.  Wave w = token row w of the 8 x 16 grid; one persistent 512-thread workgroup per CU, the next frame's
-// pixels requested a frame ahead.
-//   U8  : the exact integer blend of the pixel codes and the conv as int8 MFMA on 23-bit fixed-point weights (ItaTokTab,
-//         oracle: ita_oracle_tokenizer_u8) -- the fused tokenizer's functions, bit-identical to it;
-//   !U8 : the oracle's float blend  h0 (w0 a + w1 b) + h1 (w0 c + w1 d)  of pixels already scaled by the caller
-//         (ita_oracle_tokenizer), conv weights as they are, v_mfma_f32_16x16x4_f32; same results as
-//         ita_oracle_tokenizer bit for bit (same operation order).
-template <int E, bool U8>
-struct ItaTokStreamLds {
-  static constexpr int NCT = E / 16;                           // 16-channel output tiles
-  static constexpr int LNP = 0;                                // f32: ln_w | ln_b
-  static constexpr int CW = LNP + 2 * E * 4;                   // !U8: f32 [13][NCT][64] conv weights as A fragments; U8: ItaTokTab<E>
-  static constexpr int CB = CW + (U8 ? ItaTokTab<E>::BYTES : 13 * NCT * 64 * 4);   // !U8: f32 [E] conv bias (U8: inside the table)
-  static constexpr int TAP = CB + (U8 ? 0 : E * 4);            // int32 [52]
-  static constexpr int IMAGE = TAP + 52 * 4;
-  static constexpr int IMG = (IMAGE + 15) & ~15;               // [8 waves][9][96] pixels (u8 or f32), 3 zero columns each side
-  static constexpr int IMG_WAVE = 9 * 96 * (U8 ? 1 : 4);
-  static constexpr int TOTAL = IMG + 8 * IMG_WAVE;
-};
-struct ItaTokStreamArgs {
-  const char* image;     // device copy of the LDS image (ItaTokStreamLds<E, U8>::IMAGE bytes)
-  const void* img;       // (B,60,90) u8 or f32
-  float* tokens;         // (B,128,E)
-  int B;
-};
-template <int E, bool U8>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void ita_tok_stream_kernel(const ItaTokStreamArgs a) {
-  using L = ItaTokStreamLds<E, U8>;
-  constexpr int S = 128, EC = E / 4, NCT = L::NCT;
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const float* lnp = (const float*)(lds + L::LNP);
-  // geometry of this lane: its token (row = wave, column = lane & 15), its piece of the 9 x 96 window
-  int y0, yp, x0, xp;
-  float h1, w1;
-  bilinear_src_dev(wave, 30.0f / 8.0f, 30, y0, yp, h1);
-  bilinear_src_dev(lane & 15, 45.0f / 16.0f, 45, x0, xp, w1);
-  const int rr = lane / 6, pc = lane - 6 * rr;           // u8: window piece of this lane (lane < 54)
-  const int row = 2 * y0 - 3 + rr;                        // image row (-1 for the top row of wave 0)
-  const int o = row * 90 + 16 * pc - 3;                   // frame byte of the piece's first window byte
-  const int kq = lane >> 4, qi = lane & 15;
-  // f32 frames: window element e = lane + 64 j (j < 14) = (window row e / 96, window column e % 96)
-  constexpr int NF = U8 ? 1 : 14;
-  unsigned tk_d[5] = {0, 0, 0, 0, 0};
-  float tk_f[NF];
-  auto fetch = [&](int fb) {
-    if constexpr (U8) {
-      const uint8_t* src = (const uint8_t*)a.img + (size_t)fb * 5400;
-      const int a0 = o & ~3;
-#pragma unroll
-      for (int j = 0; j < 5; ++j) {
-        const int aj = a0 + 4 * j;
-        tk_d[j] = 0;
-        if (lane < 54 && row >= 0 && aj >= 0 && aj < 5400) tk_d[j] = *(const unsigned*)(src + aj);
-      }
-    } else {
-      const float* src = (const float*)a.img + (size_t)fb * 5400;
-#pragma unroll
-      for (int j = 0; j < NF; ++j) {
-        const int e = lane + 64 * j, wr = e / 96, wc = e - 96 * wr;
-        const int iy = 2 * y0 - 3 + wr, ix = wc - 3;
-        tk_f[j] = 0.0f;
-        if (e < 9 * 96 && iy >= 0 && iy < 60 && ix >= 0 && ix < 90) tk_f[j] = src[iy * 90 + ix];
-      }
-    }
-  };
-  if ((int)blockIdx.x < a.B) fetch(blockIdx.x);
-  for (int p = tid; p < L::IMAGE / 16; p += 512) *(i32x4*)(lds + p * 16) = *(const i32x4*)(a.image + (size_t)p * 16);
-  __syncthreads();
-  const unsigned H1 = (unsigned)(8.0f * h1) & 7u, W1 = (unsigned)(32.0f * w1) & 31u, H0 = 8u - H1, W0 = 32u - W1;
-  const unsigned w00 = (H0 * W0) & 255u, w01 = (H0 * W1) & 255u, w10 = (H1 * W0) & 255u, w11 = (H1 * W1) & 255u;
-  const float fh0 = 1.0f - h1, fw0 = 1.0f - w1;
-  char* wbase = lds + L::IMG + wave * L::IMG_WAVE;
-  const int* tap = (const int*)(lds + L::TAP);
-  const float* cw = (const float*)(lds + L::CW);
-  for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
-    if constexpr (U8) {   // window fill: funnel-shift to 16-byte pieces, mask the border
-      const int sh = o & 3;
-      unsigned o4[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o4[j] = __builtin_amdgcn_alignbyte(tk_d[j + 1], tk_d[j], sh);
-      if (pc == 0) o4[0] &= 0xff000000u;
-      if (pc == 5) o4[3] &= 0x000000ffu;
-      if (lane < 54) *(i32x4*)(wbase + rr * 96 + 16 * pc) = (i32x4){(int)o4[0], (int)o4[1], (int)o4[2], (int)o4[3]};
-    } else {
-#pragma unroll
-      for (int j = 0; j < NF; ++j)
-        if (lane + 64 * j < 9 * 96) ((float*)wbase)[lane + 64 * j] = tk_f[j];
-    }
-    if (b + (int)gridDim.x < a.B) fetch(b + gridDim.x);
-    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the window is private to this wave
-    __builtin_amdgcn_wave_barrier();
-    float xr[EC];
-    if constexpr (U8) {
-      const uint8_t* win = (const uint8_t*)wbase + 2 * x0;
-      unsigned pb[13];
-#pragma unroll
-      for (int s = 0; s < 13; ++s) {
-        const int off = tap[4 * s + kq];
-        pb[s] = (unsigned)win[off] * w00 + (unsigned)win[off + 2] * w01 + (unsigned)win[off + 192] * w10 + (unsigned)win[off + 194] * w11;
-      }
-      i32x4 a0, a1;
-      tok_u8_fragments(pb, a0, a1);
-#pragma unroll
-      for (int ct = 0; ct < NCT; ++ct) {
-        float o4[4];
-        tok_u8_tile<E>(lds + L::CW, ct, lane, kq, a0, a1, o4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) xr[4 * ct + i] = o4[i];
-      }
-    } else {
-      float tk_pt[13];
-#pragma unroll
-      for (int s = 0; s < 13; ++s) {
-        const int off = tap[4 * s + kq];
-        const float* win = (const float*)wbase + 2 * x0;
-        const float va = win[off], vb = win[off + 2], vc = win[off + 192], vd = win[off + 194];
-        tk_pt[s] = fh0 * (fw0 * va + w1 * vb) + h1 * (fw0 * vc + w1 * vd);   // ita_oracle_blend_patch's expression
-      }
-      f32x4 acc[NCT];
-#pragma unroll
-      for (int ct = 0; ct < NCT; ++ct) acc[ct] = *(const f32x4*)(lds + L::CB + (EC * kq + 4 * ct) * 4);
-#pragma unroll
-      for (int s = 0; s < 13; ++s)
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct)
-          acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(cw[(s * NCT + ct) * 64 + lane], tk_pt[s], acc[ct], 0, 0, 0);
-#pragma unroll
-      for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) xr[4 * ct + i] = acc[ct][i];
-    }
-    layernorm_q16<E>(xr, lnp, lnp + E, EC * kq);
-    st_tok_quarter<E>(a.tokens + ((size_t)b * S + wave * 16 + qi) * E, kq, xr);   // 64 contiguous bytes per token and store
-    __builtin_amdgcn_wave_barrier();      // the window is rewritten for the next frame only after these reads were issued
-  }
 }

@@ -2,7 +2,7 @@
 // steps that build it from a blob, in the order the loader runs them.
 //
 // A part of ita_plugin.hip, its only includer, and not a stand-alone header: ita_plugin.hip defines fail(), HIPCHK,
-// DevBuf, K0P / K0S, launch and the two exact-f32 launch helpers the fold uses (launch_tail, launch_gemm) ahead of the
+// DevBuf, with_E, K0P / K0S, launch and the two exact-f32 launch helpers the fold uses (launch_tail, launch_gemm) ahead of the
 // #include.
 //
 // Head counts (header field H): an ITAW0001 blob (int8 attention, int8 FFN) loads with H in {1, 2, 3, 4, 6}; its layers
@@ -150,7 +150,13 @@ struct StreamHostParams {
   const float *n1w, *n1b, *n2w, *n2b, *tlw, *tlb, *conv_w, *conv_b;
 };
 
-// The integer conv tables of the u8 tokenizer (ita_stream_kernel.h: ItaTokTab; definition: oracle/ita_oracle.c
+// the tokenizers' tap table, int32 [52]: offset ky * 96 + kx of tap t in a 9 x 96 pixel window, 0 for the pad taps 49..51
+void fill_tok_taps(char* at) {
+  int32_t* tap = (int32_t*)at;
+  for (int t = 0; t < 52; ++t) tap[t] = t < 49 ? (t / 7) * 96 + (t % 7) : 0;
+}
+
+// The integer conv tables of the u8 tokenizer (ita_tokenizer_kernel.h: ItaTokTab; definition: oracle/ita_oracle.c
 // ita_oracle_tok_quant_weights / ita_oracle_tokenizer_u8): per channel 23-bit fixed-point weights Wq = rne(w * 2^e), e = 22 -
 // exponent(max |w|), split into balanced bytes w0, w1 and the remainder w2, laid out as int8 MFMA A fragments.
 template <int E>
@@ -233,8 +239,7 @@ int build_stream_image(const StreamHostParams& p, DevBuf<char>& out) {
   if constexpr (TOK) {
     memcpy(ln + 4 * E, p.tlw, E * 4); memcpy(ln + 5 * E, p.tlb, E * 4);
     build_tok_tab<E>(p.conv_w, p.conv_b, im.data() + L::CW);
-    int32_t* tap = (int32_t*)(im.data() + L::TAP);
-    for (int t = 0; t < 52; ++t) tap[t] = t < 49 ? (t / 7) * 96 + (t % 7) : 0;
+    fill_tok_taps(im.data() + L::TAP);
   }
   bias_accumulators();
   {
@@ -440,44 +445,40 @@ int build_stream_images(Weights& w) {
 #undef NM
 
 // step 4: the LDS images of ita_tok_stream_kernel<E, U8>, when the blob has the conv weights, the bias and the LayerNorm
-int build_tokenizer_images(Weights& w) {
-  const int Ei = w.hdr.E;
-  const float *cw = hptr<float>(w, "tok.conv_w"), *cb = hptr<float>(w, "tok.conv_b"), *lw = hptr<float>(w, "tok.ln_w"),
-              *lb = hptr<float>(w, "tok.ln_b");
-  if (!cw || !cb || !lw || !lb) return ITA_OK;
-  // [0]: u8 frames (integer conv tables), [1]: f32 frames (f32 MFMA A fragments); each padded to the larger of the two
-  const int nct = Ei / 16;
-  const size_t one8 = Ei == 64 ? (size_t)ItaTokStreamLds<64, true>::IMAGE : (size_t)ItaTokStreamLds<128, true>::IMAGE;
-  const size_t onef = Ei == 64 ? (size_t)ItaTokStreamLds<64, false>::IMAGE : (size_t)ItaTokStreamLds<128, false>::IMAGE;
-  const size_t one = ((one8 > onef ? one8 : onef) + 15) & ~(size_t)15;
-  std::vector<char> im(2 * one, 0);
-  {
-    char* b0 = im.data();
-    memcpy(b0, lw, Ei * 4); memcpy(b0 + Ei * 4, lb, Ei * 4);
-    int off_tap;
-    if (Ei == 64) { build_tok_tab<64>(cw, cb, b0 + ItaTokStreamLds<64, true>::CW); off_tap = ItaTokStreamLds<64, true>::TAP; }
-    else { build_tok_tab<128>(cw, cb, b0 + ItaTokStreamLds<128, true>::CW); off_tap = ItaTokStreamLds<128, true>::TAP; }
-    int32_t* tap = (int32_t*)(b0 + off_tap);
-    for (int t = 0; t < 52; ++t) tap[t] = t < 49 ? (t / 7) * 96 + (t % 7) : 0;
-  }
-  {
-    char* b0 = im.data() + one;
-    const int off_cw = 2 * Ei * 4, off_cb = off_cw + 13 * nct * 64 * 4, off_tap = off_cb + Ei * 4;
-    memcpy(b0, lw, Ei * 4); memcpy(b0 + Ei * 4, lb, Ei * 4);
-    float* cwf = (float*)(b0 + off_cw);
+struct TokHostParams { const float *cw, *cb, *lw, *lb; };
+template <int E, bool U8>
+void build_tokenizer_image(const TokHostParams& p, char* im) {
+  using L = ItaTokStreamLds<E, U8>;
+  memcpy(im + L::LNP, p.lw, E * 4); memcpy(im + L::LNP + E * 4, p.lb, E * 4);
+  if constexpr (U8) {
+    build_tok_tab<E>(p.cw, p.cb, im + L::CW);
+  } else {   // the conv weights as they are, as v_mfma_f32_16x16x4_f32 A fragments
+    float* cwf = (float*)(im + L::CW);
     for (int st = 0; st < 13; ++st)
-      for (int ct = 0; ct < nct; ++ct)
+      for (int ct = 0; ct < L::NCT; ++ct)
         for (int lane = 0; lane < 64; ++lane) {
-          const int t = 4 * st + (lane >> 4), rho = lane & 15, ch = (Ei / 4) * (rho >> 2) + 4 * ct + (rho & 3);
-          cwf[(st * nct + ct) * 64 + lane] = t < 49 ? cw[(size_t)ch * 49 + t] : 0.0f;
+          const int t = 4 * st + (lane >> 4), rho = lane & 15, ch = (E / 4) * (rho >> 2) + 4 * ct + (rho & 3);
+          cwf[(st * L::NCT + ct) * 64 + lane] = t < 49 ? p.cw[(size_t)ch * 49 + t] : 0.0f;
         }
-    memcpy(b0 + off_cb, cb, Ei * 4);
-    int32_t* tap = (int32_t*)(b0 + off_tap);
-    for (int t = 0; t < 52; ++t) tap[t] = t < 49 ? (t / 7) * 96 + (t % 7) : 0;
+    memcpy(im + L::CB, p.cb, E * 4);
   }
-  w.tok_simg_bytes = one;
-  HIPCHK(w.tok_simg.upload(im.data(), im.size()));
-  return ITA_OK;
+  fill_tok_taps(im + L::TAP);
+}
+int build_tokenizer_images(Weights& w) {
+  const TokHostParams p{hptr<float>(w, "tok.conv_w"), hptr<float>(w, "tok.conv_b"), hptr<float>(w, "tok.ln_w"), hptr<float>(w, "tok.ln_b")};
+  if (!p.cw || !p.cb || !p.lw || !p.lb) return ITA_OK;
+  return with_E(w.hdr.E, [&](auto e) -> int {
+    constexpr int E = decltype(e)::value;
+    // [0]: u8 frames (integer conv tables), [1]: f32 frames (f32 MFMA A fragments); each padded to the larger of the two
+    constexpr size_t one8 = ItaTokStreamLds<E, true>::IMAGE, onef = ItaTokStreamLds<E, false>::IMAGE;
+    constexpr size_t one = ((one8 > onef ? one8 : onef) + 15) & ~(size_t)15;
+    std::vector<char> im(2 * one, 0);
+    build_tokenizer_image<E, true>(p, im.data());
+    build_tokenizer_image<E, false>(p, im.data() + one);
+    w.tok_simg_bytes = one;
+    HIPCHK(w.tok_simg.upload(im.data(), im.size()));
+    return ITA_OK;
+  });
 }
 
 // step 5: the exact-f32 fusion tail's conv3x3 weights re-laid [c][ky][kx][o -> 12], so one tap's 9 output weights are contiguous

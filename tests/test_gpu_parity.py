@@ -301,6 +301,37 @@ def test_fused_tokenizer_path_equals_split_path(torch_cuda, oracle, B):
     eng.close()
 
 
+@pytest.mark.parametrize("dtype", ["u8", "f32"])
+@pytest.mark.parametrize("E", [64, 128])
+def test_tokenizer_launch_second_frame_per_workgroup(torch_cuda, oracle, E, dtype):
+    """The stand-alone tokenizer runs min(B, 2 CUs) workgroups; a workgroup with a second frame fetches it a frame ahead
+    and refills its pixel windows.  B = 2 CUs + 3 is the smallest batch that reaches that path (three workgroups take a
+    second frame): the last first-round frame, the first second-round one and both ends of the batch equal the oracle
+    bit for bit, for u8 wire frames (integer blend) and for arbitrary f32 frames (float blend), at E = 64 and E = 128."""
+    torch = torch_cuda
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    B = 2 * cus + 3
+    if E == 64:
+        d = params.load_fixture(FIX_VIT[0])
+        eng, blob, fp = _engine(d, 64)
+    else:
+        d = params.load_fixture(golden_files("vit2l_*.npz")[0])
+        nl = int(d["meta.num_layers"])
+        fp = synth.float_params(int(d["meta.seed"]), E=128, num_layers=nl, tail=False)
+        eng = host.Engine(params.blob_from_record(d, fp, E=128, num_layers=nl), device=0)
+    if dtype == "u8":
+        img = synth.frames(1200 + E, B)["img_u8"]
+    else:
+        rs = np.random.RandomState(4100 + E)
+        img = (rs.standard_normal((B, 60, 90)) * np.exp(rs.uniform(-3, 3, (B, 1, 1)))).astype(np.float32)
+    tok = eng.tokenizer(torch.from_numpy(img).cuda())
+    sel = [0, 2 * cus - 1, 2 * cus, B - 1]
+    otok = oracle.tokenizer(img[sel], fp["tokenizer.conv.weight"].reshape(E, 49), fp["tokenizer.conv.bias"],
+                            fp["tokenizer.norm.weight"], fp["tokenizer.norm.bias"])
+    np.testing.assert_array_equal(tok[sel].cpu().numpy(), otok)
+    eng.close()
+
+
 def test_refine_inputs_resize_and_default_quaternion(torch_cuda, oracle):
     """refine_inputs (QAT/model.py:22-31): frames that are not 60 x 90 are resized bilinearly (align_corners=False) and a
     missing quaternion is [1,0,0,0].  The resize runs through torch on the GPU; against the same resize done by torch
