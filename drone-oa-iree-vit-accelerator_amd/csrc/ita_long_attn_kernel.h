@@ -1,4 +1,4 @@
-// ita_long_attn_kernel.h -- ITASelfAttention_QAT on LONG token sequences (S a multiple of 128, E = 128, P = 192, H = 1).
+// ita_long_attn_kernel.h -- ITASelfAttention_QAT on LONG token sequences (S a multiple of 128, E = 64 or 128, P = 192, H = 1).
 //
 // BASELINE config 5 as it is worded -- a 480 x 720 input, a 64x patch-token blow-up -- means S = 8192 tokens through the
 // attention block (reference models/ITA/QAT/layers.py:101-127, models/ITA/QAT/ITA_softmax.py:51-61).  A row of 8192 logits
@@ -9,8 +9,15 @@
 //     sweep 1: row maximum                     (of the RAW accumulators: requantisation is monotonic, one value per row is requantised)
 //     sweep 2: row sum of 256 >> (max - x)      (per key tile in 16-bit pairs, accumulated in 32 bits)
 //     sweep 3: probabilities -> A.V            (exactly ita_softmax_packed16's last step + the stream kernel's A.V)
-// Same arithmetic as the S = 128 stream kernel and the oracle (oracle/ita_oracle.c: ita_oracle_mha_q8 / _rows): int8 codes in,
-// out_proj's int8 codes out.
+// Same arithmetic as the S = 128 stream kernel and the oracle (oracle/ita_oracle.c: ita_oracle_mha_q8 / _rows).  Two I/O forms
+// (template parameter F32IO), as the stream kernel has them (its IO8 switch):
+//     int8 : int8 codes in, out_proj's int8 codes out                                                     (ita_mha_long_q8)
+//     f32  : f32 tokens in, quantised with inv_sx by the stream kernel's q_pack16; out_proj dequantised (dq_group) and, with
+//            fuse_ln, residual + LayerNorm1 (norm1 lies in the layer's attention image, ItaStreamLds::LNP), f32 out
+//                                                                               (ita_mha_long_int8, ita_encoder_layer_long)
+// Aliasing (f32 form): y may be x.  The projection launch reads all of x and writes the workspace only; in the attention
+// launch workgroup (qt, b) reads the residual rows of ITS OWN query tile and nothing else of x -- K and V come from the
+// workspace -- and every lane reads its share of a row before any lane of its wave stores to that row.
 //
 //   ita_long_proj_kernel : persistent, one 128-token tile at a time -- the stream kernel's projection phase (Q stays in
 //                          registers as MFMA B fragments, K and V^T are built as LDS images) and then the images go to
@@ -24,19 +31,25 @@
 
 struct ItaLongArgs {
   const char* image;      // the layer's attention LDS image (ItaStreamLds<128, false, false>::IMAGE bytes)
-  const int8_t* xq;       // (B, S, 128) block input codes
-  int8_t* yq;             // (B, S, 128) out_proj codes
+  const int8_t* xq;       // (B, S, E) block input codes (int8 form)
+  int8_t* yq;             // (B, S, E) out_proj codes
   char* qfrag;            // workspace (B, S/16, 3, 64 lanes, 16 B): Q as B fragments of the logits MFMA
   char* kimg;             // workspace (B, S/128, 24576): K images [12][128][16]
   char* vimg;             // workspace (B, S/128, 24576): V^T images [8][192][16], keys permuted as in the stream kernel
   int* csum;              // workspace (B, S/128, 192): 128 * column sums of V per key tile
   float mq, mk, mv, ml, mc, mo;
   int B, S;
+  // f32 form (behind the int8 form's fields, whose kernarg offsets the int8 instantiations keep):
+  const float* x;         // (B, S, E) tokens
+  float* y;               // (B, S, E): attn(x), or with fuse_ln LayerNorm1(x + attn(x)); may alias x
+  float inv_sx, so;       // input quantiser, out_proj dequantiser
+  int fuse_ln;            // + residual + LayerNorm1
 };
 
-template <bool FAST>
+template <bool FAST, int E = 128, bool F32IO = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void ita_long_proj_kernel(const ItaLongArgs a) {
-  constexpr int E = 128, S = 128, P = 192, NK = 2;
+  static_assert(E == 64 || E == 128, "one or two 64-channel k-steps");
+  constexpr int S = 128, P = 192, NK = E / 64, EC = E / 4;
   using L = ItaStreamLds<E, false, false>;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -50,10 +63,22 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   __syncthreads();
   const int ntile = a.B * (a.S / 128);
   for (int tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
-    const int8_t* xrow = a.xq + ((size_t)tile * S + token) * E + 32 * kq;
     i32x4 xf[NK];
+    if constexpr (F32IO) {   // the stream kernel's non-IO8 input path: items, transpose, q_pack16
+      float xr[EC];
+      ld_tok_items<E>(a.x + ((size_t)tile * S + token) * E, kq, xr);
+      tok_items_transpose<E>(xr);
 #pragma unroll
-    for (int c = 0; c < NK; ++c) xf[c] = *(const i32x4*)(xrow + 16 * c);
+      for (int c = 0; c < NK; ++c) {
+        unsigned p4[4];
+        q_pack16(&xr[16 * c], a.inv_sx, p4);
+        xf[c] = (i32x4){(int)p4[0], (int)p4[1], (int)p4[2], (int)p4[3]};
+      }
+    } else {
+      const int8_t* xrow = a.xq + ((size_t)tile * S + token) * E + EC * kq;
+#pragma unroll
+      for (int c = 0; c < NK; ++c) xf[c] = *(const i32x4*)(xrow + 16 * c);
+    }
     i32x4 qf[3];
     {
       ItaFr<4 * NK> fr[2];
@@ -113,15 +138,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 struct ItaLongLds {
   static constexpr int KB = 128 * 192;                 // bytes per K or V^T image
   static constexpr int K = 0, V = 2 * KB;              // K: two-slot ring; V^T: one slot
-  static constexpr int BO = 3 * KB;                    // int32 [128]: bo + ITA_ACC_BIAS
+  static constexpr int BO = 3 * KB;                    // int32 [128]: bo + ITA_ACC_BIAS (E = 64: the first 64)
   static constexpr int CS = BO + 128 * 4;              // int32 [192]: 128 * column sums of V over the whole sequence
   static constexpr int TOTAL = CS + 192 * 4;
   static_assert(2 * TOTAL <= 160 * 1024, "two workgroups per CU");
 };
 
-template <bool FAST>
+template <bool FAST, int E = 128, bool F32IO = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void ita_long_attn_kernel(const ItaLongArgs a) {
-  constexpr int E = 128, S = 128, P = 192;
+  static_assert(E == 64 || E == 128, "one or two 64-channel output groups");
+  constexpr int S = 128, P = 192, EC = E / 4;
   using LI = ItaStreamLds<E, false, false>;   // offsets inside the layer's image
   using L = ItaLongLds;
   typedef ita_u16x2 u16x2;
@@ -315,7 +341,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       }
     }
   }
-  // ---------------- context requantisation (plain int32 sums: |sum p v| <= 255 * 128), out_proj, codes out
+  // ---------------- context requantisation (plain int32 sums: |sum p v| <= 255 * 128), out_proj, codes (or f32 rows) out
   i32x4 cf[3];
 #pragma unroll
   for (int dg = 0; dg < 3; ++dg) {
@@ -330,8 +356,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   }
   __syncthreads();      // (BO was written in the prologue: visible since the first barrier; keeps the waves together for the stores)
   const int token = wave * 16 + qi;
+  float x1[F32IO ? EC : 1];   // f32 form: this lane's quarter of the output row (the sweep accumulators are dead here)
 #pragma unroll
-  for (int eg = 0; eg < 2; ++eg) {
+  for (int eg = 0; eg < E / 64; ++eg) {
     i32x4 oa[4];
     ld_obias<E>(oa, (const int*)(lds + L::BO), 4 * eg, kq);
 #pragma unroll
@@ -340,6 +367,26 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       ld_frg_ks<E>(ob, a.image + LI::WO, 4 * eg, ks, qi, kq);      // (global: 48 KB per workgroup from L2, once)
       mm_ks(ob, cf[ks], oa);
     }
-    *(i32x4*)(a.yq + (((size_t)b * a.S + (size_t)qt * 128 + token) * E) + 32 * kq + 16 * eg) = rq_group(oa, a.mo, FAST);
+    if constexpr (F32IO) {
+      float d[16];
+      dq_group(oa, a.mo, a.so, d);
+#pragma unroll
+      for (int j = 0; j < 16; ++j) x1[16 * eg + j] = d[j];
+    } else {
+      *(i32x4*)(a.yq + (((size_t)b * a.S + (size_t)qt * 128 + token) * E) + EC * kq + 16 * eg) = rq_group(oa, a.mo, FAST);
+    }
+  }
+  if constexpr (F32IO) {
+    const size_t row = (size_t)b * a.S + (size_t)qt * 128 + token;
+    if (a.fuse_ln) {   // (uniform) residual rows of this workgroup's own query tile, then LayerNorm1 as the stream kernel has it
+      float xr[EC];
+      ld_tok_items<E>(a.x + row * E, kq, xr);
+      tok_items_transpose<E>(xr);
+#pragma unroll
+      for (int i = 0; i < EC; ++i) x1[i] = xr[i] + x1[i];
+      const float* lnp = (const float*)(a.image + LI::LNP);   // n1w | n1b
+      layernorm_q16<E>(x1, lnp, lnp + E, EC * kq);
+    }
+    st_tok_quarter<E>(a.y + row * E, kq, x1);
   }
 }

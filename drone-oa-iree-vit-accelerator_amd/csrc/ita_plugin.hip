@@ -822,16 +822,25 @@ int ita_mha_int8(ita_handle h, int layer, const float* x, float* y, int batch, v
   return ita_mha_int8_taps(h, layer, x, y, batch, nullptr, stream);
 }
 
-int ita_mha_long_q8(ita_handle h, int layer, const int8_t* x_q, int8_t* out_q, int batch, int seq_len, void* stream) {
-  if (int rc = check_layer_io(h, layer, x_q, out_q, batch)) return rc;
-  if (h->w.layers[layer].attn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's attention is float32 (ITAW0003 blob): no int8 long attention");
-  if (h->w.hdr.E != 128) return fail(ITA_ERR_UNSUPPORTED, "long-sequence attention is built for E = 128 (models/ITA, models/ITA_upsample_shuffle)");
+namespace {
+
+// the refusals every long-sequence entry point shares (ITA_ERR_UNSUPPORTED, before any launch)
+int check_long(const Layer& L, int batch, int seq_len) {
+  if (L.attn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's attention is float32 (ITAW0003 blob): no int8 long attention");
   if (seq_len < 128 || seq_len % 128 || seq_len > 65536 || batch > 65535)
     return fail(ITA_ERR_UNSUPPORTED, "seq_len must be a multiple of 128 in [128, 65536], batch <= 65535");
-  const Layer& L = h->w.layers[layer];
   if (!L.simg_mha) return fail(ITA_ERR_UNSUPPORTED, "this layer has no attention image (accumulator range, or more than one head)");
+  return ITA_OK;
+}
+
+// What the three long-sequence entry points share: the refusals, the workspace, the two launches.
+// Int8 form: xq -> yq.  F32 form (x non-null): x -> y, with fuse_ln + residual + LayerNorm1.
+int launch_long(ita_context* h, int layer, const int8_t* xq, int8_t* yq, const float* x, float* y, bool fuse_ln, int batch,
+                int seq_len, hipStream_t s) {
+  const Layer& L = h->w.layers[layer];
+  if (int rc = check_long(L, batch, seq_len)) return rc;
+  if (fuse_ln && !L.n1w) return fail(ITA_ERR_BAD_BLOB, "norm1 parameters missing from the blob");
   // the logits of a long row still fit the 16-bit travel format: same bound as stream_range_ok (per key, not per row)
-  hipStream_t s = (hipStream_t)stream;
   const size_t ntile = (size_t)batch * (seq_len / 128);
   const size_t need = ntile * (3 * 24576 + 192 * 4);
   if (need > h->long_ws_bytes) {
@@ -843,20 +852,50 @@ int ita_mha_long_q8(ita_handle h, int layer, const int8_t* x_q, int8_t* out_q, i
     h->long_ws_bytes = need;
   }
   ItaLongArgs a{};
-  a.image = L.simg_mha; a.xq = x_q; a.yq = out_q;
+  a.image = L.simg_mha; a.xq = xq; a.yq = yq; a.x = x; a.y = y;
   a.qfrag = h->long_ws; a.kimg = a.qfrag + ntile * 24576; a.vimg = a.kimg + ntile * 24576;
   a.csum = (int*)(a.vimg + ntile * 24576);
   a.mq = L.ascal[ITA_A_MQ]; a.mk = L.ascal[ITA_A_MK]; a.mv = L.ascal[ITA_A_MV]; a.ml = L.ascal[ITA_A_ML];
   a.mc = L.ascal[ITA_A_MC]; a.mo = L.ascal[ITA_A_MO];
+  a.inv_sx = L.ascal[ITA_A_INV_SX]; a.so = L.ascal[ITA_A_SO]; a.fuse_ln = fuse_ln ? 1 : 0;
   a.B = batch; a.S = seq_len;
   const bool fast = L.fast_sites == ITA_SITES_ALL;
-  const int pg = ntile < (size_t)h->num_cus ? (int)ntile : h->num_cus;
-  constexpr int proj_lds = ItaStreamLds<128, false, false>::TOTAL;
-  const dim3 attn_grid(seq_len / 128, batch);
-  if (int rc = fast ? launch<ita_long_proj_kernel<true>, proj_lds>(dim3(pg), dim3(512), s, a)
-                    : launch<ita_long_proj_kernel<false>, proj_lds>(dim3(pg), dim3(512), s, a)) return rc;
-  return fast ? launch<ita_long_attn_kernel<true>, ItaLongLds::TOTAL>(attn_grid, dim3(512), s, a)
-              : launch<ita_long_attn_kernel<false>, ItaLongLds::TOTAL>(attn_grid, dim3(512), s, a);
+  const dim3 proj_grid(ntile < (size_t)h->num_cus ? (int)ntile : h->num_cus), attn_grid(seq_len / 128, batch);
+  auto run = [&](auto e, auto f32, auto fst) {
+    constexpr int E = decltype(e)::value;
+    constexpr bool F32 = decltype(f32)::value, FAST = decltype(fst)::value;
+    if (int rc = launch<ita_long_proj_kernel<FAST, E, F32>, ItaStreamLds<E, false, false>::TOTAL>(proj_grid, dim3(512), s, a)) return rc;
+    return launch<ita_long_attn_kernel<FAST, E, F32>, ItaLongLds::TOTAL>(attn_grid, dim3(512), s, a);
+  };
+  return with_E(h->w.hdr.E, [&](auto e) {
+    if (x) return fast ? run(e, std::true_type{}, std::true_type{}) : run(e, std::true_type{}, std::false_type{});
+    return fast ? run(e, std::false_type{}, std::true_type{}) : run(e, std::false_type{}, std::false_type{});
+  });
+}
+
+}  // namespace
+
+int ita_mha_long_q8(ita_handle h, int layer, const int8_t* x_q, int8_t* out_q, int batch, int seq_len, void* stream) {
+  if (int rc = check_layer_io(h, layer, x_q, out_q, batch)) return rc;
+  return launch_long(h, layer, x_q, out_q, nullptr, nullptr, false, batch, seq_len, (hipStream_t)stream);
+}
+
+int ita_mha_long_int8(ita_handle h, int layer, const float* x, float* y, int batch, int seq_len, void* stream) {
+  if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
+  return launch_long(h, layer, nullptr, nullptr, x, y, false, batch, seq_len, (hipStream_t)stream);
+}
+
+// x1 = LN1(x + attn(x)) into y by the two long launches, then the FFN block + residual + LN2 in place on y: the FFN is per
+// token, so the (batch * seq_len / 128) blocks of 128 rows are its "frames"
+int ita_encoder_layer_long(ita_handle h, int layer, const float* x, float* y, int batch, int seq_len, void* stream) {
+  if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
+  const Layer& L = h->w.layers[layer];
+  // (everything that can refuse is checked before the first launch: no partial work is left behind an error)
+  if (int rc = check_long(L, batch, seq_len)) return rc;
+  if (L.ffn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's FFN is float32 (ITAW0002 blob): no long-sequence encoder layer");
+  if (!L.n1w || !L.n2w) return fail(ITA_ERR_BAD_BLOB, "LayerNorm parameters missing from the blob");
+  if (int rc = launch_long(h, layer, nullptr, nullptr, x, y, true, batch, seq_len, (hipStream_t)stream)) return rc;
+  return launch_ffn(h, layer, y, y, batch * (seq_len / 128), true, nullptr, (hipStream_t)stream);
 }
 
 int ita_mha_q8(ita_handle h, int layer, const int8_t* x_q, int8_t* out_q, int batch, void* stream) {

@@ -34,7 +34,7 @@ HEAD_TIMEOUT = 1
 
 EXPORTED_SYMBOLS = (
     "ita_abi_version", "ita_create", "ita_destroy", "ita_load_weights", "ita_validate_blob", "ita_reserve", "ita_get_dims",
-    "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_ffn_int8", "ita_ffn_int8_taps",
+    "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_mha_long_int8", "ita_encoder_layer_long", "ita_ffn_int8", "ita_ffn_int8_taps",
     "ita_ffn_f32", "ita_get_ffn_kind", "ita_mha_f32", "ita_get_attn_kind",
     "ita_encoder_layer", "ita_tokenizer", "ita_fusion_tail", "ita_vitlstm_forward", "ita_bind_dispatch",
     "ita_profile_begin", "ita_profile_begin_sampled", "ita_profile_end", "ita_set_tail_mode", "ita_debug_encoder_stamps",
@@ -138,6 +138,8 @@ def lib():
         L.ita_resize_table.argtypes = [i, i, vp, vp, vp, i, C.POINTER(i)]
         L.ita_mha_q8.argtypes = [vp, i, vp, vp, i, vp]
         L.ita_mha_long_q8.argtypes = [vp, i, vp, vp, i, i, vp]
+        L.ita_mha_long_int8.argtypes = [vp, i, vp, vp, i, i, vp]
+        L.ita_encoder_layer_long.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_vitlstm_tail.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
         L.ita_debug_softmax_rows.argtypes = [vp, vp, vp, i, vp]
         L.ita_validate_blob.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p]
@@ -587,6 +589,41 @@ class Engine:
         _chk(lib().ita_mha_long_q8(self._h, layer, x_q.data_ptr(), out.data_ptr(), x_q.shape[0], x_q.shape[1],
                                    _stream_ptr(self.device)))
         return out
+
+    def _long_f32(self, x):
+        if x.dim() != 3 or x.shape[2] != self.E:
+            raise ITAError(f"expected (B, S, {self.E}) tokens, got {tuple(x.shape)}")
+        return _dev_f32(x)
+
+    def mha_long(self, x, layer: int = 0):
+        """attention block over a long sequence: x (B,S,E) f32, S a multiple of 128 -> attn(x) (B,S,E) f32
+        (ita_mha_long_int8: the long form of mha)"""
+        torch = _torch()
+        x = self._long_f32(x)
+        y = torch.empty_like(x)
+        _chk(lib().ita_mha_long_int8(self._h, layer, x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1],
+                                     _stream_ptr(self.device)))
+        return y
+
+    def encoder_layer_long(self, x, layer: int = 0, out=None):
+        """one encoder layer over a long sequence: x (B,S,E) f32 -> LN2(x1 + ffn(x1)), x1 = LN1(x + attn(x))
+        (ita_encoder_layer_long); out: optional contiguous f32 GPU tensor of x's shape, may be x itself"""
+        torch = _torch()
+        x = self._long_f32(x)
+        if out is None:
+            out = torch.empty_like(x)
+        elif not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.shape != x.shape:
+            raise ITAError(f"out must be a contiguous f32 GPU tensor of shape {tuple(x.shape)}")
+        _chk(lib().ita_encoder_layer_long(self._h, layer, x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1],
+                                          _stream_ptr(self.device)))
+        return out
+
+    def encode_long(self, x):
+        """all num_layers encoder layers in order over a long sequence: (B,S,E) f32 -> (B,S,E) f32"""
+        y = self.encoder_layer_long(x, 0)
+        for layer in range(1, self.num_layers):
+            self.encoder_layer_long(y, layer, out=y)
+        return y
 
     def softmax_rows(self, logits):
         """IntegerApproximatedSoftmax through the encoder kernel's own device function: int8 (R,128) -> uint8 (R,128)"""

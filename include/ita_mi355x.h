@@ -52,7 +52,8 @@ int ita_destroy(ita_handle h);
  * (ITAW0001) blob only -- ITAW0002 and ITAW0003 blobs run with one head.  Anything else: ITA_ERR_UNSUPPORTED.
  * A layer with H > 1 runs on the block kernels (ita_mha_kernel<E, H>, then the FFN block) behind the stand-alone tokenizer;
  * every entry point below serves it except those that need the one-head stream kernel, which return
- * ITA_ERR_UNSUPPORTED before any launch: ita_mha_q8, ita_mha_long_q8, ita_debug_encoder_stamps, ita_vitlstm_forward_slots.
+ * ITA_ERR_UNSUPPORTED before any launch: ita_mha_q8, ita_mha_long_q8, ita_mha_long_int8, ita_encoder_layer_long,
+ * ita_debug_encoder_stamps, ita_vitlstm_forward_slots.
  * The reference pre-loads weights into the accelerator out of band
  * (docs/HOW-TO-run-the-full-project-workflow.md:55); this is that step. */
 int ita_load_weights(ita_handle h, const void* blob, size_t nbytes);
@@ -100,12 +101,22 @@ int ita_mha_int8_taps(ita_handle h, int layer, const float* x_dev, float* y_dev,
  * Equal, byte for byte, to the x_q -> out_q taps of ita_mha_int8_taps. */
 int ita_mha_q8(ita_handle h, int layer, const int8_t* x_q_dev, int8_t* out_q_dev, int batch, void* stream);
 
-/* The same block on LONG token sequences: x_q, out_q (B, seq_len, E) s8 with seq_len a multiple of 128 (E = 128 graphs only) --
+/* The same block on LONG token sequences: x_q, out_q (B, seq_len, E) s8 with seq_len a multiple of 128 in [128, 65536],
+ * batch <= 65535, E = 64 or 128 --
  * BASELINE config 5 as it is worded (480 x 720 input, 64x patch-token blow-up: seq_len = 8192).  Same arithmetic as above
  * (layers.py:106-123, ITA_softmax.py:51-61 over a row of seq_len logits); the logits are never materialised: three sweeps over
  * the key tiles per query tile (row maximum, row sum, probabilities -> A.V), Q K^T recomputed in each.  Its Q / K / V^T
  * workspace (3 x 192 bytes per token) belongs to the handle and grows on demand (not inside a stream capture). */
 int ita_mha_long_q8(ita_handle h, int layer, const int8_t* x_q_dev, int8_t* out_q_dev, int batch, int seq_len, void* stream);
+/* The long form of ita_mha_int8: x, y (B, seq_len, E) f32, y = attn(x) -- x quantised as ita_mha_int8 quantises it, the
+ * out_proj codes of ita_mha_long_q8 dequantised.  Shape limits, workspace and refusals of ita_mha_long_q8. */
+int ita_mha_long_int8(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_len, void* stream);
+/* The long form of ita_encoder_layer: y = LN2(x1 + ffn(x1)), x1 = LN1(x + attn(x)) on (B, seq_len, E) f32 rows; x_dev may
+ * equal y_dev.  Attention + residual + LN1 are the two long launches (x1 goes to y), the FFN + residual + LN2 then run in
+ * place on y, 128 rows per block (ita_ffn_int8's kernel: the FFN is per token).  Shape limits, workspace and refusals of
+ * ita_mha_long_q8; in addition a float-FFN layer (ITAW0002 blob) is ITA_ERR_UNSUPPORTED and a blob without the layer's
+ * norm parameters ITA_ERR_BAD_BLOB -- all before any launch. */
+int ita_encoder_layer_long(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_len, void* stream);
 
 /* ITAFeedForward_QAT.forward (models/ITA/QAT/layers.py:61-75). */
 int ita_ffn_int8(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, void* stream);
@@ -124,7 +135,8 @@ int ita_get_ffn_kind(ita_handle h, int layer, int* kind);
 int ita_ffn_f32(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, void* stream);
 /* Attention kind of a loaded layer: ITA_ATTN_INT8 (ITAW0001 / ITAW0002 blob, ita_mha_int8) or ITA_ATTN_F32 (ITAW0003
  * blob: the float graph, models/ITA_single_layer_upsample_shuffle/model.py, nothing quantised).  ita_mha_int8 / _taps,
- * ita_mha_q8, ita_mha_long_q8, ita_debug_encoder_stamps and the drop-in ITASelfAttention_workgroup on an F32 layer, and
+ * ita_mha_q8, ita_mha_long_q8, ita_mha_long_int8, ita_encoder_layer_long, ita_debug_encoder_stamps and the drop-in
+ * ITASelfAttention_workgroup on an F32 layer, and
  * ita_mha_f32 on an INT8 layer, fail with ITA_ERR_UNSUPPORTED. */
 enum { ITA_ATTN_INT8 = 0, ITA_ATTN_F32 = 1 };
 int ita_get_attn_kind(ita_handle h, int layer, int* kind);
