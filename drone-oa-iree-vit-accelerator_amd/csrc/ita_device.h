@@ -462,7 +462,7 @@ __device__ __forceinline__ float ita_sigmoid(float x) { return 1.0f / (1.0f + it
 __device__ __forceinline__ float ita_tanh(float x) { return 1.0f - 2.0f / (ita_expf(2.0f * x) + 1.0f); }
 
 // source row / column and weight of F.interpolate(mode='bilinear', align_corners=False)
-__device__ __forceinline__ void bilinear_src_dev(int dst, float scale, int in, int& i0, int& ip, float& l1) {
+__host__ __device__ __forceinline__ void bilinear_src_dev(int dst, float scale, int in, int& i0, int& ip, float& l1) {
   float src = scale * ((float)dst + 0.5f) - 0.5f;
   if (src < 0.0f) src = 0.0f;
   int i = (int)src;

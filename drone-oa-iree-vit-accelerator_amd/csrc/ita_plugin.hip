@@ -31,6 +31,7 @@
 #include "ita_attn_f32_kernel.h"
 #include "ita_ingest_kernel.h"
 #include "ita_ingest_wire_kernel.h"
+#include "ita_tokenizer_long_kernel.h"
 
 namespace {
 
@@ -623,6 +624,38 @@ int check_frames(int height, int width, long long row_stride, long long frame_st
   return ITA_OK;
 }
 
+// whether every 16-token tile of a token row needs at most ITA_TOK_LONG_WIN_W pixel columns: from 2 x0 - 3 of its first token
+// to 2 (x0 + xp) + 3 of its last (x0 and x0 + xp do not decrease along a row).  The kernel's own function on the host: the
+// same float expressions give the same integers.
+bool tok_long_window_fits(float scale_x, int CW, int tok_w) {
+  for (int ox = 0; ox < tok_w; ox += 16) {
+    int xf, xl, pf, pl;
+    float l;
+    bilinear_src_dev(ox, scale_x, CW, xf, pf, l);
+    bilinear_src_dev(ox + 15, scale_x, CW, xl, pl, l);
+    if (2 * (xl + pl - xf) + 7 > ITA_TOK_LONG_WIN_W) return false;
+  }
+  return true;
+}
+
+// ita_tokenizer_long's launch: persistent 512-thread workgroups, each round takes eight consecutive (frame, 16-token tile) items
+template <typename T>
+int launch_tokenizer_long(ita_context* c, const void* src, int H, int W, long long row_stride, long long frame_stride,
+                          float depth_scale, int tok_h, int tok_w, float* tokens, int batch, hipStream_t s) {
+  const int CH = (H - 1) / 2 + 1, CW = (W - 1) / 2 + 1;
+  ItaTokLongArgs a{c->w.tok_simg + c->w.tok_simg_bytes, src, tokens, row_stride, frame_stride,
+                   (float)CH / (float)tok_h, (float)CW / (float)tok_w,   // host IEEE divisions: the oracle's bilinear_src scales
+                   depth_scale, H, W, CH, CW, tok_h, tok_w, batch};
+  const long long rounds = (long long)batch * (tok_h * tok_w / 128);
+  const int g = (int)std::min<long long>(rounds, 2ll * c->num_cus);   // <= 65 KB of LDS, <= 128 registers: two workgroups per CU
+  const bool win = tok_long_window_fits(a.scale_x, CW, tok_w);
+  return with_E(c->w.hdr.E, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    return win ? launch<ita_tok_long_kernel<E, T, true>, ItaTokLongLds<E, true>::TOTAL>(dim3(g), dim3(512), s, a)
+               : launch<ita_tok_long_kernel<E, T, false>, ItaTokLongLds<E, false>::TOTAL>(dim3(g), dim3(512), s, a);
+  });
+}
+
 WireSize* find_wire(ita_context* c, int H, int W) {
   for (WireSize& w : c->wire)
     if (w.H == H && w.W == W) return &w;
@@ -1019,6 +1052,41 @@ int ita_ingest(ita_handle h, const void* src, int pixel_dtype, int height, int w
     case ITA_PIXEL_U16: return launch_ingest<uint16_t>(h, src, height, width, row_stride, frame_stride, depth_scale, frames, batch, s);
     default: return launch_ingest<float>(h, src, height, width, row_stride, frame_stride, depth_scale, frames, batch, s);
   }
+}
+
+int ita_tokenizer_long(ita_handle h, const void* src, int pixel_dtype, int height, int width, long long row_stride,
+                       long long frame_stride, float depth_scale, int tok_h, int tok_w, float* tokens, int batch, void* stream) {
+  // every argument is judged before the handle's weights are looked at and before any HIP call
+  if (!h) return fail(ITA_ERR_INVALID_ARG, "null handle");
+  if (!src || !tokens) return fail(ITA_ERR_INVALID_ARG, "null pointer");
+  if (pixel_dtype != ITA_PIXEL_U8 && pixel_dtype != ITA_PIXEL_U16 && pixel_dtype != ITA_PIXEL_F32)
+    return fail(ITA_ERR_INVALID_ARG, "pixel_dtype must be ITA_PIXEL_U8, ITA_PIXEL_U16 or ITA_PIXEL_F32");
+  if (int rc = check_frames(height, width, row_stride, frame_stride, batch)) return rc;
+  const size_t px = pixel_dtype == ITA_PIXEL_U8 ? 1 : pixel_dtype == ITA_PIXEL_U16 ? 2 : 4;
+  if ((uintptr_t)src % px || (uintptr_t)tokens % 16)
+    return fail(ITA_ERR_INVALID_ARG, "src must be aligned to its pixel size, tokens to 16 bytes");
+  if (pixel_dtype == ITA_PIXEL_U16 && !(depth_scale > 0.0f && depth_scale <= 3.402823466e38f))
+    return fail(ITA_ERR_INVALID_ARG, "depth_scale must be finite and positive");
+  if (tok_h < 1 || tok_w < 16 || tok_w % 16 || tok_w > 65536 || (long long)tok_h * tok_w % 128 || (long long)tok_h * tok_w > 65536 ||
+      batch > 65535)
+    return fail(ITA_ERR_UNSUPPORTED, "needs tok_h >= 1, tok_w % 16 == 0, tok_h * tok_w a multiple of 128 up to 65536, batch <= 65535");
+  if (!h->w.loaded) return fail(ITA_ERR_NO_WEIGHTS, "ita_load_weights has not been called");
+  // (the image exists when the blob has the conv weights and bias and the LayerNorm: ita_load_weights)
+  if (!h->w.tok_simg) return fail(ITA_ERR_BAD_BLOB, "tokenizer parameters missing from the blob");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = (hipStream_t)stream;
+  // sampled single-stage profiling (ita_profile_begin_sampled with only_stage 0, the tokenizer) also works here
+  StageRecorder rec(h, s, false);
+  int rc = rec.mark(0, false);
+  if (rc) return rc;
+  switch (pixel_dtype) {
+    case ITA_PIXEL_U8: rc = launch_tokenizer_long<uint8_t>(h, src, height, width, row_stride, frame_stride, depth_scale, tok_h, tok_w, tokens, batch, s); break;
+    case ITA_PIXEL_U16: rc = launch_tokenizer_long<uint16_t>(h, src, height, width, row_stride, frame_stride, depth_scale, tok_h, tok_w, tokens, batch, s); break;
+    default: rc = launch_tokenizer_long<float>(h, src, height, width, row_stride, frame_stride, depth_scale, tok_h, tok_w, tokens, batch, s);
+  }
+  if (rc || (rc = rec.mark(0, true))) return rc;
+  rec.finish();
+  return ITA_OK;
 }
 
 int ita_resize_table(int n_in, int n_out, int* n0, int* count, float* coeff, int coeff_width, int* width_out) {

@@ -41,7 +41,7 @@ EXPORTED_SYMBOLS = (
     "ita_fusion_tail_load", "ita_fusion_tail_large",
     "ita_wire_unpack_packet", "ita_wire_postprocess", "ita_vitlstm_forward_slots", "ita_vitlstm_front",
     "ita_vitlstm_back", "ita_vitlstm_pipelined", "ita_vitlstm_front_ev", "ita_vitlstm_encode", "ita_vitlstm_fold", "ita_vitlstm_tail", "ita_debug_softmax_rows",
-    "ita_head_status", "ita_vitlstm_sequence", "ita_ingest", "ita_ingest_wire", "ita_ingest_wire_prepare", "ita_resize_table",
+    "ita_head_status", "ita_vitlstm_sequence", "ita_ingest", "ita_tokenizer_long", "ita_ingest_wire", "ita_ingest_wire_prepare", "ita_resize_table",
     "ITASelfAttention_workgroup", "ITASelfAttention_workgroup_expanded", "ITAFeedForward_workgroup",
 )
 
@@ -133,6 +133,7 @@ def lib():
         L.ita_vitlstm_pipelined.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, i, i, vp, vp]
         L.ita_vitlstm_sequence.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, vp, i, i, vp]
         L.ita_ingest.argtypes = [vp, vp, i, i, i, C.c_longlong, C.c_longlong, C.c_float, vp, i, vp]
+        L.ita_tokenizer_long.argtypes = [vp, vp, i, i, i, C.c_longlong, C.c_longlong, C.c_float, i, i, vp, i, vp]
         L.ita_ingest_wire.argtypes = [vp, vp, i, i, C.c_longlong, C.c_longlong, vp, i, vp]
         L.ita_ingest_wire_prepare.argtypes = [vp, i, i]
         L.ita_resize_table.argtypes = [i, i, vp, vp, vp, i, C.POINTER(i)]
@@ -405,14 +406,9 @@ class Engine:
                 return None
         return (rs, lead[-1][1]) if lead[-1][1] >= extent else None
 
-    def ingest(self, frames, depth_scale: Optional[float] = None, out=None):
-        """refine_inputs' resize as a stage of its own (ita_ingest): frames (..., H, W) on this engine's GPU, H and W in
-        [1, 4096], uint8 (value code / 255), uint16 or int16 taken as the same bits (value min(code * depth_scale, 1),
-        depth_scale default 1 / 65535) or float32 (as is) -> (N,60,90) f32, bilinear with align_corners=False, equal to
-        ingest_ref.ingest_reference bit for bit.  A view whose last dimension is dense and whose leading dimensions
-        collapse to one frame stride (a cropped camera buffer) is read through its strides without a copy; anything else
-        is made contiguous first.  The result is allocated per call, or written into out ((N,60,90) f32, contiguous); hand
-        it to forward / forward_sequence / forward_slots as f32 frames: eng.forward(eng.ingest(raw), desvel)."""
+    def _camera_frames(self, frames, depth_scale, what):
+        """the frames argument of ingest and tokenize_long -> (tensor to read, pixel dtype, H, W, N, (row stride, frame
+        stride) in pixels, depth_scale): a view that can be walked as it lies is kept, anything else made contiguous"""
         torch = _torch()
         if not hasattr(frames, "is_cuda") or not frames.is_cuda:
             raise ITAError("frames must be a GPU tensor (no CPU fallback)")
@@ -420,7 +416,7 @@ class Engine:
             raise ITAError(f"tensor lives on cuda:{frames.device.index}, the engine on cuda:{self.device}")
         kinds = {torch.uint8: PIXEL_U8, torch.uint16: PIXEL_U16, torch.int16: PIXEL_U16, torch.float32: PIXEL_F32}
         if frames.dtype not in kinds:
-            raise ITAError(f"ingest takes uint8, uint16, int16 or float32 frames, got {frames.dtype}")
+            raise ITAError(f"{what} takes uint8, uint16, int16 or float32 frames, got {frames.dtype}")
         if frames.dim() < 2:
             raise ITAError(f"frames must be (..., H, W), got {tuple(frames.shape)}")
         H, W = int(frames.shape[-2]), int(frames.shape[-1])
@@ -435,12 +431,24 @@ class Engine:
             strides = (W, H * W)
         if depth_scale is None:
             depth_scale = 1.0 / 65535.0
+        return frames, kinds[frames.dtype], H, W, N, strides, float(depth_scale)
+
+    def ingest(self, frames, depth_scale: Optional[float] = None, out=None):
+        """refine_inputs' resize as a stage of its own (ita_ingest): frames (..., H, W) on this engine's GPU, H and W in
+        [1, 4096], uint8 (value code / 255), uint16 or int16 taken as the same bits (value min(code * depth_scale, 1),
+        depth_scale default 1 / 65535) or float32 (as is) -> (N,60,90) f32, bilinear with align_corners=False, equal to
+        ingest_ref.ingest_reference bit for bit.  A view whose last dimension is dense and whose leading dimensions
+        collapse to one frame stride (a cropped camera buffer) is read through its strides without a copy; anything else
+        is made contiguous first.  The result is allocated per call, or written into out ((N,60,90) f32, contiguous); hand
+        it to forward / forward_sequence / forward_slots as f32 frames: eng.forward(eng.ingest(raw), desvel)."""
+        torch = _torch()
+        frames, kind, H, W, N, strides, depth_scale = self._camera_frames(frames, depth_scale, "ingest")
         if out is None:
             out = torch.empty((N, 60, 90), dtype=torch.float32, device=frames.device)
         elif not out.is_cuda or out.device.index != self.device or out.dtype != torch.float32 or not out.is_contiguous() \
                 or tuple(out.shape) != (N, 60, 90):
             raise ITAError(f"out must be a contiguous f32 tensor of shape ({N}, 60, 90) on cuda:{self.device}")
-        _chk(lib().ita_ingest(self._h, frames.data_ptr(), kinds[frames.dtype], H, W, strides[0], strides[1],
+        _chk(lib().ita_ingest(self._h, frames.data_ptr(), kind, H, W, strides[0], strides[1],
                               float(depth_scale), out.data_ptr(), N, _stream_ptr(self.device)))
         return out
 
@@ -622,6 +630,36 @@ class Engine:
         """all num_layers encoder layers in order over a long sequence: (B,S,E) f32 -> (B,S,E) f32"""
         y = self.encoder_layer_long(x, 0)
         for layer in range(1, self.num_layers):
+            self.encoder_layer_long(y, layer, out=y)
+        return y
+
+    def tokenize_long(self, frames, tok_h: int, tok_w: int, depth_scale: Optional[float] = None, out=None):
+        """OverlapPatchMerging for any frame size and token grid (ita_tokenizer_long): frames (..., H, W) on this engine's
+        GPU, H and W in [1, 4096], uint8 / uint16 / int16 / float32 valued and read through their strides exactly as
+        ingest does -> (N, tok_h * tok_w, E) f32 token rows, the input of mha_long / encoder_layer_long / encode_long and
+        FusionTailLarge.  tok_w a multiple of 16, tok_h * tok_w a multiple of 128 up to 65536.  Equal to
+        tokenizer_long_ref (blend_patches + the fmaf chain + LayerNorm) bit for bit.  The result is allocated per call, or
+        written into out ((N, tok_h * tok_w, E) f32, contiguous)."""
+        torch = _torch()
+        frames, kind, H, W, N, strides, depth_scale = self._camera_frames(frames, depth_scale, "tokenize_long")
+        tok_h, tok_w = int(tok_h), int(tok_w)
+        shape = (N, tok_h * tok_w, self.E)
+        if out is None:
+            if tok_h < 1 or tok_w < 1:
+                raise ITAError(f"token grid must be positive, got {tok_h} x {tok_w}")
+            out = torch.empty(shape, dtype=torch.float32, device=frames.device)
+        elif not out.is_cuda or out.device.index != self.device or out.dtype != torch.float32 or not out.is_contiguous() \
+                or tuple(out.shape) != shape:
+            raise ITAError(f"out must be a contiguous f32 tensor of shape {shape} on cuda:{self.device}")
+        _chk(lib().ita_tokenizer_long(self._h, frames.data_ptr(), kind, H, W, strides[0], strides[1], depth_scale,
+                                      tok_h, tok_w, out.data_ptr(), N, _stream_ptr(self.device)))
+        return out
+
+    def encode_frames_long(self, frames, tok_h: int, tok_w: int, depth_scale: Optional[float] = None):
+        """camera frames -> tokens -> every encoder layer: tokenize_long, then all num_layers of encoder_layer_long in
+        place on the token buffer; (..., H, W) -> (N, tok_h * tok_w, E) f32"""
+        y = self.tokenize_long(frames, tok_h, tok_w, depth_scale)
+        for layer in range(self.num_layers):
             self.encoder_layer_long(y, layer, out=y)
         return y
 

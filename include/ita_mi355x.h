@@ -174,6 +174,27 @@ typedef enum ita_pixel_dtype { ITA_PIXEL_U8 = 0, ITA_PIXEL_U16 = 1, ITA_PIXEL_F3
 int ita_ingest(ita_handle h, const void* src_dev, int pixel_dtype, int height, int width, long long row_stride,
                long long frame_stride, float depth_scale, float* frames_dev, int batch, void* stream);
 
+/* OverlapPatchMerging(in, out, 7, 2, 3, output_size) (models/ITA/QAT/layers.py:39-45) for ANY frame size and token grid: the
+ * way from a camera frame into the long-sequence path (ita_mha_long_int8, ita_encoder_layer_long, ita_fusion_tail_large;
+ * BASELINE config 5: 480 x 720 -> 64 x 128 = 8192 tokens).  `batch` frames of height x width pixels, addressed and valued
+ * as ita_ingest addresses and values them (strides in pixels; u8 f32(code) / 255.0f, u16 min(f32(code) * depth_scale,
+ * 1.0f), f32 as is) -> tokens_dev (batch, tok_h * tok_w, E) f32, token (oy, ox) in row oy * tok_w + ox:
+ *   conv 7x7, stride 2, zero padding 3 -> CH x CW = ((height-1)/2 + 1) x ((width-1)/2 + 1)
+ *   bilinear CH x CW -> tok_h x tok_w, align_corners = False (up- or down-sampling), LayerNorm over E.
+ * Conv and resize are linear, so the four bilinear neighbours are blended on the 7 x 7 input patches first and one
+ * ascending 49-step fmaf chain per token and channel, started from the bias, follows: the conv map is never written.  The
+ * result equals tokenizer_long_ref.py (blend_patches, then the chain and the LayerNorm) bit for bit, and at 60 x 90 -> 8 x
+ * 16 on f32 frames it equals ita_tokenizer(ITA_IMAGE_F32) bit for bit.
+ * Reads only the pixels [base, base + (height-1) * row_stride + width) of each frame, whatever the alignment of base;
+ * writes only the batch * tok_h * tok_w * E floats.  Stream-ordered, no allocation, no host synchronisation.  Needs loaded
+ * weights (ITA_ERR_NO_WEIGHTS) of any blob kind and head count: every blob carries the tokenizer's parameters.
+ * ITA_ERR_INVALID_ARG before any launch: the argument faults of ita_ingest (tokens_dev must be aligned to 16 bytes).
+ * ITA_ERR_UNSUPPORTED before any launch: tok_h < 1, tok_w not a positive multiple of 16, tok_h * tok_w not a multiple of
+ * 128 or above 65536, batch > 65535. */
+int ita_tokenizer_long(ita_handle h, const void* src_dev, int pixel_dtype, int height, int width, long long row_stride,
+                       long long frame_stride, float depth_scale, int tok_h, int tok_w, float* tokens_dev, int batch,
+                       void* stream);
+
 /* The reference HOST's resize as a stage in front of the graph, for hosts that decode camera frames: `batch` u8 frames of
  * height x width, row r of frame b at src_dev + b * frame_stride + r * row_stride (strides in pixels = bytes; a cropped
  * view of a larger buffer is passed as it is) -> wire_dev (batch,60,90) u8, contiguous: the wire frames ITA_IMAGE_U8
