@@ -1024,6 +1024,19 @@ int ita_debug_softmax_rows(ita_handle h, const int8_t* logits, uint8_t* probs, i
   return launch<ita_softmax_rows_kernel>(dim3((rows + 15) / 16), dim3(64), (hipStream_t)stream, logits, probs, rows);
 }
 
+int ita_debug_fast_site_ok(float mult) { return fast_site_ok(mult) ? 1 : 0; }
+
+int ita_debug_layer_forms(ita_handle h, int layer, unsigned* fast_sites, int* stream_images) {
+  if (!h || !h->w.loaded) return fail(ITA_ERR_NO_WEIGHTS, "no weights loaded");
+  if (!fast_sites || !stream_images || layer < 0 || layer >= h->w.hdr.num_layers)
+    return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
+  const Layer& L = h->w.layers[layer];
+  *fast_sites = L.fast_sites;
+  *stream_images = (L.simg_mha ? ITA_FORMS_ATTN_IMAGE : 0) | (L.simg_enc ? ITA_FORMS_LAYER_IMAGE : 0) |
+                       (L.simg_tok ? ITA_FORMS_TOK_IMAGE : 0);
+  return ITA_OK;
+}
+
 int ita_tokenizer(ita_handle h, const void* image, int image_dtype, float* tokens, int batch, void* stream) {
   int rc = check(h, batch);
   if (rc) return rc;

@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "ita_wire_unpack_packet", "ita_wire_postprocess", "ita_vitlstm_forward_slots", "ita_vitlstm_front",
     "ita_vitlstm_back", "ita_vitlstm_pipelined", "ita_vitlstm_front_ev", "ita_vitlstm_encode", "ita_vitlstm_fold", "ita_vitlstm_tail", "ita_debug_softmax_rows",
     "ita_head_status", "ita_vitlstm_sequence", "ita_ingest", "ita_tokenizer_long", "ita_ingest_wire", "ita_ingest_wire_prepare", "ita_resize_table",
+    "ita_debug_fast_site_ok", "ita_debug_layer_forms",
     "ITASelfAttention_workgroup", "ITASelfAttention_workgroup_expanded", "ITAFeedForward_workgroup",
 )
 
@@ -143,6 +144,8 @@ def lib():
         L.ita_encoder_layer_long.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_vitlstm_tail.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
         L.ita_debug_softmax_rows.argtypes = [vp, vp, vp, i, vp]
+        L.ita_debug_fast_site_ok.argtypes = [C.c_float]
+        L.ita_debug_layer_forms.argtypes = [vp, i, C.POINTER(C.c_uint), C.POINTER(i)]
         L.ita_validate_blob.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p]
         L.ita_bind_dispatch.argtypes = [vp, i, i]
         L.ita_wire_unpack_packet.argtypes = [vp, C.c_size_t, i, vp]
@@ -210,6 +213,15 @@ def resize_table(n_in: int, n_out: int):
     width = C.c_int(0)
     _chk(lib().ita_resize_table(n_in, n_out, n0.ctypes.data, count.ctypes.data, coeff.ctypes.data, cap, C.byref(width)))
     return n0, count, coeff[:, :width.value].copy()
+
+
+FORMS_ATTN_IMAGE, FORMS_LAYER_IMAGE, FORMS_TOK_IMAGE = 1, 2, 4
+
+
+def fast_site_ok(mult: float) -> bool:
+    """ita_debug_fast_site_ok: the load-time proof that a requantisation site with this float32 multiplier may round once
+    (host only: no GPU, no handle)"""
+    return bool(lib().ita_debug_fast_site_ok(C.c_float(float(mult))))
 
 
 class Engine:
@@ -291,6 +303,16 @@ class Engine:
         st = _MhaTaps(**{k: v.data_ptr() for k, v in t.items()})
         _chk(lib().ita_mha_int8_taps(self._h, layer, x.data_ptr(), y.data_ptr(), B, C.byref(st), _stream_ptr(self.device)))
         return y, t
+
+    def layer_forms(self, layer: int = 0) -> dict:
+        """ita_debug_layer_forms: which requantisation form and which kernels the layer runs -> fast_sites (the
+        ITA_SITE_* mask, bits 0..5 = Q, K, V, logits, context, out_proj), fast (all six sites proven: the stream kernels run their single-rounding instantiation),
+        attn_image (mha without taps, mha_q8 and the long entries run on the stream kernels; else block kernels or a
+        refusal), layer_image (encoder_layer is one stream-kernel launch), tok_image"""
+        m, im = C.c_uint(0), C.c_int(0)
+        _chk(lib().ita_debug_layer_forms(self._h, layer, C.byref(m), C.byref(im)))
+        return dict(fast_sites=m.value, fast=m.value == 63, attn_image=bool(im.value & FORMS_ATTN_IMAGE),
+                    layer_image=bool(im.value & FORMS_LAYER_IMAGE), tok_image=bool(im.value & FORMS_TOK_IMAGE))
 
     def attn_kind(self, layer: int = 0) -> int:
         """ATTN_INT8 (ITAW0001 / ITAW0002 blob) or ATTN_F32 (ITAW0003: the float graph's float32 attention)"""

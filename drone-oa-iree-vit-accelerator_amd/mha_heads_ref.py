@@ -11,6 +11,9 @@ are one QFunctional each, so ALL heads share one logit multiplier and one contex
 
 With H = 1 this is the block the C oracle computes (tests/test_heads_cpu.py holds the two equal); the C oracle has one
 head only.  Nothing here imports it.
+
+``ffn`` is the FFN block in the same style, and both return, on request, the int32 accumulators in front of every
+requantisation (tests/test_requant_cpu.py holds them to the C oracle; tests/requant_common.py crafts blobs on them).
 """
 from __future__ import annotations
 
@@ -33,10 +36,14 @@ def quantize(x: np.ndarray, inv_scale) -> np.ndarray:
     return np.clip(np.rint(np.asarray(x, np.float32) * f32(inv_scale)), -128, 127).astype(np.int8)
 
 
+def linear_acc(x_q: np.ndarray, w: np.ndarray, bias_q: np.ndarray) -> np.ndarray:
+    """the int32 accumulators of nnq.Linear, bias included"""
+    return x_q.astype(np.int32) @ w.astype(np.int32).T + bias_q.astype(np.int32)
+
+
 def linear_q(x_q: np.ndarray, w: np.ndarray, bias_q: np.ndarray, mult) -> np.ndarray:
     """nnq.Linear: x_q (..., K) int8, w (N, K) int8, bias_q (N,) int32 in accumulator units -> (..., N) int8"""
-    acc = x_q.astype(np.int32) @ w.astype(np.int32).T + bias_q.astype(np.int32)
-    return requant(acc, mult)
+    return requant(linear_acc(x_q, w, bias_q), mult)
 
 
 def softmax_int(logits: np.ndarray) -> np.ndarray:
@@ -69,25 +76,53 @@ def ctx_from(probs: np.ndarray, V: np.ndarray, H: int, mc) -> np.ndarray:
     return requant(acc, mc).transpose(0, 2, 1, 3).reshape(B, S, P)
 
 
-def mha(x: np.ndarray, t: Dict[str, np.ndarray], H: int = 1, i: int = 0):
+def mha(x: np.ndarray, t: Dict[str, np.ndarray], H: int = 1, i: int = 0, taps: bool = False, rq=None):
     """x: (B, S, E) float32 block input, or int8 codes x_q; t: the blob-name keyed tensors of params.attention_tensors.
     Returns (out (B, S, E) float32, taps): x_q, Q, K, V, ctx, out_q int8; logits int8 and probs uint8, both
-    (B, H, S, S), or (B, S, S) at H = 1 as the engine returns them."""
+    (B, H, S, S), or (B, S, S) at H = 1 as the engine returns them.  With taps=True a third value: the int32
+    accumulators (bias included) of the six requantisation sites, keyed Q, K, V, O (B, S, .) and L (B, H, S, S),
+    C (B, H, S, P / H).  rq: a test's stand-in rq(site, acc, mult) -> int8 codes for requant at every site (the block
+    itself is rq=None)."""
     g = lambda k: t[f"attn{i}.{k}"]
     sc = np.asarray(g("scal"), np.float32)
     P = g("wq").shape[0]
     if H < 1 or P % H:
         raise ValueError(f"H = {H} does not divide P = {P}")
+    rq = rq or (lambda site, acc, m: requant(acc, m))
     x = np.asarray(x)
     x_q = x if x.dtype == np.int8 else quantize(x, sc[INV_SX])
-    Q = linear_q(x_q, g("wq"), g("bq"), sc[MQ])
-    K = linear_q(x_q, g("wk"), g("bk"), sc[MK])
-    V = linear_q(x_q, g("wv"), g("bv"), sc[MV])
-    logits, _ = logits_from(Q, K, H, sc[ML])
+    acc = {k: linear_acc(x_q, g("w" + k.lower()), g("b" + k.lower())) for k in ("Q", "K", "V")}
+    Q, K, V = rq("Q", acc["Q"], sc[MQ]), rq("K", acc["K"], sc[MK]), rq("V", acc["V"], sc[MV])
+    acc["L"] = split_heads(Q, H).astype(np.int32) @ split_heads(K, H).astype(np.int32).transpose(0, 1, 3, 2)
+    logits = rq("L", acc["L"], sc[ML])
     probs = softmax_int(logits)
-    ctx = ctx_from(probs, V, H, sc[MC])
-    out_q = linear_q(ctx, g("wo"), g("bo"), sc[MO])
+    B, S, _ = V.shape
+    acc["C"] = probs.astype(np.int32) @ split_heads(V, H).astype(np.int32)
+    ctx = rq("C", acc["C"], sc[MC]).transpose(0, 2, 1, 3).reshape(B, S, P)
+    acc["O"] = linear_acc(ctx, g("wo"), g("bo"))
+    out_q = rq("O", acc["O"], sc[MO])
     out = out_q.astype(np.float32) * sc[SO]
     if H == 1:
         logits, probs = logits[:, 0], probs[:, 0]
-    return out, dict(x_q=x_q, Q=Q, K=K, V=V, logits=logits, probs=probs, ctx=ctx, out_q=out_q)
+    tp = dict(x_q=x_q, Q=Q, K=K, V=V, logits=logits, probs=probs, ctx=ctx, out_q=out_q)
+    return (out, tp, acc) if taps else (out, tp)
+
+
+F_INV_SX, M1, M2, S2 = range(4)   # indices of ffn{i}.scal
+
+
+def ffn(x: np.ndarray, t: Dict[str, np.ndarray], i: int = 0, taps: bool = False, rq=None):
+    """ITAFeedForward_QAT: quantise, fc1 + ReLU, fc2, dequantise.  x: (B, S, E) float32 -> (out (B, S, E) float32, taps:
+    x_q, h (after the ReLU), out_q int8).  With taps=True a third value: the int32 accumulators fc1 (B, S, F) and fc2
+    (B, S, E).  rq: as in mha, with the site names fc1 and fc2."""
+    g = lambda k: t[f"ffn{i}.{k}"]
+    sc = np.asarray(g("scal"), np.float32)
+    rq = rq or (lambda site, acc, m: requant(acc, m))
+    x_q = quantize(x, sc[F_INV_SX])
+    acc = {"fc1": linear_acc(x_q, g("w1"), g("b1"))}
+    h = np.maximum(rq("fc1", acc["fc1"], sc[M1]), 0).astype(np.int8)
+    acc["fc2"] = linear_acc(h, g("w2"), g("b2"))
+    out_q = rq("fc2", acc["fc2"], sc[M2])
+    out = out_q.astype(np.float32) * sc[S2]
+    tp = dict(x_q=x_q, h=h, out_q=out_q)
+    return (out, tp, acc) if taps else (out, tp)

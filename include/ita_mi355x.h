@@ -377,6 +377,20 @@ int ita_debug_encoder_stamps(ita_handle h, int layer, const float* x_dev, const 
  * probabilities (rows,128), both device pointers.  Needs no weights. */
 int ita_debug_softmax_rows(ita_handle h, const int8_t* logits_dev, uint8_t* probs_dev, int rows, void* stream);
 
+/* Diagnostic / test entries: which requantisation form a layer runs (read-only).
+ * ita_debug_fast_site_ok: host only, no handle: 1 when ita_load_weights' proof admits the single-rounding form for a
+ * site with this multiplier (no accumulator value rounds differently once and twice after the clamp), else 0 --
+ * also for a multiplier outside (0, 1) or below 130 / 4e6.
+ * ita_debug_layer_forms: fast_sites = the ITA_SITE_* mask (bit 0..5: Q, K, V, logits, context, out_proj) of the sites
+ * that passed; a stream kernel runs the single-rounding instantiation only when all six did (mask 63).  It is 0 for a
+ * layer without stream images.  stream_images = ITA_FORMS_* bits: the attention image (ita_mha_int8 without taps,
+ * ita_mha_q8, the long-sequence entries), the whole-layer image (ita_encoder_layer; needs an int8 FFN and both
+ * LayerNorms in the blob), the whole-layer image with the tokenizer in front.  Without the attention image the layer
+ * runs on the block kernels (stream_range_ok refused it, or H > 1). */
+enum { ITA_FORMS_ATTN_IMAGE = 1, ITA_FORMS_LAYER_IMAGE = 2, ITA_FORMS_TOK_IMAGE = 4 };
+int ita_debug_fast_site_ok(float mult);
+int ita_debug_layer_forms(ita_handle h, int layer, unsigned* fast_sites, int* stream_images);
+
 /* ---- wire format of the reference's UDP host (ita_wire.h), exported for bindings and tests ------- */
 /* frame_out: [desired_velocity, position_x, quat w, x, y, z]; returns 0, or -1 on a short packet */
 int ita_wire_unpack_packet(const uint8_t* packet, size_t nbytes, int quat_stride_bug, float* frame_out);

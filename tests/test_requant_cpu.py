@@ -1,0 +1,185 @@
+"""The requantisation step on the CPU: the load-time single-rounding proof (ita_debug_fast_site_ok) against the
+exact-arithmetic definition (requant_common.single_vs_double); the numpy definitions with accumulator taps against the
+pinned C oracle; and the crafted cases of tests/test_gpu_requant_edges.py: the accumulators they are about do occur,
+and a site that rounded once would change the block's output exactly where the multiplier is refused."""
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+import requant_common as rc
+from conftest import golden_files
+from drone_oa_iree_vit_accelerator_amd import host, mha_heads_ref as ref, params
+
+f32 = np.float32
+FIX_H1 = golden_files("blocks_E64_*.npz") + golden_files("blocks_E128_*.npz") + golden_files("vitlstm_E64_seed0_*.npz")
+
+
+def _fixture_multipliers():
+    """every attn*.scal[1..6] and ffn*.scal[1..2] of every fixture that holds int8 blocks"""
+    out = {}
+    for path in golden_files("*.npz"):
+        d = params.load_fixture(path)
+        for l in range(16):
+            if f"attn{l}.q_proj.w_q" in d:
+                for j, m in enumerate(params.attention_tensors(d, f"attn{l}.", l)[f"attn{l}.scal"][1:7]):
+                    out[f"{path.rsplit('/', 1)[-1][:-4]}.attn{l}.{rc.ATTN_SITES[j]}"] = f32(m)
+            if f"ffn{l}.fc1.w_q" in d:
+                for j, m in enumerate(params.ffn_tensors(d, f"ffn{l}.", l)[f"ffn{l}.scal"][1:3]):
+                    out[f"{path.rsplit('/', 1)[-1][:-4]}.ffn{l}.{rc.FFN_SITES[j]}"] = f32(m)
+    return out
+
+
+def test_fl32_is_float32_rounding():
+    """the exact-arithmetic rounding the definition rests on, against numpy's float32 product"""
+    rs = np.random.RandomState(1)
+    for _ in range(300):
+        a, m = int(rs.randint(-(1 << 23), 1 << 23)), f32(2.0 ** rs.uniform(-15, 0))
+        assert rc.fl32(Fraction(a) * Fraction(float(m))) == Fraction(float(f32(a) * m)), (a, m)
+    assert rc.fl32(Fraction(1, 3)) == Fraction(float(f32(1.0) / f32(3.0)))
+    assert rc.fl32(Fraction((1 << 24) + 1)) == 1 << 24 and rc.fl32(Fraction((1 << 24) + 3)) == (1 << 24) + 4   # ties to even
+
+
+def test_fast_site_ok_equals_the_exact_definition():
+    fx = _fixture_multipliers()
+    assert len(fx) >= 100
+    rs = np.random.RandomState(0)
+    sweep = [f32(3e-5 * (1.0 / 3e-5) ** u) for u in rs.uniform(0.0, 1.0, 220)]
+    sweep = [m for m in sweep if 3.3e-5 <= m < 1]
+    for e in range(1, 15):                            # exact powers of two and their float32 neighbours
+        p = f32(2.0 ** -e)
+        sweep += [p, np.nextafter(p, f32(0)), np.nextafter(p, f32(1))]
+    for m0 in (1.4e-3, 2.3e-3, 4e-3):                 # the fixtures' neighbourhoods, found refused and admitted alike
+        ok, bad = rc.find_multipliers(m0, 6, 6, 3)
+        sweep += [m for m, _ in ok + bad]
+    sweep += list(fx.values())
+    sweep = sorted({int(f32(m).view(np.uint32)) for m in sweep})
+    assert len(sweep) >= 300
+    n_refused = 0
+    for bits in sweep:
+        m = np.uint32(bits).view(np.float32)
+        diff = rc.single_vs_double(m)
+        assert host.fast_site_ok(m) == (diff == []), (m, diff)
+        n_refused += bool(diff)
+    # the fixtures' own refusals (the examples the suite's fixtures are known to hold)
+    for name in ("blocks_E128_seed0_B1.attn0.O", "blocks_E128_seed1_B1.attn0.Q", "blocks_E64_seed2_B1.ffn0.fc2",
+                 "vitlstm_E64_seed0_B2.ffn0.fc1"):
+        assert not host.fast_site_ok(fx[name]) and len(rc.single_vs_double(fx[name])) in (1, 2), name
+    print(f"{len(sweep)} multipliers, {n_refused} refused ({len(fx)} of the fixtures)")
+    assert 0.05 * len(sweep) < n_refused < 0.5 * len(sweep)
+    # outside (0, 1), and below 130 / 4e6 (the enumeration would leave the biased-float accumulator range): refused
+    for m in (0.0, -0.001, -1.0, 1.0, np.nextafter(f32(1), f32(2)), 1.5, 256.0, float("nan"), float("inf"), 3.2e-5, 1e-6, 1e-30):
+        assert host.fast_site_ok(m) is False, m
+    assert host.fast_site_ok(np.nextafter(f32(1), f32(0))) == (rc.single_vs_double(np.nextafter(f32(1), f32(0))) == [])
+
+
+@pytest.mark.parametrize("path", FIX_H1, ids=lambda p: p.rsplit("/", 1)[-1][:-4])
+def test_definitions_with_accumulators_equal_the_oracle(oracle, path):
+    d = params.load_fixture(path)
+    t = {**params.attention_tensors(d, "attn0.", 0), **params.ffn_tensors(d, "ffn0.", 0)}
+    x = d["s0.attn0.x_q.in"]
+    want, wt = oracle.mha(x, t, taps=True)
+    got, gt, acc = ref.mha(x, t, H=1, taps=True)
+    assert set(gt) == set(wt) and set(acc) == set(rc.ATTN_SITES)
+    for k in wt:
+        np.testing.assert_array_equal(gt[k], wt[k], err_msg=k)
+    np.testing.assert_array_equal(got, want)
+    sc = t["attn0.scal"]
+    for site, tap in (("Q", "Q"), ("K", "K"), ("V", "V"), ("O", "out_q")):
+        assert acc[site].dtype == np.int32
+        np.testing.assert_array_equal(ref.requant(acc[site], rc.multiplier_of(t, site)), wt[tap], err_msg=site)
+    np.testing.assert_array_equal(ref.requant(acc["L"], sc[ref.ML])[:, 0], wt["logits"])
+    np.testing.assert_array_equal(ref.requant(acc["C"], sc[ref.MC])[:, 0], wt["ctx"])
+    xf = d["s0.ffn0.x_q.in"]
+    fwant, fwt = oracle.ffn(xf, t, taps=True)
+    fgot, fgt, facc = ref.ffn(xf, t, taps=True)
+    assert set(fgt) == set(fwt) and set(facc) == set(rc.FFN_SITES)
+    for k in fwt:
+        assert fgt[k].dtype == fwt[k].dtype and fgt[k].shape == fwt[k].shape, k
+        np.testing.assert_array_equal(fgt[k], fwt[k], err_msg=k)
+    np.testing.assert_array_equal(fgot, fwant)
+    np.testing.assert_array_equal(np.maximum(ref.requant(facc["fc1"], t["ffn0.scal"][ref.M1]), 0), fwt["h"])
+    np.testing.assert_array_equal(ref.requant(facc["fc2"], t["ffn0.scal"][ref.M2]), fwt["out_q"])
+    # the two-value form is what it was
+    out2, tp2 = ref.mha(x, t, H=1)
+    np.testing.assert_array_equal(out2, want)
+    assert set(tp2) == set(wt)
+
+
+@pytest.mark.parametrize("E,site,j", rc.rounding_ids(), ids=lambda v: str(v))
+def test_rounding_cases_hold_their_accumulators(E, site, j):
+    """every wanted accumulator occurs at the site, on the routes where the construction controls it; rounding that site
+    once changes the block output for a refused multiplier and nothing for an admitted one"""
+    c = rc.rounding_case(E, site, j)
+    exp = c.expect()
+    assert (c.diff != ()) == (c.kind == "refused")
+    assert rc.single_vs_double(c.m) == list(c.diff)
+    for a in c.diff:
+        assert a in c.want and a - 1 in c.want and a + 1 in c.want
+    assert set(rc.tie_neighbours(c.m)) <= set(c.want)
+    if c.kind == "pow2":
+        fm = Fraction(float(c.m))
+        assert all((Fraction(a) * fm).denominator == 2 for a in c.want) and len(c.want) >= 8      # true ties, each of them
+    routes = ["mha"] + (["long"] if site in ("Q", "K", "V", "C", "O") else []) + (["ffn_x1"] if site in rc.FFN_SITES else [])
+    for route in routes:
+        n = c.present(rc.site_accumulators(c, exp, route))
+        print(f"{c.name} m = {c.m!r} {route}: {n} of {len(c.want)} wanted accumulators present")
+        assert n == len(c.want), route
+    if site == "L":      # the long form: the band of the first wanted accumulator, a differing one where there is one
+        assert c.want[0] in exp["long"][2]["L"] and c.present(exp["long"][2]["L"]) >= 3
+    once = rc.once_at(site)
+    if site in rc.ATTN_SITES:
+        changed = int((ref.mha(c.x, c.t, c.H, rq=once)[0] != exp["mha"][0]).sum())
+        changed_long = int((ref.mha(exp["x_long"], c.t, c.H, rq=once)[0] != exp["long"][0]).sum())
+        assert c.kind != "refused" or changed_long > 0
+        assert c.kind == "refused" or changed_long == 0
+    else:
+        changed = int((ref.ffn(c.x, c.t, rq=once)[0] != exp["ffn"][0]).sum())
+    print(f"{c.name}: rounding once changes {changed} outputs")
+    assert (changed > 0) == (c.kind == "refused")
+    out = exp["mha"][0].reshape(-1, E)
+    assert len(np.unique(out, axis=0)) > 64                # the crafted rows are not the only content
+
+
+@pytest.mark.parametrize("E,site,kind", rc.range_ids(), ids=lambda v: str(v))
+def test_range_cases_reach_the_edge(E, site, kind):
+    """the row sums lie where the case says, on both sides of stream_range_ok's two bounds, and the accumulators reach
+    the extreme of both signs; saturated results are +127 / -128"""
+    c = rc.range_case(E, site, kind)
+    exp = c.expect()
+    acc = rc.site_accumulators(c, exp)
+    assert c.present(acc) == 2 and int(acc.max()) == c.want[0] and int(acc.min()) == c.want[1]
+    if site in rc.FFN_SITES:      # ... and inside the encoder layer, the one route to the stream kernel's fc1 / fc2 forms
+        ax1 = exp["ffn_x1"][2][site]
+        assert c.present(ax1) == 2 and int(ax1.max()) == c.want[0] and int(ax1.min()) == c.want[1]
+    print(f"{c.name}: accumulators in [{acc.min()}, {acc.max()}], m = {c.m!r}")
+    if site == "L":
+        worst = Fraction(rc.L_WORST) * Fraction(float(c.m))
+        assert (worst < 32000) == rc.range_inside(c)
+        lg = exp["mha"][1]["logits"][1]
+        assert set(np.unique(lg)) == {-128, 127}
+        return
+    wn, bn = rc.LINEAR[site]
+    row = np.abs(c.t[wn].astype(np.int64)).sum(1) * 128 + np.abs(c.t[bn].astype(np.int64))
+    m = Fraction(float(c.m))
+    inside = bool((row < rc.ACC_BOUND).all() and all(Fraction(int(r)) * m < 32000 for r in row))
+    assert inside == rc.range_inside(c)
+    if kind.startswith("acc"):
+        assert int(row.max()) == (rc.ACC_BOUND - 1 if kind == "acc_in" else rc.ACC_BOUND)
+    if kind.startswith("travel"):
+        assert sorted(row)[-2:] == [rc.TRAVEL_SUM, rc.TRAVEL_SUM]
+        assert (Fraction(rc.TRAVEL_SUM) * m == 32000) == (kind == "travel_out") and Fraction(rc.TRAVEL_SUM) * m > 31999
+    tap = {"Q": "Q", "K": "K", "V": "V", "O": "out_q"}.get(site)
+    codes = exp["mha"][1][tap] if tap else exp["ffn"][1]["h" if site == "fc1" else "out_q"]
+    r1, r2 = 5, codes.shape[-1] - 3
+    hi, lo = codes[..., r1][acc[..., r1] == c.want[0]], codes[..., r2][acc[..., r2] == c.want[1]]
+    assert len(hi) and len(lo) and (hi == 127).all() and (lo == (0 if site == "fc1" else -128)).all()
+
+
+@pytest.mark.parametrize("E,site", [(64, "L"), (64, "O"), (128, "Q")], ids=lambda v: str(v))
+def test_two_head_cases_hold_their_accumulators(E, site):
+    """the same constructions under a header H = 2: the crafted channels lie in head 0"""
+    c = rc.rounding_case(E, site, 0, H=2)
+    acc = c.expect()["mha"][2][site]
+    assert c.diff and c.present(acc[:, 0] if site == "L" else acc) == len(c.want)
+    assert (ref.mha(c.x, c.t, 2, rq=rc.once_at(site))[0] != c.expect()["mha"][0]).any()
