@@ -29,6 +29,7 @@
 #include "ita_long_attn_kernel.h"
 #include "ita_ffn_f32_kernel.h"
 #include "ita_attn_f32_kernel.h"
+#include "ita_long_f32_kernel.h"
 #include "ita_ingest_kernel.h"
 #include "ita_ingest_wire_kernel.h"
 #include "ita_tokenizer_long_kernel.h"
@@ -929,6 +930,66 @@ int ita_encoder_layer_long(ita_handle h, int layer, const float* x, float* y, in
   if (!L.n1w || !L.n2w) return fail(ITA_ERR_BAD_BLOB, "LayerNorm parameters missing from the blob");
   if (int rc = launch_long(h, layer, nullptr, nullptr, x, y, true, batch, seq_len, (hipStream_t)stream)) return rc;
   return launch_ffn(h, layer, y, y, batch * (seq_len / 128), true, nullptr, (hipStream_t)stream);
+}
+
+namespace {
+
+// The float32 long attention (ita_long_f32_kernel.h) of an ITAW0003 layer: the refusals, the workspace (the int8 long
+// path's buffer, grown the same way: K and V fragment images, 192 KB per 128-token tile), the two launches.
+int launch_long_f32(ita_context* h, int layer, const float* x, float* y, bool fuse_ln, int batch, int seq_len, hipStream_t s) {
+  const Layer& L = h->w.layers[layer];
+  if (!L.attn_f32)
+    return fail(ITA_ERR_UNSUPPORTED, "this layer's attention is int8 (ITAW0001 / ITAW0002 blob): ita_mha_long_int8 runs it");
+  if (seq_len < 128 || seq_len % 128 || seq_len > 65536 || batch > 65535)
+    return fail(ITA_ERR_UNSUPPORTED, "seq_len must be a multiple of 128 in [128, 65536], batch <= 65535");
+  if (fuse_ln && !L.n1w) return fail(ITA_ERR_BAD_BLOB, "norm1 parameters missing from the blob");
+  const size_t ntile = (size_t)batch * (seq_len / 128);
+  const size_t img = ntile * 2 * ItaLongF32Lds::UNIT, need = 2 * img;
+  if (need > h->long_ws_bytes) {
+    if (capturing(s))
+      return fail(ITA_ERR_INVALID_ARG, "the long-attention workspace cannot grow inside a stream capture; run one call first");
+    HIPCHK(hipDeviceSynchronize());
+    h->long_ws_bytes = 0;
+    HIPCHK(h->long_ws.alloc(need));
+    h->long_ws_bytes = need;
+  }
+  ItaLongF32Args a{};
+  a.x = x; a.y = y;
+  a.wq = L.wqf; a.wk = L.wkf; a.wv = L.wvf; a.bq = L.bqf; a.bk = L.bkf; a.bv = L.bvf; a.wo = L.wof; a.bo = L.bof;
+  a.ln_w = L.n1w; a.ln_b = L.n1b;
+  a.kimg = (f32x4*)(char*)h->long_ws; a.vimg = (f32x4*)((char*)h->long_ws + img);
+  a.B = batch; a.S = seq_len; a.fuse_ln = fuse_ln ? 1 : 0;
+  const size_t cap = 2 * (size_t)h->num_cus;
+  const dim3 proj_grid((unsigned)(ntile < cap ? ntile : cap)), attn_grid(seq_len / 128, batch);
+  return with_E(h->w.hdr.E, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    if (int rc = launch<ita_lf32_proj_kernel<E>>(proj_grid, dim3(512), s, a)) return rc;
+    return launch<ita_lf32_attn_kernel<E>, ItaLongF32Lds::TOTAL>(attn_grid, dim3(512), s, a);
+  });
+}
+
+}  // namespace
+
+int ita_mha_long_f32(ita_handle h, int layer, const float* x, float* y, int batch, int seq_len, void* stream) {
+  if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
+  return launch_long_f32(h, layer, x, y, false, batch, seq_len, (hipStream_t)stream);
+}
+
+// The long form of launch_encoder's float-FFN branch: x1 = LN1(x + attn(x)) into y by the float long launches (ITAW0003)
+// or the int8 long launches (ITAW0002), then the float FFN block + residual + LN2 in place on y, whose kernel reads a
+// 32-row tile (and prefetches its own next one) before it stores that tile and touches no other workgroup's rows
+int ita_encoder_layer_long_f32(ita_handle h, int layer, const float* x, float* y, int batch, int seq_len, void* stream) {
+  if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
+  const Layer& L = h->w.layers[layer];
+  // (everything that can refuse is checked before the first launch: no partial work is left behind an error)
+  if (!L.ffn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's FFN is int8 (ITAW0001 blob): ita_encoder_layer_long runs it");
+  if (h->w.hdr.E != 64 && !L.w1p) return fail(ITA_ERR_UNSUPPORTED, "the float32 FFN of an ITAW0002 blob is built for E = 64");
+  if (!L.attn_f32)
+    if (int rc = check_long(L, batch, seq_len)) return rc;
+  if (!L.n1w || !L.n2w) return fail(ITA_ERR_BAD_BLOB, "LayerNorm parameters missing from the blob");
+  if (int rc = L.attn_f32 ? launch_long_f32(h, layer, x, y, true, batch, seq_len, (hipStream_t)stream)
+                          : launch_long(h, layer, nullptr, nullptr, x, y, true, batch, seq_len, (hipStream_t)stream)) return rc;
+  return launch_ffn_f32(h, layer, y, y, batch * (seq_len / 128), true, (hipStream_t)stream);
 }
 
 int ita_mha_q8(ita_handle h, int layer, const int8_t* x_q, int8_t* out_q, int batch, void* stream) {

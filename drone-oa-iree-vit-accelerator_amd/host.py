@@ -35,7 +35,7 @@ HEAD_TIMEOUT = 1
 EXPORTED_SYMBOLS = (
     "ita_abi_version", "ita_create", "ita_destroy", "ita_load_weights", "ita_validate_blob", "ita_reserve", "ita_get_dims",
     "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_mha_long_int8", "ita_encoder_layer_long", "ita_ffn_int8", "ita_ffn_int8_taps",
-    "ita_ffn_f32", "ita_get_ffn_kind", "ita_mha_f32", "ita_get_attn_kind",
+    "ita_ffn_f32", "ita_get_ffn_kind", "ita_mha_f32", "ita_get_attn_kind", "ita_mha_long_f32", "ita_encoder_layer_long_f32",
     "ita_encoder_layer", "ita_tokenizer", "ita_fusion_tail", "ita_vitlstm_forward", "ita_bind_dispatch",
     "ita_profile_begin", "ita_profile_begin_sampled", "ita_profile_end", "ita_set_tail_mode", "ita_debug_encoder_stamps",
     "ita_fusion_tail_load", "ita_fusion_tail_large",
@@ -142,6 +142,8 @@ def lib():
         L.ita_mha_long_q8.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_int8.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_encoder_layer_long.argtypes = [vp, i, vp, vp, i, i, vp]
+        L.ita_mha_long_f32.argtypes = [vp, i, vp, vp, i, i, vp]
+        L.ita_encoder_layer_long_f32.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_vitlstm_tail.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
         L.ita_debug_softmax_rows.argtypes = [vp, vp, vp, i, vp]
         L.ita_debug_fast_site_ok.argtypes = [C.c_float]
@@ -683,6 +685,45 @@ class Engine:
         y = self.tokenize_long(frames, tok_h, tok_w, depth_scale)
         for layer in range(self.num_layers):
             self.encoder_layer_long(y, layer, out=y)
+        return y
+
+    def mha_long_f32(self, x, layer: int = 0):
+        """float32 attention block over a long sequence: x (B,S,E) f32, S a multiple of 128 -> attn(x) (B,S,E) f32
+        (ita_mha_long_f32: the long form of mha_f32, for a float-attention layer)"""
+        torch = _torch()
+        x = self._long_f32(x)
+        y = torch.empty_like(x)
+        _chk(lib().ita_mha_long_f32(self._h, layer, x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1],
+                                    _stream_ptr(self.device)))
+        return y
+
+    def encoder_layer_long_f32(self, x, layer: int = 0, out=None):
+        """one encoder layer with a float FFN (ITAW0002 / ITAW0003 blob) over a long sequence: x (B,S,E) f32 ->
+        LN2(x1 + ffn(x1)), x1 = LN1(x + attn(x)) (ita_encoder_layer_long_f32); out: optional contiguous f32 GPU tensor of
+        x's shape, may be x itself"""
+        torch = _torch()
+        x = self._long_f32(x)
+        if out is None:
+            out = torch.empty_like(x)
+        elif not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.shape != x.shape:
+            raise ITAError(f"out must be a contiguous f32 GPU tensor of shape {tuple(x.shape)}")
+        _chk(lib().ita_encoder_layer_long_f32(self._h, layer, x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1],
+                                              _stream_ptr(self.device)))
+        return out
+
+    def encode_long_f32(self, x):
+        """all num_layers float-FFN encoder layers in order over a long sequence: (B,S,E) f32 -> (B,S,E) f32"""
+        y = self.encoder_layer_long_f32(x, 0)
+        for layer in range(1, self.num_layers):
+            self.encoder_layer_long_f32(y, layer, out=y)
+        return y
+
+    def encode_frames_long_f32(self, frames, tok_h: int, tok_w: int, depth_scale: Optional[float] = None):
+        """camera frames -> tokens -> every float-FFN encoder layer: tokenize_long, then all num_layers of
+        encoder_layer_long_f32 in place on the token buffer; (..., H, W) -> (N, tok_h * tok_w, E) f32"""
+        y = self.tokenize_long(frames, tok_h, tok_w, depth_scale)
+        for layer in range(self.num_layers):
+            self.encoder_layer_long_f32(y, layer, out=y)
         return y
 
     def softmax_rows(self, logits):

@@ -53,7 +53,8 @@ int ita_destroy(ita_handle h);
  * A layer with H > 1 runs on the block kernels (ita_mha_kernel<E, H>, then the FFN block) behind the stand-alone tokenizer;
  * every entry point below serves it except those that need the one-head stream kernel, which return
  * ITA_ERR_UNSUPPORTED before any launch: ita_mha_q8, ita_mha_long_q8, ita_mha_long_int8, ita_encoder_layer_long,
- * ita_debug_encoder_stamps, ita_vitlstm_forward_slots.
+ * ita_debug_encoder_stamps, ita_vitlstm_forward_slots (and ita_mha_long_f32 / ita_encoder_layer_long_f32, which take
+ * float layers only).
  * The reference pre-loads weights into the accelerator out of band
  * (docs/HOW-TO-run-the-full-project-workflow.md:55); this is that step. */
 int ita_load_weights(ita_handle h, const void* blob, size_t nbytes);
@@ -114,7 +115,7 @@ int ita_mha_long_int8(ita_handle h, int layer, const float* x_dev, float* y_dev,
 /* The long form of ita_encoder_layer: y = LN2(x1 + ffn(x1)), x1 = LN1(x + attn(x)) on (B, seq_len, E) f32 rows; x_dev may
  * equal y_dev.  Attention + residual + LN1 are the two long launches (x1 goes to y), the FFN + residual + LN2 then run in
  * place on y, 128 rows per block (ita_ffn_int8's kernel: the FFN is per token).  Shape limits, workspace and refusals of
- * ita_mha_long_q8; in addition a float-FFN layer (ITAW0002 blob) is ITA_ERR_UNSUPPORTED and a blob without the layer's
+ * ita_mha_long_q8; in addition a float-FFN layer (ITAW0002 blob: ita_encoder_layer_long_f32 runs it) is ITA_ERR_UNSUPPORTED and a blob without the layer's
  * norm parameters ITA_ERR_BAD_BLOB -- all before any launch. */
 int ita_encoder_layer_long(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_len, void* stream);
 
@@ -137,7 +138,8 @@ int ita_ffn_f32(ita_handle h, int layer, const float* x_dev, float* y_dev, int b
  * blob: the float graph, models/ITA_single_layer_upsample_shuffle/model.py, nothing quantised).  ita_mha_int8 / _taps,
  * ita_mha_q8, ita_mha_long_q8, ita_mha_long_int8, ita_encoder_layer_long, ita_debug_encoder_stamps and the drop-in
  * ITASelfAttention_workgroup on an F32 layer, and
- * ita_mha_f32 on an INT8 layer, fail with ITA_ERR_UNSUPPORTED. */
+ * ita_mha_f32 / ita_mha_long_f32 on an INT8 layer, fail with ITA_ERR_UNSUPPORTED; each message names the sibling entry
+ * (ita_mha_long_int8 <-> ita_mha_long_f32, ita_encoder_layer_long <-> ita_encoder_layer_long_f32). */
 enum { ITA_ATTN_INT8 = 0, ITA_ATTN_F32 = 1 };
 int ita_get_attn_kind(ita_handle h, int layer, int* kind);
 /* the float32 attention block of layer `layer` alone (no residual, no LayerNorm), ITASelfAttention.forward
@@ -145,6 +147,21 @@ int ita_get_attn_kind(ita_handle h, int layer, int* kind);
  * (B,128,E) f32, E = 64 or 128 (the E = 128 float graph, models/ITA_upsample_shuffle/model.py, has no fusion tail).  A
  * frame's result does not depend on the batch it runs in. */
 int ita_mha_f32(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, void* stream);
+/* The long form of ita_mha_f32: x, y (B, seq_len, E) f32, y = attn(x) over rows of seq_len keys, for a float-attention
+ * layer (ITAW0003 blob).  seq_len a multiple of 128 in [128, 65536], batch <= 65535, E = 64 or 128; anything else, and an
+ * int8-attention layer (ITAW0001 / ITAW0002 blob: ita_mha_long_int8 runs it), is ITA_ERR_UNSUPPORTED before any launch.
+ * One sweep over the key tiles with a running row maximum and sum (exp-softmax is associative); the logits are never
+ * materialised.  Its K / V workspace (2 x 768 bytes per token, shared with ita_mha_long_q8's) belongs to the handle and
+ * grows on demand (not inside a stream capture: ITA_ERR_INVALID_ARG).  A frame's result does not depend on the batch it
+ * runs in; x_dev may equal y_dev. */
+int ita_mha_long_f32(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_len, void* stream);
+/* The long form of ita_encoder_layer for a layer with a float FFN: y = LN2(x1 + ffn(x1)), x1 = LN1(x + attn(x)) on
+ * (B, seq_len, E) f32 rows; x_dev may equal y_dev.  Attention + residual + LN1 are the two launches of ita_mha_long_f32
+ * (ITAW0003 blob) or of ita_mha_long_int8 (ITAW0002 blob, with that entry's refusals); the float FFN + residual + LN2
+ * then run in place on y (ita_ffn_f32's kernel: the FFN is per token).  Shape limits and workspace as above; an int8-FFN
+ * layer (ITAW0001 blob: ita_encoder_layer_long runs it) is ITA_ERR_UNSUPPORTED and a blob without the layer's norm
+ * parameters ITA_ERR_BAD_BLOB -- all before any launch. */
+int ita_encoder_layer_long_f32(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_len, void* stream);
 /* One encoder layer as the model wires it (QAT/model.py:100-113):
  * y = LN2(x1 + ffn(x1)),  x1 = LN1(x + mha(x)).  x_dev and y_dev may alias.
  * A float-FFN layer (ITA_FFN_F32) runs ffn, the residual and LN2 in float32 (QAT_only_attn/model.py:76-88); a
