@@ -16,6 +16,9 @@
 // exact f32 tail + decoder kernels) and the whole tail becomes  dec = x2 . Wfold^T + bias'.
 //
 //   ita_gemm_f16x3_kernel<BM,BN>   C_partial[z][m][n] = sum_{k in slice z} A[m][k] W[n][k]
+// on v_mfma_f32_16x16x32_f16 with the weights as the A operand: a lane then holds four consecutive n of one frame m, one
+// 16-byte piece of the partials (and of what the LSTM head reads as f32x4), and the chip holds a higher clock under this
+// MFMA shape than under 32x32x16 (tools/microbench/mfma_rate.hip).
 // The LSTM head that consumes the partials (layers 0, 1, 2 and the fc in one launch) is ita_lstm_head_kernel.h.
 #pragma once
 #include <type_traits>
@@ -44,12 +47,13 @@ struct ItaGemmSplitArgs {
   int M, N, K;                            // K % (64 * nsplit) == 0, N % BN == 0
   int nsplit;
   int dbg;                                // diagnostic: 1 = stage only (no MFMA), 2 = MFMA only (stage once), 4 no barrier, 8 one buffer, 16/32/64 L2-resident staging
-  const _Float16 *wf_hi, *wf_lo;          // the same weights as MFMA A... B fragments, [N / 32][K / 16][lane 64][8] (tiny kernel only)
+  const _Float16 *wf_hi, *wf_lo;          // the same weights as MFMA A fragments, [N / 16][K / 32][lane 64][8] (tiny kernel only)
 };
 
 // LDS image of one operand plane for one 64-deep K tile: row-major 128-byte rows, the eight
-// 16-byte chunks of a row XOR-swizzled with (row>>1)&7 so that the 32x32x16 fragment reads
-// (lane -> row, fixed chunk) are bank-conflict free.  Tiles are filled by LDS-DMA
+// 16-byte chunks of a row XOR-swizzled with (row>>1)&7 so that the 16x16x32 fragment reads (ds_read_b128: lane l -> row l & 15,
+// chunk 4 ks + (l >> 4)) are bank-conflict free: each of the instruction's four 16-lane groups -- e.g. lanes 0-3, 12-15 at one
+// chunk and 20-27, rows 4-11, at its neighbour -- covers the sixteen 16-byte slots of a 256-byte bank row once.  Tiles are filled by LDS-DMA
 // (global_load_lds_dwordx4): LDS destination lane-linear, swizzle applied to the SOURCE chunk.
 template <int ROWS, int NT>
 __device__ __forceinline__ void stage_plane(const _Float16* __restrict__ g, int ld, int row0, int max_row, int k0,
@@ -79,13 +83,28 @@ struct ItaGemmSplitLds {
   static constexpr int TOTAL = 2 * BUF;
 };
 
-// WM x WN waves; each wave owns a (BM/WM) x (BN/WN) block of 32x32 MFMA tiles.  Two waves per SIMD
+// The per-element arithmetic of all three GEMM kernels below: k-steps of 32 in ascending order inside a K slice; in each step the
+// products lo_x.hi_w, hi_x.lo_w, hi_x.hi_w, in that order, each one v_mfma_f32_16x16x32_f16 with A = weights, B = activations
+// (lane l: A row n = l & 15, B column m = l & 15, both k = 8 (l >> 4) .. + 7), accumulated in f32.
+__device__ __forceinline__ void gemm_mfma_f16x3(f32x4& acc, f16x8 wh, f16x8 wl, f16x8 xh, f16x8 xl) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh, acc, 0, 0, 0);
+}
+// C layout with the weights as A: row n = 4 (l >> 4) + e, column m = l & 15 -- a lane's accumulator is out[m][n .. n + 3], one
+// 16-byte piece.  `rows` = the partial rows of the workgroup's K slice from its first frame on; m, n relative to that.
+template <bool WRITE_THROUGH>
+__device__ __forceinline__ void store_partial(__amdgpu_buffer_rsrc_t rows, int m, int n, int N, f32x4 v) {
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rows, (m * N + n) * 4, 0, WRITE_THROUGH ? ITA_SC1 : 0);
+}
+
+// WM x WN waves; each wave owns a (BM/WM) x (BN/WN) block of 16x16 MFMA tiles.  Two waves per SIMD
 // (WM*WN = 8) let one wave's MFMAs run while its partner waits for the LDS-DMA of the next K tile.
 template <int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(64 * WM * WN) void ita_gemm_f16x3_kernel(const ItaGemmSplitArgs g) {
   using L = ItaGemmSplitLds<BM, BN>;
   constexpr int NT = 64 * WM * WN;
-  constexpr int TM = BM / (32 * WM), TN = BN / (32 * WN);   // 32x32 MFMA tiles per wave per dim
+  constexpr int TM = BM / (16 * WM), TN = BN / (16 * WN);   // 16x16 MFMA tiles per wave per dim
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
@@ -98,15 +117,13 @@ __global__ __launch_bounds__(64 * WM * WN) void ita_gemm_f16x3_kernel(const ItaG
   const int m0 = (tile / ntn) * BM, n0 = (tile % ntn) * BN;
   const int kslice = g.K / g.nsplit, kbeg = zsplit * kslice;
   const int nt = kslice / 64;
-  const int r = lane & 31, h = lane >> 5;
+  const int r = lane & 15, q = lane >> 4;
 
-  f32x16 acc[TM][TN];
+  f32x4 acc[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
+    for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
 
   auto stage = [&](int buf, int t) {
     char* b = lds + buf * L::BUF;
@@ -123,28 +140,24 @@ __global__ __launch_bounds__(64 * WM * WN) void ita_gemm_f16x3_kernel(const ItaG
     const char* b = lds + buf * L::BUF;
     const char *ah = b, *al = b + L::A_PLANE, *wh = b + 2 * L::A_PLANE, *wl = wh + L::W_PLANE;
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
+    for (int ks = 0; ks < 2; ++ks) {
       f16x8 fah[TM], fal[TM], fwh[TN], fwl[TN];
 #pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int row = wm * (BM / WM) + i * 32 + r;
-        fah[i] = frag_f16(ah, row, 2 * ks + h);
-        fal[i] = frag_f16(al, row, 2 * ks + h);
+      for (int j = 0; j < TN; ++j) {
+        const int row = wn * (BN / WN) + j * 16 + r;
+        fwh[j] = frag_f16(wh, row, 4 * ks + q);
+        fwl[j] = frag_f16(wl, row, 4 * ks + q);
       }
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int row = wn * (BN / WN) + j * 32 + r;
-        fwh[j] = frag_f16(wh, row, 2 * ks + h);
-        fwl[j] = frag_f16(wl, row, 2 * ks + h);
+      for (int i = 0; i < TM; ++i) {
+        const int row = wm * (BM / WM) + i * 16 + r;
+        fah[i] = frag_f16(ah, row, 4 * ks + q);
+        fal[i] = frag_f16(al, row, 4 * ks + q);
       }
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fal[i], fwh[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fah[i], fwl[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fah[i], fwh[j], acc[i][j], 0, 0, 0);
-        }
+        for (int j = 0; j < TN; ++j) gemm_mfma_f16x3(acc[i][j], fwh[j], fwl[j], fah[i], fal[i]);
     }
   };
   int cur = 0;
@@ -156,21 +169,15 @@ __global__ __launch_bounds__(64 * WM * WN) void ita_gemm_f16x3_kernel(const ItaG
     if (!(g.dbg & 4)) __syncthreads();
     cur ^= 1;
   }
-  // C layout: col n = lane&31, row m = (e&3) + 8*(e>>2) + 4*h.  The partials are stored write-through (relaxed agent-scope
-  // atomic stores = global_store_dword sc1): plain stores left their 16.8 MB (1024 frames) dirty in the XCDs' L2s, to be
-  // written back at the kernel boundary in front of the LSTM head (same-box A/B: 1.5 us per step less; the stored values
-  // do not change).  Not a raw buffer store of the bit-cast element: hipcc (ROCm 7) stored element 0 for every e.
-  float* out = g.out + (size_t)zsplit * g.M * g.N;
+  // The partials are stored write-through (sc1), 16 bytes per lane: plain stores left their 16.8 MB (1024 frames) dirty in the
+  // XCDs' L2s, to be written back at the kernel boundary in front of the LSTM head ("Write-through partials").
+  const __amdgpu_buffer_rsrc_t rows = ita_rsrc(g.out + ((size_t)zsplit * g.M + m0) * g.N);
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
-      const int n = n0 + wn * (BN / WN) + j * 32 + r;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int m = m0 + wm * (BM / WM) + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        if (m < g.M) __hip_atomic_store(out + (size_t)m * g.N + n, acc[i][j][e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      const int m = wm * (BM / WM) + i * 16 + r;
+      if (m0 + m < g.M) store_partial<true>(rows, m, n0 + wn * (BN / WN) + j * 16 + 4 * q, g.N, acc[i][j]);
     }
 }
 
@@ -180,16 +187,15 @@ __global__ __launch_bounds__(64 * WM * WN) void ita_gemm_f16x3_kernel(const ItaG
 // of three 64-deep k-tiles).  grid.x = N/32 * nsplit with id % nsplit = the K slice (each XCD's L2 sees one
 // slice of A and of G0), grid.y = ceil(M / (32 MT)); the launcher picks MT (ita_plugin.hip: launch_gemm_split).
 // What this shape answers (all measured, 128 frames unless noted): a fragment is 16 bytes per lane at ROW r, so a
-// wave-load of fragments touches 32 cache lines for 32 bytes each and the load pipeline's per-instruction cost, not
+// wave-load of fragments touches 16 cache lines for 64 bytes each and the load pipeline's per-instruction cost, not
 // bandwidth or latency, sets the pace -- one wave streaming its own tile into a register ring took 20 us whether its
 // lines were hot or cold (8 us per operand; fetching whole lines per lane pair, touching everything first or placing
 // the K slices per XCD changed nothing); the same wave with an LDS-DMA ring (8 whole lines per wave-instruction) 14 us,
 // because an LDS-DMA piece costs its issuing wave ~100 cycles.  So the issue is spread over four waves, and the W tile
 // is staged once for the M tiles that share it.
-// Per output element the arithmetic is IDENTICAL to the large kernel's -- the same v_mfma_f32_32x32x16_f16 on the
-// same operand values in the same lane slots, k-steps in the same order, the same three products per step -- so a
-// frame's result does not depend on which of the two kernels served its batch (tests: a 5-frame batch against
-// rows of a 1024-frame batch, bit for bit).
+// Per output element the arithmetic is IDENTICAL to the large kernel's (gemm_mfma_f16x3 above: the same MFMA on the same operand
+// values in the same lane slots, k-steps in the same order, the same three products per step) -- so a frame's result does
+// not depend on which of the kernels served its batch (tests: a 5-frame batch against rows of a 1024-frame batch, bit for bit).
 // k-tiles in the LDS ring (4..8 where 160 KB hold them measured 1-3 % slower at every M)
 constexpr int ITA_GEMM_SMALL_NSTG = 3;
 constexpr int ita_gemm_small_lds(int mt) { return ITA_GEMM_SMALL_NSTG * (2 * mt + 2) * 32 * 128; }
@@ -200,7 +206,7 @@ __global__ __launch_bounds__(256) void ita_gemm_f16x3_small_kernel(const ItaGemm
   constexpr int DMA = 2 * MT + 2;   // LDS-DMA wave-instructions per wave and k-tile
   static_assert(NSTG == 3 && DMA < 64, "one younger k-tile in flight at the wait; vmcnt range");
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), r = lane & 31, h = lane >> 5;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), r = lane & 15, q = lane >> 4;
   const int z = blockIdx.x % g.nsplit, n0 = (blockIdx.x / g.nsplit) * 32, m0 = blockIdx.y * 32 * MT;
   const int kslice = g.K / g.nsplit, kbeg = z * kslice, nt = kslice / 64;
   auto stage = [&](int kt, int slot) {
@@ -214,9 +220,11 @@ __global__ __launch_bounds__(256) void ita_gemm_f16x3_small_kernel(const ItaGemm
 #pragma unroll
   for (int s = 0; s < NSTG - 1; ++s)
     if (s < nt) stage(s, s);
-  f32x16 acc;
+  f32x4 acc[2][2];   // [16 frames of the M tile][16 columns of the W tile]
 #pragma unroll
-  for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
   const bool compute = wave < MT && m0 + 32 * wave < g.M;
   for (int kt = 0; kt < nt; ++kt) {
     // The compiler does not track LDS-DMA, so the waits are explicit.  This wave's pieces of tile kt have landed when
@@ -232,67 +240,93 @@ __global__ __launch_bounds__(256) void ita_gemm_f16x3_small_kernel(const ItaGemm
       const char* b = lds + (kt % NSTG) * STG;
       const char *pah = b + wave * PLANE, *pal = b + APL + wave * PLANE, *pwh = b + 2 * APL, *pwl = pwh + PLANE;
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const f16x8 ah = frag_f16(pah, r, 2 * ks + h), al = frag_f16(pal, r, 2 * ks + h);
-        const f16x8 wh = frag_f16(pwh, r, 2 * ks + h), wl = frag_f16(pwl, r, 2 * ks + h);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wh, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wl, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wh, acc, 0, 0, 0);
+      for (int ks = 0; ks < 2; ++ks) {
+        f16x8 ah[2], al[2], wh[2], wl[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          wh[t] = frag_f16(pwh, 16 * t + r, 4 * ks + q); wl[t] = frag_f16(pwl, 16 * t + r, 4 * ks + q);
+          ah[t] = frag_f16(pah, 16 * t + r, 4 * ks + q); al[t] = frag_f16(pal, 16 * t + r, 4 * ks + q);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) gemm_mfma_f16x3(acc[i][j], wh[j], wl[j], ah[i], al[i]);
       }
     }
   }
   if (!compute) return;
-  // C layout: col n = lane&31, row m = (e&3) + 8*(e>>2) + 4*h
-  float* out = g.out + (size_t)z * g.M * g.N;
+  const __amdgpu_buffer_rsrc_t rows = ita_rsrc(g.out + ((size_t)z * g.M + m0) * g.N);
 #pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    const int m = m0 + 32 * wave + (e & 3) + 8 * (e >> 2) + 4 * h;
-    if (m < g.M) out[(size_t)m * g.N + n0 + r] = acc[e];
-  }
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int m = 32 * wave + 16 * i + r;
+      if (m0 + m < g.M) store_partial<false>(rows, m, n0 + 16 * j + 4 * q, g.N, acc[i][j]);
+    }
 }
 
 // ---- and for M <= 32 (one M tile: the single-drone deployment): one wave per 32 x 32 output tile and K slice streams
-// its fragments straight from L2 into an 8-slot register ring (7 k-steps in flight); grid (N/32, 1, nsplit).  With a
+// its fragments straight from L2 into a 4-slot register ring (3 k-steps of 32 in flight); grid (N/32, 1, nsplit).  With a
 // single M tile nothing is shared inside a workgroup, and the barrier per k-tile of the kernel above costs more than
-// the row-strided loads it avoids (M = 1: 5 us here, 8 us there).  Same arithmetic per output element again.
+// the row-strided loads it avoids (M = 1: 5 us here, 8 us there).  Same arithmetic per output element again.  MI = the 16-frame
+// MFMA tiles the batch fills (1 for M <= 16: the second tile's loads and MFMAs would serve no frame).
+template <int MI>
 __global__ __launch_bounds__(64) void ita_gemm_f16x3_tiny_kernel(const ItaGemmSplitArgs g) {
-  const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
+  const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
   const int n0 = blockIdx.x * 32, m0 = blockIdx.y * 32, z = blockIdx.z;
-  const int kslice = g.K / g.nsplit, kbeg = z * kslice, nstep = kslice / 16;
-  const size_t ao = (size_t)min(m0 + r, g.M - 1) * g.lda + kbeg + 8 * h;
-  // W comes from its fragment-order copy: 1 KB contiguous per wave-load.  From the row-major matrix a fragment load
-  // touches 32 cache lines for 32 bytes each, which one CU pulls 4-6x slower (tools/microbench/cu_fill_rows.hip);
-  // A keeps its row-major planes -- at M = 1 all its lanes read the same row.
-  const size_t wo = (((size_t)blockIdx.x * (g.K / 16) + kbeg / 16) * 64 + lane) * 8;
-  constexpr int R = 8;
-  f16x8 ah[R], al[R], wh[R], wl[R];
+  const int kslice = g.K / g.nsplit, kbeg = z * kslice, nstep = kslice / 32;
+  size_t ao[MI], wo[2];
+#pragma unroll
+  for (int t = 0; t < MI; ++t) ao[t] = (size_t)min(m0 + 16 * t + r, g.M - 1) * g.lda + kbeg + 8 * q;
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    // W comes from its fragment-order copy: 1 KB contiguous per wave-load.  From the row-major matrix a fragment load
+    // touches 16 cache lines for 64 bytes each, which one CU pulls several times slower (tools/microbench/cu_fill_rows.hip);
+    // A keeps its row-major planes -- at M = 1 all its lanes read the same row.
+    wo[t] = (((size_t)(2 * blockIdx.x + t) * (g.K / 32) + kbeg / 32) * 64 + lane) * 8;
+  }
+  constexpr int R = 4;
+  f16x8 ah[R][MI], al[R][MI], wh[R][2], wl[R][2];
   auto fetch = [&](int s, int slot) {
-    ah[slot] = *(const f16x8*)(g.a_hi + ao + 16 * s);
-    al[slot] = *(const f16x8*)(g.a_lo + ao + 16 * s);
-    wh[slot] = *(const f16x8*)(g.wf_hi + wo + (size_t)s * 512);
-    wl[slot] = *(const f16x8*)(g.wf_lo + wo + (size_t)s * 512);
+#pragma unroll
+    for (int t = 0; t < MI; ++t) {
+      ah[slot][t] = *(const f16x8*)(g.a_hi + ao[t] + 32 * s);
+      al[slot][t] = *(const f16x8*)(g.a_lo + ao[t] + 32 * s);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      wh[slot][t] = *(const f16x8*)(g.wf_hi + wo[t] + (size_t)s * 512);
+      wl[slot][t] = *(const f16x8*)(g.wf_lo + wo[t] + (size_t)s * 512);
+    }
   };
 #pragma unroll
-  for (int s = 0; s < R; ++s) fetch(s, s);
-  f32x16 acc;
+  for (int s = 0; s < R; ++s)
+    if (s < nstep) fetch(s, s);
+  f32x4 acc[MI][2];
 #pragma unroll
-  for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
   for (int s0 = 0; s0 < nstep; s0 += R) {
 #pragma unroll
-    for (int j = 0; j < R; ++j) {
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[j], wh[j], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[j], wl[j], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[j], wh[j], acc, 0, 0, 0);
-      if (s0 + R + j < nstep) fetch(s0 + R + j, j);
+    for (int u = 0; u < R; ++u) {
+      if (s0 + u < nstep) {
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) gemm_mfma_f16x3(acc[i][j], wh[u][j], wl[u][j], ah[u][i], al[u][i]);
+      }
+      if (s0 + R + u < nstep) fetch(s0 + R + u, u);
     }
   }
-  // C layout: col n = lane&31, row m = (e&3) + 8*(e>>2) + 4*h
-  float* out = g.out + (size_t)z * g.M * g.N;
+  const __amdgpu_buffer_rsrc_t rows = ita_rsrc(g.out + ((size_t)z * g.M + m0) * g.N);
 #pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    const int m = m0 + (e & 3) + 8 * (e >> 2) + 4 * h;
-    if (m < g.M) out[(size_t)m * g.N + n0 + r] = acc[e];
-  }
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int m = 16 * i + r;
+      if (m0 + m < g.M) store_partial<false>(rows, m, n0 + 16 * j + 4 * q, g.N, acc[i][j]);
+    }
 }
 
 // f32 rows -> the hi / lo f16 planes the split-precision GEMM reads (the encoder kernels write them directly;

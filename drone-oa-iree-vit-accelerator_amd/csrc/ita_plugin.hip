@@ -577,7 +577,8 @@ int launch_gemm_split(const _Float16* a_hi, const _Float16* a_lo, int lda, const
   static const int dbg = getenv("ITA_GEMM_DBG") ? atoi(getenv("ITA_GEMM_DBG")) : 0;
   ItaGemmSplitArgs g{a_hi, a_lo, lda, w_hi, w_lo, ldw, out, M, N, K, nsplit, dbg, wf_hi, wf_lo};
   if (M <= 32 && N % 32 == 0 && wf_hi && wf_lo)   // one M tile: one wave per 32 x 32 tile and K slice
-    return launch<ita_gemm_f16x3_tiny_kernel>(dim3(N / 32, 1, nsplit), dim3(64), s, g);
+    return M <= 16 ? launch<ita_gemm_f16x3_tiny_kernel<1>>(dim3(N / 32, 1, nsplit), dim3(64), s, g)
+                   : launch<ita_gemm_f16x3_tiny_kernel<2>>(dim3(N / 32, 1, nsplit), dim3(64), s, g);
   if (M <= 256 && N % 32 == 0) {   // a few M tiles: four-wave workgroups share the staging, same arithmetic
     // M tiles per workgroup: up to four (128 frames: 128 workgroups).  Fewer tiles per workgroup fill the chip -- MT = ceil(M / 64)
     // gives 256 workgroups from 64 frames on and the kernel alone gets 1.4-2.9 us faster (64 / 128 frames, one stream) -- but in

@@ -51,7 +51,7 @@ struct Weights {
   // split-precision (f16 hi/lo) tail: folded tail+decoder matrix and LSTM weights, pre-scaled
   int kfold = 8192, ldfold = 8192 + 64;    // K and plane row stride of the folded GEMM (see the constants at the top of ita_plugin.hip)
   bool folded = false;
-  DevBuf<_Float16> foldf_hi, foldf_lo;     // G0 once more as B... MFMA fragments [16][K/16][64][8], for batches of <= 32 frames
+  DevBuf<_Float16> foldf_hi, foldf_lo;     // G0 once more as 16x16x32 MFMA A fragments [N/16][K/32][64][8], for batches of <= 32 frames
   DevBuf<_Float16> fold_hi, fold_lo;       // [512][LDFOLD]: G0 = W_ih0[:, :512] . Wfold, rows in permuted gate order
   DevBuf<float> fold_bias;                 // [512] gate-major: W_ih0[:, :512] . dec(tail(0)) + b_ih0 + b_hh0
   float fold_inv_scale = 1.0f;
@@ -603,12 +603,12 @@ int build_fold(Weights& w, int num_cus) {
   {
     // the same values in fragment order for ita_gemm_f16x3_tiny_kernel (same scale: max |w| is the same)
     std::vector<float> wfr((size_t)512 * KFOLD);
-    for (int nt = 0; nt < 16; ++nt)
-      for (int st = 0; st < KFOLD / 16; ++st)
+    for (int nt = 0; nt < 32; ++nt)
+      for (int st = 0; st < KFOLD / 32; ++st)
         for (int lane = 0; lane < 64; ++lane)
           for (int j = 0; j < 8; ++j)
-            wfr[(((size_t)nt * (KFOLD / 16) + st) * 64 + lane) * 8 + j] =
-                wf[(size_t)(nt * 32 + (lane & 31)) * LDFOLD + st * 16 + 8 * (lane >> 5) + j];
+            wfr[(((size_t)nt * (KFOLD / 32) + st) * 64 + lane) * 8 + j] =
+                wf[(size_t)(nt * 16 + (lane & 15)) * LDFOLD + st * 32 + 8 * (lane >> 4) + j];
     float inv2 = 0.0f;
     if ((rc = split_upload(wfr, w.foldf_hi, w.foldf_lo, &inv2))) return rc;
     if (inv2 != w.fold_inv_scale) return fail(ITA_ERR_UNSUPPORTED, "fragment copy of the folded weights got a different scale");
