@@ -143,13 +143,12 @@ __device__ __forceinline__ void pk_unbias_scale(f32x2 (&x)[8], float mult) {
       : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7])
       : "s"(c2), "s"(m2));
 }
-// block output: d[4t+i] = float(int8 code) * scale for sixteen biased accumulators: 8 + 8 + 16 + 16 + 8
-__device__ __forceinline__ void dq16_b(const i32x4 (&acc)[4], float mult, float scale, float (&d)[16]) {
+// sixteen biased accumulators -> their int8 codes as floats, f[4t+i] = clamp(rne(acc[t][i] * mult)): 8 + 8 + 16 + 16
+__device__ __forceinline__ void rq16_b_f(const i32x4 (&acc)[4], float mult, float (&f)[16]) {
   f32x2 x[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) x[k] = (f32x2){__int_as_float(acc[k >> 1][2 * (k & 1)]), __int_as_float(acc[k >> 1][2 * (k & 1) + 1])};
   pk_unbias_scale(x, mult);
-  float f[16];
 #pragma unroll
   for (int k = 0; k < 8; ++k) { f[2 * k] = x[k].x; f[2 * k + 1] = x[k].y; }
   const float lo = -128.0f, hi = 127.0f;
@@ -189,12 +188,20 @@ __device__ __forceinline__ void dq16_b(const i32x4 (&acc)[4], float mult, float 
       : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]), "+v"(f[6]), "+v"(f[7]), "+v"(f[8]), "+v"(f[9]),
         "+v"(f[10]), "+v"(f[11]), "+v"(f[12]), "+v"(f[13]), "+v"(f[14]), "+v"(f[15])
       : "s"(lo), "v"(hi));
+}
+// block output: d[4t+i] = float(int8 code) * scale for sixteen biased accumulators: rq16_b_f + 8; c (taps): the codes
+__device__ __forceinline__ void dq16_b(const i32x4 (&acc)[4], float mult, float scale, float (&d)[16], float (&c)[16]) {
+  rq16_b_f(acc, mult, c);
   const f32x2 s2 = {scale, scale};
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    const f32x2 v = (f32x2){f[2 * k], f[2 * k + 1]} * s2;
+    const f32x2 v = (f32x2){c[2 * k], c[2 * k + 1]} * s2;
     d[2 * k] = v.x; d[2 * k + 1] = v.y;
   }
+}
+__device__ __forceinline__ void dq16_b(const i32x4 (&acc)[4], float mult, float scale, float (&d)[16]) {
+  float c[16];
+  dq16_b(acc, mult, scale, d, c);
 }
 // ---- round-3 requantisation of biased accumulators: the clamp moves behind the rounding, into the integer domain, where
 // ONE instruction saturates two values (v_sat_pk_u8_i16) -- 2.75 VALU instructions per value instead of 3.0, and 2.25 where a

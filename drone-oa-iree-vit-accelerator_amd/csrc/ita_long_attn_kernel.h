@@ -26,6 +26,12 @@
 //                          by LDS-DMA into a two-slot ring (one barrier per key tile), V^T tiles (sweep 3) into one slot (a second
 //                          barrier per step); context requantised, out_proj with its fragments from the layer image in L2,
 //                          codes stored 16 bytes per lane
+//
+// Taps (ita_mha_long_int8_taps): both kernel bodies are function templates with a TAPS switch; the production kernels are
+// the bodies with TAPS = false, ita_long_proj_taps_kernel / ita_long_attn_taps_kernel the f32 form with TAPS = true.  Under
+// `if constexpr (TAPS)` there are stores only, of the registers the sweeps compute with -- a tap is the production value,
+// there is no second arithmetic.  Stage tensors in natural row-major layout; logits, probabilities, row maximum and row
+// sum for the query rows the row table (S int32: output index or -1) selects, keys at their natural index.
 #pragma once
 #include "ita_stream_kernel.h"
 
@@ -46,8 +52,21 @@ struct ItaLongArgs {
   int fuse_ln;            // + residual + LayerNorm1
 };
 
-template <bool FAST, int E = 128, bool F32IO = false>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void ita_long_proj_kernel(const ItaLongArgs a) {
+// what the taps kernels store besides (any pointer may be null; plain vector stores)
+struct ItaLongTapArgs {
+  int8_t *xq, *Q, *K, *V;   // projection launch: (B, S, E) / (B, S, P) codes, V un-permuted
+  int8_t *ctx, *outq;       // attention launch: (B, S, P) context codes, (B, S, E) out_proj codes
+  const int* rowidx;        // S entries, the same for every frame: output index of a chosen query row, or -1; null: no rows
+  int n_rows;
+  int8_t* logits;           // (B, n_rows, S)
+  uint8_t* probs;           // (B, n_rows, S)
+  int8_t* row_max;          // (B, n_rows): the clamped row maximum
+  int* row_sum;             // (B, n_rows): sum of 256 >> shift
+};
+
+template <bool FAST, int E, bool F32IO, bool TAPS>
+__device__ __forceinline__ void ita_long_proj_body(const ItaLongArgs& a, const ItaLongTapArgs& tp) {
+  static_assert(!TAPS || F32IO, "the taps entry has the f32 form only");
   static_assert(E == 64 || E == 128, "one or two 64-channel k-steps");
   constexpr int S = 128, P = 192, NK = E / 64, EC = E / 4;
   using L = ItaStreamLds<E, false, false>;
@@ -79,6 +98,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
       for (int c = 0; c < NK; ++c) xf[c] = *(const i32x4*)(xrow + 16 * c);
     }
+    if constexpr (TAPS) {
+      if (tp.xq) {
+#pragma unroll
+        for (int c = 0; c < NK; ++c) *(i32x4*)(tp.xq + ((size_t)tile * S + token) * E + EC * kq + 16 * c) = xf[c];
+      }
+    }
     i32x4 qf[3];
     {
       ItaFr<4 * NK> fr[2];
@@ -94,7 +119,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         if (mat == 0) {
           qf[gg] = rq_group(acc, a.mq, FAST);
         } else if (mat == 1) {
-          *(i32x4*)(lds + L::K + (((4 * gg + kq) * S + token) << 4)) = rq_group(acc, a.mk, FAST);
+          const i32x4 k4 = rq_group(acc, a.mk, FAST);
+          *(i32x4*)(lds + L::K + (((4 * gg + kq) * S + token) << 4)) = k4;
+          if constexpr (TAPS) {   // byte 4t + i <-> feature 16 (4 gg + t) + 4 kq + i of this lane's token
+            if (tp.K) {
+#pragma unroll
+              for (int t = 0; t < 4; ++t) *(int*)(tp.K + ((size_t)tile * S + token) * P + (4 * gg + t) * 16 + 4 * kq) = k4[t];
+            }
+          }
         } else {
           const i32x4 p4 = rq_group(acc, a.mv, FAST);
 #pragma unroll
@@ -102,6 +134,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const int d = (4 * gg + t) * 16 + qi;
             *(int*)(lds + L::VT + (((((wave >> 2) * 4 + kq) * P) + d) << 4) + 4 * (wave & 3)) = p4[t];
             atomicAdd(&colsum[d], __builtin_amdgcn_sdot4(p4[t], 0x01010101, 0, false) << 7);
+          }
+          if constexpr (TAPS) {   // roles swapped: byte i of p4[t] <-> token 16 wave + 4 kq + i, feature d
+            if (tp.V) {
+#pragma unroll
+              for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                  tp.V[((size_t)tile * S + wave * 16 + 4 * kq + i) * P + (4 * gg + t) * 16 + qi] = (int8_t)(p4[t] >> (8 * i));
+            }
           }
         }
       };
@@ -119,6 +160,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // Q: this wave's 16 tokens as three B fragments (one per 64-feature k-step), 1 KB per wave and k-step
 #pragma unroll
     for (int ks = 0; ks < 3; ++ks) *(i32x4*)(a.qfrag + ((((size_t)tile * 8 + wave) * 3 + ks) * 64 + lane) * 16) = qf[ks];
+    if constexpr (TAPS) {   // the same bytes at their natural place (the K layout above)
+      if (tp.Q) {
+#pragma unroll
+        for (int ks = 0; ks < 3; ++ks)
+#pragma unroll
+          for (int t = 0; t < 4; ++t) *(int*)(tp.Q + ((size_t)tile * S + token) * P + (4 * ks + t) * 16 + 4 * kq) = qf[ks][t];
+      }
+    }
     __syncthreads();     // K, V^T and the column sums of this tile are complete
     for (int p = tid; p < 2 * S * P / 16; p += 512) {
       const i32x4 v = *(const i32x4*)(lds + L::K + p * 16);      // (K and V^T are adjacent in the LDS layout)
@@ -129,6 +178,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     __syncthreads();     // images copied: the next tile may overwrite them
     if (tid < P) colsum[tid] = 0;
   }
+}
+
+template <bool FAST, int E = 128, bool F32IO = false>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void ita_long_proj_kernel(const ItaLongArgs a) {
+  ita_long_proj_body<FAST, E, F32IO, false>(a, ItaLongTapArgs{});
+}
+template <bool FAST, int E>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void ita_long_proj_taps_kernel(const ItaLongArgs a,
+                                                                                                           const ItaLongTapArgs tp) {
+  ita_long_proj_body<FAST, E, true, true>(a, tp);
 }
 
 // 73 KB of LDS and 128 registers: two workgroups per CU, four waves per SIMD -- this kernel is a stream of dependent MFMA -> requantise
@@ -144,8 +203,9 @@ struct ItaLongLds {
   static_assert(2 * TOTAL <= 160 * 1024, "two workgroups per CU");
 };
 
-template <bool FAST, int E = 128, bool F32IO = false>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void ita_long_attn_kernel(const ItaLongArgs a) {
+template <bool FAST, int E, bool F32IO, bool TAPS>
+__device__ __forceinline__ void ita_long_attn_body(const ItaLongArgs& a, const ItaLongTapArgs& tp) {
+  static_assert(!TAPS || F32IO, "the taps entry has the f32 form only");
   static_assert(E == 64 || E == 128, "one or two 64-channel output groups");
   constexpr int S = 128, P = 192, EC = E / 4;
   using LI = ItaStreamLds<E, false, false>;   // offsets inside the layer's image
@@ -283,6 +343,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   const u16x2 mm = {(unsigned short)m, (unsigned short)m};
   const unsigned short capv = (unsigned short)min(m - (32768 - 128), 15);
   const u16x2 cap = {capv, capv}, one = {256, 256};
+  // taps: the output row of this lane's query (the four kq lanes of a query agree), and whether the wave has any
+  int ri = -1;
+  bool wave_rows = false;
+  size_t rowoff = 0;      // (b * n_rows + ri) * S: where this query's logit / probability row starts
+  if constexpr (TAPS) {
+    if (tp.rowidx) ri = tp.rowidx[qt * 128 + wave * 16 + qi];
+    wave_rows = __builtin_amdgcn_ballot_w64(ri >= 0) != 0;
+    rowoff = ((size_t)b * tp.n_rows + (size_t)max(ri, 0)) * a.S;
+  }
   // ---------------- sweep 2: row sum (nkt is even or odd: the ring slot of tile kt is (sweep * nkt + kt) & 1)
   int sumlo = 0;
   for (int kt = 0; kt < nkt; ++kt) {
@@ -294,11 +363,27 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
     for (int j = 0; j < 16; ++j) s2 += one >> __builtin_elementwise_min(__builtin_elementwise_sub_sat(mm, w[j]), cap);
     sumlo += (int)s2.x + (int)s2.y;       // <= 32 * 256 per tile and lane
+    if constexpr (TAPS) {   // w[2 j16 + j] = keys 16 j16 + 4 kq + 2 j, + 1 of this tile, biased and unclamped: four int8 codes per store
+      if (wave_rows && tp.logits && ri >= 0) {
+#pragma unroll
+        for (int j16 = 0; j16 < 8; ++j16) {
+          const int c0 = min(max((int)w[2 * j16].x - 32768, -128), 127), c1 = min(max((int)w[2 * j16].y - 32768, -128), 127);
+          const int c2 = min(max((int)w[2 * j16 + 1].x - 32768, -128), 127), c3 = min(max((int)w[2 * j16 + 1].y - 32768, -128), 127);
+          *(unsigned*)(tp.logits + rowoff + (size_t)kt * 128 + 16 * j16 + 4 * kq) = pack4(c0, c1, c2, c3);
+        }
+      }
+    }
   }
   int sum = sum1632_i(sumlo);
   sum = max(sum, 1);
   const int inv_hi = ((int)floorf((1.0f / (float)sum) * 16711680.0f)) >> 8;
   const u16x2 iv = {(unsigned short)inv_hi, (unsigned short)inv_hi};
+  if constexpr (TAPS) {
+    if (ri >= 0 && kq == 0) {
+      if (tp.row_max) tp.row_max[(size_t)b * tp.n_rows + ri] = (int8_t)(m - 32768);
+      if (tp.row_sum) tp.row_sum[(size_t)b * tp.n_rows + ri] = sum;
+    }
+  }
   // ---------------- sweep 3: probabilities and A.V; the accumulators start from 128 * column sums (u8 probabilities ride the
   // signed MFMA as p - 128, as in the stream kernel)
   i32x4 va[3][4];
@@ -324,7 +409,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         const u16x2 s1 = __builtin_elementwise_min(__builtin_elementwise_sub_sat(mm, w[2 * k4 + 1]), cap);
         const unsigned p01 = __builtin_bit_cast(unsigned, (u16x2)(iv >> s0));
         const unsigned p23 = __builtin_bit_cast(unsigned, (u16x2)(iv >> s1));
-        pf[kb][t] = (int)(__builtin_amdgcn_perm(p23, p01, 0x06040200u) ^ 0x80808080u);
+        const unsigned p4 = __builtin_amdgcn_perm(p23, p01, 0x06040200u);   // u8 probabilities of keys 64 kb + 16 t + 4 kq + 0..3
+        pf[kb][t] = (int)(p4 ^ 0x80808080u);
+        if constexpr (TAPS) {
+          if (wave_rows && tp.probs && ri >= 0) *(unsigned*)(tp.probs + rowoff + (size_t)kt * 128 + 64 * kb + 16 * t + 4 * kq) = p4;
+        }
       }
     // V^T tile kt (requested first: the three K pieces of the next step may still be on their way)
     if (kt + 1 < nkt) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
@@ -356,6 +445,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   }
   __syncthreads();      // (BO was written in the prologue: visible since the first barrier; keeps the waves together for the stores)
   const int token = wave * 16 + qi;
+  if constexpr (TAPS) {   // byte 4t + i of cf[dg] <-> feature 16 (4 dg + t) + 4 kq + i
+    if (tp.ctx) {
+#pragma unroll
+      for (int dg = 0; dg < 3; ++dg)
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+          *(int*)(tp.ctx + ((size_t)b * a.S + (size_t)qt * 128 + token) * P + (4 * dg + t) * 16 + 4 * kq) = cf[dg][t];
+    }
+  }
   float x1[F32IO ? EC : 1];   // f32 form: this lane's quarter of the output row (the sweep accumulators are dead here)
 #pragma unroll
   for (int eg = 0; eg < E / 64; ++eg) {
@@ -369,7 +467,18 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     }
     if constexpr (F32IO) {
       float d[16];
-      dq_group(oa, a.mo, a.so, d);
+      if constexpr (TAPS) {   // the codes dq_group scales: c[4t + i] <-> channel EC kq + 16 eg + 4t + i
+        float c[16];
+        dq_group_codes(oa, a.mo, a.so, d, c);
+        if (tp.outq) {
+          i32x4 o4;
+#pragma unroll
+          for (int t = 0; t < 4; ++t) o4[t] = (int)pack4((int)c[4 * t], (int)c[4 * t + 1], (int)c[4 * t + 2], (int)c[4 * t + 3]);
+          *(i32x4*)(tp.outq + (((size_t)b * a.S + (size_t)qt * 128 + token) * E) + EC * kq + 16 * eg) = o4;
+        }
+      } else {
+        dq_group(oa, a.mo, a.so, d);
+      }
 #pragma unroll
       for (int j = 0; j < 16; ++j) x1[16 * eg + j] = d[j];
     } else {
@@ -389,4 +498,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     }
     st_tok_quarter<E>(a.y + row * E, kq, x1);
   }
+}
+
+template <bool FAST, int E = 128, bool F32IO = false>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void ita_long_attn_kernel(const ItaLongArgs a) {
+  ita_long_attn_body<FAST, E, F32IO, false>(a, ItaLongTapArgs{});
+}
+template <bool FAST, int E>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void ita_long_attn_taps_kernel(const ItaLongArgs a,
+                                                                                                           const ItaLongTapArgs tp) {
+  ita_long_attn_body<FAST, E, true, true>(a, tp);
 }

@@ -208,6 +208,9 @@ struct ita_context {
   // long-sequence attention (ita_mha_long_q8): Q fragments, K / V^T images, column sums; grown on demand
   DevBuf<char> long_ws;
   size_t long_ws_bytes = 0;
+  // ita_mha_long_int8_taps: the row table (token -> output row, or -1), ITA_LONG_MAX_SEQ entries, and its host copy
+  DevBuf<int> long_rows;
+  std::vector<int> long_rows_host;
   // staging for the host-buffer drop-in symbols
   DevBuf<float> dsp_in, dsp_out;
   std::vector<float> dsp_host;
@@ -860,21 +863,45 @@ int ita_mha_int8(ita_handle h, int layer, const float* x, float* y, int batch, v
 namespace {
 
 // the refusals every long-sequence entry point shares (ITA_ERR_UNSUPPORTED, before any launch)
-int check_long(const Layer& L, int batch, int seq_len) {
-  if (L.attn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's attention is float32 (ITAW0003 blob): no int8 long attention");
+int check_long(const Layer& L, int batch, int seq_len, bool taps = false) {
+  if (L.attn_f32)
+    return fail(ITA_ERR_UNSUPPORTED, taps ? "this layer's attention is float32 (ITAW0003 blob): its flash kernel keeps no row probabilities, there are no taps"
+                                          : "this layer's attention is float32 (ITAW0003 blob): no int8 long attention");
   if (seq_len < 128 || seq_len % 128 || seq_len > 65536 || batch > 65535)
     return fail(ITA_ERR_UNSUPPORTED, "seq_len must be a multiple of 128 in [128, 65536], batch <= 65535");
   if (!L.simg_mha) return fail(ITA_ERR_UNSUPPORTED, "this layer has no attention image (accumulator range, or more than one head)");
   return ITA_OK;
 }
 
-// What the three long-sequence entry points share: the refusals, the workspace, the two launches.
-// Int8 form: xq -> yq.  F32 form (x non-null): x -> y, with fuse_ln + residual + LayerNorm1.
+// The taps' own refusals (ITA_ERR_INVALID_ARG)
+constexpr int ITA_LONG_MAX_ROWS = 1024, ITA_LONG_MAX_SEQ = 65536;
+int check_long_taps(const ita_mha_long_taps& t, int seq_len, hipStream_t s) {
+  if (t.n_rows < 0 || t.n_rows > ITA_LONG_MAX_ROWS) return fail(ITA_ERR_INVALID_ARG, "n_rows must be in [0, 1024]");
+  if (t.n_rows > 0 && !t.rows) return fail(ITA_ERR_INVALID_ARG, "n_rows > 0 without rows");
+  for (int i = 0; i < t.n_rows; ++i)
+    if (t.rows[i] < 0 || t.rows[i] >= seq_len || (i > 0 && t.rows[i] <= t.rows[i - 1]))
+      return fail(ITA_ERR_INVALID_ARG, "rows must be strictly increasing token indices in [0, seq_len)");
+  if (t.n_rows == 0 && (t.logits || t.probs || t.row_max || t.row_sum))
+    return fail(ITA_ERR_INVALID_ARG, "logits, probs, row_max and row_sum are per chosen row: n_rows is 0");
+  auto misaligned = [](const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) != 0; };
+  if (misaligned(t.x_q, 16) || misaligned(t.out_q, 16) || misaligned(t.Q, 4) || misaligned(t.K, 4) || misaligned(t.ctx, 4) ||
+      misaligned(t.logits, 4) || misaligned(t.probs, 4) || misaligned(t.row_sum, 4))
+    return fail(ITA_ERR_INVALID_ARG, "x_q and out_q must be 16-byte aligned; Q, K, ctx, logits, probs and row_sum 4-byte aligned");
+  if (capturing(s))
+    return fail(ITA_ERR_INVALID_ARG, "ita_mha_long_int8_taps cannot run inside a stream capture (its row table is rebuilt on the host)");
+  return ITA_OK;
+}
+
+// What the long-sequence entry points share: the refusals, the workspace, the two launches.
+// Int8 form: xq -> yq.  F32 form (x non-null): x -> y, with fuse_ln + residual + LayerNorm1; with taps (f32 form only)
+// the taps kernels run instead: the same bodies and the stores of ita_mha_long_taps.
 int launch_long(ita_context* h, int layer, const int8_t* xq, int8_t* yq, const float* x, float* y, bool fuse_ln, int batch,
-                int seq_len, hipStream_t s) {
+                int seq_len, hipStream_t s, const ita_mha_long_taps* taps = nullptr) {
   const Layer& L = h->w.layers[layer];
-  if (int rc = check_long(L, batch, seq_len)) return rc;
+  if (int rc = check_long(L, batch, seq_len, taps != nullptr)) return rc;
   if (fuse_ln && !L.n1w) return fail(ITA_ERR_BAD_BLOB, "norm1 parameters missing from the blob");
+  if (taps)
+    if (int rc = check_long_taps(*taps, seq_len, s)) return rc;
   // the logits of a long row still fit the 16-bit travel format: same bound as stream_range_ok (per key, not per row)
   const size_t ntile = (size_t)batch * (seq_len / 128);
   const size_t need = ntile * (3 * 24576 + 192 * 4);
@@ -896,9 +923,29 @@ int launch_long(ita_context* h, int layer, const int8_t* xq, int8_t* yq, const f
   a.B = batch; a.S = seq_len;
   const bool fast = L.fast_sites == ITA_SITES_ALL;
   const dim3 proj_grid(ntile < (size_t)h->num_cus ? (int)ntile : h->num_cus), attn_grid(seq_len / 128, batch);
+  ItaLongTapArgs tp{};
+  if (taps) {
+    tp.xq = taps->x_q; tp.Q = taps->Q; tp.K = taps->K; tp.V = taps->V; tp.ctx = taps->ctx; tp.outq = taps->out_q;
+    tp.logits = taps->logits; tp.probs = taps->probs; tp.row_max = taps->row_max; tp.row_sum = taps->row_sum;
+    tp.n_rows = taps->n_rows;
+    if (taps->n_rows > 0) {   // token -> output row; the copy has left the host vector when the wait returns
+      if (!h->long_rows) HIPCHK(h->long_rows.alloc(ITA_LONG_MAX_SEQ));
+      h->long_rows_host.assign((size_t)seq_len, -1);
+      for (int i = 0; i < taps->n_rows; ++i) h->long_rows_host[taps->rows[i]] = i;
+      HIPCHK(hipMemcpyAsync(h->long_rows, h->long_rows_host.data(), (size_t)seq_len * sizeof(int), hipMemcpyHostToDevice, s));
+      HIPCHK(hipStreamSynchronize(s));
+      tp.rowidx = h->long_rows;
+    }
+  }
   auto run = [&](auto e, auto f32, auto fst) {
     constexpr int E = decltype(e)::value;
     constexpr bool F32 = decltype(f32)::value, FAST = decltype(fst)::value;
+    if constexpr (F32) {
+      if (taps) {
+        if (int rc = launch<ita_long_proj_taps_kernel<FAST, E>, ItaStreamLds<E, false, false>::TOTAL>(proj_grid, dim3(512), s, a, tp)) return rc;
+        return launch<ita_long_attn_taps_kernel<FAST, E>, ItaLongLds::TOTAL>(attn_grid, dim3(512), s, a, tp);
+      }
+    }
     if (int rc = launch<ita_long_proj_kernel<FAST, E, F32>, ItaStreamLds<E, false, false>::TOTAL>(proj_grid, dim3(512), s, a)) return rc;
     return launch<ita_long_attn_kernel<FAST, E, F32>, ItaLongLds::TOTAL>(attn_grid, dim3(512), s, a);
   };
@@ -918,6 +965,13 @@ int ita_mha_long_q8(ita_handle h, int layer, const int8_t* x_q, int8_t* out_q, i
 int ita_mha_long_int8(ita_handle h, int layer, const float* x, float* y, int batch, int seq_len, void* stream) {
   if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
   return launch_long(h, layer, nullptr, nullptr, x, y, false, batch, seq_len, (hipStream_t)stream);
+}
+
+int ita_mha_long_int8_taps(ita_handle h, int layer, const float* x, float* y, int batch, int seq_len,
+                           const ita_mha_long_taps* taps, void* stream) {
+  if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
+  const ita_mha_long_taps none{};
+  return launch_long(h, layer, nullptr, nullptr, x, y, false, batch, seq_len, (hipStream_t)stream, taps ? taps : &none);
 }
 
 // x1 = LN1(x + attn(x)) into y by the two long launches, then the FFN block + residual + LN2 in place on y: the FFN is per

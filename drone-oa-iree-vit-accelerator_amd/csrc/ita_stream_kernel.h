@@ -251,6 +251,10 @@ __device__ __forceinline__ void dq_group(const i32x4 (&acc)[4], float mult, floa
   }
   dq16_b(acc, mult, scale, d);
 }
+// the same, and the codes it scaled: c[4t+i] = d[4t+i] / scale as integers in [-128, 127] (the long taps kernel stores them)
+__device__ __forceinline__ void dq_group_codes(const i32x4 (&acc)[4], float mult, float scale, float (&d)[16], float (&c)[16]) {
+  dq16_b(acc, mult, scale, d, c);
+}
 
 // (amdgpu_waves_per_eu(2, 2): the workgroup owns the CU's LDS, so two waves per SIMD is all there will ever be -- without
 // it the scheduler trades instruction-level parallelism for registers it has no use for: the LDS size is dynamic)

@@ -34,7 +34,7 @@ HEAD_TIMEOUT = 1
 
 EXPORTED_SYMBOLS = (
     "ita_abi_version", "ita_create", "ita_destroy", "ita_load_weights", "ita_validate_blob", "ita_reserve", "ita_get_dims",
-    "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_mha_long_int8", "ita_encoder_layer_long", "ita_ffn_int8", "ita_ffn_int8_taps",
+    "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_mha_long_int8", "ita_mha_long_int8_taps", "ita_encoder_layer_long", "ita_ffn_int8", "ita_ffn_int8_taps",
     "ita_ffn_f32", "ita_get_ffn_kind", "ita_mha_f32", "ita_get_attn_kind", "ita_mha_long_f32", "ita_encoder_layer_long_f32",
     "ita_encoder_layer", "ita_tokenizer", "ita_fusion_tail", "ita_vitlstm_forward", "ita_bind_dispatch",
     "ita_profile_begin", "ita_profile_begin_sampled", "ita_profile_end", "ita_set_tail_mode", "ita_debug_encoder_stamps",
@@ -89,6 +89,17 @@ class _MhaTaps(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("x_q", "Q", "K", "V", "logits", "probs", "ctx", "out_q")]
 
 
+class _MhaLongTaps(C.Structure):      # ita_mha_long_taps
+    _fields_ = [(n, C.c_void_p) for n in ("x_q", "Q", "K", "V", "ctx", "out_q")] + \
+               [("rows", C.POINTER(C.c_int)), ("n_rows", C.c_int)] + \
+               [(n, C.c_void_p) for n in ("logits", "probs", "row_max", "row_sum")]
+
+
+LONG_TENSOR_TAPS = ("x_q", "Q", "K", "V", "ctx", "out_q")
+LONG_ROW_TAPS = ("logits", "probs", "row_max", "row_sum")
+LONG_MAX_ROWS = 1024
+
+
 class _FfnTaps(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("x_q", "h", "out_q")]
 
@@ -141,6 +152,7 @@ def lib():
         L.ita_mha_q8.argtypes = [vp, i, vp, vp, i, vp]
         L.ita_mha_long_q8.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_int8.argtypes = [vp, i, vp, vp, i, i, vp]
+        L.ita_mha_long_int8_taps.argtypes = [vp, i, vp, vp, i, i, C.POINTER(_MhaLongTaps), vp]
         L.ita_encoder_layer_long.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_f32.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_encoder_layer_long_f32.argtypes = [vp, i, vp, vp, i, i, vp]
@@ -636,6 +648,73 @@ class Engine:
         _chk(lib().ita_mha_long_int8(self._h, layer, x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1],
                                      _stream_ptr(self.device)))
         return y
+
+    def _long_taps(self, x, rows, layer, want):
+        """ita_mha_long_int8_taps asking for the taps named in `want` only -> (y, dict of those taps)"""
+        torch = _torch()
+        x = self._long_f32(x)
+        B, S = x.shape[0], x.shape[1]
+        rows = [int(r) for r in rows]
+        n = len(rows)
+        y = torch.empty_like(x)
+        i8, u8, i32 = torch.int8, torch.uint8, torch.int32
+        spec = dict(x_q=((B, S, self.E), i8), Q=((B, S, self.P), i8), K=((B, S, self.P), i8), V=((B, S, self.P), i8),
+                    ctx=((B, S, self.P), i8), out_q=((B, S, self.E), i8), logits=((B, n, S), i8), probs=((B, n, S), u8),
+                    row_max=((B, n), i8), row_sum=((B, n), i32))
+        unknown = [k for k in want if k not in spec]
+        if unknown:
+            raise ITAError(f"no such long tap: {unknown}")
+        t = {k: torch.empty(spec[k][0], dtype=spec[k][1], device=x.device) for k in spec if k in want}
+        st = _MhaLongTaps(**{k: v.data_ptr() for k, v in t.items()})
+        arr = (C.c_int * max(n, 1))(*rows)
+        st.rows, st.n_rows = (arr if n else None), n
+        _chk(lib().ita_mha_long_int8_taps(self._h, layer, x.data_ptr(), y.data_ptr(), B, S, C.byref(st),
+                                          _stream_ptr(self.device)))
+        return y, t
+
+    def mha_long_taps(self, x, rows=(), layer: int = 0):
+        """mha_long with its int tensors read out (ita_mha_long_int8_taps): x (B,S,E) f32 -> (attn(x), taps).  taps: x_q,
+        out_q (B,S,E) int8; Q, K, V, ctx (B,S,P) int8; and, for the query rows `rows` (strictly increasing token
+        indices, at most 1024, the same of every frame): logits (B,n,S) int8, probs (B,n,S) uint8, row_max (B,n) int8,
+        row_sum (B,n) int32.  Without rows the dict holds the six tensors only.  The taps are the long kernels' own values."""
+        rows = list(rows)
+        return self._long_taps(x, rows, layer, LONG_TENSOR_TAPS + (LONG_ROW_TAPS if rows else ()))
+
+    def attention_rows_long(self, x, rows, layer: int = 0):
+        """what the tokens `rows` of a long sequence attend to: x (B,S,E) f32 -> the integer softmax's uint8 probabilities
+        (B, len(rows), S) of those query rows (the reference's attn_weights); rows strictly increasing, at most 1024"""
+        return self._long_taps(x, rows, layer, ("probs",))[1]["probs"]
+
+    def attention_map_long(self, frames, tok_h: int, tok_w: int, queries, layer: int = 0, depth_scale: Optional[float] = None):
+        """attention maps of chosen tokens over the token grid of camera frames: tokenize_long, the encoder layers below
+        `layer` (encoder_layer_long, or encoder_layer_long_f32 where the layer's FFN is float), then attention_rows_long of
+        `layer` for the tokens queries = [(ty, tx), ...] -> (N, len(queries), tok_h, tok_w) uint8 in the order of queries.
+        Duplicate or out-of-grid queries raise ValueError."""
+        tok_h, tok_w = int(tok_h), int(tok_w)
+        toks = []
+        for ty, tx in queries:
+            ty, tx = int(ty), int(tx)
+            if not (0 <= ty < tok_h and 0 <= tx < tok_w):
+                raise ValueError(f"query ({ty}, {tx}) lies outside the {tok_h} x {tok_w} token grid")
+            toks.append(ty * tok_w + tx)
+        if len(set(toks)) != len(toks):
+            raise ValueError("duplicate queries")
+        if not 0 <= int(layer) < self.num_layers:
+            raise ValueError(f"layer {layer} out of range")
+        y = self.tokenize_long(frames, tok_h, tok_w, depth_scale)
+        for l in range(int(layer)):
+            if self.ffn_kind(l) == FFN_F32:
+                self.encoder_layer_long_f32(y, l, out=y)
+            else:
+                self.encoder_layer_long(y, l, out=y)
+        order = sorted(range(len(toks)), key=toks.__getitem__)
+        probs = self.attention_rows_long(y, [toks[j] for j in order], int(layer))
+        unsort = [0] * len(order)
+        for pos, j in enumerate(order):
+            unsort[j] = pos
+        torch = _torch()
+        probs = probs[:, torch.tensor(unsort, dtype=torch.long, device=probs.device)] if toks else probs
+        return probs.reshape(probs.shape[0], len(toks), tok_h, tok_w)
 
     def encoder_layer_long(self, x, layer: int = 0, out=None):
         """one encoder layer over a long sequence: x (B,S,E) f32 -> LN2(x1 + ffn(x1)), x1 = LN1(x + attn(x))

@@ -52,8 +52,8 @@ int ita_destroy(ita_handle h);
  * (ITAW0001) blob only -- ITAW0002 and ITAW0003 blobs run with one head.  Anything else: ITA_ERR_UNSUPPORTED.
  * A layer with H > 1 runs on the block kernels (ita_mha_kernel<E, H>, then the FFN block) behind the stand-alone tokenizer;
  * every entry point below serves it except those that need the one-head stream kernel, which return
- * ITA_ERR_UNSUPPORTED before any launch: ita_mha_q8, ita_mha_long_q8, ita_mha_long_int8, ita_encoder_layer_long,
- * ita_debug_encoder_stamps, ita_vitlstm_forward_slots (and ita_mha_long_f32 / ita_encoder_layer_long_f32, which take
+ * ITA_ERR_UNSUPPORTED before any launch: ita_mha_q8, ita_mha_long_q8, ita_mha_long_int8, ita_mha_long_int8_taps,
+ * ita_encoder_layer_long, ita_debug_encoder_stamps, ita_vitlstm_forward_slots (and ita_mha_long_f32 / ita_encoder_layer_long_f32, which take
  * float layers only).
  * The reference pre-loads weights into the accelerator out of band
  * (docs/HOW-TO-run-the-full-project-workflow.md:55); this is that step. */
@@ -112,6 +112,27 @@ int ita_mha_long_q8(ita_handle h, int layer, const int8_t* x_q_dev, int8_t* out_
 /* The long form of ita_mha_int8: x, y (B, seq_len, E) f32, y = attn(x) -- x quantised as ita_mha_int8 quantises it, the
  * out_proj codes of ita_mha_long_q8 dequantised.  Shape limits, workspace and refusals of ita_mha_long_q8. */
 int ita_mha_long_int8(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_len, void* stream);
+/* ita_mha_long_int8 with the stage tensors and, for chosen query rows, the attention rows read out: y is what
+ * ita_mha_long_int8 writes, bit for bit, and every tap is the value the long kernels compute with (the taps kernels are
+ * the production kernels' bodies plus stores).  Device pointers, natural row-major layouts, any of them may be NULL:
+ * x_q, out_q (B, seq_len, E) s8 (16-byte aligned); Q, K, V, ctx (B, seq_len, P) s8 (4-byte aligned).  rows: a HOST array of n_rows strictly increasing token
+ * indices in [0, seq_len), the same query rows of every frame; for each, logits (s8, clamped as the softmax reads them) and
+ * probs (u8: the reference's attn_weights) (B, n_rows, seq_len), 4-byte aligned, row_max (B, n_rows) s8 and row_sum (B, n_rows) s32 (the row's
+ * maximum logit and the sum of 256 >> (max - logit) the probabilities are divided by).  taps == NULL: all-null taps.
+ * Refusals, all before any launch, outputs and taps untouched: whatever ita_mha_long_int8 refuses, with the same status
+ * (a float-attention layer: its flash kernel keeps no row probabilities); ITA_ERR_INVALID_ARG for n_rows outside
+ * [0, 1024], n_rows > 0 without rows, rows not strictly increasing or out of range, a row-indexed pointer (logits,
+ * probs, row_max, row_sum) with n_rows == 0, a misaligned tap, and for a call inside a stream capture (the row table
+ * is rebuilt on the host and copied to the handle's device table on `stream` in every call that gives rows). */
+typedef struct ita_mha_long_taps {
+  int8_t *x_q, *Q, *K, *V, *ctx, *out_q;  /* (B,S,E) / (B,S,P) s8, any may be NULL */
+  const int* rows;                         /* HOST array, strictly increasing token indices in [0, seq_len) */
+  int n_rows;                              /* 0 .. 1024 */
+  int8_t* logits; uint8_t* probs;          /* (B, n_rows, seq_len) */
+  int8_t* row_max; int* row_sum;           /* (B, n_rows) */
+} ita_mha_long_taps;
+int ita_mha_long_int8_taps(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_len,
+                           const ita_mha_long_taps* taps, void* stream);
 /* The long form of ita_encoder_layer: y = LN2(x1 + ffn(x1)), x1 = LN1(x + attn(x)) on (B, seq_len, E) f32 rows; x_dev may
  * equal y_dev.  Attention + residual + LN1 are the two long launches (x1 goes to y), the FFN + residual + LN2 then run in
  * place on y, 128 rows per block (ita_ffn_int8's kernel: the FFN is per token).  Shape limits, workspace and refusals of
