@@ -43,6 +43,14 @@
 // reads nothing of x but its own 16 rows (its Q in the prologue, its residual), each before it stores them.
 //
 // Roofline: 2 x 2 x B x S^2 x 192 flop for the two sweeps' GEMMs: 32 x 8192 -> 1.65 TFLOP, >= 10.5 ms at 157.3 TF.
+//
+// Taps (ita_mha_long_f32_taps): both kernel bodies are function templates with a TAPS switch, as in ita_long_attn_kernel.h;
+// the production kernels are the bodies with TAPS = false, ita_lf32_proj_taps_kernel / ita_lf32_attn_taps_kernel those with
+// TAPS = true.  Under `if constexpr (TAPS)` there are stores only, of the registers the launches compute with: K and V (the
+// projection's accumulators), Q (the prologue's), ctx (after the multiplication by 1 / l), and for the query rows the row
+// table (S int32: output index or -1) selects the sweep's logits s at their natural key index, the final running maximum
+// m and the final row sum l.  The sweep never holds a probability e^(s - m_final) / l: ita_lf32_probs_kernel forms
+// ita_expf(logit - row_max) * (1.0f / row_sum) from those three stored values behind the attention launch.
 #pragma once
 #include "ita_attn_f32_kernel.h"
 
@@ -59,6 +67,16 @@ struct ItaLongF32Args {
   int fuse_ln;
 };
 
+// what the taps kernels store besides (any pointer may be null; plain vector stores)
+struct ItaLongF32TapArgs {
+  float *K, *V;               // projection launch: (B, S, P), natural [token][feature]
+  float *Q, *ctx;             // attention launch: (B, S, P)
+  const int* rowidx;          // S entries, the same for every frame: output index of a chosen query row, or -1; null: no rows
+  int n_rows;
+  float* logits;              // (B, n_rows, S): the sweep's s, before it becomes e^(s - m)
+  float *row_max, *row_sum;   // (B, n_rows): the final m, the final l after the cross-lane add
+};
+
 struct ItaLongF32Lds {
   static constexpr int NFT = 12, NKT = 4;                  // feature tiles, 16-key tiles of a 64-key unit
   static constexpr int UNIT_F4 = NFT * NKT * 64;           // f32x4 per unit
@@ -70,8 +88,8 @@ struct ItaLongF32Lds {
   static_assert(128 * (128 + 4) * 4 <= 2 * UNIT, "the x + out rows overlay the K ring");
 };
 
-template <int E>
-__global__ __launch_bounds__(512) void ita_lf32_proj_kernel(const ItaLongF32Args a) {
+template <int E, bool TAPS>
+__device__ __forceinline__ void ita_lf32_proj_body(const ItaLongF32Args& a, const ItaLongF32TapArgs& tp) {
   static_assert(E == 64 || E == 128, "four or eight 16-channel k groups");
   using L = ItaLongF32Lds;
   constexpr int S = 128, NFT = L::NFT, NG = E / 16;
@@ -112,6 +130,13 @@ __global__ __launch_bounds__(512) void ita_lf32_proj_kernel(const ItaLongF32Args
       }
       kd[ft * L::NKT * 64] = ka[0];
       kd[(ft + 1) * L::NKT * 64] = ka[1];
+      if constexpr (TAPS) {   // the same accumulators at K[token 16 wave + col][16 ft + 4 slot + 0..3]
+        if (tp.K) {
+          float* kr = tp.K + ((size_t)tile * S + 16 * wave + col) * 192 + 4 * slot;
+          *(f32x4*)(kr + 16 * ft) = ka[0];
+          *(f32x4*)(kr + 16 * (ft + 1)) = ka[1];
+        }
+      }
     }
     // V: lane (feature 16 ft + col, slot) holds V[16 wave + 4 slot + r][feature]
 #pragma unroll
@@ -138,12 +163,30 @@ __global__ __launch_bounds__(512) void ita_lf32_proj_kernel(const ItaLongF32Args
       }
       vd[ft * L::NKT * 64] = va[0];
       vd[(ft + 1) * L::NKT * 64] = va[1];
+      if constexpr (TAPS) {   // element r is token 16 wave + 4 slot + r of feature 16 ft + col
+        if (tp.V) {
+          float* vr = tp.V + ((size_t)tile * S + 16 * wave + 4 * slot) * 192 + col;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            vr[r * 192 + 16 * ft] = va[0][r];
+            vr[r * 192 + 16 * (ft + 1)] = va[1][r];
+          }
+        }
+      }
     }
   }
 }
-
 template <int E>
-__global__ __launch_bounds__(512) void ita_lf32_attn_kernel(const ItaLongF32Args a) {
+__global__ __launch_bounds__(512) void ita_lf32_proj_kernel(const ItaLongF32Args a) {
+  ita_lf32_proj_body<E, false>(a, ItaLongF32TapArgs{});
+}
+template <int E>
+__global__ __launch_bounds__(512) void ita_lf32_proj_taps_kernel(const ItaLongF32Args a, const ItaLongF32TapArgs tp) {
+  ita_lf32_proj_body<E, true>(a, tp);
+}
+
+template <int E, bool TAPS>
+__device__ __forceinline__ void ita_lf32_attn_body(const ItaLongF32Args& a, const ItaLongF32TapArgs& tp) {
   static_assert(E == 64 || E == 128, "four or eight 16-channel groups");
   using L = ItaLongF32Lds;
   constexpr int P = 192, XS = E + 4, NFT = L::NFT, NKT = L::NKT, NG = E / 16, EC = E / 4;
@@ -203,6 +246,20 @@ __global__ __launch_bounds__(512) void ita_lf32_attn_kernel(const ItaLongF32Args
 #pragma unroll
     for (int ft = 0; ft < NFT; ++ft) q[ft] = qs[ft * 64];
   }
+  // taps: the output row of this lane's query (the four slot lanes of a query agree), and whether the wave has any
+  int ri = -1;
+  bool wave_rows = false;
+  size_t rowoff = 0;      // (b * n_rows + ri) * S: where this query's logit row starts
+  if constexpr (TAPS) {
+    if (tp.Q) {           // the fragments the sweep multiplies with: Q[query][16 ft + 4 slot + 0..3]
+      float* qr = tp.Q + ((size_t)b * a.S + (size_t)qt * 128 + t0 + col) * P + 4 * slot;
+#pragma unroll
+      for (int ft = 0; ft < NFT; ++ft) *(f32x4*)(qr + 16 * ft) = q[ft];
+    }
+    if (tp.rowidx) ri = tp.rowidx[qt * 128 + t0 + col];
+    wave_rows = __builtin_amdgcn_ballot_w64(ri >= 0) != 0;
+    rowoff = ((size_t)b * tp.n_rows + (size_t)max(ri, 0)) * a.S;
+  }
 
   // the sweep: running maximum m (the same in the four lanes of a query), this lane's share l of the running sum (its 16
   // keys of every unit; the four shares carry the same factors, so they are added once, at the end), context c
@@ -249,6 +306,13 @@ __global__ __launch_bounds__(512) void ita_lf32_attn_kernel(const ItaLongF32Args
       }
 #pragma unroll
       for (int kt = 0; kt < NKT; ++kt) s[kt] += t[(NFT - 1) & 1][kt];
+    }
+    if constexpr (TAPS) {   // s[kt] = keys 64 u + 16 kt + 4 slot + 0..3 of query col: 16 bytes per store, before s becomes e^(s - m)
+      if (wave_rows && tp.logits && ri >= 0) {
+        float* lr = tp.logits + rowoff + 64 * u + 4 * slot;
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt) *(f32x4*)(lr + 16 * kt) = s[kt];
+      }
     }
     // running softmax over the unit's 64 keys of query col: 16 in the lane, the rest in lanes col + 16 slot
     {
@@ -297,6 +361,17 @@ __global__ __launch_bounds__(512) void ita_lf32_attn_kernel(const ItaLongF32Args
     const float inv = 1.0f / l;
 #pragma unroll
     for (int ft = 0; ft < NFT; ++ft) c[ft] *= inv;
+    if constexpr (TAPS) {
+      if (ri >= 0 && slot == 0) {
+        if (tp.row_max) tp.row_max[(size_t)b * tp.n_rows + ri] = m;
+        if (tp.row_sum) tp.row_sum[(size_t)b * tp.n_rows + ri] = l;
+      }
+      if (tp.ctx) {       // out_proj's operand: ctx[query][16 ft + 4 slot + 0..3]
+        float* cr = tp.ctx + ((size_t)b * a.S + (size_t)qt * 128 + t0 + col) * P + 4 * slot;
+#pragma unroll
+        for (int ft = 0; ft < NFT; ++ft) *(f32x4*)(cr + 16 * ft) = c[ft];
+      }
+    }
   }
 
   // out^T = Wo ctx^T + bo: lane (query col, slot) holds out[query][16 et + 4 slot + r]
@@ -343,5 +418,32 @@ __global__ __launch_bounds__(512) void ita_lf32_attn_kernel(const ItaLongF32Args
     float* yrow = a.y + ((size_t)b * a.S + (size_t)qt * 128 + t0 + tok) * E + qtr * EC;
 #pragma unroll
     for (int i = 0; i < EC; i += 4) *(f32x4*)(yrow + i) = (f32x4){r[i], r[i + 1], r[i + 2], r[i + 3]};
+  }
+}
+template <int E>
+__global__ __launch_bounds__(512) void ita_lf32_attn_kernel(const ItaLongF32Args a) {
+  ita_lf32_attn_body<E, false>(a, ItaLongF32TapArgs{});
+}
+template <int E>
+__global__ __launch_bounds__(512) void ita_lf32_attn_taps_kernel(const ItaLongF32Args a, const ItaLongF32TapArgs tp) {
+  ita_lf32_attn_body<E, true>(a, tp);
+}
+
+// probs[b, i, k] = ita_expf(logits[b, i, k] - row_max[b, i]) * (1.0f / row_sum[b, i]): one subtraction, ita_expf, one
+// division and one multiplication, each rounded on its own (the build keeps -ffp-contract=off).  One workgroup per
+// (frame, chosen row), 16 bytes per lane and step.  lg may be probs itself (the caller asked for no logits): a lane reads
+// the four values it then overwrites, and no other lane touches them.
+__global__ __launch_bounds__(256) void ita_lf32_probs_kernel(const float* lg, float* probs, const float* row_max,
+                                                             const float* row_sum, int S) {
+  const size_t row = blockIdx.x;
+  const float m = row_max[row], inv = 1.0f / row_sum[row];
+  const f32x4* src = (const f32x4*)(lg + row * S);
+  f32x4* dst = (f32x4*)(probs + row * S);
+  for (int i = threadIdx.x; i < S / 4; i += 256) {
+    const f32x4 v = src[i];
+    f32x4 p;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) p[r] = ita_expf(v[r] - m) * inv;
+    dst[i] = p;
   }
 }

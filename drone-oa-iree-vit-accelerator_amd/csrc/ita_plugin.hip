@@ -211,6 +211,9 @@ struct ita_context {
   // ita_mha_long_int8_taps: the row table (token -> output row, or -1), ITA_LONG_MAX_SEQ entries, and its host copy
   DevBuf<int> long_rows;
   std::vector<int> long_rows_host;
+  // ita_mha_long_f32_taps: row_max | row_sum of a call that asks for probs without them, 2 x batch x n_rows; grown on demand
+  DevBuf<float> long_rowstat;
+  size_t long_rowstat_n = 0;
   // staging for the host-buffer drop-in symbols
   DevBuf<float> dsp_in, dsp_out;
   std::vector<float> dsp_host;
@@ -865,7 +868,8 @@ namespace {
 // the refusals every long-sequence entry point shares (ITA_ERR_UNSUPPORTED, before any launch)
 int check_long(const Layer& L, int batch, int seq_len, bool taps = false) {
   if (L.attn_f32)
-    return fail(ITA_ERR_UNSUPPORTED, taps ? "this layer's attention is float32 (ITAW0003 blob): its flash kernel keeps no row probabilities, there are no taps"
+    return fail(ITA_ERR_UNSUPPORTED, taps ? "this layer's attention is float32 (ITAW0003 blob): its flash kernel keeps no row probabilities, there are no taps "
+                                            "here: ita_mha_long_f32_taps reads a float layer out"
                                           : "this layer's attention is float32 (ITAW0003 blob): no int8 long attention");
   if (seq_len < 128 || seq_len % 128 || seq_len > 65536 || batch > 65535)
     return fail(ITA_ERR_UNSUPPORTED, "seq_len must be a multiple of 128 in [128, 65536], batch <= 65535");
@@ -875,20 +879,38 @@ int check_long(const Layer& L, int batch, int seq_len, bool taps = false) {
 
 // The taps' own refusals (ITA_ERR_INVALID_ARG)
 constexpr int ITA_LONG_MAX_ROWS = 1024, ITA_LONG_MAX_SEQ = 65536;
-int check_long_taps(const ita_mha_long_taps& t, int seq_len, hipStream_t s) {
-  if (t.n_rows < 0 || t.n_rows > ITA_LONG_MAX_ROWS) return fail(ITA_ERR_INVALID_ARG, "n_rows must be in [0, 1024]");
-  if (t.n_rows > 0 && !t.rows) return fail(ITA_ERR_INVALID_ARG, "n_rows > 0 without rows");
-  for (int i = 0; i < t.n_rows; ++i)
-    if (t.rows[i] < 0 || t.rows[i] >= seq_len || (i > 0 && t.rows[i] <= t.rows[i - 1]))
+// the chosen rows of either long taps entry (ita_mha_long_taps, ita_mha_long_f32_taps: the same four row-indexed taps)
+// row_ptr: is any of logits, probs, row_max, row_sum given
+int check_long_rows(const int* rows, int n_rows, bool row_ptr, int seq_len) {
+  if (n_rows < 0 || n_rows > ITA_LONG_MAX_ROWS) return fail(ITA_ERR_INVALID_ARG, "n_rows must be in [0, 1024]");
+  if (n_rows > 0 && !rows) return fail(ITA_ERR_INVALID_ARG, "n_rows > 0 without rows");
+  for (int i = 0; i < n_rows; ++i)
+    if (rows[i] < 0 || rows[i] >= seq_len || (i > 0 && rows[i] <= rows[i - 1]))
       return fail(ITA_ERR_INVALID_ARG, "rows must be strictly increasing token indices in [0, seq_len)");
-  if (t.n_rows == 0 && (t.logits || t.probs || t.row_max || t.row_sum))
+  if (n_rows == 0 && row_ptr)
     return fail(ITA_ERR_INVALID_ARG, "logits, probs, row_max and row_sum are per chosen row: n_rows is 0");
-  auto misaligned = [](const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) != 0; };
+  return ITA_OK;
+}
+bool misaligned(const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) != 0; }
+
+int check_long_taps(const ita_mha_long_taps& t, int seq_len, hipStream_t s) {
+  if (int rc = check_long_rows(t.rows, t.n_rows, t.logits || t.probs || t.row_max || t.row_sum, seq_len)) return rc;
   if (misaligned(t.x_q, 16) || misaligned(t.out_q, 16) || misaligned(t.Q, 4) || misaligned(t.K, 4) || misaligned(t.ctx, 4) ||
       misaligned(t.logits, 4) || misaligned(t.probs, 4) || misaligned(t.row_sum, 4))
     return fail(ITA_ERR_INVALID_ARG, "x_q and out_q must be 16-byte aligned; Q, K, ctx, logits, probs and row_sum 4-byte aligned");
   if (capturing(s))
     return fail(ITA_ERR_INVALID_ARG, "ita_mha_long_int8_taps cannot run inside a stream capture (its row table is rebuilt on the host)");
+  return ITA_OK;
+}
+
+// The handle's row table for a taps call that gives rows: token -> output row, or -1; the copy has left the host vector
+// when the wait returns
+int upload_long_rows(ita_context* h, const int* rows, int n_rows, int seq_len, hipStream_t s) {
+  if (!h->long_rows) HIPCHK(h->long_rows.alloc(ITA_LONG_MAX_SEQ));
+  h->long_rows_host.assign((size_t)seq_len, -1);
+  for (int i = 0; i < n_rows; ++i) h->long_rows_host[rows[i]] = i;
+  HIPCHK(hipMemcpyAsync(h->long_rows, h->long_rows_host.data(), (size_t)seq_len * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));
   return ITA_OK;
 }
 
@@ -928,12 +950,8 @@ int launch_long(ita_context* h, int layer, const int8_t* xq, int8_t* yq, const f
     tp.xq = taps->x_q; tp.Q = taps->Q; tp.K = taps->K; tp.V = taps->V; tp.ctx = taps->ctx; tp.outq = taps->out_q;
     tp.logits = taps->logits; tp.probs = taps->probs; tp.row_max = taps->row_max; tp.row_sum = taps->row_sum;
     tp.n_rows = taps->n_rows;
-    if (taps->n_rows > 0) {   // token -> output row; the copy has left the host vector when the wait returns
-      if (!h->long_rows) HIPCHK(h->long_rows.alloc(ITA_LONG_MAX_SEQ));
-      h->long_rows_host.assign((size_t)seq_len, -1);
-      for (int i = 0; i < taps->n_rows; ++i) h->long_rows_host[taps->rows[i]] = i;
-      HIPCHK(hipMemcpyAsync(h->long_rows, h->long_rows_host.data(), (size_t)seq_len * sizeof(int), hipMemcpyHostToDevice, s));
-      HIPCHK(hipStreamSynchronize(s));
+    if (taps->n_rows > 0) {
+      if (int rc = upload_long_rows(h, taps->rows, taps->n_rows, seq_len, s)) return rc;
       tp.rowidx = h->long_rows;
     }
   }
@@ -990,14 +1008,27 @@ int ita_encoder_layer_long(ita_handle h, int layer, const float* x, float* y, in
 namespace {
 
 // The float32 long attention (ita_long_f32_kernel.h) of an ITAW0003 layer: the refusals, the workspace (the int8 long
-// path's buffer, grown the same way: K and V fragment images, 192 KB per 128-token tile), the two launches.
-int launch_long_f32(ita_context* h, int layer, const float* x, float* y, bool fuse_ln, int batch, int seq_len, hipStream_t s) {
+// path's buffer, grown the same way: K and V fragment images, 192 KB per 128-token tile), the two launches.  With taps
+// (ita_mha_long_f32_taps) the taps kernels run instead, the same bodies and the stores of ItaLongF32TapArgs, and behind
+// them the probabilities' elementwise launch.
+int launch_long_f32(ita_context* h, int layer, const float* x, float* y, bool fuse_ln, int batch, int seq_len, hipStream_t s,
+                    const struct ita_mha_long_f32_taps* taps = nullptr) {
   const Layer& L = h->w.layers[layer];
   if (!L.attn_f32)
-    return fail(ITA_ERR_UNSUPPORTED, "this layer's attention is int8 (ITAW0001 / ITAW0002 blob): ita_mha_long_int8 runs it");
+    return fail(ITA_ERR_UNSUPPORTED, taps ? "this layer's attention is int8 (ITAW0001 / ITAW0002 blob): ita_mha_long_int8_taps reads it out"
+                                          : "this layer's attention is int8 (ITAW0001 / ITAW0002 blob): ita_mha_long_int8 runs it");
   if (seq_len < 128 || seq_len % 128 || seq_len > 65536 || batch > 65535)
     return fail(ITA_ERR_UNSUPPORTED, "seq_len must be a multiple of 128 in [128, 65536], batch <= 65535");
   if (fuse_ln && !L.n1w) return fail(ITA_ERR_BAD_BLOB, "norm1 parameters missing from the blob");
+  if (taps) {   // the taps' own refusals (ITA_ERR_INVALID_ARG)
+    if (int rc = check_long_rows(taps->rows, taps->n_rows, taps->logits || taps->probs || taps->row_max || taps->row_sum, seq_len))
+      return rc;
+    if (misaligned(taps->Q, 16) || misaligned(taps->K, 16) || misaligned(taps->V, 16) || misaligned(taps->ctx, 16) ||
+        misaligned(taps->logits, 16) || misaligned(taps->probs, 16) || misaligned(taps->row_max, 4) || misaligned(taps->row_sum, 4))
+      return fail(ITA_ERR_INVALID_ARG, "Q, K, V, ctx, logits and probs must be 16-byte aligned; row_max and row_sum 4-byte aligned");
+    if (capturing(s))
+      return fail(ITA_ERR_INVALID_ARG, "ita_mha_long_f32_taps cannot run inside a stream capture (its row table is rebuilt on the host)");
+  }
   const size_t ntile = (size_t)batch * (seq_len / 128);
   const size_t img = ntile * 2 * ItaLongF32Lds::UNIT, need = 2 * img;
   if (need > h->long_ws_bytes) {
@@ -1016,10 +1047,40 @@ int launch_long_f32(ita_context* h, int layer, const float* x, float* y, bool fu
   a.B = batch; a.S = seq_len; a.fuse_ln = fuse_ln ? 1 : 0;
   const size_t cap = 2 * (size_t)h->num_cus;
   const dim3 proj_grid((unsigned)(ntile < cap ? ntile : cap)), attn_grid(seq_len / 128, batch);
+  if (!taps)
+    return with_E(h->w.hdr.E, [&](auto e) {
+      constexpr int E = decltype(e)::value;
+      if (int rc = launch<ita_lf32_proj_kernel<E>>(proj_grid, dim3(512), s, a)) return rc;
+      return launch<ita_lf32_attn_kernel<E>, ItaLongF32Lds::TOTAL>(attn_grid, dim3(512), s, a);
+    });
+  ItaLongF32TapArgs tp{};
+  tp.Q = taps->Q; tp.K = taps->K; tp.V = taps->V; tp.ctx = taps->ctx;
+  tp.n_rows = taps->n_rows;
+  const size_t nrow = (size_t)batch * taps->n_rows;
+  if (taps->n_rows > 0) {
+    if (int rc = upload_long_rows(h, taps->rows, taps->n_rows, seq_len, s)) return rc;
+    tp.rowidx = h->long_rows;
+    // the sweep's logits go to the caller's buffer, or where the probabilities will stand (turned in place below)
+    tp.logits = taps->logits ? taps->logits : taps->probs;
+    tp.row_max = taps->row_max; tp.row_sum = taps->row_sum;
+    if (taps->probs && !(taps->row_max && taps->row_sum)) {   // the probabilities need both: the handle's own pair
+      if (2 * nrow > h->long_rowstat_n) {
+        HIPCHK(hipDeviceSynchronize());
+        h->long_rowstat_n = 0;
+        HIPCHK(h->long_rowstat.alloc(2 * nrow));
+        h->long_rowstat_n = 2 * nrow;
+      }
+      if (!tp.row_max) tp.row_max = h->long_rowstat;
+      if (!tp.row_sum) tp.row_sum = h->long_rowstat + nrow;
+    }
+  }
   return with_E(h->w.hdr.E, [&](auto e) {
     constexpr int E = decltype(e)::value;
-    if (int rc = launch<ita_lf32_proj_kernel<E>>(proj_grid, dim3(512), s, a)) return rc;
-    return launch<ita_lf32_attn_kernel<E>, ItaLongF32Lds::TOTAL>(attn_grid, dim3(512), s, a);
+    if (int rc = launch<ita_lf32_proj_taps_kernel<E>>(proj_grid, dim3(512), s, a, tp)) return rc;
+    if (int rc = launch<ita_lf32_attn_taps_kernel<E>, ItaLongF32Lds::TOTAL>(attn_grid, dim3(512), s, a, tp)) return rc;
+    if (!taps->probs) return (int)ITA_OK;
+    return launch<ita_lf32_probs_kernel>(dim3((unsigned)nrow), dim3(256), s, (const float*)tp.logits, taps->probs,
+                                         (const float*)tp.row_max, (const float*)tp.row_sum, seq_len);
   });
 }
 
@@ -1028,6 +1089,13 @@ int launch_long_f32(ita_context* h, int layer, const float* x, float* y, bool fu
 int ita_mha_long_f32(ita_handle h, int layer, const float* x, float* y, int batch, int seq_len, void* stream) {
   if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
   return launch_long_f32(h, layer, x, y, false, batch, seq_len, (hipStream_t)stream);
+}
+
+int ita_mha_long_f32_taps(ita_handle h, int layer, const float* x, float* y, int batch, int seq_len,
+                          const struct ita_mha_long_f32_taps* taps, void* stream) {
+  if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
+  const struct ita_mha_long_f32_taps none{};
+  return launch_long_f32(h, layer, x, y, false, batch, seq_len, (hipStream_t)stream, taps ? taps : &none);
 }
 
 // The long form of launch_encoder's float-FFN branch: x1 = LN1(x + attn(x)) into y by the float long launches (ITAW0003)

@@ -35,7 +35,7 @@ HEAD_TIMEOUT = 1
 EXPORTED_SYMBOLS = (
     "ita_abi_version", "ita_create", "ita_destroy", "ita_load_weights", "ita_validate_blob", "ita_reserve", "ita_get_dims",
     "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_mha_long_int8", "ita_mha_long_int8_taps", "ita_encoder_layer_long", "ita_ffn_int8", "ita_ffn_int8_taps",
-    "ita_ffn_f32", "ita_get_ffn_kind", "ita_mha_f32", "ita_get_attn_kind", "ita_mha_long_f32", "ita_encoder_layer_long_f32",
+    "ita_ffn_f32", "ita_get_ffn_kind", "ita_mha_f32", "ita_get_attn_kind", "ita_mha_long_f32", "ita_mha_long_f32_taps", "ita_encoder_layer_long_f32",
     "ita_encoder_layer", "ita_tokenizer", "ita_fusion_tail", "ita_vitlstm_forward", "ita_bind_dispatch",
     "ita_profile_begin", "ita_profile_begin_sampled", "ita_profile_end", "ita_set_tail_mode", "ita_debug_encoder_stamps",
     "ita_fusion_tail_load", "ita_fusion_tail_large",
@@ -100,6 +100,15 @@ LONG_ROW_TAPS = ("logits", "probs", "row_max", "row_sum")
 LONG_MAX_ROWS = 1024
 
 
+class _MhaLongF32Taps(C.Structure):   # ita_mha_long_f32_taps
+    _fields_ = [(n, C.c_void_p) for n in ("Q", "K", "V", "ctx")] + \
+               [("rows", C.POINTER(C.c_int)), ("n_rows", C.c_int)] + \
+               [(n, C.c_void_p) for n in ("logits", "probs", "row_max", "row_sum")]
+
+
+LONG_F32_TENSOR_TAPS = ("Q", "K", "V", "ctx")
+
+
 class _FfnTaps(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("x_q", "h", "out_q")]
 
@@ -155,6 +164,7 @@ def lib():
         L.ita_mha_long_int8_taps.argtypes = [vp, i, vp, vp, i, i, C.POINTER(_MhaLongTaps), vp]
         L.ita_encoder_layer_long.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_f32.argtypes = [vp, i, vp, vp, i, i, vp]
+        L.ita_mha_long_f32_taps.argtypes = [vp, i, vp, vp, i, i, C.POINTER(_MhaLongF32Taps), vp]
         L.ita_encoder_layer_long_f32.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_vitlstm_tail.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
         L.ita_debug_softmax_rows.argtypes = [vp, vp, vp, i, vp]
@@ -690,6 +700,11 @@ class Engine:
         `layer` (encoder_layer_long, or encoder_layer_long_f32 where the layer's FFN is float), then attention_rows_long of
         `layer` for the tokens queries = [(ty, tx), ...] -> (N, len(queries), tok_h, tok_w) uint8 in the order of queries.
         Duplicate or out-of-grid queries raise ValueError."""
+        return self._attention_map_walk(frames, tok_h, tok_w, queries, layer, depth_scale, self.attention_rows_long)
+
+    def _attention_map_walk(self, frames, tok_h, tok_w, queries, layer, depth_scale, rows_fn):
+        """what attention_map_long and attention_map_long_f32 share: the query checks, tokenize_long, the encoder layers
+        below `layer`, rows_fn(tokens, sorted token indices, layer) and the un-sorting into the order of queries"""
         tok_h, tok_w = int(tok_h), int(tok_w)
         toks = []
         for ty, tx in queries:
@@ -708,7 +723,7 @@ class Engine:
             else:
                 self.encoder_layer_long(y, l, out=y)
         order = sorted(range(len(toks)), key=toks.__getitem__)
-        probs = self.attention_rows_long(y, [toks[j] for j in order], int(layer))
+        probs = rows_fn(y, [toks[j] for j in order], int(layer))
         unsort = [0] * len(order)
         for pos, j in enumerate(order):
             unsort[j] = pos
@@ -775,6 +790,46 @@ class Engine:
         _chk(lib().ita_mha_long_f32(self._h, layer, x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1],
                                     _stream_ptr(self.device)))
         return y
+
+    def _long_f32_taps(self, x, rows, layer, want):
+        """ita_mha_long_f32_taps asking for the taps named in `want` only -> (y, dict of those taps)"""
+        torch = _torch()
+        x = self._long_f32(x)
+        B, S = x.shape[0], x.shape[1]
+        rows = [int(r) for r in rows]
+        n = len(rows)
+        y = torch.empty_like(x)
+        spec = dict(Q=(B, S, self.P), K=(B, S, self.P), V=(B, S, self.P), ctx=(B, S, self.P), logits=(B, n, S),
+                    probs=(B, n, S), row_max=(B, n), row_sum=(B, n))
+        unknown = [k for k in want if k not in spec]
+        if unknown:
+            raise ITAError(f"no such long float tap: {unknown}")
+        t = {k: torch.empty(spec[k], dtype=torch.float32, device=x.device) for k in spec if k in want}
+        st = _MhaLongF32Taps(**{k: v.data_ptr() for k, v in t.items()})
+        arr = (C.c_int * max(n, 1))(*rows)
+        st.rows, st.n_rows = (arr if n else None), n
+        _chk(lib().ita_mha_long_f32_taps(self._h, layer, x.data_ptr(), y.data_ptr(), B, S, C.byref(st),
+                                         _stream_ptr(self.device)))
+        return y, t
+
+    def mha_long_f32_taps(self, x, rows=(), layer: int = 0):
+        """mha_long_f32 with its f32 tensors read out (ita_mha_long_f32_taps): x (B,S,E) f32 -> (attn(x), taps).  taps: Q,
+        K, V, ctx (B,S,P); and, for the query rows `rows` (strictly increasing token indices, at most 1024, the same of
+        every frame): logits, probs (B,n,S), row_max, row_sum (B,n).  Without rows the dict holds the four tensors only.
+        Every tap is the long kernels' own value; probs = ita_expf(logits - row_max) * (1 / row_sum), formed from them."""
+        rows = list(rows)
+        return self._long_f32_taps(x, rows, layer, LONG_F32_TENSOR_TAPS + (LONG_ROW_TAPS if rows else ()))
+
+    def attention_rows_long_f32(self, x, rows, layer: int = 0):
+        """what the tokens `rows` of a long sequence attend to in a float-attention layer: x (B,S,E) f32 -> the softmax
+        probabilities (B, len(rows), S) f32 of those query rows; rows strictly increasing, at most 1024"""
+        return self._long_f32_taps(x, rows, layer, ("probs",))[1]["probs"]
+
+    def attention_map_long_f32(self, frames, tok_h: int, tok_w: int, queries, layer: int = 0, depth_scale: Optional[float] = None):
+        """attention_map_long for a float-attention layer: tokenize_long, the encoder layers below `layer`
+        (encoder_layer_long_f32), then attention_rows_long_f32 of `layer` for the tokens queries = [(ty, tx), ...] ->
+        (N, len(queries), tok_h, tok_w) f32 in the order of queries.  Duplicate or out-of-grid queries raise ValueError."""
+        return self._attention_map_walk(frames, tok_h, tok_w, queries, layer, depth_scale, self.attention_rows_long_f32)
 
     def encoder_layer_long_f32(self, x, layer: int = 0, out=None):
         """one encoder layer with a float FFN (ITAW0002 / ITAW0003 blob) over a long sequence: x (B,S,E) f32 ->

@@ -120,7 +120,7 @@ int ita_mha_long_int8(ita_handle h, int layer, const float* x_dev, float* y_dev,
  * probs (u8: the reference's attn_weights) (B, n_rows, seq_len), 4-byte aligned, row_max (B, n_rows) s8 and row_sum (B, n_rows) s32 (the row's
  * maximum logit and the sum of 256 >> (max - logit) the probabilities are divided by).  taps == NULL: all-null taps.
  * Refusals, all before any launch, outputs and taps untouched: whatever ita_mha_long_int8 refuses, with the same status
- * (a float-attention layer: its flash kernel keeps no row probabilities); ITA_ERR_INVALID_ARG for n_rows outside
+ * (a float-attention layer: its flash kernel keeps no row probabilities, ita_mha_long_f32_taps reads it out); ITA_ERR_INVALID_ARG for n_rows outside
  * [0, 1024], n_rows > 0 without rows, rows not strictly increasing or out of range, a row-indexed pointer (logits,
  * probs, row_max, row_sum) with n_rows == 0, a misaligned tap, and for a call inside a stream capture (the row table
  * is rebuilt on the host and copied to the handle's device table on `stream` in every call that gives rows). */
@@ -159,8 +159,9 @@ int ita_ffn_f32(ita_handle h, int layer, const float* x_dev, float* y_dev, int b
  * blob: the float graph, models/ITA_single_layer_upsample_shuffle/model.py, nothing quantised).  ita_mha_int8 / _taps,
  * ita_mha_q8, ita_mha_long_q8, ita_mha_long_int8, ita_encoder_layer_long, ita_debug_encoder_stamps and the drop-in
  * ITASelfAttention_workgroup on an F32 layer, and
- * ita_mha_f32 / ita_mha_long_f32 on an INT8 layer, fail with ITA_ERR_UNSUPPORTED; each message names the sibling entry
- * (ita_mha_long_int8 <-> ita_mha_long_f32, ita_encoder_layer_long <-> ita_encoder_layer_long_f32). */
+ * ita_mha_f32 / ita_mha_long_f32 / ita_mha_long_f32_taps on an INT8 layer, fail with ITA_ERR_UNSUPPORTED; each message names the
+ * sibling entry (ita_mha_long_int8 <-> ita_mha_long_f32, ita_mha_long_int8_taps <-> ita_mha_long_f32_taps,
+ * ita_encoder_layer_long <-> ita_encoder_layer_long_f32). */
 enum { ITA_ATTN_INT8 = 0, ITA_ATTN_F32 = 1 };
 int ita_get_attn_kind(ita_handle h, int layer, int* kind);
 /* the float32 attention block of layer `layer` alone (no residual, no LayerNorm), ITASelfAttention.forward
@@ -176,6 +177,34 @@ int ita_mha_f32(ita_handle h, int layer, const float* x_dev, float* y_dev, int b
  * grows on demand (not inside a stream capture: ITA_ERR_INVALID_ARG).  A frame's result does not depend on the batch it
  * runs in; x_dev may equal y_dev. */
 int ita_mha_long_f32(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_len, void* stream);
+/* ita_mha_long_f32 with the stage tensors and, for chosen query rows, the attention rows read out -- the float sibling of
+ * ita_mha_long_int8_taps: y is what ita_mha_long_f32 writes, bit for bit, and every tap is the f32 register value the two
+ * launches compute with (the taps kernels are the production kernels' bodies plus stores).  Device pointers, natural
+ * row-major layouts, any of them may be NULL: Q, K, V (B, seq_len, P): the projections' accumulators; ctx (B, seq_len, P):
+ * the context after the multiplication by 1 / row_sum, out_proj's operand.  rows: a HOST array of n_rows strictly
+ * increasing token indices in [0, seq_len), the same query rows of every frame; for each, logits (B, n_rows, seq_len): the
+ * sweep's Q K^T row before the exponential; row_max (B, n_rows): the final running maximum; row_sum (B, n_rows): the
+ * final running sum, whose reciprocal scales the context; probs (B, n_rows, seq_len).  The flash sweep never holds a
+ * probability, so probs is DEFINED from the three production values, by a small elementwise launch behind the attention:
+ *     probs = ita_expf(logits - row_max) * (1.0f / row_sum)
+ * one subtraction, the library's exp (oracle: ita_oracle_expf), one division and one multiplication, each a separately
+ * rounded f32 operation.  Q, K, V, ctx, logits and probs must be 16-byte aligned, row_max and row_sum 4-byte.
+ * taps == NULL: all-null taps.  Refusals, all before any launch, outputs and taps untouched: whatever ita_mha_long_f32
+ * refuses, with the same status (an int8-attention layer: ita_mha_long_int8_taps reads it out); ITA_ERR_INVALID_ARG for
+ * n_rows outside [0, 1024], n_rows > 0 without rows, rows not strictly increasing or out of range, a row-indexed pointer
+ * (logits, probs, row_max, row_sum) with n_rows == 0, a misaligned tap, and for a call inside a stream capture (the row
+ * table is rebuilt on the host and copied to the handle's device table on `stream` in every call that gives rows).
+ * The struct has a tag and no typedef name -- that identifier is the entry's -- so callers write
+ * `struct ita_mha_long_f32_taps`. */
+struct ita_mha_long_f32_taps {
+  float *Q, *K, *V, *ctx;        /* (B, seq_len, P) f32, natural row-major, any may be NULL */
+  const int* rows;               /* HOST array, strictly increasing token indices in [0, seq_len) */
+  int n_rows;                    /* 0 .. 1024 */
+  float *logits, *probs;         /* (B, n_rows, seq_len) */
+  float *row_max, *row_sum;      /* (B, n_rows) */
+};
+int ita_mha_long_f32_taps(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_len,
+                          const struct ita_mha_long_f32_taps* taps, void* stream);
 /* The long form of ita_encoder_layer for a layer with a float FFN: y = LN2(x1 + ffn(x1)), x1 = LN1(x + attn(x)) on
  * (B, seq_len, E) f32 rows; x_dev may equal y_dev.  Attention + residual + LN1 are the two launches of ita_mha_long_f32
  * (ITAW0003 blob) or of ita_mha_long_int8 (ITAW0002 blob, with that entry's refusals); the float FFN + residual + LN2
