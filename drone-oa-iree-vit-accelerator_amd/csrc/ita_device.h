@@ -22,6 +22,22 @@
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// Buffer resource over everything from p on (raw, no bounds in use: the callers keep their offsets below 2 GB).  p must be
+// wave-uniform, the per-lane part of an address goes into the byte offset of the load / store.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t ita_rsrc(const void* p) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, 0x7FFFFFFF, 0x00020000);
+}
+constexpr int ITA_SC1 = 16;   // buffer load / store cache policy: write-through store, L1-bypassing load
+
+// Write-through hand-overs: what one launch of a step writes for the NEXT launch to read leaves the
+// XCD's L2 while the producer still computes when it is stored sc1, instead of as dirty lines at the kernel boundary.
+// 16 bytes to base + byte_off; without WRITE_THROUGH the same buffer store with no cache policy.
+template <bool WRITE_THROUGH>
+__device__ __forceinline__ void ita_store16(__amdgpu_buffer_rsrc_t base, int byte_off, u32x4 v) {
+  __builtin_amdgcn_raw_buffer_store_b128(v, base, byte_off, 0, WRITE_THROUGH ? ITA_SC1 : 0);
+}
 
 #define ITA_MAGIC_F 12582912.0f   /* 1.5 * 2^23: adding it rounds to nearest-even integer */
 #define ITA_MAGIC_I 0x4B400000
@@ -634,4 +650,20 @@ __device__ __forceinline__ void st_tok_quarter(float* row, int kq, const float (
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       *(f32x4*)(row + 4 * (PQ * i + 4 * jj + kq)) = (f32x4){t[16 * jj + 4 * i], t[16 * jj + 4 * i + 1], t[16 * jj + 4 * i + 2], t[16 * jj + 4 * i + 3]};
+}
+// the same for rows that the next launch reads: write-through stores of token `token` of the frame whose rows start at
+// `frame` (wave-uniform, so the byte offsets stay below 64 KB at any batch size)
+template <int E>
+__device__ __forceinline__ void st_tok_quarter_next(__amdgpu_buffer_rsrc_t frame, int token, int kq, const float (&y)[E / 4]) {
+  constexpr int PQ = E / 16, NJ = E / 64;
+  float t[E / 4];
+#pragma unroll
+  for (int i = 0; i < E / 4; ++i) t[i] = y[i];
+  tok_items_transpose<E>(t);
+#pragma unroll
+  for (int jj = 0; jj < NJ; ++jj)
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      ita_store16<true>(frame, (token * E + 4 * (PQ * i + 4 * jj + kq)) * 4,
+                        __builtin_bit_cast(u32x4, (f32x4){t[16 * jj + 4 * i], t[16 * jj + 4 * i + 1], t[16 * jj + 4 * i + 2], t[16 * jj + 4 * i + 3]}));
 }

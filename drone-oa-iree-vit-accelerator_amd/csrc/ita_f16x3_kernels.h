@@ -28,12 +28,7 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t ita_rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, 0x7FFFFFFF, 0x00020000);
-}
-constexpr int ITA_SC1 = 16;   // buffer load / store cache policy: write-through store, L1-bypassing load
+// (u32x4, ita_rsrc and ITA_SC1, the sc1 buffer store forms' pieces: ita_device.h)
 
 __device__ __forceinline__ void split_f16(float x, _Float16& hi, _Float16& lo) {
   hi = (_Float16)x;

@@ -680,32 +680,46 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       for (int i = 0; i < EC; ++i) yv[i] = x1[i];
     }
     {
-      if (a.y) st_tok_quarter<E>(a.y + ((size_t)b * S + token) * E, kq, yv);
-      if (!(ITA_ABLATE & 128) && a.y_hi) {
+      // Both outputs are read by the next launch, from other XCDs: write-through stores (ita_device.h) on a resource per
+      // frame, so the byte offsets stay below 32 KB (f32 rows: 64 KB) at any batch size.  The planes of E = 128 stay plain:
+      // a lane's 64 bytes of a row leave as four stores 64 bytes apart, quarter lines that cost that launch +8 us written
+      // through (E = 64: half lines, -0.9 us; DESIGN.md section 4, profiles/handover_ab.txt)
+      constexpr bool PLANES_WT = E == 64;
+      float* y_f32 = a.y;
+      _Float16* y_hi = a.y_hi;
+      // (opaque copies: the two null tests are then scalar compares here, per frame, instead of two lane masks held in SGPR pairs
+      // across the frame loop -- the four SGPRs the resource needs; without them E = 64 with the tokenizer spills two SGPRs)
+      asm volatile("" : "+s"(y_f32), "+s"(y_hi));
+      if (y_f32) st_tok_quarter_next<E>(ita_rsrc(y_f32 + (size_t)b * S * E), token, kq, yv);
+      if (!(ITA_ABLATE & 128) && y_hi) {
         typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+        h8 vh[EC / 8], vl[EC / 8];
 #pragma unroll
-        for (int i = 0; i < EC; i += 8) {
-          h8 vh, vl;
+        for (int i = 0; i < EC; ++i) {
+          const _Float16 hh = (_Float16)yv[i];
+          vh[i >> 3][i & 7] = hh;
+          vl[i >> 3][i & 7] = (_Float16)(yv[i] - (float)hh);
+        }
+        const int po = token * E + EC * kq;   // halves from the frame's row on
+        if constexpr (ITA_ABLATE & 256) {   // values stay live, one 2-byte store instead of two 16-byte ones
 #pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const _Float16 hh = (_Float16)yv[i + j];
-            vh[j] = hh;
-            vl[j] = (_Float16)(yv[i + j] - (float)hh);
-          }
-          const size_t po = (size_t)b * a.ld_planes + token * E + EC * kq + i;
-          if constexpr (ITA_ABLATE & 256) {   // values stay live, one 2-byte store instead of two 16-byte ones
-            a.y_hi[po] = vh[0] + vh[1] + vh[2] + vh[3] + vh[4] + vh[5] + vh[6] + vh[7] + vl[0] + vl[1] + vl[2] + vl[3] + vl[4] + vl[5] + vl[6] + vl[7];
-          } else {
-            *(h8*)(a.y_hi + po) = vh;
-            *(h8*)(a.y_lo + po) = vl;
-          }
+          for (int i = 0; i < EC / 8; ++i)
+            a.y_hi[(size_t)b * a.ld_planes + po + 8 * i] = vh[i][0] + vh[i][1] + vh[i][2] + vh[i][3] + vh[i][4] + vh[i][5] + vh[i][6] + vh[i][7] + vl[i][0] + vl[i][1] + vl[i][2] + vl[i][3] + vl[i][4] + vl[i][5] + vl[i][6] + vl[i][7];
+        } else {
+          // one plane after the other: one resource (four SGPRs) live at a time
+          const __amdgpu_buffer_rsrc_t f_hi = ita_rsrc(y_hi + (size_t)b * a.ld_planes);
+#pragma unroll
+          for (int i = 0; i < EC / 8; ++i) ita_store16<PLANES_WT>(f_hi, (po + 8 * i) * 2, __builtin_bit_cast(u32x4, vh[i]));
+          const __amdgpu_buffer_rsrc_t f_lo = ita_rsrc(a.y_lo + (size_t)b * a.ld_planes);
+#pragma unroll
+          for (int i = 0; i < EC / 8; ++i) ita_store16<PLANES_WT>(f_lo, (po + 8 * i) * 2, __builtin_bit_cast(u32x4, vl[i]));
         }
       }
     }
     ITA_SSTAMP(11);
     // ---------------- the next frame's tokens: blend and the four conv tiles (each: six int8 MFMAs + 24 VALU + 8 LDS reads) here,
     // after LayerNorm2 and the output stores, where the kernel has registers to spare -- nothing of the tokenizer is live across
-    // the FFN (244 VGPRs).  Measured on one box, encoder launch of 1024 frames: round-2 kernel 58.4 us, this placement 52.1; the
+    // the FFN (246 VGPRs).  Measured on one box, encoder launch of 1024 frames: round-2 kernel 58.4 us, this placement 52.1; the
     // blend after B2 52.5, the four tiles right after the blend in front of out_proj 52.9, the tiles spread over the out_proj /
     // fc1 steps +1.5 (~20 more live registers at the kernel's tightest point: 7 spilled).  Those placements were removed.
     if constexpr (TOK != 0 && !(ITA_ABLATE & 4)) {

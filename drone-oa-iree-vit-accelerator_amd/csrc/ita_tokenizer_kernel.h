@@ -262,7 +262,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void i
         for (int i = 0; i < 4; ++i) xr[4 * ct + i] = acc[ct][i];
     }
     layernorm_q16<E>(xr, lnp, lnp + E, EC * kq);
-    st_tok_quarter<E>(a.tokens + ((size_t)b * S + wave * 16 + qi) * E, kq, xr);   // 64 contiguous bytes per token and store
+    // 64 contiguous bytes per token and store; the encoder launch behind this one reads them: write-through
+    st_tok_quarter_next<E>(ita_rsrc(a.tokens + (size_t)b * S * E), wave * 16 + qi, kq, xr);
     __builtin_amdgcn_wave_barrier();      // the window is rewritten for the next frame only after these reads were issued
   }
 }
