@@ -27,6 +27,7 @@
 #include "ita_int8_kernels.h"
 #include "ita_stream_kernel.h"
 #include "ita_long_attn_kernel.h"
+#include "ita_long_stats_kernel.h"
 #include "ita_ffn_f32_kernel.h"
 #include "ita_attn_f32_kernel.h"
 #include "ita_long_f32_kernel.h"
@@ -914,6 +915,33 @@ int upload_long_rows(ita_context* h, const int* rows, int n_rows, int seq_len, h
   return ITA_OK;
 }
 
+// The handle's long-attention workspace, for ntile tiles of 128 tokens: it grows outside a stream capture only (a captured
+// graph keeps raw pointers into it), behind a device synchronisation
+int ensure_long_ws(ita_context* h, size_t ntile, hipStream_t s) {
+  const size_t need = ntile * (3 * 24576 + 192 * 4);
+  if (need <= h->long_ws_bytes) return ITA_OK;
+  if (capturing(s))
+    return fail(ITA_ERR_INVALID_ARG, "the long-attention workspace cannot grow inside a stream capture; run one call first");
+  HIPCHK(hipDeviceSynchronize());
+  h->long_ws_bytes = 0;
+  HIPCHK(h->long_ws.alloc(need));
+  h->long_ws_bytes = need;
+  return ITA_OK;
+}
+
+// The two long kernels' arguments over that workspace (the I/O pointers and fuse_ln are the caller's to set)
+ItaLongArgs long_args(ita_context* h, const Layer& L, size_t ntile, int batch, int seq_len) {
+  ItaLongArgs a{};
+  a.image = L.simg_mha;
+  a.qfrag = h->long_ws; a.kimg = a.qfrag + ntile * 24576; a.vimg = a.kimg + ntile * 24576;
+  a.csum = (int*)(a.vimg + ntile * 24576);
+  a.mq = L.ascal[ITA_A_MQ]; a.mk = L.ascal[ITA_A_MK]; a.mv = L.ascal[ITA_A_MV]; a.ml = L.ascal[ITA_A_ML];
+  a.mc = L.ascal[ITA_A_MC]; a.mo = L.ascal[ITA_A_MO];
+  a.inv_sx = L.ascal[ITA_A_INV_SX]; a.so = L.ascal[ITA_A_SO];
+  a.B = batch; a.S = seq_len;
+  return a;
+}
+
 // What the long-sequence entry points share: the refusals, the workspace, the two launches.
 // Int8 form: xq -> yq.  F32 form (x non-null): x -> y, with fuse_ln + residual + LayerNorm1; with taps (f32 form only)
 // the taps kernels run instead: the same bodies and the stores of ita_mha_long_taps.
@@ -926,23 +954,9 @@ int launch_long(ita_context* h, int layer, const int8_t* xq, int8_t* yq, const f
     if (int rc = check_long_taps(*taps, seq_len, s)) return rc;
   // the logits of a long row still fit the 16-bit travel format: same bound as stream_range_ok (per key, not per row)
   const size_t ntile = (size_t)batch * (seq_len / 128);
-  const size_t need = ntile * (3 * 24576 + 192 * 4);
-  if (need > h->long_ws_bytes) {
-    if (capturing(s))
-      return fail(ITA_ERR_INVALID_ARG, "the long-attention workspace cannot grow inside a stream capture; run one call first");
-    HIPCHK(hipDeviceSynchronize());
-    h->long_ws_bytes = 0;
-    HIPCHK(h->long_ws.alloc(need));
-    h->long_ws_bytes = need;
-  }
-  ItaLongArgs a{};
-  a.image = L.simg_mha; a.xq = xq; a.yq = yq; a.x = x; a.y = y;
-  a.qfrag = h->long_ws; a.kimg = a.qfrag + ntile * 24576; a.vimg = a.kimg + ntile * 24576;
-  a.csum = (int*)(a.vimg + ntile * 24576);
-  a.mq = L.ascal[ITA_A_MQ]; a.mk = L.ascal[ITA_A_MK]; a.mv = L.ascal[ITA_A_MV]; a.ml = L.ascal[ITA_A_ML];
-  a.mc = L.ascal[ITA_A_MC]; a.mo = L.ascal[ITA_A_MO];
-  a.inv_sx = L.ascal[ITA_A_INV_SX]; a.so = L.ascal[ITA_A_SO]; a.fuse_ln = fuse_ln ? 1 : 0;
-  a.B = batch; a.S = seq_len;
+  if (int rc = ensure_long_ws(h, ntile, s)) return rc;
+  ItaLongArgs a = long_args(h, L, ntile, batch, seq_len);
+  a.xq = xq; a.yq = yq; a.x = x; a.y = y; a.fuse_ln = fuse_ln ? 1 : 0;
   const bool fast = L.fast_sites == ITA_SITES_ALL;
   const dim3 proj_grid(ntile < (size_t)h->num_cus ? (int)ntile : h->num_cus), attn_grid(seq_len / 128, batch);
   ItaLongTapArgs tp{};
@@ -990,6 +1004,45 @@ int ita_mha_long_int8_taps(ita_handle h, int layer, const float* x, float* y, in
   if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
   const ita_mha_long_taps none{};
   return launch_long(h, layer, nullptr, nullptr, x, y, false, batch, seq_len, (hipStream_t)stream, taps ? taps : &none);
+}
+
+// The production projection launch (f32 form), then ita_long_stats_kernel over its workspace: no y, no A.V, no out_proj
+int ita_mha_long_int8_stats(ita_handle h, int layer, const float* x, int batch, int seq_len, const ita_mha_long_stats* st,
+                            void* stream) {
+  if (int rc = check(h, batch)) return rc;
+  if (!x || !st || layer < 0 || layer >= h->w.hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
+  const Layer& L = h->w.layers[layer];
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = check_long(L, batch, seq_len)) return rc;
+  if (!st->row_max && !st->row_sum && !st->row_mass && !st->row_nnz && !st->col_mass && !st->col_nnz)
+    return fail(ITA_ERR_INVALID_ARG, "ita_mha_long_int8_stats: all six outputs are null");
+  if (misaligned(st->row_sum, 4) || misaligned(st->row_mass, 4) || misaligned(st->row_nnz, 4) || misaligned(st->col_mass, 4) ||
+      misaligned(st->col_nnz, 4))
+    return fail(ITA_ERR_INVALID_ARG, "row_sum, row_mass, row_nnz, col_mass and col_nnz must be 4-byte aligned");
+  const size_t ntile = (size_t)batch * (seq_len / 128);
+  if (int rc = ensure_long_ws(h, ntile, s)) return rc;
+  ItaLongArgs a = long_args(h, L, ntile, batch, seq_len);
+  a.x = x;
+  ItaLongStatsArgs sa{};
+  sa.qfrag = a.qfrag; sa.kimg = a.kimg; sa.ml = a.ml; sa.B = batch; sa.S = seq_len;
+  sa.row_max = st->row_max; sa.row_sum = st->row_sum; sa.row_mass = st->row_mass; sa.row_nnz = st->row_nnz;
+  sa.col_mass = st->col_mass; sa.col_nnz = st->col_nnz;
+  // the kernel ADDS into the column arrays: they are zeroed on the stream first, by a kernel (inside a stream capture the
+  // call is kernel nodes only)
+  if (sa.col_mass || sa.col_nnz) {
+    const size_t n = (size_t)batch * seq_len, blocks = (n + 255) / 256;
+    if (int rc = launch<ita_long_stats_zero_kernel>(dim3(blocks < 2048 ? (int)blocks : 2048), dim3(256), s, sa.col_mass, sa.col_nnz, n))
+      return rc;
+  }
+  const bool fast = L.fast_sites == ITA_SITES_ALL;
+  const dim3 proj_grid(ntile < (size_t)h->num_cus ? (int)ntile : h->num_cus), grid(seq_len / 128, batch);
+  auto run = [&](auto e, auto fst) {
+    constexpr int E = decltype(e)::value;
+    constexpr bool FAST = decltype(fst)::value;
+    if (int rc = launch<ita_long_proj_kernel<FAST, E, true>, ItaStreamLds<E, false, false>::TOTAL>(proj_grid, dim3(512), s, a)) return rc;
+    return launch<ita_long_stats_kernel<FAST>, ItaLongStatsLds::TOTAL>(grid, dim3(512), s, sa);
+  };
+  return with_E(h->w.hdr.E, [&](auto e) { return fast ? run(e, std::true_type{}) : run(e, std::false_type{}); });
 }
 
 // x1 = LN1(x + attn(x)) into y by the two long launches, then the FFN block + residual + LN2 in place on y: the FFN is per

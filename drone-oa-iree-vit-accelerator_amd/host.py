@@ -34,7 +34,7 @@ HEAD_TIMEOUT = 1
 
 EXPORTED_SYMBOLS = (
     "ita_abi_version", "ita_create", "ita_destroy", "ita_load_weights", "ita_validate_blob", "ita_reserve", "ita_get_dims",
-    "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_mha_long_int8", "ita_mha_long_int8_taps", "ita_encoder_layer_long", "ita_ffn_int8", "ita_ffn_int8_taps",
+    "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_mha_long_int8", "ita_mha_long_int8_taps", "ita_mha_long_int8_stats", "ita_encoder_layer_long", "ita_ffn_int8", "ita_ffn_int8_taps",
     "ita_ffn_f32", "ita_get_ffn_kind", "ita_mha_f32", "ita_get_attn_kind", "ita_mha_long_f32", "ita_mha_long_f32_taps", "ita_encoder_layer_long_f32",
     "ita_encoder_layer", "ita_tokenizer", "ita_fusion_tail", "ita_vitlstm_forward", "ita_bind_dispatch",
     "ita_profile_begin", "ita_profile_begin_sampled", "ita_profile_end", "ita_set_tail_mode", "ita_debug_encoder_stamps",
@@ -100,6 +100,13 @@ LONG_ROW_TAPS = ("logits", "probs", "row_max", "row_sum")
 LONG_MAX_ROWS = 1024
 
 
+class _MhaLongStats(C.Structure):     # ita_mha_long_stats
+    _fields_ = [(n, C.c_void_p) for n in ("row_max", "row_sum", "row_mass", "row_nnz", "col_mass", "col_nnz")]
+
+
+LONG_STATS = ("row_max", "row_sum", "row_mass", "row_nnz", "col_mass", "col_nnz")
+
+
 class _MhaLongF32Taps(C.Structure):   # ita_mha_long_f32_taps
     _fields_ = [(n, C.c_void_p) for n in ("Q", "K", "V", "ctx")] + \
                [("rows", C.POINTER(C.c_int)), ("n_rows", C.c_int)] + \
@@ -162,6 +169,7 @@ def lib():
         L.ita_mha_long_q8.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_int8.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_int8_taps.argtypes = [vp, i, vp, vp, i, i, C.POINTER(_MhaLongTaps), vp]
+        L.ita_mha_long_int8_stats.argtypes = [vp, i, vp, i, i, C.POINTER(_MhaLongStats), vp]
         L.ita_encoder_layer_long.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_f32.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_f32_taps.argtypes = [vp, i, vp, vp, i, i, C.POINTER(_MhaLongF32Taps), vp]
@@ -702,9 +710,54 @@ class Engine:
         Duplicate or out-of-grid queries raise ValueError."""
         return self._attention_map_walk(frames, tok_h, tok_w, queries, layer, depth_scale, self.attention_rows_long)
 
+    def _long_stats(self, x, layer, want):
+        """ita_mha_long_int8_stats asking for the statistics named in `want` only -> dict of those"""
+        torch = _torch()
+        x = self._long_f32(x)
+        B, S = x.shape[0], x.shape[1]
+        unknown = [k for k in want if k not in LONG_STATS]
+        if unknown:
+            raise ITAError(f"no such long statistic: {unknown}")
+        t = {k: torch.empty((B, S), dtype=torch.int8 if k == "row_max" else torch.int32, device=x.device)
+             for k in LONG_STATS if k in want}
+        st = _MhaLongStats(**{k: v.data_ptr() for k, v in t.items()})
+        _chk(lib().ita_mha_long_int8_stats(self._h, layer, x.data_ptr(), B, S, C.byref(st), _stream_ptr(self.device)))
+        return t
+
+    def attention_stats_long(self, x, layer: int = 0):
+        """row and column statistics of the whole S x S integer-softmax matrix of a long sequence, which is never held
+        (ita_mha_long_int8_stats): x (B,S,E) f32 -> dict of (B,S) tensors.  Per query row: row_max int8, row_sum int32 (as
+        mha_long_taps has them), row_mass int32 = sum of the row's uint8 probabilities (256 if nothing was lost, 0 for a row
+        the integer softmax killed), row_nnz int32 = keys the row still sees.  Per key: col_mass int32 = attention received
+        from all queries, col_nnz int32 = queries that see the key.  Equal to attention_stats_ref.stats."""
+        return self._long_stats(x, layer, LONG_STATS)
+
+    def attention_received_long(self, x, layer: int = 0):
+        """attention received by every token of a long sequence: x (B,S,E) f32 -> col_mass (B,S) int32, the column sums
+        of the uint8 probabilities over all S queries"""
+        return self._long_stats(x, layer, ("col_mass",))["col_mass"]
+
+    def attention_received_map_long(self, frames, tok_h: int, tok_w: int, layer: int = 0, depth_scale: Optional[float] = None):
+        """attention received on the token grid of camera frames: tokenize_long, the encoder layers below `layer`, then
+        attention_received_long of `layer` -> (N, tok_h, tok_w) int32"""
+        y = self._tokens_below(frames, int(tok_h), int(tok_w), layer, depth_scale)
+        return self.attention_received_long(y, int(layer)).reshape(y.shape[0], int(tok_h), int(tok_w))
+
+    def _tokens_below(self, frames, tok_h, tok_w, layer, depth_scale):
+        """tokenize_long and the encoder layers below `layer`: the token rows that layer's attention reads"""
+        if not 0 <= int(layer) < self.num_layers:
+            raise ValueError(f"layer {layer} out of range")
+        y = self.tokenize_long(frames, tok_h, tok_w, depth_scale)
+        for l in range(int(layer)):
+            if self.ffn_kind(l) == FFN_F32:
+                self.encoder_layer_long_f32(y, l, out=y)
+            else:
+                self.encoder_layer_long(y, l, out=y)
+        return y
+
     def _attention_map_walk(self, frames, tok_h, tok_w, queries, layer, depth_scale, rows_fn):
-        """what attention_map_long and attention_map_long_f32 share: the query checks, tokenize_long, the encoder layers
-        below `layer`, rows_fn(tokens, sorted token indices, layer) and the un-sorting into the order of queries"""
+        """what attention_map_long and attention_map_long_f32 share: the query checks, the walk below `layer`
+        (_tokens_below), rows_fn(tokens, sorted token indices, layer) and the un-sorting into the order of queries"""
         tok_h, tok_w = int(tok_h), int(tok_w)
         toks = []
         for ty, tx in queries:
@@ -714,14 +767,7 @@ class Engine:
             toks.append(ty * tok_w + tx)
         if len(set(toks)) != len(toks):
             raise ValueError("duplicate queries")
-        if not 0 <= int(layer) < self.num_layers:
-            raise ValueError(f"layer {layer} out of range")
-        y = self.tokenize_long(frames, tok_h, tok_w, depth_scale)
-        for l in range(int(layer)):
-            if self.ffn_kind(l) == FFN_F32:
-                self.encoder_layer_long_f32(y, l, out=y)
-            else:
-                self.encoder_layer_long(y, l, out=y)
+        y = self._tokens_below(frames, tok_h, tok_w, layer, depth_scale)
         order = sorted(range(len(toks)), key=toks.__getitem__)
         probs = rows_fn(y, [toks[j] for j in order], int(layer))
         unsort = [0] * len(order)

@@ -53,7 +53,7 @@ int ita_destroy(ita_handle h);
  * A layer with H > 1 runs on the block kernels (ita_mha_kernel<E, H>, then the FFN block) behind the stand-alone tokenizer;
  * every entry point below serves it except those that need the one-head stream kernel, which return
  * ITA_ERR_UNSUPPORTED before any launch: ita_mha_q8, ita_mha_long_q8, ita_mha_long_int8, ita_mha_long_int8_taps,
- * ita_encoder_layer_long, ita_debug_encoder_stamps, ita_vitlstm_forward_slots (and ita_mha_long_f32 / ita_encoder_layer_long_f32, which take
+ * ita_mha_long_int8_stats, ita_encoder_layer_long, ita_debug_encoder_stamps, ita_vitlstm_forward_slots (and ita_mha_long_f32 / ita_encoder_layer_long_f32, which take
  * float layers only).
  * The reference pre-loads weights into the accelerator out of band
  * (docs/HOW-TO-run-the-full-project-workflow.md:55); this is that step. */
@@ -133,6 +133,23 @@ typedef struct ita_mha_long_taps {
 } ita_mha_long_taps;
 int ita_mha_long_int8_taps(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_len,
                            const ita_mha_long_taps* taps, void* stream);
+/* Row and column statistics of the WHOLE seq_len x seq_len probability matrix of ita_mha_long_int8 (H = 1), which is never
+ * held: x (B, seq_len, E) f32 is read only, there is no y.  Per query row i (all (B, seq_len), device pointers, any may be
+ * NULL): row_max s8 and row_sum s32 as ita_mha_long_taps has them, row_mass s32 = sum_j p[i, j] (256 if the integer
+ * softmax lost nothing, 0 for a row it killed), row_nnz s32 = #{j : p[i, j] > 0}.  Per key column j: col_mass s32 =
+ * sum_i p[i, j] ("attention received", at most 255 * 65 536), col_nnz s32 = #{i : p[i, j] > 0}.  Equal, bit for bit, to
+ * attention_stats_ref.py.  The production projection launch, then one sweep kernel that repeats the three Q K^T sweeps
+ * and reduces the probabilities instead of multiplying them with V; the column arrays are zeroed on `stream` (a small kernel:
+ * a captured call is kernel nodes only) and added to with integer atomics, so the result does not depend on the order of arrival.  Refusals, all before any
+ * launch or memset, outputs untouched: whatever ita_mha_long_int8 refuses, with the same status; ITA_ERR_INVALID_ARG for
+ * a NULL x_dev or stats, all six pointers NULL, or an s32 output that is not 4-byte aligned.  Workspace of
+ * ita_mha_long_q8: once it holds the call there is no host synchronisation and no allocation, the call may be captured. */
+typedef struct ita_mha_long_stats {
+  int8_t* row_max; int* row_sum; int* row_mass; int* row_nnz;   /* (batch, seq_len) each, may be NULL */
+  int* col_mass; int* col_nnz;                                    /* (batch, seq_len) each, may be NULL */
+} ita_mha_long_stats;
+int ita_mha_long_int8_stats(ita_handle h, int layer, const float* x_dev, int batch, int seq_len,
+                            const ita_mha_long_stats* stats, void* stream);
 /* The long form of ita_encoder_layer: y = LN2(x1 + ffn(x1)), x1 = LN1(x + attn(x)) on (B, seq_len, E) f32 rows; x_dev may
  * equal y_dev.  Attention + residual + LN1 are the two long launches (x1 goes to y), the FFN + residual + LN2 then run in
  * place on y, 128 rows per block (ita_ffn_int8's kernel: the FFN is per token).  Shape limits, workspace and refusals of
