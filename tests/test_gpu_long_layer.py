@@ -12,6 +12,7 @@ selects, i.e. which instantiation of ita_long_proj_kernel / ita_long_attn_kernel
     E = 64   blocks_E64_seed2_B1   exact      vitlstm_E64_seed0_B2  FAST      vitlstm_E64_seed1_B2, _seed2_B2  exact
     E = 128  blocks_E128_seed0_B1  exact (site O fails)     blocks_E128_seed1_B1  exact (site Q fails)
              vit2l_E128_s0_B2      exact, both layers       vit2l_us_E128_s1_B2   FAST, both layers
+test_long_f32_quantiser_edges gives the f32 entries ties, saturating and zero tokens on the FAST and the exact one of each E;
 so both forms run at both E, in the int8 form (E = 128 exact: tests/test_gpu_parity.py; E = 128 FAST: vit2l_us here) and
 in the f32 form."""
 import functools
@@ -162,6 +163,47 @@ def test_encoder_layer_long_equals_oracle(oracle, E, S, B):
             assert eng.encoder_layer_long(alias, l, out=alias) is alias
             assert torch.equal(alias, got), f"{name} layer {l}: out aliasing x"
         eng.close()
+
+
+QUANT_EDGES = [(E64_VIT[0], True), (E64_VIT[1], False), (E128_VIT, False), (E128_FAST, True)]
+
+
+@pytest.mark.parametrize("name,fast", QUANT_EDGES)
+def test_long_f32_quantiser_edges(oracle, name, fast):
+    """the long kernels' f32 input at the quantiser's edges, which _long_f32's offsets of (-0.4, 0.4) never reach: zero
+    tokens, saturating +-50 tokens, a 1e30 token, exact ties 0.5 s and 1.5 s (to even: 0 and 2), a token scaled by 30, among
+    ordinary ones at S = 256; mha_long, encoder_layer_long and the statistics against the oracle composition, on the FAST
+    and on the exact fixture of each E"""
+    from drone_oa_iree_vit_accelerator_amd import attention_stats_ref as asr
+    E, _, t, fp, blob = _case(name)
+    eng = host.Engine(blob, device=0)
+    forms = eng.layer_forms(0)
+    assert forms["fast"] == fast and forms["attn_image"], (name, forms)
+    S, B = 256, 2
+    x = _long_f32(S + B, B, S, E, t)
+    s = np.float32(float(params.load_fixture(golden_files(name + ".npz")[0])["attn0.quant.scale"]))
+    x[0, 0:3], x[0, 3:6], x[0, 6:9] = 0.0, 50.0, -50.0
+    x[0, 130] = 1e30
+    x[0, 140], x[0, 141] = np.float32(0.5) * s, np.float32(1.5) * s
+    x[0, 150] *= 30.0
+    x[1, 127:129], x[1, 200], x[1, 201] = 0.0, -50.0, np.float32(1.5) * s
+    x[1, 255, ::2] *= 30.0
+    oy, otaps = oracle.mha(x, t, taps=True)
+    xq = otaps["x_q"]
+    assert (xq[0, 140] == 0).all() and (xq[0, 141] == 2).all() and (xq[1, 201] == 2).all()      # ties to even
+    assert (xq[0, 130] == 127).all() and (xq[0, 3:6] == 127).all() and (xq[0, 6:9] == -128).all() and (xq[0, 0:3] == 0).all()
+    assert (np.abs(xq[0, 150].astype(np.int32)) >= 127).sum() > E // 2
+    xc = _cu(x)
+    np.testing.assert_array_equal(eng.mha_long(xc).cpu().numpy(), oy, err_msg=name)
+    np.testing.assert_array_equal(eng.mha_long_q8(_cu(xq)).cpu().numpy(), otaps["out_q"], err_msg=name)
+    want = _layer(oracle, x, t, fp, 0)
+    got = eng.encoder_layer_long(xc, 0).cpu().numpy()
+    print(f"{name}: the 1e30 token's row: oracle {want[0, 130, :4]}, engine {got[0, 130, :4]}")
+    np.testing.assert_array_equal(got, want, err_msg=name)
+    st = eng.attention_stats_long(xc)
+    for k, v in asr.stats(x, t).items():
+        np.testing.assert_array_equal(st[k].cpu().numpy(), v, err_msg=f"{name} statistic {k}")
+    eng.close()
 
 
 def test_encode_long_is_the_layers_chained(oracle):
