@@ -31,6 +31,7 @@
 #include "ita_ffn_f32_kernel.h"
 #include "ita_attn_f32_kernel.h"
 #include "ita_long_f32_kernel.h"
+#include "ita_long_f32_stats_kernel.h"
 #include "ita_ingest_kernel.h"
 #include "ita_ingest_wire_kernel.h"
 #include "ita_tokenizer_long_kernel.h"
@@ -206,7 +207,8 @@ struct ita_context {
   std::vector<hipEvent_t> pipe_ev;   // ita_vitlstm_pipelined: front-done / back-done rings + fork/join
   DevBuf<float> pipe_h;              // ita_vitlstm_pipelined: second copy of (h, c), 2 x (3, pipe_cap, 128)
   int pipe_cap = 0;
-  // long-sequence attention (ita_mha_long_q8): Q fragments, K / V^T images, column sums; grown on demand
+  // long-sequence attention (ita_mha_long_q8): Q fragments, K / V^T images, column sums; the float entries' K / V images
+  // and, behind them, ita_mha_long_f32_stats' column partials; grown on demand
   DevBuf<char> long_ws;
   size_t long_ws_bytes = 0;
   // ita_mha_long_int8_taps: the row table (token -> output row, or -1), ITA_LONG_MAX_SEQ entries, and its host copy
@@ -1060,6 +1062,27 @@ int ita_encoder_layer_long(ita_handle h, int layer, const float* x, float* y, in
 
 namespace {
 
+// the refusals every long float entry point shares (ITA_ERR_UNSUPPORTED, before any launch); int8_layer: what to say of
+// an int8-attention layer, naming the sibling entry
+int check_long_f32(const Layer& L, int batch, int seq_len, const char* int8_layer) {
+  if (!L.attn_f32) return fail(ITA_ERR_UNSUPPORTED, int8_layer);
+  if (seq_len < 128 || seq_len % 128 || seq_len > 65536 || batch > 65535)
+    return fail(ITA_ERR_UNSUPPORTED, "seq_len must be a multiple of 128 in [128, 65536], batch <= 65535");
+  return ITA_OK;
+}
+
+// The handle's long workspace at `need` bytes for a float entry: as ensure_long_ws, outside a stream capture only
+int ensure_long_f32_ws(ita_context* h, size_t need, hipStream_t s) {
+  if (need <= h->long_ws_bytes) return ITA_OK;
+  if (capturing(s))
+    return fail(ITA_ERR_INVALID_ARG, "the long-attention workspace cannot grow inside a stream capture; run one call first");
+  HIPCHK(hipDeviceSynchronize());
+  h->long_ws_bytes = 0;
+  HIPCHK(h->long_ws.alloc(need));
+  h->long_ws_bytes = need;
+  return ITA_OK;
+}
+
 // The float32 long attention (ita_long_f32_kernel.h) of an ITAW0003 layer: the refusals, the workspace (the int8 long
 // path's buffer, grown the same way: K and V fragment images, 192 KB per 128-token tile), the two launches.  With taps
 // (ita_mha_long_f32_taps) the taps kernels run instead, the same bodies and the stores of ItaLongF32TapArgs, and behind
@@ -1067,11 +1090,9 @@ namespace {
 int launch_long_f32(ita_context* h, int layer, const float* x, float* y, bool fuse_ln, int batch, int seq_len, hipStream_t s,
                     const struct ita_mha_long_f32_taps* taps = nullptr) {
   const Layer& L = h->w.layers[layer];
-  if (!L.attn_f32)
-    return fail(ITA_ERR_UNSUPPORTED, taps ? "this layer's attention is int8 (ITAW0001 / ITAW0002 blob): ita_mha_long_int8_taps reads it out"
-                                          : "this layer's attention is int8 (ITAW0001 / ITAW0002 blob): ita_mha_long_int8 runs it");
-  if (seq_len < 128 || seq_len % 128 || seq_len > 65536 || batch > 65535)
-    return fail(ITA_ERR_UNSUPPORTED, "seq_len must be a multiple of 128 in [128, 65536], batch <= 65535");
+  if (int rc = check_long_f32(L, batch, seq_len,
+                              taps ? "this layer's attention is int8 (ITAW0001 / ITAW0002 blob): ita_mha_long_int8_taps reads it out"
+                                   : "this layer's attention is int8 (ITAW0001 / ITAW0002 blob): ita_mha_long_int8 runs it")) return rc;
   if (fuse_ln && !L.n1w) return fail(ITA_ERR_BAD_BLOB, "norm1 parameters missing from the blob");
   if (taps) {   // the taps' own refusals (ITA_ERR_INVALID_ARG)
     if (int rc = check_long_rows(taps->rows, taps->n_rows, taps->logits || taps->probs || taps->row_max || taps->row_sum, seq_len))
@@ -1083,15 +1104,8 @@ int launch_long_f32(ita_context* h, int layer, const float* x, float* y, bool fu
       return fail(ITA_ERR_INVALID_ARG, "ita_mha_long_f32_taps cannot run inside a stream capture (its row table is rebuilt on the host)");
   }
   const size_t ntile = (size_t)batch * (seq_len / 128);
-  const size_t img = ntile * 2 * ItaLongF32Lds::UNIT, need = 2 * img;
-  if (need > h->long_ws_bytes) {
-    if (capturing(s))
-      return fail(ITA_ERR_INVALID_ARG, "the long-attention workspace cannot grow inside a stream capture; run one call first");
-    HIPCHK(hipDeviceSynchronize());
-    h->long_ws_bytes = 0;
-    HIPCHK(h->long_ws.alloc(need));
-    h->long_ws_bytes = need;
-  }
+  const size_t img = ntile * 2 * ItaLongF32Lds::UNIT;
+  if (int rc = ensure_long_f32_ws(h, 2 * img, s)) return rc;
   ItaLongF32Args a{};
   a.x = x; a.y = y;
   a.wq = L.wqf; a.wk = L.wkf; a.wv = L.wvf; a.bq = L.bqf; a.bk = L.bkf; a.bv = L.bvf; a.wo = L.wof; a.bo = L.bof;
@@ -1149,6 +1163,54 @@ int ita_mha_long_f32_taps(ita_handle h, int layer, const float* x, float* y, int
   if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
   const struct ita_mha_long_f32_taps none{};
   return launch_long_f32(h, layer, x, y, false, batch, seq_len, (hipStream_t)stream, taps ? taps : &none);
+}
+
+// The production projection launch, then ita_lf32_stats_kernel over its K image and, for the columns, the reduction of the
+// query tiles' partials (ita_long_f32_stats_kernel.h): no y, no P.V, no out_proj.  The workspace is the float long
+// workspace (K and V images: the projection kernel writes both) and behind it the partials, (B, S/128, S) f32 and s32,
+// of a call that asks for a column statistic.
+int ita_mha_long_f32_stats(ita_handle h, int layer, const float* x, int batch, int seq_len, float p_min,
+                           const struct ita_mha_long_f32_stats* st, void* stream) {
+  // the argument rules come first: they need neither the handle's contents nor the device
+  if (!h || !x || !st) return fail(ITA_ERR_INVALID_ARG, "null handle, x_dev or stats");
+  if (!st->row_max && !st->row_sum && !st->row_gap && !st->row_nnz && !st->col_mass && !st->col_nnz)
+    return fail(ITA_ERR_INVALID_ARG, "ita_mha_long_f32_stats: all six outputs are null");
+  if (misaligned(st->row_max, 4) || misaligned(st->row_sum, 4) || misaligned(st->row_gap, 4) || misaligned(st->row_nnz, 4) ||
+      misaligned(st->col_mass, 4) || misaligned(st->col_nnz, 4))
+    return fail(ITA_ERR_INVALID_ARG, "every output must be 4-byte aligned");
+  if (!(p_min > 0.0f && p_min <= 1.0f)) return fail(ITA_ERR_INVALID_ARG, "p_min must be in (0, 1]");   // NaN fails both
+  if (int rc = check(h, batch)) return rc;
+  if (layer < 0 || layer >= h->w.hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad layer");
+  const Layer& L = h->w.layers[layer];
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = check_long_f32(L, batch, seq_len,
+                              "this layer's attention is int8 (ITAW0001 / ITAW0002 blob): ita_mha_long_int8_stats reads it out")) return rc;
+  const size_t nqt = (size_t)seq_len / 128, ntile = (size_t)batch * nqt;
+  const size_t img = ntile * 2 * ItaLongF32Lds::UNIT, part = ntile * seq_len * 4;
+  const bool cols = st->col_mass || st->col_nnz;
+  if (int rc = ensure_long_f32_ws(h, 2 * img + (cols ? 2 * part : 0), s)) return rc;
+  ItaLongF32Args a{};
+  a.x = x;
+  a.wk = L.wkf; a.wv = L.wvf; a.bk = L.bkf; a.bv = L.bvf;
+  a.kimg = (f32x4*)(char*)h->long_ws; a.vimg = (f32x4*)((char*)h->long_ws + img);
+  a.B = batch; a.S = seq_len;
+  ItaLongF32StatsArgs sa{};
+  sa.x = x; sa.wq = L.wqf; sa.bq = L.bqf; sa.kimg = a.kimg;
+  sa.B = batch; sa.S = seq_len; sa.p_min = p_min;
+  sa.row_max = st->row_max; sa.row_sum = st->row_sum; sa.row_gap = st->row_gap; sa.row_nnz = st->row_nnz;
+  if (st->col_mass) sa.part_mass = (float*)((char*)h->long_ws + 2 * img);
+  if (st->col_nnz) sa.part_nnz = (int*)((char*)h->long_ws + 2 * img + part);
+  const size_t cap = 2 * (size_t)h->num_cus;
+  const dim3 proj_grid((unsigned)(ntile < cap ? ntile : cap)), grid(seq_len / 128, batch);
+  return with_E(h->w.hdr.E, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    if (int rc = launch<ita_lf32_proj_kernel<E>>(proj_grid, dim3(512), s, a)) return rc;
+    if (int rc = launch<ita_lf32_stats_kernel<E>, ItaLongF32Lds::TOTAL>(grid, dim3(512), s, sa)) return rc;
+    if (!cols) return (int)ITA_OK;
+    const size_t n = (size_t)batch * seq_len, blocks = (n + 255) / 256;
+    return launch<ita_lf32_colsum_kernel>(dim3(blocks < 4096 ? (unsigned)blocks : 4096u), dim3(256), s, (const float*)sa.part_mass,
+                                          (const int*)sa.part_nnz, st->col_mass, st->col_nnz, (int)nqt, seq_len, n);
+  });
 }
 
 // The long form of launch_encoder's float-FFN branch: x1 = LN1(x + attn(x)) into y by the float long launches (ITAW0003)

@@ -35,7 +35,7 @@ HEAD_TIMEOUT = 1
 EXPORTED_SYMBOLS = (
     "ita_abi_version", "ita_create", "ita_destroy", "ita_load_weights", "ita_validate_blob", "ita_reserve", "ita_get_dims",
     "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_mha_long_int8", "ita_mha_long_int8_taps", "ita_mha_long_int8_stats", "ita_encoder_layer_long", "ita_ffn_int8", "ita_ffn_int8_taps",
-    "ita_ffn_f32", "ita_get_ffn_kind", "ita_mha_f32", "ita_get_attn_kind", "ita_mha_long_f32", "ita_mha_long_f32_taps", "ita_encoder_layer_long_f32",
+    "ita_ffn_f32", "ita_get_ffn_kind", "ita_mha_f32", "ita_get_attn_kind", "ita_mha_long_f32", "ita_mha_long_f32_taps", "ita_mha_long_f32_stats", "ita_encoder_layer_long_f32",
     "ita_encoder_layer", "ita_tokenizer", "ita_fusion_tail", "ita_vitlstm_forward", "ita_bind_dispatch",
     "ita_profile_begin", "ita_profile_begin_sampled", "ita_profile_end", "ita_set_tail_mode", "ita_debug_encoder_stamps",
     "ita_fusion_tail_load", "ita_fusion_tail_large",
@@ -116,6 +116,13 @@ class _MhaLongF32Taps(C.Structure):   # ita_mha_long_f32_taps
 LONG_F32_TENSOR_TAPS = ("Q", "K", "V", "ctx")
 
 
+class _MhaLongF32Stats(C.Structure):  # struct ita_mha_long_f32_stats
+    _fields_ = [(n, C.c_void_p) for n in ("row_max", "row_sum", "row_gap", "row_nnz", "col_mass", "col_nnz")]
+
+
+LONG_F32_STATS = ("row_max", "row_sum", "row_gap", "row_nnz", "col_mass", "col_nnz")
+
+
 class _FfnTaps(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("x_q", "h", "out_q")]
 
@@ -173,6 +180,7 @@ def lib():
         L.ita_encoder_layer_long.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_f32.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_f32_taps.argtypes = [vp, i, vp, vp, i, i, C.POINTER(_MhaLongF32Taps), vp]
+        L.ita_mha_long_f32_stats.argtypes = [vp, i, vp, i, i, C.c_float, C.POINTER(_MhaLongF32Stats), vp]
         L.ita_encoder_layer_long_f32.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_vitlstm_tail.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
         L.ita_debug_softmax_rows.argtypes = [vp, vp, vp, i, vp]
@@ -876,6 +884,45 @@ class Engine:
         (encoder_layer_long_f32), then attention_rows_long_f32 of `layer` for the tokens queries = [(ty, tx), ...] ->
         (N, len(queries), tok_h, tok_w) f32 in the order of queries.  Duplicate or out-of-grid queries raise ValueError."""
         return self._attention_map_walk(frames, tok_h, tok_w, queries, layer, depth_scale, self.attention_rows_long_f32)
+
+    def _long_f32_stats(self, x, layer, want, p_min):
+        """ita_mha_long_f32_stats asking for the statistics named in `want` only -> dict of those"""
+        torch = _torch()
+        x = self._long_f32(x)
+        B, S = x.shape[0], x.shape[1]
+        unknown = [k for k in want if k not in LONG_F32_STATS]
+        if unknown:
+            raise ITAError(f"no such long float statistic: {unknown}")
+        t = {k: torch.empty((B, S), dtype=torch.int32 if k.endswith("_nnz") else torch.float32, device=x.device)
+             for k in LONG_F32_STATS if k in want}
+        st = _MhaLongF32Stats(**{k: v.data_ptr() for k, v in t.items()})
+        _chk(lib().ita_mha_long_f32_stats(self._h, layer, x.data_ptr(), B, S, float(p_min), C.byref(st),
+                                          _stream_ptr(self.device)))
+        return t
+
+    def attention_stats_long_f32(self, x, layer: int = 0, p_min: float = 1.0 / 256):
+        """row and column statistics of the whole S x S softmax matrix of a float-attention layer over a long sequence,
+        which is never held (ita_mha_long_f32_stats): x (B,S,E) f32 -> dict of (B,S) tensors.  With the probability of
+        mha_long_f32_taps, p = ita_expf(logit - row_max) * (1 / row_sum): per query row row_max, row_sum f32 (as the taps
+        have them), row_gap f32 = sum_j p (row_max - logit), row_nnz int32 = keys with p >= p_min, and row_entropy f32 =
+        log(row_sum) + row_gap, formed here with torch; per key col_mass f32 = attention received from all queries,
+        col_nnz int32 = queries with p >= p_min.  The default p_min is about where a uint8 probability of the integer
+        softmax stops being zero.  The same input gives the same bits on every call, whatever the batch around a frame.
+        Held to attention_stats_f32_ref.stats_from_taps."""
+        t = self._long_f32_stats(x, layer, LONG_F32_STATS, p_min)
+        t["row_entropy"] = _torch().log(t["row_sum"]) + t["row_gap"]
+        return t
+
+    def attention_received_long_f32(self, x, layer: int = 0):
+        """attention received by every token of a long sequence in a float-attention layer: x (B,S,E) f32 -> col_mass
+        (B,S) f32, the column sums of the probabilities over all S queries"""
+        return self._long_f32_stats(x, layer, ("col_mass",), 1.0 / 256)["col_mass"]
+
+    def attention_received_map_long_f32(self, frames, tok_h: int, tok_w: int, layer: int = 0, depth_scale: Optional[float] = None):
+        """attention received on the token grid of camera frames in a float-attention layer: tokenize_long, the encoder
+        layers below `layer`, then attention_received_long_f32 of `layer` -> (N, tok_h, tok_w) f32"""
+        y = self._tokens_below(frames, int(tok_h), int(tok_w), layer, depth_scale)
+        return self.attention_received_long_f32(y, int(layer)).reshape(y.shape[0], int(tok_h), int(tok_w))
 
     def encoder_layer_long_f32(self, x, layer: int = 0, out=None):
         """one encoder layer with a float FFN (ITAW0002 / ITAW0003 blob) over a long sequence: x (B,S,E) f32 ->

@@ -53,7 +53,7 @@ int ita_destroy(ita_handle h);
  * A layer with H > 1 runs on the block kernels (ita_mha_kernel<E, H>, then the FFN block) behind the stand-alone tokenizer;
  * every entry point below serves it except those that need the one-head stream kernel, which return
  * ITA_ERR_UNSUPPORTED before any launch: ita_mha_q8, ita_mha_long_q8, ita_mha_long_int8, ita_mha_long_int8_taps,
- * ita_mha_long_int8_stats, ita_encoder_layer_long, ita_debug_encoder_stamps, ita_vitlstm_forward_slots (and ita_mha_long_f32 / ita_encoder_layer_long_f32, which take
+ * ita_mha_long_int8_stats, ita_encoder_layer_long, ita_debug_encoder_stamps, ita_vitlstm_forward_slots (and ita_mha_long_f32 / ita_mha_long_f32_stats / ita_encoder_layer_long_f32, which take
  * float layers only).
  * The reference pre-loads weights into the accelerator out of band
  * (docs/HOW-TO-run-the-full-project-workflow.md:55); this is that step. */
@@ -176,8 +176,9 @@ int ita_ffn_f32(ita_handle h, int layer, const float* x_dev, float* y_dev, int b
  * blob: the float graph, models/ITA_single_layer_upsample_shuffle/model.py, nothing quantised).  ita_mha_int8 / _taps,
  * ita_mha_q8, ita_mha_long_q8, ita_mha_long_int8, ita_encoder_layer_long, ita_debug_encoder_stamps and the drop-in
  * ITASelfAttention_workgroup on an F32 layer, and
- * ita_mha_f32 / ita_mha_long_f32 / ita_mha_long_f32_taps on an INT8 layer, fail with ITA_ERR_UNSUPPORTED; each message names the
+ * ita_mha_f32 / ita_mha_long_f32 / ita_mha_long_f32_taps / ita_mha_long_f32_stats on an INT8 layer, fail with ITA_ERR_UNSUPPORTED; each message names the
  * sibling entry (ita_mha_long_int8 <-> ita_mha_long_f32, ita_mha_long_int8_taps <-> ita_mha_long_f32_taps,
+ * ita_mha_long_int8_stats <-> ita_mha_long_f32_stats,
  * ita_encoder_layer_long <-> ita_encoder_layer_long_f32). */
 enum { ITA_ATTN_INT8 = 0, ITA_ATTN_F32 = 1 };
 int ita_get_attn_kind(ita_handle h, int layer, int* kind);
@@ -222,6 +223,31 @@ struct ita_mha_long_f32_taps {
 };
 int ita_mha_long_f32_taps(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_len,
                           const struct ita_mha_long_f32_taps* taps, void* stream);
+/* Row and column statistics of the WHOLE seq_len x seq_len probability matrix of ita_mha_long_f32, which is never held --
+ * the float sibling of ita_mha_long_int8_stats: x (B, seq_len, E) f32 is read only, there is no y.  With s, m and l the
+ * logits, the final running maximum and the final row sum of the production sweep, the probability is the one
+ * ita_mha_long_f32_taps defines, p[i, j] = ita_expf(s[i, j] - m[i]) * (1.0f / l[i]), each operation rounded on its own.
+ * Per query row i (all (B, seq_len), device pointers, any may be NULL): row_max f32 = m[i] and row_sum f32 = l[i], bit
+ * for bit the taps' values; row_gap f32 = sum_j p[i, j] * (m[i] - s[i, j]) >= 0 (the row's entropy is log(row_sum) +
+ * row_gap); row_nnz s32 = #{j : p[i, j] >= p_min}.  Per key column j: col_mass f32 = sum_i p[i, j] ("attention
+ * received"; a frame's column masses add up to about seq_len), col_nnz s32 = #{i : p[i, j] >= p_min}.
+ * The f32 sums are taken in one fixed order (csrc/ita_long_f32_stats_kernel.h; no floating-point atomics): the same input
+ * gives the same bits on every call, and a frame's result does not depend on the batch it runs in.  The production
+ * projection launch, one kernel that runs the production sweep for m and l and a second sweep that recomputes the logits
+ * and reduces p, and for the columns a reduction of the query tiles' partial sums: kernel launches only, so the call
+ * may be captured once the workspace holds it.  Workspace: ita_mha_long_f32's, plus 2 x 4 x seq_len bytes per
+ * 128-token tile when a column statistic is asked for; it grows on demand (not inside a stream capture:
+ * ITA_ERR_INVALID_ARG).  A call that asks for row statistics only launches no column reduction and stores no partials.
+ * Refusals, all before any launch, outputs untouched: whatever ita_mha_long_f32 refuses, with the same status (an
+ * int8-attention layer: ita_mha_long_int8_stats reads it out); ITA_ERR_INVALID_ARG for a NULL x_dev or stats, all six
+ * pointers NULL, an output that is not 4-byte aligned, and p_min that is NaN, <= 0 or > 1.
+ * As with ita_mha_long_f32_taps the struct has a tag and no typedef name -- that identifier is the entry's. */
+struct ita_mha_long_f32_stats {
+  float* row_max; float* row_sum; float* row_gap; int* row_nnz;   /* (batch, seq_len) each, may be NULL */
+  float* col_mass; int* col_nnz;                                    /* (batch, seq_len) each, may be NULL */
+};
+int ita_mha_long_f32_stats(ita_handle h, int layer, const float* x_dev, int batch, int seq_len, float p_min,
+                           const struct ita_mha_long_f32_stats* stats, void* stream);
 /* The long form of ita_encoder_layer for a layer with a float FFN: y = LN2(x1 + ffn(x1)), x1 = LN1(x + attn(x)) on
  * (B, seq_len, E) f32 rows; x_dev may equal y_dev.  Attention + residual + LN1 are the two launches of ita_mha_long_f32
  * (ITAW0003 blob) or of ita_mha_long_int8 (ITAW0002 blob, with that entry's refusals); the float FFN + residual + LN2
