@@ -575,6 +575,25 @@ __device__ __forceinline__ int max1632_i(int v) {
   r = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
   return max((int)r[0], (int)r[1]);
 }
+// sum over the 16 lanes of a DPP row, the same bits in every lane of the row: rotate right by 8, 4, 2, 1 and add.  Every
+// step adds a lane's value and its partner's: with v[q] the value of lane q, a[q] = v[q] + v[q + 8], b[q] = a[q] + a[q + 4],
+// c[q] = b[q] + b[q + 2], sum = c[0] + c[1]
+template <int CTRL>
+__device__ __forceinline__ unsigned ita_row_ror(unsigned v) {
+  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
+}
+__device__ __forceinline__ unsigned ita_row16_sum(unsigned v) {
+  v += ita_row_ror<0x128>(v);   // row_ror:8
+  v += ita_row_ror<0x124>(v);
+  v += ita_row_ror<0x122>(v);
+  return v + ita_row_ror<0x121>(v);
+}
+__device__ __forceinline__ float ita_row16_sumf(float v) {
+  v = v + __uint_as_float(ita_row_ror<0x128>(__float_as_uint(v)));
+  v = v + __uint_as_float(ita_row_ror<0x124>(__float_as_uint(v)));
+  v = v + __uint_as_float(ita_row_ror<0x122>(__float_as_uint(v)));
+  return v + __uint_as_float(ita_row_ror<0x121>(__float_as_uint(v)));
+}
 
 // LayerNorm over E channels held E/4 per lane by the four lanes qi, qi+16, qi+32, qi+48, in the oracle's
 // summation order: the quarter sums p_kq sequentially over consecutive channels, combined (p0+p1)+(p2+p3)

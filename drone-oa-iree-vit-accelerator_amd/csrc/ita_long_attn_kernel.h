@@ -203,11 +203,69 @@ struct ItaLongLds {
   static_assert(2 * TOTAL <= 160 * 1024, "two workgroups per CU");
 };
 
+// The K Q^T tile, shared by ita_long_attn_body and ita_long_stats_kernel (ita_long_stats_kernel.h), which call it through
+// one-line lambdas.  stage and next_tile are NOT shared: as a function, with the LDS array named or passed, they change
+// the production kernels' instruction streams ("Long attention, shared"), so each kernel keeps its own.
+// K Q^T of a wave's 16 queries (qf: three B fragments) against the 128-key tile at kb, two 16-key blocks at a time: the
+// fragments of pair p + 1 load while pair p multiplies, and epil(p, acc) takes a pair's biased accumulators one step later
+// (ita_stream_kernel's attention core)
+template <class Epil>
+__device__ __forceinline__ void ita_long_qk_tile(const char* kb, const i32x4 (&qf)[3], int kq, int qi, Epil epil) {
+  struct KFr { i32x4 w[6]; } kfr[2];
+  i32x4 la[2][2];
+  auto ldk = [&](int p, KFr& f) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int ks = 0; ks < 3; ++ks) f.w[t * 3 + ks] = *(const i32x4*)(kb + (((4 * ks + kq) * 128 + (2 * p + t) * 16 + qi) << 4));
+  };
+  auto mmk = [&](const KFr& f, i32x4 (&acc)[2]) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      acc[t] = (i32x4){ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS};
+#pragma unroll
+      for (int ks = 0; ks < 3; ++ks) acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(f.w[t * 3 + ks], qf[ks], acc[t], 0, 0, 0);
+    }
+  };
+  ldk(0, kfr[0]);
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    if (p + 1 < 4) ldk(p + 1, kfr[(p + 1) & 1]);
+    mmk(kfr[p & 1], la[p & 1]);
+    if (p > 0) epil(p - 1, la[(p - 1) & 1]);
+    ITA_SCHED_BARRIER();
+  }
+  epil(3, la[1]);
+}
+// the tile's logits, requantised to biased u16 pairs
+template <bool FAST>
+__device__ __forceinline__ void ita_long_logits(const char* kb, const i32x4 (&qf)[3], int kq, int qi, float ml, ita_u16x2 (&w)[16]) {
+  ita_long_qk_tile(kb, qf, kq, qi, [&](int p, const i32x4 (&acc)[2]) {
+    unsigned w4[4];
+    if constexpr (FAST) lg8_v3<ITA_RQ_FAST>(acc, ml, w4);
+    else lg8_v3<ITA_RQ_EXACT>(acc, ml, w4);
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) w[2 * (2 * p + t) + j] = __builtin_bit_cast(ita_u16x2, w4[2 * t + j]);
+  });
+}
+// the same products, reduced to the running maximum of this lane's accumulators (all of them belong to query qi)
+__device__ __forceinline__ void ita_long_logits_max(const char* kb, const i32x4 (&qf)[3], int kq, int qi, int& mx) {
+  ita_long_qk_tile(kb, qf, kq, qi, [&](int, const i32x4 (&acc)[2]) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      mx = max(max(mx, acc[t][0]), acc[t][1]);           // (v_max3_i32)
+      mx = max(max(mx, acc[t][2]), acc[t][3]);
+    }
+  });
+}
+
 template <bool FAST, int E, bool F32IO, bool TAPS>
 __device__ __forceinline__ void ita_long_attn_body(const ItaLongArgs& a, const ItaLongTapArgs& tp) {
   static_assert(!TAPS || F32IO, "the taps entry has the f32 form only");
   static_assert(E == 64 || E == 128, "one or two 64-channel output groups");
-  constexpr int S = 128, P = 192, EC = E / 4;
+  constexpr int P = 192, EC = E / 4;
   using LI = ItaStreamLds<E, false, false>;   // offsets inside the layer's image
   using L = ItaLongLds;
   typedef ita_u16x2 u16x2;
@@ -240,78 +298,8 @@ __device__ __forceinline__ void ita_long_attn_body(const ItaLongArgs& a, const I
 #pragma unroll
   for (int ks = 0; ks < 3; ++ks) qf[ks] = *(const i32x4*)(a.qfrag + ((((tile0 + qt) * 8 + wave) * 3 + ks) * 64 + lane) * 16);
 
-  // logits of this wave's 16 queries against one 128-key tile, as biased u16 pairs (ita_stream_kernel's attention core)
-  auto logits = [&](const char* kb, u16x2 (&w)[16]) {
-    struct KFr { i32x4 w[6]; } kfr[2];
-    i32x4 la[2][2];
-    auto ldk = [&](int p, KFr& f) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int ks = 0; ks < 3; ++ks) f.w[t * 3 + ks] = *(const i32x4*)(kb + (((4 * ks + kq) * S + (2 * p + t) * 16 + qi) << 4));
-    };
-    auto mmk = [&](const KFr& f, i32x4 (&acc)[2]) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        acc[t] = (i32x4){ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS};
-#pragma unroll
-        for (int ks = 0; ks < 3; ++ks) acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(f.w[t * 3 + ks], qf[ks], acc[t], 0, 0, 0);
-      }
-    };
-    auto epil = [&](int p, const i32x4 (&acc)[2]) {
-      unsigned w4[4];
-      if constexpr (FAST) lg8_v3<ITA_RQ_FAST>(acc, a.ml, w4);
-      else lg8_v3<ITA_RQ_EXACT>(acc, a.ml, w4);
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) w[2 * (2 * p + t) + j] = __builtin_bit_cast(u16x2, w4[2 * t + j]);
-    };
-    ldk(0, kfr[0]);
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      if (p + 1 < 4) ldk(p + 1, kfr[(p + 1) & 1]);
-      mmk(kfr[p & 1], la[p & 1]);
-      if (p > 0) epil(p - 1, la[(p - 1) & 1]);
-      ITA_SCHED_BARRIER();
-    }
-    epil(3, la[1]);
-  };
-  // the same products, reduced to the running maximum of this lane's accumulators (all of them belong to query qi)
-  auto logits_max = [&](const char* kb, int& mx) {
-    struct KFr { i32x4 w[6]; } kfr[2];
-    i32x4 la[2][2];
-    auto ldk = [&](int p, KFr& f) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int ks = 0; ks < 3; ++ks) f.w[t * 3 + ks] = *(const i32x4*)(kb + (((4 * ks + kq) * S + (2 * p + t) * 16 + qi) << 4));
-    };
-    auto mmk = [&](const KFr& f, i32x4 (&acc)[2]) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        acc[t] = (i32x4){ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS};
-#pragma unroll
-        for (int ks = 0; ks < 3; ++ks) acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(f.w[t * 3 + ks], qf[ks], acc[t], 0, 0, 0);
-      }
-    };
-    auto epil = [&](const i32x4 (&acc)[2]) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        mx = max(max(mx, acc[t][0]), acc[t][1]);           // (v_max3_i32)
-        mx = max(max(mx, acc[t][2]), acc[t][3]);
-      }
-    };
-    ldk(0, kfr[0]);
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      if (p + 1 < 4) ldk(p + 1, kfr[(p + 1) & 1]);
-      mmk(kfr[p & 1], la[p & 1]);
-      if (p > 0) epil(la[(p - 1) & 1]);
-      ITA_SCHED_BARRIER();
-    }
-    epil(la[1]);
-  };
+  auto logits = [&](const char* kb, u16x2 (&w)[16]) { ita_long_logits<FAST>(kb, qf, kq, qi, a.ml, w); };
+  auto logits_max = [&](const char* kb, int& mx) { ita_long_logits_max(kb, qf, kq, qi, mx); };
   // one step of sweeps 1 and 2: steps are counted through the sweeps (step = sweep * nkt + kt), the K tile of a step sits in
   // ring slot step & 1 with its DMA waited for here; the next step's tile goes out after the barrier (the last step of a
   // sweep prefetches tile 0 for the next sweep)

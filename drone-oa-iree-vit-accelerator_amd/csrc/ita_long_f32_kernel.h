@@ -185,6 +185,102 @@ __global__ __launch_bounds__(512) void ita_lf32_proj_taps_kernel(const ItaLongF3
   ita_lf32_proj_body<E, true>(a, tp);
 }
 
+// What ita_lf32_attn_body and ita_lf32_stats_kernel (ita_long_f32_stats_kernel.h) share.  The statistics' row_max and
+// row_sum are the production bits because both kernels run these functions and nothing else up to m and l.  (stage is a
+// lambda in each kernel: DESIGN section 4, "Long attention, shared".)
+// Q^T of a wave's 16 queries: rows = features 16 ft + 4 slot + r, column = query col; xsrc is the lane's x row at channel
+// 4 slot.  A rolled loop (unrolled, its independent block sums take more registers than a lane has) that parks the tiles
+// at qs (the lane's own place in LDS, stride 64 f32x4 per feature tile); each lane reads back what it wrote itself
+template <int E>
+__device__ __forceinline__ void ita_lf32_q_prologue(const float* xsrc, const float* wq, const float* bq, int col, int slot,
+                                                    f32x4* qs, f32x4 (&q)[ItaLongF32Lds::NFT]) {
+  constexpr int NFT = ItaLongF32Lds::NFT, NG = E / 16;
+  f32x4 xf[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) xf[g] = *(const f32x4*)(xsrc + 16 * g);
+#pragma unroll 1
+  for (int ft = 0; ft < NFT; ft += 2) {
+    f32x4 qa[2];
+    const float* wqr[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      qa[u] = *(const f32x4*)(bq + 16 * (ft + u) + 4 * slot);
+      wqr[u] = wq + (16 * (ft + u) + col) * E + 4 * slot;
+    }
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      const f32x4 w0 = *(const f32x4*)(wqr[0] + 16 * g), w1 = *(const f32x4*)(wqr[1] + 16 * g);
+      f32x4 t0 = {0, 0, 0, 0}, t1 = {0, 0, 0, 0};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        t0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[r], xf[g][r], t0, 0, 0, 0);
+        t1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[r], xf[g][r], t1, 0, 0, 0);
+      }
+      qa[0] += t0;
+      qa[1] += t1;
+    }
+    qs[ft * 64] = qa[0];
+    qs[(ft + 1) * 64] = qa[1];
+  }
+#pragma unroll
+  for (int ft = 0; ft < NFT; ++ft) q[ft] = qs[ft * 64];
+}
+// S^T = K Q^T of the 64-key unit at kb: tile kt, lane (query col, slot) holds S[query][16 kt + 4 slot + r].  Block sums:
+// the 16 features of tile ft are chained from zero (t) and the block goes onto the logit one step later, behind the next
+// tile's MFMAs; the fragments of tile ft + 1 load while tile ft computes (the steps are kept apart: interleaved, the twelve
+// independent blocks take more registers than a lane has)
+__device__ __forceinline__ void ita_lf32_logits(const f32x4* kb, int lane, const f32x4 (&q)[ItaLongF32Lds::NFT],
+                                                f32x4 (&s)[ItaLongF32Lds::NKT]) {
+  constexpr int NFT = ItaLongF32Lds::NFT, NKT = ItaLongF32Lds::NKT;
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt) s[kt] = (f32x4){0, 0, 0, 0};
+  f32x4 kf[2][NKT], t[2][NKT];
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt) kf[0][kt] = kb[kt * 64 + lane];
+#pragma unroll
+  for (int ft = 0; ft < NFT; ++ft) {
+    if (ft + 1 < NFT) {
+#pragma unroll
+      for (int kt = 0; kt < NKT; ++kt) kf[(ft + 1) & 1][kt] = kb[((ft + 1) * NKT + kt) * 64 + lane];
+    }
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) t[ft & 1][kt] = (f32x4){0, 0, 0, 0};
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int kt = 0; kt < NKT; ++kt)
+        t[ft & 1][kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[ft & 1][kt][r], q[ft][r], t[ft & 1][kt], 0, 0, 0);
+    if (ft > 0) {
+#pragma unroll
+      for (int kt = 0; kt < NKT; ++kt) s[kt] += t[(ft - 1) & 1][kt];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt) s[kt] += t[(NFT - 1) & 1][kt];
+}
+// The running maximum over a unit's 64 keys of query col (16 in the lane, the rest in lanes col + 16 slot): m becomes
+// mn = max(m, max s), which is returned, and down = e^(m - mn) rescales what was summed under the old m (first unit: the
+// clamp's e^-87, times zeros)
+__device__ __forceinline__ float ita_lf32_running_max(const f32x4 (&s)[ItaLongF32Lds::NKT], float& m, float& down) {
+  float mt = s[0][0];
+#pragma unroll
+  for (int kt = 0; kt < ItaLongF32Lds::NKT; ++kt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) mt = fmaxf(mt, s[kt][r]);
+  mt = fmaxf(mt, __int_as_float(xor16_i(__float_as_int(mt))));
+  mt = fmaxf(mt, __int_as_float(xor32_i(__float_as_int(mt))));
+  const float mn = fmaxf(m, mt);
+  down = ita_expf(m - mn);
+  m = mn;
+  return mn;
+}
+// the four slot lanes' shares of a query's sum, (v0 + v1) + (v2 + v3): the same bits in all four lanes
+__device__ __forceinline__ float ita_lf32_sum_slots(float v) {
+  v = v + __int_as_float(xor16_i(__float_as_int(v)));
+  return v + __int_as_float(xor32_i(__float_as_int(v)));
+}
+
 template <int E, bool TAPS>
 __device__ __forceinline__ void ita_lf32_attn_body(const ItaLongF32Args& a, const ItaLongF32TapArgs& tp) {
   static_assert(E == 64 || E == 128, "four or eight 16-channel groups");
@@ -209,43 +305,11 @@ __device__ __forceinline__ void ita_lf32_attn_body(const ItaLongF32Args& a, cons
   };
   stage(kimg, L::K);
 
-  // Q^T of the wave's queries: rows = features 16 ft + 4 slot + r, column = query col.  A rolled loop (unrolled, its
-  // independent block sums take more registers than a lane has) that parks the tiles in the second K slot and the V slot,
-  // free until every wave has passed the first barrier of the sweep; each lane reads back what it wrote itself
+  // Q^T of the wave's queries, parked in the second K slot and the V slot: free until every wave has passed the first
+  // barrier of the sweep
   const float* xsrc = a.x + ((size_t)b * a.S + (size_t)qt * 128 + t0 + col) * E + 4 * slot;
   f32x4 q[NFT];
-  {
-    f32x4* qs = (f32x4*)(lds + L::K + L::UNIT) + wave * NFT * 64 + lane;
-    f32x4 xf[NG];
-#pragma unroll
-    for (int g = 0; g < NG; ++g) xf[g] = *(const f32x4*)(xsrc + 16 * g);
-#pragma unroll 1
-    for (int ft = 0; ft < NFT; ft += 2) {
-      f32x4 qa[2];
-      const float* wqr[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        qa[u] = *(const f32x4*)(a.bq + 16 * (ft + u) + 4 * slot);
-        wqr[u] = a.wq + (16 * (ft + u) + col) * E + 4 * slot;
-      }
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        const f32x4 w0 = *(const f32x4*)(wqr[0] + 16 * g), w1 = *(const f32x4*)(wqr[1] + 16 * g);
-        f32x4 t0 = {0, 0, 0, 0}, t1 = {0, 0, 0, 0};
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          t0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[r], xf[g][r], t0, 0, 0, 0);
-          t1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[r], xf[g][r], t1, 0, 0, 0);
-        }
-        qa[0] += t0;
-        qa[1] += t1;
-      }
-      qs[ft * 64] = qa[0];
-      qs[(ft + 1) * 64] = qa[1];
-    }
-#pragma unroll
-    for (int ft = 0; ft < NFT; ++ft) q[ft] = qs[ft * 64];
-  }
+  ita_lf32_q_prologue<E>(xsrc, a.wq, a.bq, col, slot, (f32x4*)(lds + L::K + L::UNIT) + wave * NFT * 64 + lane, q);
   // taps: the output row of this lane's query (the four slot lanes of a query agree), and whether the wave has any
   int ri = -1;
   bool wave_rows = false;
@@ -276,37 +340,7 @@ __device__ __forceinline__ void ita_lf32_attn_body(const ItaLongF32Args& a, cons
     // S^T = K Q^T: tile kt, lane (query col, slot) holds S[query][64 u + 16 kt + 4 slot + r]
     const f32x4* kb = (const f32x4*)(lds + L::K + (u & 1) * L::UNIT);
     f32x4 s[NKT];
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) s[kt] = (f32x4){0, 0, 0, 0};
-    // block sums: the 16 features of tile ft are chained from zero (t) and the block goes onto the logit one step later,
-    // behind the next tile's MFMAs; the fragments of tile ft + 1 load while tile ft computes (the steps are kept apart:
-    // interleaved, the twelve independent blocks take more registers than a lane has)
-    {
-      f32x4 kf[2][NKT], t[2][NKT];
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt) kf[0][kt] = kb[kt * 64 + lane];
-#pragma unroll
-      for (int ft = 0; ft < NFT; ++ft) {
-        if (ft + 1 < NFT) {
-#pragma unroll
-          for (int kt = 0; kt < NKT; ++kt) kf[(ft + 1) & 1][kt] = kb[((ft + 1) * NKT + kt) * 64 + lane];
-        }
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt) t[ft & 1][kt] = (f32x4){0, 0, 0, 0};
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-          for (int kt = 0; kt < NKT; ++kt)
-            t[ft & 1][kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[ft & 1][kt][r], q[ft][r], t[ft & 1][kt], 0, 0, 0);
-        if (ft > 0) {
-#pragma unroll
-          for (int kt = 0; kt < NKT; ++kt) s[kt] += t[(ft - 1) & 1][kt];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt) s[kt] += t[(NFT - 1) & 1][kt];
-    }
+    ita_lf32_logits(kb, lane, q, s);
     if constexpr (TAPS) {   // s[kt] = keys 64 u + 16 kt + 4 slot + 0..3 of query col: 16 bytes per store, before s becomes e^(s - m)
       if (wave_rows && tp.logits && ri >= 0) {
         float* lr = tp.logits + rowoff + 64 * u + 4 * slot;
@@ -316,16 +350,8 @@ __device__ __forceinline__ void ita_lf32_attn_body(const ItaLongF32Args& a, cons
     }
     // running softmax over the unit's 64 keys of query col: 16 in the lane, the rest in lanes col + 16 slot
     {
-      float mt = s[0][0];
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) mt = fmaxf(mt, s[kt][r]);
-      mt = fmaxf(mt, __int_as_float(xor16_i(__float_as_int(mt))));
-      mt = fmaxf(mt, __int_as_float(xor32_i(__float_as_int(mt))));
-      const float mn = fmaxf(m, mt);
-      const float down = ita_expf(m - mn);   // first unit: the clamp's e^-87, times l = 0 and c = 0
-      m = mn;
+      float down;
+      const float mn = ita_lf32_running_max(s, m, down);
       float sum = 0.0f;
 #pragma unroll
       for (int kt = 0; kt < NKT; ++kt)
@@ -356,8 +382,7 @@ __device__ __forceinline__ void ita_lf32_attn_body(const ItaLongF32Args& a, cons
     }
   }
   {
-    l = l + __int_as_float(xor16_i(__float_as_int(l)));   // the same sum in all four lanes of the query
-    l = l + __int_as_float(xor32_i(__float_as_int(l)));
+    l = ita_lf32_sum_slots(l);
     const float inv = 1.0f / l;
 #pragma unroll
     for (int ft = 0; ft < NFT; ++ft) c[ft] *= inv;

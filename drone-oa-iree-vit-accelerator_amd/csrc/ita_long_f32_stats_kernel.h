@@ -6,7 +6,7 @@
 //                              K units by LDS-DMA into the two-slot ring of ItaLongF32Lds, one barrier per step (there
 //                              is no V).  Steps 0 .. nu - 1 are sweep 1, steps nu .. 2 nu - 1 sweep 2 (nu = S / 64 is
 //                              even, so unit u sits in ring slot u & 1 in both; the last step of sweep 1 prefetches unit 0).
-//     prologue  Q^T of the wave's queries: ita_lf32_attn_body's, instruction for instruction
+//     prologue  Q^T of the wave's queries: ita_lf32_attn_body's
 //     sweep 1   ita_lf32_attn_body's loop without V and c[]: the same block-summed S^T, the same mn / down /
 //               l = l * down + sum, the same closing xor16 / xor32 add: m and l are the production bits
 //     sweep 2   the same MFMA chains again, so s is bit-equal to sweep 1's; per element, each operation rounded on its own,
@@ -14,9 +14,10 @@
 //               and p is reduced along the row and along the column
 //   ita_lf32_colsum_kernel   : one thread per (frame, key): the query tiles' partials added in ascending tile order
 //
-// The Q prologue, stage and the logits chain are COPIES of ita_lf32_attn_body's: moving them into functions shared by both
-// kernels would have to leave the production and taps instruction streams unchanged, and ita_long_f32_kernel.h is left
-// untouched instead, as ita_long_stats_kernel.h leaves ita_long_attn_kernel.h ("Long float statistics").
+// The Q prologue, the logits chain, the running maximum and the closing add are ita_long_f32_kernel.h's functions
+// (ita_lf32_q_prologue, _logits, _running_max, _sum_slots), which ita_lf32_attn_body runs too: m and l cannot drift from
+// the production bits.  stage stays a lambda in both kernels: as a shared function it made this kernel 0.4 to 0.9 % slower
+// ("Long attention, shared").
 //
 // THE ORDER OF EVERY FLOAT ADDITION (no floating-point atomics anywhere; tests/long_f32_stats_common.py is this in numpy):
 //   row_gap   lane (query col, slot) holds keys 64 u + 16 kt + 4 slot + r of its query.  The lane's share starts at 0.0f and
@@ -60,34 +61,12 @@ struct ItaLongF32StatsLds {
   static_assert(CN + 2 * 8 * 64 * 4 <= L::TOTAL, "the column tables sit in the V slot");
 };
 
-// sum over the 16 lanes of a DPP row, the same bits in every lane of the row: rotate right by 8, 4, 2, 1 and add (header)
-template <int CTRL>
-__device__ __forceinline__ float ita_row_ror_addf(float v) {
-  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float ita_row16_sumf(float v) {
-  v = ita_row_ror_addf<0x128>(v);   // row_ror:8
-  v = ita_row_ror_addf<0x124>(v);
-  v = ita_row_ror_addf<0x122>(v);
-  return ita_row_ror_addf<0x121>(v);
-}
-template <int CTRL>
-__device__ __forceinline__ unsigned ita_row_ror_addu(unsigned v) {
-  return v + (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
-}
-__device__ __forceinline__ unsigned ita_row16_sumu(unsigned v) {
-  v = ita_row_ror_addu<0x128>(v);
-  v = ita_row_ror_addu<0x124>(v);
-  v = ita_row_ror_addu<0x122>(v);
-  return ita_row_ror_addu<0x121>(v);
-}
-
 template <int E>
 __global__ __launch_bounds__(512) void ita_lf32_stats_kernel(const ItaLongF32StatsArgs a) {
   static_assert(E == 64 || E == 128, "four or eight 16-channel groups");
   using L = ItaLongF32Lds;
   using T = ItaLongF32StatsLds;
-  constexpr int NFT = L::NFT, NKT = L::NKT, NG = E / 16;
+  constexpr int NFT = L::NFT, NKT = L::NKT;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -109,42 +88,11 @@ __global__ __launch_bounds__(512) void ita_lf32_stats_kernel(const ItaLongF32Sta
   };
   stage(kimg, L::K);
 
-  // Q^T of the wave's queries (ita_lf32_attn_body's prologue): parked in the second K slot and the V slot, free until every
-  // wave has passed the first barrier of sweep 1; each lane reads back what it wrote itself
+  // Q^T of the wave's queries, parked in the second K slot and the V slot: free until every wave has passed the first
+  // barrier of sweep 1
   const float* xsrc = a.x + ((size_t)b * a.S + (size_t)qt * 128 + t0 + col) * E + 4 * slot;
   f32x4 q[NFT];
-  {
-    f32x4* qs = (f32x4*)(lds + L::K + L::UNIT) + wave * NFT * 64 + lane;
-    f32x4 xf[NG];
-#pragma unroll
-    for (int g = 0; g < NG; ++g) xf[g] = *(const f32x4*)(xsrc + 16 * g);
-#pragma unroll 1
-    for (int ft = 0; ft < NFT; ft += 2) {
-      f32x4 qa[2];
-      const float* wqr[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        qa[u] = *(const f32x4*)(a.bq + 16 * (ft + u) + 4 * slot);
-        wqr[u] = a.wq + (16 * (ft + u) + col) * E + 4 * slot;
-      }
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        const f32x4 w0 = *(const f32x4*)(wqr[0] + 16 * g), w1 = *(const f32x4*)(wqr[1] + 16 * g);
-        f32x4 t0 = {0, 0, 0, 0}, t1 = {0, 0, 0, 0};
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          t0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[r], xf[g][r], t0, 0, 0, 0);
-          t1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[r], xf[g][r], t1, 0, 0, 0);
-        }
-        qa[0] += t0;
-        qa[1] += t1;
-      }
-      qs[ft * 64] = qa[0];
-      qs[(ft + 1) * 64] = qa[1];
-    }
-#pragma unroll
-    for (int ft = 0; ft < NFT; ++ft) q[ft] = qs[ft * 64];
-  }
+  ita_lf32_q_prologue<E>(xsrc, a.wq, a.bq, col, slot, (f32x4*)(lds + L::K + L::UNIT) + wave * NFT * 64 + lane, q);
 
   // the top of a step: its K unit (ring slot step & 1) has landed for every wave and every wave is done with the step
   // before, so the other slot is free for the next step's unit (unit 0 again behind the last step of sweep 1)
@@ -154,53 +102,15 @@ __global__ __launch_bounds__(512) void ita_lf32_stats_kernel(const ItaLongF32Sta
     const int nx = step + 1;
     if (nx < nstep) stage(kimg + (size_t)(nx < nu ? nx : nx - nu) * L::UNIT, L::K + (nx & 1) * L::UNIT);
   };
-  // S^T = K Q^T of one unit (ita_lf32_attn_body's block sums): tile kt, lane (query col, slot) holds
-  // S[query][64 u + 16 kt + 4 slot + r]
-  auto logits = [&](const f32x4* kb, f32x4 (&s)[NKT]) {
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) s[kt] = (f32x4){0, 0, 0, 0};
-    f32x4 kf[2][NKT], t[2][NKT];
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) kf[0][kt] = kb[kt * 64 + lane];
-#pragma unroll
-    for (int ft = 0; ft < NFT; ++ft) {
-      if (ft + 1 < NFT) {
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt) kf[(ft + 1) & 1][kt] = kb[((ft + 1) * NKT + kt) * 64 + lane];
-      }
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt) t[ft & 1][kt] = (f32x4){0, 0, 0, 0};
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt)
-          t[ft & 1][kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[ft & 1][kt][r], q[ft][r], t[ft & 1][kt], 0, 0, 0);
-      if (ft > 0) {
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt) s[kt] += t[(ft - 1) & 1][kt];
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) s[kt] += t[(NFT - 1) & 1][kt];
-  };
 
   // ---------------- sweep 1: the running maximum m and this lane's share l of the running sum, as the production sweep
   float m = -__builtin_inff(), l = 0.0f;
   for (int u = 0; u < nu; ++u) {
     step_top(u);
     f32x4 s[NKT];
-    logits((const f32x4*)(lds + L::K + (u & 1) * L::UNIT), s);
-    float mt = s[0][0];
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) mt = fmaxf(mt, s[kt][r]);
-    mt = fmaxf(mt, __int_as_float(xor16_i(__float_as_int(mt))));
-    mt = fmaxf(mt, __int_as_float(xor32_i(__float_as_int(mt))));
-    const float mn = fmaxf(m, mt);
-    const float down = ita_expf(m - mn);   // first unit: the clamp's e^-87, times l = 0
-    m = mn;
+    ita_lf32_logits((const f32x4*)(lds + L::K + (u & 1) * L::UNIT), lane, q, s);
+    float down;
+    const float mn = ita_lf32_running_max(s, m, down);   // first unit: down is the clamp's e^-87, times l = 0
     float sum = 0.0f;
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt)
@@ -208,8 +118,7 @@ __global__ __launch_bounds__(512) void ita_lf32_stats_kernel(const ItaLongF32Sta
       for (int r = 0; r < 4; ++r) sum += ita_expf(s[kt][r] - mn);
     l = l * down + sum;
   }
-  l = l + __int_as_float(xor16_i(__float_as_int(l)));   // the same sum in all four lanes of the query
-  l = l + __int_as_float(xor32_i(__float_as_int(l)));
+  l = ita_lf32_sum_slots(l);   // the same sum in all four lanes of the query
   const size_t row = (size_t)b * a.S + (size_t)qt * 128 + t0 + col;
   if (slot == 0) {
     if (a.row_max) a.row_max[row] = m;
@@ -249,7 +158,7 @@ __global__ __launch_bounds__(512) void ita_lf32_stats_kernel(const ItaLongF32Sta
     step_top(nu + u);
     if (cols && u > 0) flush(u - 1);
     f32x4 s[NKT];
-    logits((const f32x4*)(lds + L::K + (u & 1) * L::UNIT), s);
+    ita_lf32_logits((const f32x4*)(lds + L::K + (u & 1) * L::UNIT), lane, q, s);
     unsigned f4[NKT];   // byte r of word kt: is p of key 16 kt + 4 slot + r at least p_min
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) {
@@ -273,7 +182,7 @@ __global__ __launch_bounds__(512) void ita_lf32_stats_kernel(const ItaLongF32Sta
         f32x4 cs;
 #pragma unroll
         for (int r = 0; r < 4; ++r) cs[r] = ita_row16_sumf(s[kt][r]);
-        const unsigned c4 = ita_row16_sumu(f4[kt]);   // <= 16 per byte
+        const unsigned c4 = ita_row16_sum(f4[kt]);   // <= 16 per byte
         if (col == 0) {
           *(f32x4*)(cmw + 16 * kt) = cs;
           *(i32x4*)(cnw + 16 * kt) = (i32x4){(int)(c4 & 0xffu), (int)((c4 >> 8) & 0xffu), (int)((c4 >> 16) & 0xffu), (int)(c4 >> 24)};
@@ -285,8 +194,7 @@ __global__ __launch_bounds__(512) void ita_lf32_stats_kernel(const ItaLongF32Sta
     __syncthreads();       // the last unit's column tables are complete
     flush(nu - 1);
   }
-  gap = gap + __int_as_float(xor16_i(__float_as_int(gap)));
-  gap = gap + __int_as_float(xor32_i(__float_as_int(gap)));
+  gap = ita_lf32_sum_slots(gap);
   nnz = sum1632_i(nnz);
   if (slot == 0) {
     if (a.row_gap) a.row_gap[row] = gap;

@@ -8,9 +8,9 @@
 // There is no V staging, no second barrier per step and no out_proj.  Same grid as ita_long_attn_kernel: (S / 128, B), 512
 // threads, wave w owns queries 16 w .. 16 w + 15 of its query tile, K tiles by LDS-DMA into the two-slot ring.
 //
-// The stage / next_tile / logits / logits_max lambdas are COPIES of ita_long_attn_body's: hoisting them into functions shared
-// by both kernels would have to leave the 8 + 8 production and 4 + 4 taps instruction streams unchanged, and
-// ita_long_attn_kernel.h is left untouched instead ("Long-sequence statistics").
+// The K Q^T tile pipeline and its two epilogues are ita_long_attn_kernel.h's (ita_long_logits, ita_long_logits_max): the
+// logits of both kernels come from one routine.  stage and next_tile stay lambdas in both files: shared as a function,
+// in either form, they change the production kernels' instruction streams ("Long attention, shared").
 //
 // Lane (qi = lane & 15, kq = lane >> 4) of wave w holds, per key tile, eight words p4[k4], k4 = 4 kb + t: byte i is the
 // probability of key 64 kb + 16 t + 4 kq + i = 4 (4 k4 + kq) + i of the tile for query 16 w + qi.
@@ -48,18 +48,6 @@ struct ItaLongStatsLds {
   static_assert(2 * TOTAL <= 160 * 1024, "two workgroups per CU");
 };
 
-// sum over the 16 lanes of a DPP row, in every lane of the row: rotate right by 8, 4, 2, 1 and add
-template <int CTRL>
-__device__ __forceinline__ unsigned ita_row_ror_add(unsigned v) {
-  return v + (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
-}
-__device__ __forceinline__ unsigned ita_row16_sum(unsigned v) {
-  v = ita_row_ror_add<0x128>(v);   // row_ror:8
-  v = ita_row_ror_add<0x124>(v);
-  v = ita_row_ror_add<0x122>(v);
-  return ita_row_ror_add<0x121>(v);
-}
-
 // The column arrays start from zero: n int32 of each (either may be null), one int32 per lane and grid-stride step -- the
 // arrays are only 4-byte aligned.  A kernel and not a memset, so that a captured call is kernel nodes only: a memset node in
 // front of the launches did not survive the second replay of a captured call ("Long-sequence statistics").
@@ -72,7 +60,6 @@ __global__ __launch_bounds__(256) void ita_long_stats_zero_kernel(int* c0, int* 
 
 template <bool FAST>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void ita_long_stats_kernel(const ItaLongStatsArgs a) {
-  constexpr int S = 128;
   using L = ItaLongStatsLds;
   typedef ita_u16x2 u16x2;
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -99,78 +86,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
   for (int ks = 0; ks < 3; ++ks) qf[ks] = *(const i32x4*)(a.qfrag + ((((tile0 + qt) * 8 + wave) * 3 + ks) * 64 + lane) * 16);
 
-  // logits of this wave's 16 queries against one 128-key tile, as biased u16 pairs
-  auto logits = [&](const char* kb, u16x2 (&w)[16]) {
-    struct KFr { i32x4 w[6]; } kfr[2];
-    i32x4 la[2][2];
-    auto ldk = [&](int p, KFr& f) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int ks = 0; ks < 3; ++ks) f.w[t * 3 + ks] = *(const i32x4*)(kb + (((4 * ks + kq) * S + (2 * p + t) * 16 + qi) << 4));
-    };
-    auto mmk = [&](const KFr& f, i32x4 (&acc)[2]) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        acc[t] = (i32x4){ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS};
-#pragma unroll
-        for (int ks = 0; ks < 3; ++ks) acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(f.w[t * 3 + ks], qf[ks], acc[t], 0, 0, 0);
-      }
-    };
-    auto epil = [&](int p, const i32x4 (&acc)[2]) {
-      unsigned w4[4];
-      if constexpr (FAST) lg8_v3<ITA_RQ_FAST>(acc, a.ml, w4);
-      else lg8_v3<ITA_RQ_EXACT>(acc, a.ml, w4);
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) w[2 * (2 * p + t) + j] = __builtin_bit_cast(u16x2, w4[2 * t + j]);
-    };
-    ldk(0, kfr[0]);
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      if (p + 1 < 4) ldk(p + 1, kfr[(p + 1) & 1]);
-      mmk(kfr[p & 1], la[p & 1]);
-      if (p > 0) epil(p - 1, la[(p - 1) & 1]);
-      ITA_SCHED_BARRIER();
-    }
-    epil(3, la[1]);
-  };
-  // the same products, reduced to the running maximum of this lane's accumulators (all of them belong to query qi)
-  auto logits_max = [&](const char* kb, int& mx) {
-    struct KFr { i32x4 w[6]; } kfr[2];
-    i32x4 la[2][2];
-    auto ldk = [&](int p, KFr& f) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int ks = 0; ks < 3; ++ks) f.w[t * 3 + ks] = *(const i32x4*)(kb + (((4 * ks + kq) * S + (2 * p + t) * 16 + qi) << 4));
-    };
-    auto mmk = [&](const KFr& f, i32x4 (&acc)[2]) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        acc[t] = (i32x4){ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS};
-#pragma unroll
-        for (int ks = 0; ks < 3; ++ks) acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(f.w[t * 3 + ks], qf[ks], acc[t], 0, 0, 0);
-      }
-    };
-    auto epil = [&](const i32x4 (&acc)[2]) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        mx = max(max(mx, acc[t][0]), acc[t][1]);
-        mx = max(max(mx, acc[t][2]), acc[t][3]);
-      }
-    };
-    ldk(0, kfr[0]);
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      if (p + 1 < 4) ldk(p + 1, kfr[(p + 1) & 1]);
-      mmk(kfr[p & 1], la[p & 1]);
-      if (p > 0) epil(la[(p - 1) & 1]);
-      ITA_SCHED_BARRIER();
-    }
-    epil(la[1]);
-  };
+  auto logits = [&](const char* kb, u16x2 (&w)[16]) { ita_long_logits<FAST>(kb, qf, kq, qi, a.ml, w); };
+  auto logits_max = [&](const char* kb, int& mx) { ita_long_logits_max(kb, qf, kq, qi, mx); };
   // one step of sweeps 1 and 2 (step = sweep * nkt + kt): the K tile of a step sits in ring slot step & 1 with its DMA waited
   // for here; the next step's tile goes out after the barrier (the last step of a sweep prefetches tile 0 for the next sweep)
   auto next_tile = [&](int step, int kt) {

@@ -868,14 +868,20 @@ int ita_mha_int8(ita_handle h, int layer, const float* x, float* y, int batch, v
 
 namespace {
 
-// the refusals every long-sequence entry point shares (ITA_ERR_UNSUPPORTED, before any launch)
+// the sequence lengths and batches every long-sequence entry point, int8 or float, takes (ITA_ERR_UNSUPPORTED)
+int check_long_shape(int batch, int seq_len) {
+  if (seq_len < 128 || seq_len % 128 || seq_len > 65536 || batch > 65535)
+    return fail(ITA_ERR_UNSUPPORTED, "seq_len must be a multiple of 128 in [128, 65536], batch <= 65535");
+  return ITA_OK;
+}
+
+// the refusals every long-sequence int8 entry point shares (ITA_ERR_UNSUPPORTED, before any launch)
 int check_long(const Layer& L, int batch, int seq_len, bool taps = false) {
   if (L.attn_f32)
     return fail(ITA_ERR_UNSUPPORTED, taps ? "this layer's attention is float32 (ITAW0003 blob): its flash kernel keeps no row probabilities, there are no taps "
                                             "here: ita_mha_long_f32_taps reads a float layer out"
                                           : "this layer's attention is float32 (ITAW0003 blob): no int8 long attention");
-  if (seq_len < 128 || seq_len % 128 || seq_len > 65536 || batch > 65535)
-    return fail(ITA_ERR_UNSUPPORTED, "seq_len must be a multiple of 128 in [128, 65536], batch <= 65535");
+  if (int rc = check_long_shape(batch, seq_len)) return rc;
   if (!L.simg_mha) return fail(ITA_ERR_UNSUPPORTED, "this layer has no attention image (accumulator range, or more than one head)");
   return ITA_OK;
 }
@@ -917,10 +923,9 @@ int upload_long_rows(ita_context* h, const int* rows, int n_rows, int seq_len, h
   return ITA_OK;
 }
 
-// The handle's long-attention workspace, for ntile tiles of 128 tokens: it grows outside a stream capture only (a captured
-// graph keeps raw pointers into it), behind a device synchronisation
-int ensure_long_ws(ita_context* h, size_t ntile, hipStream_t s) {
-  const size_t need = ntile * (3 * 24576 + 192 * 4);
+// The handle's long-attention workspace (int8 and float entries share the buffer) at `need` bytes: it grows outside a
+// stream capture only (a captured graph keeps raw pointers into it), behind a device synchronisation
+int ensure_long_ws(ita_context* h, size_t need, hipStream_t s) {
   if (need <= h->long_ws_bytes) return ITA_OK;
   if (capturing(s))
     return fail(ITA_ERR_INVALID_ARG, "the long-attention workspace cannot grow inside a stream capture; run one call first");
@@ -931,7 +936,9 @@ int ensure_long_ws(ita_context* h, size_t ntile, hipStream_t s) {
   return ITA_OK;
 }
 
-// The two long kernels' arguments over that workspace (the I/O pointers and fuse_ln are the caller's to set)
+// The int8 workspace of ntile tiles of 128 tokens (Q fragments, K and V^T images, column sums), and the two long kernels'
+// arguments over it (the I/O pointers and fuse_ln are the caller's to set)
+constexpr size_t long_int8_ws(size_t ntile) { return ntile * (3 * 24576 + 192 * 4); }
 ItaLongArgs long_args(ita_context* h, const Layer& L, size_t ntile, int batch, int seq_len) {
   ItaLongArgs a{};
   a.image = L.simg_mha;
@@ -956,7 +963,7 @@ int launch_long(ita_context* h, int layer, const int8_t* xq, int8_t* yq, const f
     if (int rc = check_long_taps(*taps, seq_len, s)) return rc;
   // the logits of a long row still fit the 16-bit travel format: same bound as stream_range_ok (per key, not per row)
   const size_t ntile = (size_t)batch * (seq_len / 128);
-  if (int rc = ensure_long_ws(h, ntile, s)) return rc;
+  if (int rc = ensure_long_ws(h, long_int8_ws(ntile), s)) return rc;
   ItaLongArgs a = long_args(h, L, ntile, batch, seq_len);
   a.xq = xq; a.yq = yq; a.x = x; a.y = y; a.fuse_ln = fuse_ln ? 1 : 0;
   const bool fast = L.fast_sites == ITA_SITES_ALL;
@@ -1008,6 +1015,16 @@ int ita_mha_long_int8_taps(ita_handle h, int layer, const float* x, float* y, in
   return launch_long(h, layer, nullptr, nullptr, x, y, false, batch, seq_len, (hipStream_t)stream, taps ? taps : &none);
 }
 
+namespace {
+// The output refusals of the two statistics entries (ITA_ERR_INVALID_ARG): all six outputs null, or one of those stored as
+// 32-bit words (out[first_word] and the ones behind it) off a 4-byte boundary; the entry gives its own two messages
+int check_long_stats_outputs(const void* const (&out)[6], int first_word, const char* all_null, const char* unaligned) {
+  if (std::none_of(out, out + 6, [](const void* p) { return p != nullptr; })) return fail(ITA_ERR_INVALID_ARG, all_null);
+  if (std::any_of(out + first_word, out + 6, [](const void* p) { return misaligned(p, 4); })) return fail(ITA_ERR_INVALID_ARG, unaligned);
+  return ITA_OK;
+}
+}  // namespace
+
 // The production projection launch (f32 form), then ita_long_stats_kernel over its workspace: no y, no A.V, no out_proj
 int ita_mha_long_int8_stats(ita_handle h, int layer, const float* x, int batch, int seq_len, const ita_mha_long_stats* st,
                             void* stream) {
@@ -1016,13 +1033,11 @@ int ita_mha_long_int8_stats(ita_handle h, int layer, const float* x, int batch, 
   const Layer& L = h->w.layers[layer];
   hipStream_t s = (hipStream_t)stream;
   if (int rc = check_long(L, batch, seq_len)) return rc;
-  if (!st->row_max && !st->row_sum && !st->row_mass && !st->row_nnz && !st->col_mass && !st->col_nnz)
-    return fail(ITA_ERR_INVALID_ARG, "ita_mha_long_int8_stats: all six outputs are null");
-  if (misaligned(st->row_sum, 4) || misaligned(st->row_mass, 4) || misaligned(st->row_nnz, 4) || misaligned(st->col_mass, 4) ||
-      misaligned(st->col_nnz, 4))
-    return fail(ITA_ERR_INVALID_ARG, "row_sum, row_mass, row_nnz, col_mass and col_nnz must be 4-byte aligned");
+  if (int rc = check_long_stats_outputs({st->row_max, st->row_sum, st->row_mass, st->row_nnz, st->col_mass, st->col_nnz}, 1,   // row_max: int8
+                                        "ita_mha_long_int8_stats: all six outputs are null",
+                                        "row_sum, row_mass, row_nnz, col_mass and col_nnz must be 4-byte aligned")) return rc;
   const size_t ntile = (size_t)batch * (seq_len / 128);
-  if (int rc = ensure_long_ws(h, ntile, s)) return rc;
+  if (int rc = ensure_long_ws(h, long_int8_ws(ntile), s)) return rc;
   ItaLongArgs a = long_args(h, L, ntile, batch, seq_len);
   a.x = x;
   ItaLongStatsArgs sa{};
@@ -1066,21 +1081,7 @@ namespace {
 // an int8-attention layer, naming the sibling entry
 int check_long_f32(const Layer& L, int batch, int seq_len, const char* int8_layer) {
   if (!L.attn_f32) return fail(ITA_ERR_UNSUPPORTED, int8_layer);
-  if (seq_len < 128 || seq_len % 128 || seq_len > 65536 || batch > 65535)
-    return fail(ITA_ERR_UNSUPPORTED, "seq_len must be a multiple of 128 in [128, 65536], batch <= 65535");
-  return ITA_OK;
-}
-
-// The handle's long workspace at `need` bytes for a float entry: as ensure_long_ws, outside a stream capture only
-int ensure_long_f32_ws(ita_context* h, size_t need, hipStream_t s) {
-  if (need <= h->long_ws_bytes) return ITA_OK;
-  if (capturing(s))
-    return fail(ITA_ERR_INVALID_ARG, "the long-attention workspace cannot grow inside a stream capture; run one call first");
-  HIPCHK(hipDeviceSynchronize());
-  h->long_ws_bytes = 0;
-  HIPCHK(h->long_ws.alloc(need));
-  h->long_ws_bytes = need;
-  return ITA_OK;
+  return check_long_shape(batch, seq_len);
 }
 
 // The float32 long attention (ita_long_f32_kernel.h) of an ITAW0003 layer: the refusals, the workspace (the int8 long
@@ -1105,7 +1106,7 @@ int launch_long_f32(ita_context* h, int layer, const float* x, float* y, bool fu
   }
   const size_t ntile = (size_t)batch * (seq_len / 128);
   const size_t img = ntile * 2 * ItaLongF32Lds::UNIT;
-  if (int rc = ensure_long_f32_ws(h, 2 * img, s)) return rc;
+  if (int rc = ensure_long_ws(h, 2 * img, s)) return rc;
   ItaLongF32Args a{};
   a.x = x; a.y = y;
   a.wq = L.wqf; a.wk = L.wkf; a.wv = L.wvf; a.bq = L.bqf; a.bk = L.bkf; a.bv = L.bvf; a.wo = L.wof; a.bo = L.bof;
@@ -1173,11 +1174,8 @@ int ita_mha_long_f32_stats(ita_handle h, int layer, const float* x, int batch, i
                            const struct ita_mha_long_f32_stats* st, void* stream) {
   // the argument rules come first: they need neither the handle's contents nor the device
   if (!h || !x || !st) return fail(ITA_ERR_INVALID_ARG, "null handle, x_dev or stats");
-  if (!st->row_max && !st->row_sum && !st->row_gap && !st->row_nnz && !st->col_mass && !st->col_nnz)
-    return fail(ITA_ERR_INVALID_ARG, "ita_mha_long_f32_stats: all six outputs are null");
-  if (misaligned(st->row_max, 4) || misaligned(st->row_sum, 4) || misaligned(st->row_gap, 4) || misaligned(st->row_nnz, 4) ||
-      misaligned(st->col_mass, 4) || misaligned(st->col_nnz, 4))
-    return fail(ITA_ERR_INVALID_ARG, "every output must be 4-byte aligned");
+  if (int rc = check_long_stats_outputs({st->row_max, st->row_sum, st->row_gap, st->row_nnz, st->col_mass, st->col_nnz}, 0,
+                                        "ita_mha_long_f32_stats: all six outputs are null", "every output must be 4-byte aligned")) return rc;
   if (!(p_min > 0.0f && p_min <= 1.0f)) return fail(ITA_ERR_INVALID_ARG, "p_min must be in (0, 1]");   // NaN fails both
   if (int rc = check(h, batch)) return rc;
   if (layer < 0 || layer >= h->w.hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad layer");
@@ -1188,7 +1186,7 @@ int ita_mha_long_f32_stats(ita_handle h, int layer, const float* x, int batch, i
   const size_t nqt = (size_t)seq_len / 128, ntile = (size_t)batch * nqt;
   const size_t img = ntile * 2 * ItaLongF32Lds::UNIT, part = ntile * seq_len * 4;
   const bool cols = st->col_mass || st->col_nnz;
-  if (int rc = ensure_long_f32_ws(h, 2 * img + (cols ? 2 * part : 0), s)) return rc;
+  if (int rc = ensure_long_ws(h, 2 * img + (cols ? 2 * part : 0), s)) return rc;
   ItaLongF32Args a{};
   a.x = x;
   a.wk = L.wkf; a.wv = L.wvf; a.bk = L.bkf; a.bv = L.bvf;
