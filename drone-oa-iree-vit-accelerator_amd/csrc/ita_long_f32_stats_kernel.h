@@ -20,9 +20,11 @@
 // ("Long attention, shared").
 //
 // THE ORDER OF EVERY FLOAT ADDITION (no floating-point atomics anywhere; tests/long_f32_stats_common.py is this in numpy):
-//   row_gap   lane (query col, slot) holds keys 64 u + 16 kt + 4 slot + r of its query.  The lane's share starts at 0.0f and
-//             takes gap = gap + p * d for u ascending, inside a unit kt ascending, inside a tile r ascending.  The four
-//             slot lanes are then added as l is: g = g + xor16(g), g = g + xor32(g), that is (g0 + g1) + (g2 + g3).
+//   row_gap   lane (query col, slot) holds keys 64 u + 16 kt + 4 slot + r of its query.  Inside a unit the lane's 16
+//             products are added from 0.0f, gu = gu + p * d for kt ascending, inside a tile r ascending; the lane's share
+//             starts at 0.0f and takes gap = gap + gu for u ascending.  (One chain of all S / 4 products lost 4.1e-5 of a
+//             row_gap near 2 at S = 65536 on flat rows: 16384 small addends onto a running sum.)  The four slot lanes
+//             are then added as l is: g = g + xor16(g), g = g + xor32(g), that is (g0 + g1) + (g2 + g3).
 //   col_mass  (a) inside a wave, per key: the 16 query lanes of a DPP row by rotate-and-add, row_ror 8, 4, 2, 1.  Every
 //                 step adds a lane's value and its partner's, so all lanes hold the same bits: with v[q] the value of
 //                 query 16 w + q,  a[q] = v[q] + v[q + 8] (q < 8),  b[q] = a[q] + a[q + 4] (q < 4),
@@ -160,6 +162,7 @@ __global__ __launch_bounds__(512) void ita_lf32_stats_kernel(const ItaLongF32Sta
     f32x4 s[NKT];
     ita_lf32_logits((const f32x4*)(lds + L::K + (u & 1) * L::UNIT), lane, q, s);
     unsigned f4[NKT];   // byte r of word kt: is p of key 16 kt + 4 slot + r at least p_min
+    float gu = 0.0f;    // the unit's share of row_gap
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) {
       f4[kt] = 0;
@@ -168,12 +171,13 @@ __global__ __launch_bounds__(512) void ita_lf32_stats_kernel(const ItaLongF32Sta
         const float d = m - s[kt][r];
         const float p = ita_expf(s[kt][r] - m) * inv;
         s[kt][r] = p;
-        gap = gap + p * d;
+        gu = gu + p * d;
         const unsigned f = p >= a.p_min ? 1u : 0u;
         nnz += (int)f;
         f4[kt] |= f << (8 * r);
       }
     }
+    gap = gap + gu;
     if (cols) {
       float* cmw = cm + (u & 1) * 512 + wave * 64 + 4 * slot;
       int* cnw = cn + (u & 1) * 512 + wave * 64 + 4 * slot;

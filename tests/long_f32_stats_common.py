@@ -139,9 +139,11 @@ def sweeps(s, p_min=P_MIN, mutation=None):
     pd = p * d
     g = np.zeros((B, S, 4), np.float32)
     for u in range(nu):
+        gu = np.zeros((B, S, 4), np.float32)        # the unit's 16 products first, then onto the lane's share
         for kt in range(4):
             for r in range(4):
-                g = g + pd[:, :, 64 * u + 16 * kt + r:64 * u + 16 * kt + 16:4]
+                gu = gu + pd[:, :, 64 * u + 16 * kt + r:64 * u + 16 * kt + 16:4]
+        g = g + gu
     row_gap = (g[..., 0] + g[..., 1]) + (g[..., 2] if mutation == "lane_missing" else g[..., 2] + g[..., 3])
     # columns: 16 query lanes of a wave by rotate-and-add 8, 4, 2, 1; the 8 waves in order; the tiles in order
     v, c = p.reshape(B, nqt, 8, 16, S), keep.reshape(B, nqt, 8, 16, S).astype(np.int32)
