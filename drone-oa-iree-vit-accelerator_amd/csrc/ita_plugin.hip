@@ -28,6 +28,7 @@
 #include "ita_stream_kernel.h"
 #include "ita_long_attn_kernel.h"
 #include "ita_long_stats_kernel.h"
+#include "ita_long_prop_kernel.h"
 #include "ita_ffn_f32_kernel.h"
 #include "ita_attn_f32_kernel.h"
 #include "ita_long_f32_kernel.h"
@@ -1058,6 +1059,52 @@ int ita_mha_long_int8_stats(ita_handle h, int layer, const float* x, int batch, 
     constexpr bool FAST = decltype(fst)::value;
     if (int rc = launch<ita_long_proj_kernel<FAST, E, true>, ItaStreamLds<E, false, false>::TOTAL>(proj_grid, dim3(512), s, a)) return rc;
     return launch<ita_long_stats_kernel<FAST>, ItaLongStatsLds::TOTAL>(grid, dim3(512), s, sa);
+  };
+  return with_E(h->w.hdr.E, [&](auto e) { return fast ? run(e, std::true_type{}) : run(e, std::false_type{}); });
+}
+
+// out = w . P (ita_long_prop_kernel.h): the production projection launch, ita_long_stats_kernel for the row maximum and row
+// sum of every query (into the workspace: no column arrays, so no zero launch), the prep kernel, the transposed sweep
+int ita_mha_long_int8_propagate(ita_handle h, int layer, const float* x, int batch, int seq_len, const int8_t* w, int n_w,
+                                int32_t* out, void* stream) {
+  if (int rc = check(h, batch)) return rc;
+  if (!x || !w || !out || layer < 0 || layer >= h->w.hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
+  const Layer& L = h->w.layers[layer];
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = check_long(L, batch, seq_len)) return rc;
+  if (n_w < 1 || n_w > 64) return fail(ITA_ERR_INVALID_ARG, "ita_mha_long_int8_propagate: n_w must be in [1, 64]");
+  if (misaligned(w, 4) || misaligned(out, 16))
+    return fail(ITA_ERR_INVALID_ARG, "ita_mha_long_int8_propagate: w_dev must be 4-byte aligned, out_dev 16-byte aligned");
+  const size_t ntile = (size_t)batch * (seq_len / 128), ng = (size_t)(n_w + 15) / 16;
+  // behind the int8 workspace: row-parameter images, weight images, row_sum, 128 * weight row sums, row_max
+  const size_t base = long_int8_ws(ntile), rowp = ntile * 1024, wimg = ntile * ng * 2048, rsum = ntile * 128 * 4,
+               wsum = (size_t)batch * 64 * 4, rmax = ntile * 128;
+  if (int rc = ensure_long_ws(h, base + rowp + wimg + rsum + wsum + rmax, s)) return rc;
+  ItaLongArgs a = long_args(h, L, ntile, batch, seq_len);
+  a.x = x;
+  char* p = a.qfrag + base;
+  ItaLongPropPrepArgs pa{};
+  pa.rowp = p; pa.wimg = p + rowp;
+  int* row_sum = (int*)(p + rowp + wimg);
+  pa.wsum = (int*)(p + rowp + wimg + rsum);
+  int8_t* row_max = (int8_t*)(p + rowp + wimg + rsum + wsum);
+  pa.row_max = row_max; pa.row_sum = row_sum; pa.w = w; pa.B = batch; pa.S = seq_len; pa.n_w = n_w;
+  ItaLongStatsArgs sa{};
+  sa.qfrag = a.qfrag; sa.kimg = a.kimg; sa.ml = a.ml; sa.B = batch; sa.S = seq_len;
+  sa.row_max = row_max; sa.row_sum = row_sum;
+  ItaLongPropArgs ka{};
+  ka.qfrag = a.qfrag; ka.kimg = a.kimg; ka.rowp = pa.rowp; ka.wimg = pa.wimg; ka.wsum = pa.wsum; ka.ml = a.ml;
+  ka.B = batch; ka.S = seq_len; ka.n_w = n_w; ka.out = out;
+  const bool fast = L.fast_sites == ITA_SITES_ALL;
+  const dim3 proj_grid(ntile < (size_t)h->num_cus ? (int)ntile : h->num_cus), grid(seq_len / 128, batch);
+  const dim3 prep_grid(seq_len / 128 + 16 * (int)ng, batch);
+  auto run = [&](auto e, auto fst) {
+    constexpr int E = decltype(e)::value;
+    constexpr bool FAST = decltype(fst)::value;
+    if (int rc = launch<ita_long_proj_kernel<FAST, E, true>, ItaStreamLds<E, false, false>::TOTAL>(proj_grid, dim3(512), s, a)) return rc;
+    if (int rc = launch<ita_long_stats_kernel<FAST>, ItaLongStatsLds::TOTAL>(grid, dim3(512), s, sa)) return rc;
+    if (int rc = launch<ita_long_prop_prep_kernel>(prep_grid, dim3(512), s, pa)) return rc;
+    return launch<ita_long_prop_kernel<FAST>, ItaLongPropLds::TOTAL>(grid, dim3(512), s, ka);
   };
   return with_E(h->w.hdr.E, [&](auto e) { return fast ? run(e, std::true_type{}) : run(e, std::false_type{}); });
 }

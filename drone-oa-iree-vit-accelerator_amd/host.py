@@ -34,7 +34,7 @@ HEAD_TIMEOUT = 1
 
 EXPORTED_SYMBOLS = (
     "ita_abi_version", "ita_create", "ita_destroy", "ita_load_weights", "ita_validate_blob", "ita_reserve", "ita_get_dims",
-    "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_mha_long_int8", "ita_mha_long_int8_taps", "ita_mha_long_int8_stats", "ita_encoder_layer_long", "ita_ffn_int8", "ita_ffn_int8_taps",
+    "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_mha_long_int8", "ita_mha_long_int8_taps", "ita_mha_long_int8_stats", "ita_mha_long_int8_propagate", "ita_encoder_layer_long", "ita_ffn_int8", "ita_ffn_int8_taps",
     "ita_ffn_f32", "ita_get_ffn_kind", "ita_mha_f32", "ita_get_attn_kind", "ita_mha_long_f32", "ita_mha_long_f32_taps", "ita_mha_long_f32_stats", "ita_encoder_layer_long_f32",
     "ita_encoder_layer", "ita_tokenizer", "ita_fusion_tail", "ita_vitlstm_forward", "ita_bind_dispatch",
     "ita_profile_begin", "ita_profile_begin_sampled", "ita_profile_end", "ita_set_tail_mode", "ita_debug_encoder_stamps",
@@ -105,6 +105,28 @@ class _MhaLongStats(C.Structure):     # ita_mha_long_stats
 
 
 LONG_STATS = ("row_max", "row_sum", "row_mass", "row_nnz", "col_mass", "col_nnz")
+LONG_MAX_WEIGHT_ROWS = 64      # ita_mha_long_int8_propagate: n_w in [1, 64]
+ROLLOUT_QMAX = 2097151         # attention rollout: a vector is quantised to 21 bits, three base-128 digits
+ROLLOUT_CHUNK = LONG_MAX_WEIGHT_ROWS // 3      # vectors per ita_mha_long_int8_propagate call
+
+
+def rollout_digits(q):
+    """the three base-128 digit planes of q: integers in [0, 2^21), (..., n, S) -> int8 (..., 3 n, S) with row k n + j =
+    (q[j] >> 7 k) & 127 (numpy)"""
+    import numpy as np
+    q = np.asarray(q, np.int64)
+    if q.min(initial=0) < 0 or q.max(initial=0) > ROLLOUT_QMAX:
+        raise ValueError("rollout_digits takes integers in [0, 2^21)")
+    return np.concatenate([(q >> (7 * k)) & 127 for k in range(3)], axis=-2).astype(np.int8)
+
+
+def rollout_combine(d):
+    """d = rollout_digits(q) @ P, integer (..., 3 n, S) -> q @ P = sum_k 128^k d[k n : (k + 1) n], int64 (..., n, S) (numpy)"""
+    import numpy as np
+    d = np.asarray(d).astype(np.int64)
+    n = d.shape[-2] // 3
+    assert d.shape[-2] == 3 * n, d.shape
+    return d[..., :n, :] + (d[..., n:2 * n, :] << 7) + (d[..., 2 * n:, :] << 14)
 
 
 class _MhaLongF32Taps(C.Structure):   # ita_mha_long_f32_taps
@@ -177,6 +199,7 @@ def lib():
         L.ita_mha_long_int8.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_int8_taps.argtypes = [vp, i, vp, vp, i, i, C.POINTER(_MhaLongTaps), vp]
         L.ita_mha_long_int8_stats.argtypes = [vp, i, vp, i, i, C.POINTER(_MhaLongStats), vp]
+        L.ita_mha_long_int8_propagate.argtypes = [vp, i, vp, i, i, vp, i, vp, vp]
         L.ita_encoder_layer_long.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_f32.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_f32_taps.argtypes = [vp, i, vp, vp, i, i, C.POINTER(_MhaLongF32Taps), vp]
@@ -750,6 +773,91 @@ class Engine:
         attention_received_long of `layer` -> (N, tok_h, tok_w) int32"""
         y = self._tokens_below(frames, int(tok_h), int(tok_w), layer, depth_scale)
         return self.attention_received_long(y, int(layer)).reshape(y.shape[0], int(tok_h), int(tok_w))
+
+    def attention_propagate_long(self, x, w, layer: int = 0):
+        """weighted column sums of the whole S x S integer-softmax matrix of a long sequence, which is never held
+        (ita_mha_long_int8_propagate): x (B,S,E) f32, w int8 GPU tensor (B,R,S), or (R,S) for the same weights of every
+        frame (copied B times), 1 <= R <= 64 -> out (B,R,S) int32, out[b,r,j] = sum_i w[b,r,i] p[b,i,j] with p the uint8
+        probabilities of attention_rows_long.  Exact: equal to attention_propagate_ref.propagate.  All-ones weights give
+        attention_received_long, a one-hot row gives that probability row.  Every partial sum fits int32 for any int8
+        weight at S <= 32768 and at S = 65536 for weights in [-127, 127] (127 * 128 * 65536 < 2^30, twice); the weights
+        are not scanned."""
+        torch = _torch()
+        x = self._long_f32(x)
+        B, S = x.shape[0], x.shape[1]
+        if not w.is_cuda or w.dtype != torch.int8 or w.dim() not in (2, 3) or w.shape[-1] != S or (w.dim() == 3 and w.shape[0] != B):
+            raise ITAError(f"w must be an int8 GPU tensor of shape ({B}, R, {S}) or (R, {S}), got {w.dtype} {tuple(w.shape)}")
+        if w.dim() == 2:
+            w = w.unsqueeze(0).expand(B, -1, -1)
+        w = w.contiguous()
+        out = torch.empty((B, w.shape[1], S), dtype=torch.int32, device=x.device)
+        _chk(lib().ita_mha_long_int8_propagate(self._h, layer, x.data_ptr(), B, S, w.data_ptr(), w.shape[1], out.data_ptr(),
+                                               _stream_ptr(self.device)))
+        return out
+
+    def attention_rollout_long(self, x, rows=None, first_layer: int = 0):
+        """attention rollout (Abnar & Zuidema) through the int8 attention layers first_layer .. num_layers - 1 of a long
+        sequence: identity residual, attention matrix P_l / 256.  x (B,S,E) f32: the token rows entering first_layer;
+        rows: token indices in any order (duplicates raise ValueError), or None for the single start vector 1 / S ->
+        (B, n, S) float64 on x's device: how much output token rows[n] depends on every input token.  The layers run out
+        of place (encoder_layer_long, or encoder_layer_long_f32 where the FFN is float) and each layer's input is kept;
+        from the last layer down, with v = one-hot(rows) at the start,
+            s = max_j v (1 where that is 0);  q = rint((v / s) * 2097151)
+            v <- 0.5 * (v + ((float64(q . P_l) * (s / 2097151)) / 256))
+        where q . P_l comes from attention_propagate_long on the three base-128 digit rows of q (rollout_digits,
+        rollout_combine): 21 vectors per call, more in chunks.  Equal to attention_rollout_ref.rollout bit for bit."""
+        import numpy as np
+        torch = _torch()
+        x = self._long_f32(x)
+        B, S = x.shape[0], x.shape[1]
+        first_layer = int(first_layer)
+        if not 0 <= first_layer < self.num_layers:
+            raise ValueError(f"first_layer {first_layer} out of range")
+        if rows is None:
+            v = np.full((B, 1, S), 1.0 / S, np.float64)
+        else:
+            rows = [int(r) for r in rows]
+            if any(not 0 <= r < S for r in rows):
+                raise ValueError(f"rows must be token indices in [0, {S})")
+            if len(set(rows)) != len(rows):
+                raise ValueError("duplicate rows")
+            v = np.zeros((B, len(rows), S), np.float64)
+            for n, r in enumerate(rows):
+                v[:, n, r] = 1.0
+        xs = [x]
+        for l in range(first_layer, self.num_layers - 1):
+            step = self.encoder_layer_long_f32 if self.ffn_kind(l) == FFN_F32 else self.encoder_layer_long
+            xs.append(step(xs[-1], l))
+        for l in range(self.num_layers - 1, first_layer - 1, -1):
+            s = v.max(-1, keepdims=True)
+            s = np.where(s == 0, 1.0, s)
+            q = np.rint((v / s) * float(ROLLOUT_QMAX)).astype(np.int64)
+            qp = np.empty(v.shape, np.int64)
+            for c0 in range(0, v.shape[1], ROLLOUT_CHUNK):
+                c = slice(c0, min(c0 + ROLLOUT_CHUNK, v.shape[1]))
+                d = torch.from_numpy(rollout_digits(q[:, c])).to(x.device)
+                qp[:, c] = rollout_combine(self.attention_propagate_long(xs[l - first_layer], d, l).cpu().numpy())
+            v = 0.5 * (v + ((qp.astype(np.float64) * (s / float(ROLLOUT_QMAX))) / 256.0))
+        return torch.from_numpy(v).to(x.device)
+
+    def attention_rollout_map_long(self, frames, tok_h: int, tok_w: int, queries=None, depth_scale: Optional[float] = None):
+        """attention rollout on the token grid of camera frames: tokenize_long, then attention_rollout_long through every
+        layer for the tokens queries = [(ty, tx), ...] (None: the single start vector 1 / S) -> (N, n, tok_h, tok_w)
+        float64 in the order of queries.  Duplicate or out-of-grid queries raise ValueError."""
+        tok_h, tok_w = int(tok_h), int(tok_w)
+        toks = None
+        if queries is not None:
+            toks = []
+            for ty, tx in queries:
+                ty, tx = int(ty), int(tx)
+                if not (0 <= ty < tok_h and 0 <= tx < tok_w):
+                    raise ValueError(f"query ({ty}, {tx}) lies outside the {tok_h} x {tok_w} token grid")
+                toks.append(ty * tok_w + tx)
+            if len(set(toks)) != len(toks):
+                raise ValueError("duplicate queries")
+        y = self.tokenize_long(frames, tok_h, tok_w, depth_scale)
+        v = self.attention_rollout_long(y, toks)
+        return v.reshape(v.shape[0], v.shape[1], tok_h, tok_w)
 
     def _tokens_below(self, frames, tok_h, tok_w, layer, depth_scale):
         """tokenize_long and the encoder layers below `layer`: the token rows that layer's attention reads"""

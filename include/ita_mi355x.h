@@ -53,7 +53,7 @@ int ita_destroy(ita_handle h);
  * A layer with H > 1 runs on the block kernels (ita_mha_kernel<E, H>, then the FFN block) behind the stand-alone tokenizer;
  * every entry point below serves it except those that need the one-head stream kernel, which return
  * ITA_ERR_UNSUPPORTED before any launch: ita_mha_q8, ita_mha_long_q8, ita_mha_long_int8, ita_mha_long_int8_taps,
- * ita_mha_long_int8_stats, ita_encoder_layer_long, ita_debug_encoder_stamps, ita_vitlstm_forward_slots (and ita_mha_long_f32 / ita_mha_long_f32_stats / ita_encoder_layer_long_f32, which take
+ * ita_mha_long_int8_stats, ita_mha_long_int8_propagate, ita_encoder_layer_long, ita_debug_encoder_stamps, ita_vitlstm_forward_slots (and ita_mha_long_f32 / ita_mha_long_f32_stats / ita_encoder_layer_long_f32, which take
  * float layers only).
  * The reference pre-loads weights into the accelerator out of band
  * (docs/HOW-TO-run-the-full-project-workflow.md:55); this is that step. */
@@ -150,6 +150,24 @@ typedef struct ita_mha_long_stats {
 } ita_mha_long_stats;
 int ita_mha_long_int8_stats(ita_handle h, int layer, const float* x_dev, int batch, int seq_len,
                             const ita_mha_long_stats* stats, void* stream);
+/* Weighted column sums of the WHOLE seq_len x seq_len probability matrix of ita_mha_long_int8 (H = 1), which is never held:
+ *     out[b, r, j] = sum_i w[b, r, i] * p[b, i, j]      w s8 (B, n_w, seq_len), out s32 (B, n_w, seq_len), 1 <= n_w <= 64
+ * with p[b, i, j] the u8 probability of query i for key j, the bits of ita_mha_long_taps' probs.  col_mass of
+ * ita_mha_long_int8_stats is w = all ones, a probability row is w = one-hot.  The result is exact (equal to
+ * attention_propagate_ref.py); the same input gives the same bytes on every call (no atomics).  Range: every partial sum
+ * the kernel forms is 128 sum_i w + sum_{i < n} w (p - 128), with |sum w (p - 128)| and |128 sum w| each at most
+ * 128 * 128 * seq_len, so it and the result fit s32 for ANY s8 weight at seq_len <= 32 768, and at seq_len = 65 536 for
+ * weights in [-127, 127] (127 * 128 * 65 536 < 2^30 each).  The weights are not scanned: beyond that bound the sums wrap.
+ * x (B, seq_len, E) f32 is read only; w and out must not overlap each other or x.  Launches: the production projection,
+ * ita_long_stats_kernel for the row maximum and row sum of every query (into the workspace), a small kernel that packs them
+ * per token, sums the weight rows and permutes w into MFMA operand images, and ita_long_prop_kernel, the transposed sweep
+ * (csrc/ita_long_prop_kernel.h).  Workspace: ita_mha_long_q8's plus, per 128-token tile, 1664 + 2048 ceil(n_w / 16) bytes
+ * and 256 bytes per frame; once it holds the call there is no host synchronisation and no allocation, the call may be
+ * captured and is kernel nodes only.  Refusals, all before any launch, out untouched: whatever ita_mha_long_int8 refuses,
+ * with the same status; ITA_ERR_INVALID_ARG for a NULL x_dev, w_dev or out_dev, a bad layer, n_w outside [1, 64], w_dev
+ * off a 4-byte boundary or out_dev off a 16-byte boundary. */
+int ita_mha_long_int8_propagate(ita_handle h, int layer, const float* x_dev, int batch, int seq_len,
+                                const int8_t* w_dev, int n_w, int32_t* out_dev, void* stream);
 /* The long form of ita_encoder_layer: y = LN2(x1 + ffn(x1)), x1 = LN1(x + attn(x)) on (B, seq_len, E) f32 rows; x_dev may
  * equal y_dev.  Attention + residual + LN1 are the two long launches (x1 goes to y), the FFN + residual + LN2 then run in
  * place on y, 128 rows per block (ita_ffn_int8's kernel: the FFN is per token).  Shape limits, workspace and refusals of
