@@ -231,18 +231,54 @@ __device__ __forceinline__ void dq16_b(const i32x4 (&acc)[4], float mult, float 
 //           the reference's two roundings only for accumulator values whose exact product lies within half an ulp of a
 //           rounding tie without being one; ita_load_weights enumerates every accumulator value of the clamp range for the
 //           site's multiplier (fast_site_ok) and enables this form only when none differs.
+//   fused : the accumulator was started at an integer C chosen per site at load time instead of at 1.5*2^23 (its pattern is
+//           still the float C + sum), and t = fma(acc_bits, m, K), K = magic - round(C m), in ONE v_pk_fma_f32 and nothing
+//           else: 1.75 instructions per value.  C is picked so that C m lies within ~1e-6 of an integer; the same
+//           enumeration as for the fast form then shows that no accumulator value of the clamp range lands that close to a
+//           tie (ita_weights_load.h: fused_site), else the site, and with it the layer, keeps the fast or exact form.
+//   fused relu : the fused form against K = 1.5*2^23 - round(C m), no + 128: the low 16 bits are r itself, signed; one
+//           v_pk_min_i16 with 127 per pair, then the u8 saturation clamps at 0: the codes are 0 .. 127 and need no sign
+//           flip -- 2.0 instructions per value.  Proven per multiplier like the fused form, on codes clamped to [0, 127].
 //   relu  : the exact form with the lower clamp moved into the multiply: y/256 = fl(x * (m/256)) with the VOP3P clamp
 //           modifier ([0, 1] <-> y in [0, 256]), t = y/256 + (1.5*2^23 + 128)/256 (ulp 2^-8: same integer rounding, same low
 //           bits), the u8 saturation then gives min(r, 127) + 128.
 #define ITA_MAGIC128_F 12583040.0f        /* 1.5 * 2^23 + 128 */
 #define ITA_MAGIC32K_F 12615680.0f        /* 1.5 * 2^23 + 32768: low 16 bits = r + 32768 = r ^ 0x8000 (order-preserving u16) */
-enum { ITA_RQ_EXACT = 0, ITA_RQ_FAST = 1, ITA_RQ_RELU = 2 };
+enum { ITA_RQ_EXACT = 0, ITA_RQ_FAST = 1, ITA_RQ_RELU = 2, ITA_RQ_FUSED = 3, ITA_RQ_FUSED_RELU = 4 };
 
 template <int NP, int MODE>   // NP register pairs: acc bit patterns -> float patterns whose low 16 bits hold rne(acc * mult) + bias
 __device__ __forceinline__ void pk_requant_round(f32x2 (&x)[NP], float mult, float magic) {
   static_assert(NP == 8 || NP == 4, "");
   const f32x2 c2 = {-ITA_MAGIC_F, -ITA_MAGIC_F};
-  if constexpr (MODE == ITA_RQ_FAST) {
+  if constexpr (MODE == ITA_RQ_FUSED || MODE == ITA_RQ_FUSED_RELU) {
+    // `magic` is the site's K = magic - round(C m); the accumulators were started at the site's C (copied into a VGPR pair
+    // inside the block for the same two reasons as in the fast form below)
+    const f32x2 m2 = {mult, mult}, g2s = {magic, magic};
+    f32x2 g2;
+    if constexpr (NP == 8) {
+      asm("s_nop 7\n\ts_nop 1\n\t"
+        "v_pk_mov_b32 %8, %10, %10\n\t"
+        "v_pk_fma_f32 %0, %0, %9, %8\n\t"
+        "v_pk_fma_f32 %1, %1, %9, %8\n\t"
+        "v_pk_fma_f32 %2, %2, %9, %8\n\t"
+        "v_pk_fma_f32 %3, %3, %9, %8\n\t"
+        "v_pk_fma_f32 %4, %4, %9, %8\n\t"
+        "v_pk_fma_f32 %5, %5, %9, %8\n\t"
+        "v_pk_fma_f32 %6, %6, %9, %8\n\t"
+        "v_pk_fma_f32 %7, %7, %9, %8"
+          : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]), "=&v"(g2)
+          : "s"(m2), "s"(g2s));
+    } else {
+      asm("s_nop 7\n\ts_nop 1\n\t"
+        "v_pk_mov_b32 %4, %6, %6\n\t"
+        "v_pk_fma_f32 %0, %0, %5, %4\n\t"
+        "v_pk_fma_f32 %1, %1, %5, %4\n\t"
+        "v_pk_fma_f32 %2, %2, %5, %4\n\t"
+        "v_pk_fma_f32 %3, %3, %5, %4"
+          : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "=&v"(g2)
+          : "s"(m2), "s"(g2s));
+    }
+  } else if constexpr (MODE == ITA_RQ_FAST) {
     // (an instruction reads at most one SGPR operand: the magic constant is copied into a VGPR pair inside the block -- as a
     //  loop-invariant VGPR pair the compiler would hoist it out of the frame loop and, at 256 registers, spill it)
     const f32x2 m2 = {mult, mult}, g2s = {magic, magic};
@@ -387,28 +423,57 @@ __device__ __forceinline__ i32x4 sat_pack16(const unsigned (&w)[8]) {
       : "v"(w[0]), "v"(w[1]), "v"(w[2]), "v"(w[3]), "v"(w[4]), "v"(w[5]), "v"(w[6]), "v"(w[7]), "s"(flip));
   return (i32x4){(int)p0, (int)p1, (int)p2, (int)p3};
 }
+// the same for the fused ReLU form: the halves hold r (no + 128); min(r, 127) per half, then the u8 saturation = clamp(r, 0, 127)
+__device__ __forceinline__ i32x4 sat_pack16_relu(unsigned (&w)[8]) {
+  unsigned p0, p1, p2, p3;
+  const unsigned c127 = 0x007F007Fu;
+  asm(
+      "v_pk_min_i16 %4, %4, %12\n\t"
+      "v_pk_min_i16 %5, %5, %12\n\t"
+      "v_pk_min_i16 %6, %6, %12\n\t"
+      "v_pk_min_i16 %7, %7, %12\n\t"
+      "v_pk_min_i16 %8, %8, %12\n\t"
+      "v_pk_min_i16 %9, %9, %12\n\t"
+      "v_pk_min_i16 %10, %10, %12\n\t"
+      "v_pk_min_i16 %11, %11, %12\n\t"
+      "v_sat_pk_u8_i16_sdwa %0, %4 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:DWORD\n\t"
+      "v_sat_pk_u8_i16_sdwa %1, %6 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:DWORD\n\t"
+      "v_sat_pk_u8_i16_sdwa %2, %8 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:DWORD\n\t"
+      "v_sat_pk_u8_i16_sdwa %3, %10 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:DWORD\n\t"
+      "v_sat_pk_u8_i16_sdwa %0, %5 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD\n\t"
+      "v_sat_pk_u8_i16_sdwa %1, %7 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD\n\t"
+      "v_sat_pk_u8_i16_sdwa %2, %9 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD\n\t"
+      "v_sat_pk_u8_i16_sdwa %3, %11 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD\n\t"
+      "s_nop 0"
+      : "=&v"(p0), "=&v"(p1), "=&v"(p2), "=&v"(p3), "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]), "+v"(w[4]), "+v"(w[5]),
+        "+v"(w[6]), "+v"(w[7])
+      : "s"(c127));
+  return (i32x4){(int)p0, (int)p1, (int)p2, (int)p3};
+}
 // requantise + pack sixteen biased accumulators (four 16x16 tiles): byte 4t + i of the result <-> acc[t][i]
+// (kf: the site's K of the fused form, unused by the others)
 template <int MODE>
-__device__ __forceinline__ i32x4 rq_pack16_v3(const i32x4 (&acc)[4], float mult) {
+__device__ __forceinline__ i32x4 rq_pack16_v3(const i32x4 (&acc)[4], float mult, float kf = 0.0f) {
   f32x2 x[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) x[k] = (f32x2){__int_as_float(acc[k >> 1][2 * (k & 1)]), __int_as_float(acc[k >> 1][2 * (k & 1) + 1])};
   if constexpr (MODE == ITA_RQ_RELU) pk_requant_round<8, MODE>(x, mult * 0.00390625f, ITA_MAGIC128_F * 0.00390625f);
-  else pk_requant_round<8, MODE>(x, mult, ITA_MAGIC128_F);
+  else pk_requant_round<8, MODE>(x, mult, (MODE == ITA_RQ_FUSED || MODE == ITA_RQ_FUSED_RELU) ? kf : ITA_MAGIC128_F);
   unsigned w[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k)   // {lo16(x.x), lo16(x.y)}
     w[k] = __builtin_amdgcn_perm(__float_as_uint(x[k].y), __float_as_uint(x[k].x), 0x05040100u);
+  if constexpr (MODE == ITA_RQ_FUSED_RELU) return sat_pack16_relu(w);
   return sat_pack16(w);
 }
 // logits: eight biased accumulators (two key tiles) -> four dwords of two ORDER-PRESERVING u16 each: rne(acc * mult) + 32768,
 // unclamped (the integer softmax clamps: ita_softmax_packed16).  Pair k <-> acc[k >> 1][2 (k & 1)], [.. + 1].
 template <int MODE>
-__device__ __forceinline__ void lg8_v3(const i32x4 (&acc)[2], float mult, unsigned (&w)[4]) {
+__device__ __forceinline__ void lg8_v3(const i32x4 (&acc)[2], float mult, unsigned (&w)[4], float kf = 0.0f) {
   f32x2 x[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) x[k] = (f32x2){__int_as_float(acc[k >> 1][2 * (k & 1)]), __int_as_float(acc[k >> 1][2 * (k & 1) + 1])};
-  pk_requant_round<4, MODE>(x, mult, ITA_MAGIC32K_F);
+  pk_requant_round<4, MODE>(x, mult, MODE == ITA_RQ_FUSED ? kf : ITA_MAGIC32K_F);
 #pragma unroll
   for (int k = 0; k < 4; ++k) w[k] = __builtin_amdgcn_perm(__float_as_uint(x[k].y), __float_as_uint(x[k].x), 0x05040100u);
 }

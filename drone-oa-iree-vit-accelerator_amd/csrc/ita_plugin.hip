@@ -371,10 +371,15 @@ struct StreamIo {
   StageRecorder* mid = nullptr;   // launch_encoder: marks the attention / FFN boundary of a layer that runs as two launches
 };
 
-// the stream kernel's instantiations without stamps; `fast` picks the single-rounding one (all six sites proven: fast_site_ok)
+// the stream kernel's instantiations without stamps; `fast` picks the single-rounding one (all six sites proven: fast_site_ok),
+// `fused` the one-fma one (a.image then holds the layer's own accumulator bases: Layer::fused)
 template <int E, bool FFN, int TOK, bool IO8>
-int launch_stream_kernel(bool fast, dim3 grid, hipStream_t s, const ItaStreamArgs& a) {
+int launch_stream_kernel(bool fast, int fused, dim3 grid, hipStream_t s, const ItaStreamArgs& a) {
   constexpr int lds = ItaStreamLds<E, FFN, TOK != 0>::TOTAL;
+  if constexpr (FFN) {
+    if (fused == 2) return launch<ita_stream_kernel<E, FFN, TOK, false, IO8, true, 2>, lds>(grid, dim3(512), s, a);
+  }
+  if (fused) return launch<ita_stream_kernel<E, FFN, TOK, false, IO8, true, 1>, lds>(grid, dim3(512), s, a);
   return fast ? launch<ita_stream_kernel<E, FFN, TOK, false, IO8, true>, lds>(grid, dim3(512), s, a)
               : launch<ita_stream_kernel<E, FFN, TOK, false, IO8, false>, lds>(grid, dim3(512), s, a);
 }
@@ -394,31 +399,38 @@ int launch_stream(ita_context* c, int layer, int mode, bool fuse_ln, const Strea
   a.fast_sites = L.fast_sites;
   const dim3 grid(B < c->num_cus ? B : c->num_cus), block(512);
   const bool fast = L.fast_sites == ITA_SITES_ALL;
+  // the fused form: its own images, and the constants of its five sites
+  const int fused = (L.fused && !io.stamps) ? (L.fused_relu ? 2 : 1) : 0;   // (2: fc1 as well, the whole-layer flavours)
+  if (fused) {
+    a.k1 = L.fused_k[5];
+    a.kq = L.fused_k[0]; a.kk = L.fused_k[1]; a.kv = L.fused_k[2]; a.kl = L.fused_k[3]; a.kc = L.fused_k[4];
+    a.c_l = L.fused_c[3]; a.c_c = L.fused_c[4];
+  }
   if (mode == 2) {
     if (!L.simg_mha) return fail(ITA_ERR_UNSUPPORTED, "this layer has no attention image (accumulator range, or more than one head)");
-    a.image = L.simg_mha;
-    return with_E(c->w.hdr.E, [&](auto e) { return launch_stream_kernel<decltype(e)::value, false, 0, true>(fast, grid, s, a); });
+    a.image = fused ? L.fimg_mha : L.simg_mha;
+    return with_E(c->w.hdr.E, [&](auto e) { return launch_stream_kernel<decltype(e)::value, false, 0, true>(fast, fused, grid, s, a); });
   }
   if (mode == 1) {
     if (!L.simg_mha) return fail(ITA_ERR_BAD_BLOB, "attention image missing");
     if (fuse_ln && !L.n1w) return fail(ITA_ERR_BAD_BLOB, "norm1 parameters missing from the blob");
-    a.image = L.simg_mha;
-    return with_E(c->w.hdr.E, [&](auto e) { return launch_stream_kernel<decltype(e)::value, false, 0, false>(fast, grid, s, a); });
+    a.image = fused ? L.fimg_mha : L.simg_mha;
+    return with_E(c->w.hdr.E, [&](auto e) { return launch_stream_kernel<decltype(e)::value, false, 0, false>(fast, fused, grid, s, a); });
   }
   if (io.img) {
     if (!L.simg_tok) return fail(ITA_ERR_BAD_BLOB, "tokenizer / LayerNorm parameters missing from the blob");
-    a.image = L.simg_tok;
+    a.image = fused ? L.fimg_tok : L.simg_tok;
     if (io.stamps) return launch<ita_stream_kernel<64, true, 1, true>, ItaStreamLds<64, true, true>::TOTAL>(grid, block, s, a);
-    return launch_stream_kernel<64, true, 1, false>(fast, grid, s, a);
+    return launch_stream_kernel<64, true, 1, false>(fast, fused, grid, s, a);
   }
   if (!L.simg_enc) return fail(ITA_ERR_BAD_BLOB, "LayerNorm parameters missing from the blob");
-  a.image = L.simg_enc;
+  a.image = fused ? L.fimg_enc : L.simg_enc;
   if (c->w.hdr.E == 128) {   // attention + FFN of an E = 128 layer in one launch; fc1 / fc2 weights are read from the global image
     if (io.stamps) return fail(ITA_ERR_UNSUPPORTED, "phase stamps are built for the E = 64 encoder");
-    return launch_stream_kernel<128, true, 0, false>(fast, grid, s, a);
+    return launch_stream_kernel<128, true, 0, false>(fast, fused, grid, s, a);
   }
   if (io.stamps) return launch<ita_stream_kernel<64, true, 0, true>, ItaStreamLds<64, true, false>::TOTAL>(grid, block, s, a);
-  return launch_stream_kernel<64, true, 0, false>(fast, grid, s, a);
+  return launch_stream_kernel<64, true, 0, false>(fast, fused, grid, s, a);
 }
 
 int launch_mha_stream(ita_context* c, int layer, const float* x, float* y, int B, bool fuse, hipStream_t s) {
@@ -1369,6 +1381,29 @@ int ita_debug_softmax_rows(ita_handle h, const int8_t* logits, uint8_t* probs, i
 }
 
 int ita_debug_fast_site_ok(float mult) { return fast_site_ok(mult) ? 1 : 0; }
+int ita_debug_fused_site(float mult, int* C, float* K) {
+  if (!C || !K) return 0;
+  return fused_site(mult, ITA_MAGIC128_F, ITA_FUSED_DMAX, C, K) ? 1 : 0;
+}
+int ita_debug_fused_check(float mult, int form, int C, float* K) {
+  float k = 0.0f;
+  const int ok = fused_site_check(mult, form == 1 ? ITA_MAGIC32K_F : form == 2 ? ITA_MAGIC_F : ITA_MAGIC128_F, C, &k) ? 1 : 0;
+  if (K) *K = k;
+  return ok;
+}
+int ita_debug_layer_fused(ita_handle h, int layer, unsigned* fused_sites, int* fused, int* C6, float* K6) {
+  if (!h || !h->w.loaded) return fail(ITA_ERR_NO_WEIGHTS, "no weights loaded");
+  if (!fused_sites || !fused || layer < 0 || layer >= h->w.hdr.num_layers)
+    return fail(ITA_ERR_INVALID_ARG, "ita_debug_layer_fused: null output or layer out of range");
+  const Layer& L = h->w.layers[layer];
+  *fused_sites = L.fused_sites;
+  *fused = L.fused ? (L.fused_relu ? 2 : 1) : 0;
+  for (int i = 0; i < 6; ++i) {
+    if (C6) C6[i] = L.fused_c[i];
+    if (K6) K6[i] = L.fused_k[i];
+  }
+  return ITA_OK;
+}
 
 int ita_debug_layer_forms(ita_handle h, int layer, unsigned* fast_sites, int* stream_images) {
   if (!h || !h->w.loaded) return fail(ITA_ERR_NO_WEIGHTS, "no weights loaded");

@@ -56,8 +56,15 @@ struct ItaStreamArgs {
   // ita_load_weights has enumerated every accumulator value of the site's clamp range and found the two forms equal.
   // Informational inside the kernel: the launcher picks the FAST instantiation when all six bits are set.
   unsigned fast_sites;
+  // the FUSED instantiation (the launcher picks it when every fused site of the layer is proven, ita_weights_load.h:
+  // fused_site): the logits' and the column sums' accumulator bases C_L, C_C, and K_site = magic - round(C_site m_site) of
+  // Q, K, V, logits and context.  The bases of Q, K and V are in the image's biases.  Unused by the other instantiations.
+  int c_l, c_c;
+  float kq, kk, kv, kl, kc, k1;   // k1: fc1's K of the fused ReLU form (FUSED == 2; its base is in the image's b1)
 };
-enum { ITA_SITE_Q = 1, ITA_SITE_K = 2, ITA_SITE_V = 4, ITA_SITE_L = 8, ITA_SITE_C = 16, ITA_SITE_O = 32, ITA_SITES_ALL = 63 };
+enum { ITA_SITE_Q = 1, ITA_SITE_K = 2, ITA_SITE_V = 4, ITA_SITE_L = 8, ITA_SITE_C = 16, ITA_SITE_O = 32, ITA_SITES_ALL = 63,
+       ITA_SITES_FUSED = 31 /* the sites the fused instantiation changes: all but out_proj */,
+       ITA_SITE_FC1 = 32 /* in the FUSED mask only (the fast mask's bit 5 is out_proj): fc1's fused ReLU form */ };
 
 #define ITA_SCHED_BARRIER() __builtin_amdgcn_sched_barrier(0)
 
@@ -235,10 +242,13 @@ __device__ __forceinline__ void mm_group(const ItaFr<4 * NKS>& f, const i32x4 (&
 // requantise four tiles and pack them: ONE B fragment of the next GEMM (byte 4t+i <-> row 4kq+i of tile t).
 // fast (wave-uniform): this site's multiplier passed the load-time single-rounding proof (ita_device.h: rq_pack16_v3);
 // RELU: fc1, clamp to [0, 127].
-template <bool RELU = false>
-__device__ __forceinline__ i32x4 rq_group(const i32x4 (&acc)[4], float mult, bool fast) {
+// FUSED: the accumulators started at the site's own base and kf is its K (one fma per pair, ita_device.h)
+template <bool RELU = false, bool FUSED = false>
+__device__ __forceinline__ i32x4 rq_group(const i32x4 (&acc)[4], float mult, bool fast, float kf = 0.0f) {
   if constexpr (ITA_ABLATE & 1) return acc[0] ^ acc[1] ^ acc[2] ^ acc[3];
+  if constexpr (RELU && FUSED) return rq_pack16_v3<ITA_RQ_FUSED_RELU>(acc, mult, kf);
   if constexpr (RELU) return rq_pack16_v3<ITA_RQ_RELU>(acc, mult);
+  if constexpr (FUSED) return rq_pack16_v3<ITA_RQ_FUSED>(acc, mult, kf);
   if (fast) return rq_pack16_v3<ITA_RQ_FAST>(acc, mult);
   return rq_pack16_v3<ITA_RQ_EXACT>(acc, mult);
 }
@@ -262,9 +272,14 @@ __device__ __forceinline__ void dq_group_codes(const i32x4 (&acc)[4], float mult
 // A compile-time switch, two instantiations: as a run-time flag per site the two forms sit side by side in the frame loop
 // and the ~40 uniform branches per frame cost more than the shorter form saves (measured: 56.7 us against 56.5 for the
 // round-2 form, 54.0 with the fast form compiled in, 55.3 with the exact one).
-template <int E, bool FFN, int TOK, bool STAMP = false, bool IO8 = false, bool FAST = false>
+// FUSED (implies FAST at the out_proj site of the int8 I/O form, the only one it leaves alone): Q, K, V, logits and context
+// run the one-fma form on accumulators started at per-site bases, chosen and proven at load time; FUSED == 2: fc1 runs the
+// fused ReLU form as well (its own proof).  A template argument for the same reason.
+template <int E, bool FFN, int TOK, bool STAMP = false, bool IO8 = false, bool FAST = false, int FUSED = 0>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void ita_stream_kernel(const ItaStreamArgs a) {
   static_assert(!IO8 || (!FFN && TOK == 0), "int8 I/O is the attention block's form");
+  static_assert(FUSED == 0 || FUSED == 1 || (FUSED == 2 && FFN), "the fused ReLU form is fc1's");
+  static_assert(FUSED == 0 || FAST, "the fused instantiation keeps the fast form at out_proj");
   using L = ItaStreamLds<E, FFN, TOK != 0>;
   constexpr int S = 128, P = 192, F = 256, EC = E / 4, NK = E / 64, NTE = E / 16;
   static_assert(!TOK || (E == 64 && FFN), "the fused tokenizer is built for the ITAViTLSTM shape");
@@ -291,6 +306,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #define fl site_fast(ITA_SITE_L)
 #define fc site_fast(ITA_SITE_C)
 #define fo site_fast(ITA_SITE_O)
+  // accumulator bases of the two sites whose accumulators do not start from the image's biases (wave-uniform)
+  const int base_l = FUSED ? a.c_l : ITA_ACC_BIAS, base_c = FUSED ? a.c_c : ITA_ACC_BIAS;
 
   // waves 4-7 were dispatched second and lose every VALU arbitration against their SIMD partner (MI355X guide,
   // "Two waves per SIMD", item 4): static priority evens the pair out
@@ -376,7 +393,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // first frame is the only thing left between their arrival and the frame loop (pixels first, with the weights parked in
     // registers until the tokenizer was done, put the weights' LDS stores behind it)
     if constexpr (TOK != 0) tok_fetch(blockIdx.x, ol);
-    if (tid < 2 * P) colsum[tid] = ITA_ACC_BIAS;
+    if (tid < 2 * P) colsum[tid] = base_c;
 #pragma unroll
     for (int j = 0; j < NTJ; ++j) {
       const int p = tid + 512 * j;
@@ -443,13 +460,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       auto epilogue = [&](int g, const i32x4 (&acc)[4]) {
         const int mat = g / 3, gg = g - 3 * mat;
         if (mat == 0) {
-          qf[gg] = rq_group(acc, a.mq, fq);
+          qf[gg] = rq_group<false, FUSED != 0>(acc, a.mq, fq, a.kq);
         } else if (mat == 1) {
-          *(i32x4*)(lds + L::K + (((4 * gg + kq) * S + token) << 4)) = rq_group(acc, a.mk, fk);
+          *(i32x4*)(lds + L::K + (((4 * gg + kq) * S + token) << 4)) = rq_group<false, FUSED != 0>(acc, a.mk, fk, a.kk);
         } else {
           // V with the roles swapped (A = tokens, B = weights): lane (feature qi, kq) holds keys 16w + 4kq + i of
           // feature 16 dt + qi -- one dword of the V^T slot (key block w>>2, k-group kq), at word w&3
-          const i32x4 p4 = rq_group(acc, a.mv, fv);
+          const i32x4 p4 = rq_group<false, FUSED != 0>(acc, a.mv, fv, a.kv);
 #pragma unroll
           for (int t = 0; t < 4; ++t) {
             const int d = (4 * gg + t) * 16 + qi;
@@ -523,7 +540,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       auto mmk = [&](const KFr& f, i32x4 (&acc)[2]) {
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-          acc[t] = (i32x4){ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS};
+          acc[t] = (i32x4){base_l, base_l, base_l, base_l};
 #pragma unroll
           for (int ks = 0; ks < 3; ++ks) acc[t] = mfma16(f.w[t * 3 + ks], qf[ks], acc[t]);
         }
@@ -531,7 +548,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       auto epil = [&](int p, const i32x4 (&acc)[2]) {
         // low 16 bits = rne(logit) + 32768, unclamped: the softmax clamps (ita_softmax_packed16)
         unsigned w4[4];
-        if (fl) lg8_v3<ITA_RQ_FAST>(acc, a.ml, w4);
+        if constexpr (FUSED) lg8_v3<ITA_RQ_FUSED>(acc, a.ml, w4, a.kl);
+        else if (fl) lg8_v3<ITA_RQ_FAST>(acc, a.ml, w4);
         else lg8_v3<ITA_RQ_EXACT>(acc, a.ml, w4);
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -564,21 +582,21 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       for (int st = 0; st < 6; ++st) {
         if (st + 1 < 6) ldv(st + 1, vb[(st + 1) & 1]);
         mm_ks(vb[st & 1], pf[st & 1], va[st >> 1]);
-        if (st == 3) cf[0] = rq_group(va[0], a.mc, fc);
+        if (st == 3) cf[0] = rq_group<false, FUSED != 0>(va[0], a.mc, fc, a.kc);
         ITA_SCHED_BARRIER();   // keep the step's loads ahead of the next step's MFMAs
       }
       ITA_SSTAMP(5);
       if constexpr (!(ITA_ABLATE & 64)) lds_barrier();   // B2: every wave is done with K, V^T and this frame's column sums
       ITA_SSTAMP(6);
-      if (tid < P) cs[tid] = ITA_ACC_BIAS;   // this parity is next accumulated after the NEXT frame's B2
+      if (tid < P) cs[tid] = base_c;   // this parity is next accumulated after the NEXT frame's B2
       ld_frg_ks<E>(ob[0], lds + L::WO, 0, 0, qi, kq);
       ld_obias<E>(oa, l_bo, 0, kq);
       // the next frame's pixel window, before this frame's global stores (one in-order vmcnt for loads and stores)
       if constexpr (TOK != 0) { if (more) tok_fill(ol); }
-      cf[1] = rq_group(va[1], a.mc, fc);
+      cf[1] = rq_group<false, FUSED != 0>(va[1], a.mc, fc, a.kc);
       ld_frg_ks<E>(ob[1], lds + L::WO, 0, 1, qi, kq);
       mm_ks(ob[0], cf[0], oa);
-      cf[2] = rq_group(va[2], a.mc, fc);
+      cf[2] = rq_group<false, FUSED != 0>(va[2], a.mc, fc, a.kc);
     }
 
     // ---------------- out_proj + residual + LayerNorm1 (k-step 0 of the first group is already in flight)
@@ -644,12 +662,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         if (g >= 1) ld_frg_ks<E>(wb[(g - 1) & 1], w2p, 0, g - 1, qi, kq);
         mm_group<NK, false>(ffr[g & 1], x1f, fa[g % 3]);
         if (g >= 2) mm_ks(wb[(g - 2) & 1], hf[g - 2], ya);
-        if (g >= 1) hf[g - 1] = rq_group<true>(fa[(g - 1) % 3], a.m1, false);
+        if (g >= 1) hf[g - 1] = rq_group<true, FUSED == 2>(fa[(g - 1) % 3], a.m1, false, a.k1);
         ITA_SCHED_BARRIER();   // keep the step's loads ahead of the next step's MFMAs
       }
       ld_frg_ks<E>(wb[1], w2p, 0, 3, qi, kq);
       mm_ks(wb[0], hf[2], ya);
-      hf[3] = rq_group<true>(fa[3 % 3], a.m1, false);
+      hf[3] = rq_group<true, FUSED == 2>(fa[3 % 3], a.m1, false, a.k1);
       mm_ks(wb[1], hf[3], ya);
       ITA_SSTAMP(8);
       {

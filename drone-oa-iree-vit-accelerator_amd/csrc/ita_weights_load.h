@@ -31,6 +31,17 @@ struct Layer {
   // tokenizer in front (layer 0 of the E = 64 model), attention block only
   DevBuf<char> simg_enc, simg_tok, simg_mha;
   unsigned fast_sites = 0;   // ITA_SITE_* bits: requantisation sites proven equal under single rounding (fast_site_ok)
+  // fused requantisation (fused_site): the proven sites among Q, K, V, logits and context (less what ITA_FUSED_SITES turns
+  // off), their accumulator bases and K constants in that order, and -- when all five are in, and the layer is fast --
+  // second copies of the images with those bases in the Q, K and V biases.  The first copies keep the default base: the
+  // long-sequence kernels read simg_mha, the stamped diagnostic instantiations the other two.
+  // Entry / bit 5 is fc1 (the fused ReLU form, a proof of its own): with it the whole-layer images carry fc1's base in b1
+  // and the FUSED == 2 instantiation runs; without it they keep the default there and FUSED == 1 runs.
+  unsigned fused_sites = 0;
+  bool fused = false, fused_relu = false;
+  int fused_c[6] = {ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS};
+  float fused_k[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  DevBuf<char> fimg_enc, fimg_tok, fimg_mha;
 };
 
 // Everything one ita_load_weights call produces.  Raw pointers point into dblob; every DevBuf is a buffer derived from
@@ -199,8 +210,9 @@ void build_tok_tab(const float* conv_w, const float* conv_b, char* tab) {
       }
 }
 
+// cb: the accumulator bases of the Q, K, V and fc1 sites (fused form: Layer::fused_c[0, 1, 2, 5]), or null: ITA_ACC_BIAS
 template <int E, bool FFN, bool TOK>
-int build_stream_image(const StreamHostParams& p, DevBuf<char>& out) {
+int build_stream_image(const StreamHostParams& p, DevBuf<char>& out, const int* cb = nullptr) {
   using L = ItaStreamLds<E, FFN, TOK>;
   constexpr int P = 192, F = 256;
   std::vector<char> im(L::GIMAGE, 0);   // (E = 128 with FFN: fc1 / fc2 weights lie behind the LDS part)
@@ -228,7 +240,12 @@ int build_stream_image(const StreamHostParams& p, DevBuf<char>& out) {
   float* ln = (float*)(im.data() + L::LNP);
   if (p.n1w && p.n1b) { memcpy(ln, p.n1w, E * 4); memcpy(ln + E, p.n1b, E * 4); }
   auto bias_accumulators = [&]() {   // accumulators start at ITA_ACC_BIAS + bias (ita_device.h: scale_clamp_b)
-    for (int i = 0; i < L::NBIAS; ++i) bias[i] = (int32_t)((uint32_t)bias[i] + (uint32_t)ITA_ACC_BIAS);
+    for (int i = 0; i < L::NBIAS; ++i) {
+      int base = ITA_ACC_BIAS;
+      if (cb && i < 3 * P) base = cb[i / P];
+      else if (cb && FFN && i >= 3 * P + E && i < 3 * P + E + F) base = cb[5];
+      bias[i] = (int32_t)((uint32_t)bias[i] + (uint32_t)base);
+    }
   };
   if constexpr (FFN) {
     natural(L::W12G ? L::GW1 : L::W1, p.w1, F, E);
@@ -306,6 +323,116 @@ unsigned fast_sites_of(const float* ascal) {
   for (int i = 0; i < 6; ++i)
     if (fast_site_ok(ascal[idx[i]])) mask |= 1u << i;   // bit order = ITA_SITE_Q, _K, _V, _L, _C, _O
   return mask;
+}
+
+// Fused requantisation of one site: the accumulator starts at an integer C near 1.5 * 2^23 instead of at it, its bit pattern
+// is still the float C + sum, and ONE fma(C + sum, m, K) with K = magic - k, k = round(C m), yields rne(sum m + magic + eps),
+// eps = C m - k: no subtraction of the base.  The search takes the C within +-dmax of ITA_ACC_BIAS whose C m lies closest to
+// an integer (exact integer arithmetic on m's mantissa), and for the best few enumerates every accumulator value of the
+// clamp range -- the range fast_site_ok walks -- in the arithmetic of v_pk_fma_f32 (IEEE fmaf; this file is compiled with
+// contraction off): a C is accepted when the clamped code equals that of the reference's two roundings for every value.
+// magic: ITA_MAGIC128_F (codes travel as r + 128, u8 saturation), ITA_MAGIC32K_F (logits: r + 32768, clamped by the
+// integer softmax, which reads nothing of a logit but its clamped value: ita_softmax_packed16) or ITA_MAGIC_F (fc1's fused
+// ReLU form: r itself travels, min with 127 and the u8 saturation clamp it to [0, 127]).
+constexpr int ITA_FUSED_DMAX = 1 << 18, ITA_FUSED_TRIES = 8;
+// the enumeration for one given C: true when the fused form equals the reference on the whole clamp range; *K is set whenever
+// K is an exact float in [2^23, 2^24)
+bool fused_site_check(float m, float magic, int C, float* K) {
+  if (!(m > 0.0f) || !(m < 1.0f)) return false;
+  const double lim = 130.0 / (double)m;
+  if (lim > 4.0e6) return false;
+  const long long dC = (long long)C - (long long)ITA_ACC_BIAS;
+  if (dC < -(1ll << 22) || dC >= (1ll << 22)) return false;
+  const long long A = (long long)lim + 2;
+  if (A + (dC < 0 ? -dC : dC) >= (1ll << 22)) return false;   // C + a must stay a float with ulp 1: [2^23, 2^24)
+  // (the pattern 0x4B000000 + t is the float 2^23 + t; a 24-bit integer times a 24-bit mantissa is exact in double)
+  const double cval = (double)((long long)C - 0x4B000000ll) + 8388608.0;
+  const double k = nearbyint(cval * (double)m);
+  const double kd = (double)magic - k;
+  if (!(kd >= 8388608.0) || !(kd < 16777216.0)) return false;
+  const float Kf = (float)kd;                                 // an integer below 2^24: exact
+  *K = Kf;
+  const bool l16 = magic == ITA_MAGIC32K_F, relu = magic == ITA_MAGIC_F;
+  auto code = [l16, relu](float t) {
+    unsigned u;
+    memcpy(&u, &t, 4);
+    if (relu) {   // low 16 bits = r, signed
+      const int v = (int)(int16_t)(u & 0xffffu);
+      return v < 0 ? 0 : v > 127 ? 127 : v;
+    }
+    if (l16) {   // low 16 bits = r + 32768 (unsigned); the softmax clamps r to [-128, 127]
+      const int v = (int)(u & 0xffffu) - 32768;
+      return v < -128 ? -128 : v > 127 ? 127 : v;
+    }
+    const int v = (int)(int16_t)(u & 0xffffu);   // r + 128, then the u8 saturation
+    return v < 0 ? 0 : v > 255 ? 255 : v;
+  };
+  for (long long a = -A; a <= A; ++a) {
+    const float y = (float)a * m;
+    uint32_t bits = (uint32_t)((long long)C + a);
+    float f;
+    memcpy(&f, &bits, 4);
+    if (code(y + magic) != code(fmaf(f, m, Kf))) return false;
+  }
+  return true;
+}
+// the search: *C, *K of the first accepted candidate
+bool fused_site(float m, float magic, int dmax, int* C, float* K) {
+  if (!(m > 0.0f) || !(m < 1.0f) || 130.0 / (double)m > 4.0e6 || dmax < 0) return false;
+  if (dmax > ITA_FUSED_DMAX) dmax = ITA_FUSED_DMAX;
+  uint32_t mb;
+  memcpy(&mb, &m, 4);
+  const int ex = (int)(mb >> 23);
+  if (ex == 0) return false;                                  // (a denormal multiplier is below the range bound anyway)
+  const uint64_t M = (mb & 0x7fffffu) | 0x800000u;            // m = M * 2^-s
+  const int s = 150 - ex;                                     // m < 1: s >= 24; 130 / m <= 4e6: s <= 39
+  if (s < 24 || s > 39) return false;
+  const uint64_t one = 1ull << s, mask = one - 1;
+  struct Cand { uint64_t d; int C; };
+  Cand best[ITA_FUSED_TRIES];
+  int nb = 0;
+  const long long c0 = (long long)ITA_ACC_BIAS - 0x4B000000ll + 8388608ll;   // the float value of the default base
+  for (int d = -dmax; d <= dmax; ++d) {
+    const uint64_t fr = ((uint64_t)(c0 + d) * M) & mask;      // (C M) mod 2^s: below 2^24 * 2^24, exact
+    const uint64_t dist = fr < one - fr ? fr : one - fr;
+    if (nb == ITA_FUSED_TRIES && dist >= best[nb - 1].d) continue;
+    int j = nb < ITA_FUSED_TRIES ? nb++ : nb - 1;
+    while (j > 0 && best[j - 1].d > dist) { best[j] = best[j - 1]; --j; }
+    best[j] = Cand{dist, (int)((long long)ITA_ACC_BIAS + d)};
+  }
+  for (int i = 0; i < nb; ++i)
+    if (fused_site_check(m, magic, best[i].C, K)) { *C = best[i].C; return true; }
+  return false;
+}
+
+// The fused sites of a layer whose accumulators stream_range_ok admitted: Q, K, V (bases in the image's biases: the base
+// may move only as far as the worst row sum leaves room below 2^22), logits (|sum| <= 192 * 128 * 128) and context
+// (<= 255 * 128).  ITA_FUSED_SITES (diagnostic, read at load time) is ANDed onto the proven mask: it can only turn sites off.
+void prove_fused(Layer& L, const StreamHostParams& p, int E, bool ffn) {
+  auto room = [](const int8_t* w, const int32_t* b, int rows, int k) {
+    long long worst = 0;
+    for (int r = 0; r < rows; ++r) {
+      long long sum = 0;
+      for (int i = 0; i < k; ++i) sum += w[(size_t)r * k + i] < 0 ? -(long long)w[(size_t)r * k + i] : w[(size_t)r * k + i];
+      sum = sum * 128 + (b[r] < 0 ? -(long long)b[r] : b[r]);
+      worst = sum > worst ? sum : worst;
+    }
+    return (int)((1ll << 22) - 1 - worst);   // (stream_range_ok: worst < 2^22)
+  };
+  const int idx[5] = {ITA_A_MQ, ITA_A_MK, ITA_A_MV, ITA_A_ML, ITA_A_MC};
+  const int dmax[5] = {room(p.wq, p.bq, 192, E), room(p.wk, p.bk, 192, E), room(p.wv, p.bv, 192, E),
+                       (1 << 22) - 1 - 192 * 128 * 128, (1 << 22) - 1 - 255 * 128};
+  unsigned proven = 0;
+  for (int i = 0; i < 5; ++i)
+    if (fused_site(L.ascal[idx[i]], i == 3 ? ITA_MAGIC32K_F : ITA_MAGIC128_F, dmax[i], &L.fused_c[i], &L.fused_k[i])) proven |= 1u << i;
+  unsigned mask = ITA_SITES_FUSED | ITA_SITE_FC1;
+  if (const char* e = getenv("ITA_FUSED_SITES")) mask = (unsigned)strtoul(e, nullptr, 0);
+  if (ffn && fused_site(L.fscal[ITA_F_M1], ITA_MAGIC_F, room(p.w1, p.b1, 256, E), &L.fused_c[5], &L.fused_k[5])) proven |= ITA_SITE_FC1;
+  mask &= proven;
+  L.fused_sites = mask;
+  L.fused = (mask & ITA_SITES_FUSED) == ITA_SITES_FUSED && L.fast_sites == ITA_SITES_ALL;
+  L.fused_relu = L.fused && (mask & ITA_SITE_FC1);
+  if (!L.fused_relu) L.fused_c[5] = ITA_ACC_BIAS;   // the images keep fc1's default base
 }
 
 // ---- the steps of ita_load_weights, in the order the loader runs them; each returns an ITA_* code, and the loader
@@ -430,13 +557,20 @@ int build_stream_images(Weights& w) {
     const bool lns = !L.ffn_f32 && sp.n1w && sp.n1b && sp.n2w && sp.n2b && stream_range_ok(sp, hdr.E, true, L.ascal, L.fscal);
     if (!stream_range_ok(sp, hdr.E, false, L.ascal, L.fscal)) continue;   // no images: this layer runs on the block kernels
     L.fast_sites = fast_sites_of(L.ascal);
+    prove_fused(L, sp, hdr.E, lns);
+    const int* fc = L.fused ? L.fused_c : nullptr;
     if (hdr.E == 64) {
       rc = build_stream_image<64, false, false>(sp, L.simg_mha);
       if (!rc && lns) rc = build_stream_image<64, true, false>(sp, L.simg_enc);
       if (!rc && lns && i == 0 && sp.tlw && sp.tlb && sp.conv_w && sp.conv_b) rc = build_stream_image<64, true, true>(sp, L.simg_tok);
+      if (!rc && fc) rc = build_stream_image<64, false, false>(sp, L.fimg_mha, fc);
+      if (!rc && fc && L.simg_enc) rc = build_stream_image<64, true, false>(sp, L.fimg_enc, fc);
+      if (!rc && fc && L.simg_tok) rc = build_stream_image<64, true, true>(sp, L.fimg_tok, fc);
     } else {
       rc = build_stream_image<128, false, false>(sp, L.simg_mha);
       if (!rc && lns) rc = build_stream_image<128, true, false>(sp, L.simg_enc);
+      if (!rc && fc) rc = build_stream_image<128, false, false>(sp, L.fimg_mha, fc);
+      if (!rc && fc && L.simg_enc) rc = build_stream_image<128, true, false>(sp, L.fimg_enc, fc);
     }
     if (rc) return rc;
   }

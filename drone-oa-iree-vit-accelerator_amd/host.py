@@ -42,7 +42,7 @@ EXPORTED_SYMBOLS = (
     "ita_wire_unpack_packet", "ita_wire_postprocess", "ita_vitlstm_forward_slots", "ita_vitlstm_front",
     "ita_vitlstm_back", "ita_vitlstm_pipelined", "ita_vitlstm_front_ev", "ita_vitlstm_encode", "ita_vitlstm_fold", "ita_vitlstm_tail", "ita_debug_softmax_rows",
     "ita_head_status", "ita_vitlstm_sequence", "ita_ingest", "ita_tokenizer_long", "ita_ingest_wire", "ita_ingest_wire_prepare", "ita_resize_table",
-    "ita_debug_fast_site_ok", "ita_debug_layer_forms",
+    "ita_debug_fast_site_ok", "ita_debug_layer_forms", "ita_debug_fused_site", "ita_debug_fused_check", "ita_debug_layer_fused",
     "ITASelfAttention_workgroup", "ITASelfAttention_workgroup_expanded", "ITAFeedForward_workgroup",
 )
 
@@ -209,6 +209,9 @@ def lib():
         L.ita_debug_softmax_rows.argtypes = [vp, vp, vp, i, vp]
         L.ita_debug_fast_site_ok.argtypes = [C.c_float]
         L.ita_debug_layer_forms.argtypes = [vp, i, C.POINTER(C.c_uint), C.POINTER(i)]
+        L.ita_debug_fused_site.argtypes = [C.c_float, C.POINTER(i), C.POINTER(C.c_float)]
+        L.ita_debug_fused_check.argtypes = [C.c_float, i, i, C.POINTER(C.c_float)]
+        L.ita_debug_layer_fused.argtypes = [vp, i, C.POINTER(C.c_uint), C.POINTER(i), C.POINTER(i), C.POINTER(C.c_float)]
         L.ita_validate_blob.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p]
         L.ita_bind_dispatch.argtypes = [vp, i, i]
         L.ita_wire_unpack_packet.argtypes = [vp, C.c_size_t, i, vp]
@@ -285,6 +288,28 @@ def fast_site_ok(mult: float) -> bool:
     """ita_debug_fast_site_ok: the load-time proof that a requantisation site with this float32 multiplier may round once
     (host only: no GPU, no handle)"""
     return bool(lib().ita_debug_fast_site_ok(C.c_float(float(mult))))
+
+
+ACC_BIAS = 0x4B400000      # the default accumulator base of the stream kernels: the pattern of the float 1.5 * 2^23
+FUSED_SITES = ("Q", "K", "V", "L", "C")   # bit order of the fused mask
+
+
+def fused_site(mult: float):
+    """ita_debug_fused_site: the load-time search for an accumulator base C (an int32 pattern near ACC_BIAS) and the constant K
+    with which one fma(C + sum, mult, K) requantises a site like the reference -> (C, K), or None when no candidate passes
+    the enumeration or mult is out of range (host only: no GPU, no handle)"""
+    c, k = C.c_int(0), C.c_float(0.0)
+    if not lib().ita_debug_fused_site(C.c_float(float(mult)), C.byref(c), C.byref(k)):
+        return None
+    return c.value, k.value
+
+
+def fused_check(mult: float, base: int, logits: bool = False, relu: bool = False):
+    """ita_debug_fused_check: the enumeration alone, on a given base -> (accepted, K); logits: the 16-bit travel form of
+    the logits, relu: fc1's form (codes 0 .. 127)"""
+    k = C.c_float(0.0)
+    ok = lib().ita_debug_fused_check(C.c_float(float(mult)), 1 if logits else 2 if relu else 0, int(base), C.byref(k))
+    return bool(ok), k.value
 
 
 class Engine:
@@ -376,6 +401,15 @@ class Engine:
         _chk(lib().ita_debug_layer_forms(self._h, layer, C.byref(m), C.byref(im)))
         return dict(fast_sites=m.value, fast=m.value == 63, attn_image=bool(im.value & FORMS_ATTN_IMAGE),
                     layer_image=bool(im.value & FORMS_LAYER_IMAGE), tok_image=bool(im.value & FORMS_TOK_IMAGE))
+
+    def layer_fused(self, layer: int = 0) -> dict:
+        """ita_debug_layer_fused: fused_sites (bits 0..5 = Q, K, V, logits, context, fc1: proven, and not turned off by
+        ITA_FUSED_SITES), fused (the stream kernels run their one-fma instantiation on this layer), fused_relu (the
+        whole-layer flavours run fc1's fused ReLU form too), C and K per site"""
+        m, f = C.c_uint(0), C.c_int(0)
+        c6, k6 = (C.c_int * 6)(), (C.c_float * 6)()
+        _chk(lib().ita_debug_layer_fused(self._h, layer, C.byref(m), C.byref(f), c6, k6))
+        return dict(fused_sites=m.value, fused=f.value >= 1, fused_relu=f.value == 2, C=list(c6), K=list(k6))
 
     def attn_kind(self, layer: int = 0) -> int:
         """ATTN_INT8 (ITAW0001 / ITAW0002 blob) or ATTN_F32 (ITAW0003: the float graph's float32 attention)"""

@@ -519,6 +519,21 @@ enum { ITA_FORMS_ATTN_IMAGE = 1, ITA_FORMS_LAYER_IMAGE = 2, ITA_FORMS_TOK_IMAGE 
 int ita_debug_fast_site_ok(float mult);
 int ita_debug_layer_forms(ita_handle h, int layer, unsigned* fast_sites, int* stream_images);
 
+/* Diagnostic / test entries: the fused requantisation form.  A site's accumulators start at an
+ * integer pattern C near 0x4B400000 and one fma(C + sum, mult, K) replaces un-bias, scale and round.
+ * ita_debug_fused_site: host only: the load-time search.  1 and *C, *K when a base within 2^18 of 0x4B400000 passes the
+ * enumeration of every accumulator value of the clamp range against the reference's two roundings; else 0 (also for a
+ * multiplier outside (0, 1) or below 130 / 4e6, or a K outside [2^23, 2^24)).
+ * ita_debug_fused_check: the enumeration alone on a given C; form 0: int8 codes, 1: the logits' 16-bit travel form, clamped
+ * as the integer softmax clamps it, 2: fc1's ReLU form (codes 0 .. 127); *K (may be null) receives the K it used.
+ * ita_debug_layer_fused: fused_sites = bits 0..5 (Q, K, V, logits, context, fc1) proven for this layer and left on by the
+ * environment variable ITA_FUSED_SITES (a mask ANDed onto the proven sites when the weights are loaded); fused = 1 when
+ * the stream kernels run the fused instantiation (bits 0..4 all set, and fast_sites == 63), 2 when the whole-layer
+ * flavours run fc1's fused ReLU form as well (bit 5), else 0; C6 / K6 (may be null): the six bases and constants. */
+int ita_debug_fused_site(float mult, int* C, float* K);
+int ita_debug_fused_check(float mult, int form, int C, float* K);
+int ita_debug_layer_fused(ita_handle h, int layer, unsigned* fused_sites, int* fused, int* C6, float* K6);
+
 /* ---- wire format of the reference's UDP host (ita_wire.h), exported for bindings and tests ------- */
 /* frame_out: [desired_velocity, position_x, quat w, x, y, z]; returns 0, or -1 on a short packet */
 int ita_wire_unpack_packet(const uint8_t* packet, size_t nbytes, int quat_stride_bug, float* frame_out);

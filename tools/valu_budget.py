@@ -4,13 +4,17 @@ Compiles csrc/ita_plugin.hip to assembly, takes ita_stream_kernel<64, true, 1> f
 function (the loop body; inline-asm requantisation blocks are expanded in the assembly) and groups the opcodes.
 Counts are per WAVE and frame; a frame is 8 waves.  usage: python tools/valu_budget.py [extra hipcc flags]
 The single-rounding permission of the requantisation sites is a template argument: the default counts the FAST instantiation
-(all six sites of the layer proven at load time), --exact the other one; -DITA_FORCE_SITES=<mask> fixes the form per site."""
+(all six sites of the layer proven at load time), --exact the two-rounding one, --fused the one-fma one (Q, K, V, logits and
+context proven for per-site accumulator bases), --fused-relu the one with fc1's fused ReLU form as well; -DITA_FORCE_SITES=<mask> fixes the fast form per site.  The last line is the
+kernel's register and scratch figures from the code object's metadata."""
 import collections, os, re, subprocess, sys, tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(REPO, "drone-oa-iree-vit-accelerator_amd", "csrc", "ita_plugin.hip")
-# <E = 64, FFN, TOK = 1, no stamps, f32 I/O, FAST>: the instantiation the bench blob runs; --exact counts the one with FAST = false
-KERNEL = "_Z17ita_stream_kernelILi64ELb1ELi1ELb0ELb0ELb%dEEv13ItaStreamArgs" % (0 if "--exact" in sys.argv else 1)
+# <E = 64, FFN, TOK = 1, no stamps, f32 I/O, FAST, FUSED>: the bench blob runs the fused one
+FLAGS = ("--exact", "--fused", "--fused-relu")
+KERNEL = "_Z17ita_stream_kernelILi64ELb1ELi1ELb0ELb0ELb%dELi%dEEv13ItaStreamArgs" % (
+    0 if "--exact" in sys.argv else 1, 2 if "--fused-relu" in sys.argv else 1 if "--fused" in sys.argv else 0)
 CLASSES = [
     ("requantise: unbias + scale + round (v_pk_add/mul/fma_f32, v_pk_mov)", r"^v_pk_(add|mul|fma)_f32|^v_pk_mov"),
     ("requantise: float clamp (v_med3_f32)", r"^v_med3_f32"),
@@ -27,7 +31,7 @@ def main():
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "k.s")
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-I",
-                               os.path.join(REPO, "include"), "--cuda-device-only", "-S", "-o", out, SRC] + [a for a in sys.argv[1:] if a != "--exact"],
+                               os.path.join(REPO, "include"), "--cuda-device-only", "-S", "-o", out, SRC] + [a for a in sys.argv[1:] if a not in FLAGS],
                               stderr=subprocess.DEVNULL)
         lines = open(out).read().split("\n")
     beg = next(i for i, l in enumerate(lines) if l.startswith(KERNEL + ":"))
@@ -55,6 +59,10 @@ def main():
     n = sum(left.values())
     print(f"  {'other (' + ', '.join(sorted(left, key=left.get, reverse=True)[:4]) + ' ...)':58s} {n:9d} {8 * n:10d} {100.0 * n / total:5.1f}%")
     print(f"  {'all':58s} {total:9d} {8 * total:10d}")
+    text = "\n".join(lines)
+    meta = next(b for b in text.split("- .agpr_count:")[1:] if re.search(r"\.name:\s+" + KERNEL + r"\s", b))
+    fields = ("vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size")
+    print("  code object: " + "  ".join(k + " " + re.search(r"\." + k + r":\s+(\d+)", meta).group(1) for k in fields))
 
 
 if __name__ == "__main__":
