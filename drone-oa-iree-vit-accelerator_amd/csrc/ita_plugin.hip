@@ -33,6 +33,7 @@
 #include "ita_attn_f32_kernel.h"
 #include "ita_long_f32_kernel.h"
 #include "ita_long_f32_stats_kernel.h"
+#include "ita_long_f32_prop_kernel.h"
 #include "ita_ingest_kernel.h"
 #include "ita_ingest_wire_kernel.h"
 #include "ita_tokenizer_long_kernel.h"
@@ -1267,6 +1268,45 @@ int ita_mha_long_f32_stats(ita_handle h, int layer, const float* x, int batch, i
     const size_t n = (size_t)batch * seq_len, blocks = (n + 255) / 256;
     return launch<ita_lf32_colsum_kernel>(dim3(blocks < 4096 ? (unsigned)blocks : 4096u), dim3(256), s, (const float*)sa.part_mass,
                                           (const int*)sa.part_nnz, st->col_mass, st->col_nnz, (int)nqt, seq_len, n);
+  });
+}
+
+// out = w . P (ita_long_f32_prop_kernel.h): the K and Q images in one projection launch, ita_lf32_stats_kernel for the row
+// maximum and row sum of every query (rows only: sweep 1, into the workspace), the transposed sweep.  The workspace is the
+// float long workspace (the Q image stands where the V image does) and behind it row_max and row_sum, (B, S) f32 each.
+int ita_mha_long_f32_propagate(ita_handle h, int layer, const float* x, int batch, int seq_len, const float* w, int n_w,
+                               float* out, void* stream) {
+  if (int rc = check(h, batch)) return rc;
+  if (!x || !w || !out || layer < 0 || layer >= h->w.hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
+  const Layer& L = h->w.layers[layer];
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = check_long_f32(L, batch, seq_len,
+                              "this layer's attention is int8 (ITAW0001 / ITAW0002 blob): ita_mha_long_int8_propagate propagates through it")) return rc;
+  if (n_w < 1 || n_w > 64) return fail(ITA_ERR_INVALID_ARG, "ita_mha_long_f32_propagate: n_w must be in [1, 64]");
+  if (misaligned(w, 16) || misaligned(out, 16))
+    return fail(ITA_ERR_INVALID_ARG, "ita_mha_long_f32_propagate: w_dev and out_dev must be 16-byte aligned");
+  const size_t ntile = (size_t)batch * (seq_len / 128);
+  const size_t img = ntile * 2 * ItaLongF32Lds::UNIT, rows = (size_t)batch * seq_len * 4;
+  if (int rc = ensure_long_ws(h, 2 * img + 2 * rows, s)) return rc;
+  char* ws = (char*)h->long_ws;
+  ItaLongF32PropProjArgs pa{};
+  pa.x = x; pa.wk = L.wkf; pa.bk = L.bkf; pa.wq = L.wqf; pa.bq = L.bqf;
+  pa.kimg = (f32x4*)ws; pa.qimg = (f32x4*)(ws + img);
+  pa.B = batch; pa.S = seq_len;
+  ItaLongF32StatsArgs sa{};
+  sa.x = x; sa.wq = L.wqf; sa.bq = L.bqf; sa.kimg = pa.kimg;
+  sa.B = batch; sa.S = seq_len; sa.p_min = 1.0f;
+  sa.row_max = (float*)(ws + 2 * img); sa.row_sum = (float*)(ws + 2 * img + rows);
+  ItaLongF32PropArgs ka{};
+  ka.kimg = pa.kimg; ka.qimg = pa.qimg; ka.row_max = sa.row_max; ka.row_sum = sa.row_sum;
+  ka.w = w; ka.out = out; ka.B = batch; ka.S = seq_len; ka.n_w = n_w;
+  const size_t cap = 2 * (size_t)h->num_cus;
+  const dim3 proj_grid((unsigned)(ntile < cap ? ntile : cap)), grid(seq_len / 128, batch);
+  return with_E(h->w.hdr.E, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    if (int rc = launch<ita_lf32_projkq_kernel<E>>(proj_grid, dim3(512), s, pa)) return rc;
+    if (int rc = launch<ita_lf32_stats_kernel<E>, ItaLongF32Lds::TOTAL>(grid, dim3(512), s, sa)) return rc;
+    return launch<ita_lf32_prop_kernel, ItaLongF32PropLds::TOTAL>(grid, dim3(512), s, ka);
   });
 }
 

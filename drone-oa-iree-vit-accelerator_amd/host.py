@@ -35,7 +35,7 @@ HEAD_TIMEOUT = 1
 EXPORTED_SYMBOLS = (
     "ita_abi_version", "ita_create", "ita_destroy", "ita_load_weights", "ita_validate_blob", "ita_reserve", "ita_get_dims",
     "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_mha_long_int8", "ita_mha_long_int8_taps", "ita_mha_long_int8_stats", "ita_mha_long_int8_propagate", "ita_encoder_layer_long", "ita_ffn_int8", "ita_ffn_int8_taps",
-    "ita_ffn_f32", "ita_get_ffn_kind", "ita_mha_f32", "ita_get_attn_kind", "ita_mha_long_f32", "ita_mha_long_f32_taps", "ita_mha_long_f32_stats", "ita_encoder_layer_long_f32",
+    "ita_ffn_f32", "ita_get_ffn_kind", "ita_mha_f32", "ita_get_attn_kind", "ita_mha_long_f32", "ita_mha_long_f32_taps", "ita_mha_long_f32_stats", "ita_mha_long_f32_propagate", "ita_encoder_layer_long_f32",
     "ita_encoder_layer", "ita_tokenizer", "ita_fusion_tail", "ita_vitlstm_forward", "ita_bind_dispatch",
     "ita_profile_begin", "ita_profile_begin_sampled", "ita_profile_end", "ita_set_tail_mode", "ita_debug_encoder_stamps",
     "ita_fusion_tail_load", "ita_fusion_tail_large",
@@ -108,6 +108,7 @@ LONG_STATS = ("row_max", "row_sum", "row_mass", "row_nnz", "col_mass", "col_nnz"
 LONG_MAX_WEIGHT_ROWS = 64      # ita_mha_long_int8_propagate: n_w in [1, 64]
 ROLLOUT_QMAX = 2097151         # attention rollout: a vector is quantised to 21 bits, three base-128 digits
 ROLLOUT_CHUNK = LONG_MAX_WEIGHT_ROWS // 3      # vectors per ita_mha_long_int8_propagate call
+ROLLOUT_F32_CHUNK = LONG_MAX_WEIGHT_ROWS       # vectors per ita_mha_long_f32_propagate call
 
 
 def rollout_digits(q):
@@ -204,6 +205,7 @@ def lib():
         L.ita_mha_long_f32.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_f32_taps.argtypes = [vp, i, vp, vp, i, i, C.POINTER(_MhaLongF32Taps), vp]
         L.ita_mha_long_f32_stats.argtypes = [vp, i, vp, i, i, C.c_float, C.POINTER(_MhaLongF32Stats), vp]
+        L.ita_mha_long_f32_propagate.argtypes = [vp, i, vp, i, i, vp, i, vp, vp]
         L.ita_encoder_layer_long_f32.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_vitlstm_tail.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
         L.ita_debug_softmax_rows.argtypes = [vp, vp, vp, i, vp]
@@ -1065,6 +1067,89 @@ class Engine:
         layers below `layer`, then attention_received_long_f32 of `layer` -> (N, tok_h, tok_w) f32"""
         y = self._tokens_below(frames, int(tok_h), int(tok_w), layer, depth_scale)
         return self.attention_received_long_f32(y, int(layer)).reshape(y.shape[0], int(tok_h), int(tok_w))
+
+    def attention_propagate_long_f32(self, x, w, layer: int = 0):
+        """weighted column sums of the whole S x S softmax matrix of a float-attention layer over a long sequence, which
+        is never held (ita_mha_long_f32_propagate): x (B,S,E) f32, w f32 GPU tensor (B,R,S), or (R,S) for the same weights
+        of every frame (copied B times), 1 <= R <= 64 -> out (B,R,S) f32, out[b,r,j] = sum_i w[b,r,i] p[b,i,j] with p the
+        probabilities of attention_rows_long_f32.  The f32 sums are taken in one fixed order: a one-hot row gives that
+        probability row bit for bit, all-ones weights give attention_received_long_f32 up to the order of the additions,
+        a row's bits do not depend on R, its place among the rows or the batch.  Held to
+        attention_propagate_f32_ref.propagate_from_taps within gamma_(S+2) sum |w| p.  The weights are not scanned."""
+        torch = _torch()
+        x = self._long_f32(x)
+        B, S = x.shape[0], x.shape[1]
+        if not w.is_cuda or w.dtype != torch.float32 or w.dim() not in (2, 3) or w.shape[-1] != S or (w.dim() == 3 and w.shape[0] != B):
+            raise ITAError(f"w must be an f32 GPU tensor of shape ({B}, R, {S}) or (R, {S}), got {w.dtype} {tuple(w.shape)}")
+        if w.dim() == 2:
+            w = w.unsqueeze(0).expand(B, -1, -1)
+        w = w.contiguous()
+        out = torch.empty((B, w.shape[1], S), dtype=torch.float32, device=x.device)
+        _chk(lib().ita_mha_long_f32_propagate(self._h, layer, x.data_ptr(), B, S, w.data_ptr(), w.shape[1], out.data_ptr(),
+                                              _stream_ptr(self.device)))
+        return out
+
+    def attention_rollout_long_f32(self, x, rows=None, first_layer: int = 0):
+        """attention rollout (Abnar & Zuidema) through the float-attention layers first_layer .. num_layers - 1 of a long
+        sequence: identity residual, attention matrix P_l of layer l.  x (B,S,E) f32: the token rows entering
+        first_layer; rows: token indices in any order (duplicates and out-of-range rows raise ValueError), or None for
+        the single start vector 1 / S -> (B, n, S) f32: how much output token rows[n] depends on every input token.  The
+        layers run out of place (encoder_layer_long_f32) and each layer's input is kept; from the last layer down, with
+        v = one-hot(rows) at the start,
+            v <- 0.5 * (v + attention_propagate_long_f32(x_l, v, l))
+        the add and the scale in torch f32 on the GPU, 64 vectors per call and more in chunks.  Held to
+        attention_rollout_f32_ref.rollout64.  A layer that is not float attention raises ITAError
+        (attention_rollout_long walks int8 layers)."""
+        torch = _torch()
+        x = self._long_f32(x)
+        B, S = x.shape[0], x.shape[1]
+        first_layer = int(first_layer)
+        if not 0 <= first_layer < self.num_layers:
+            raise ValueError(f"first_layer {first_layer} out of range")
+        for l in range(first_layer, self.num_layers):
+            if self.attn_kind(l) != ATTN_F32:
+                raise ITAError(f"layer {l} has int8 attention: attention_rollout_long walks int8 layers")
+        if rows is None:
+            v = torch.full((B, 1, S), 1.0 / S, dtype=torch.float32, device=x.device)
+        else:
+            rows = [int(r) for r in rows]
+            if any(not 0 <= r < S for r in rows):
+                raise ValueError(f"rows must be token indices in [0, {S})")
+            if len(set(rows)) != len(rows):
+                raise ValueError("duplicate rows")
+            v = torch.zeros((B, len(rows), S), dtype=torch.float32, device=x.device)
+            if rows:
+                v[:, torch.arange(len(rows), device=x.device), torch.tensor(rows, dtype=torch.long, device=x.device)] = 1.0
+        xs = [x]
+        for l in range(first_layer, self.num_layers - 1):
+            xs.append(self.encoder_layer_long_f32(xs[-1], l))
+        for l in range(self.num_layers - 1, first_layer - 1, -1):
+            nxt = torch.empty_like(v)
+            for c0 in range(0, v.shape[1], ROLLOUT_F32_CHUNK):
+                c = slice(c0, min(c0 + ROLLOUT_F32_CHUNK, v.shape[1]))
+                nxt[:, c] = 0.5 * (v[:, c] + self.attention_propagate_long_f32(xs[l - first_layer], v[:, c].contiguous(), l))
+            v = nxt
+        return v
+
+    def attention_rollout_map_long_f32(self, frames, tok_h: int, tok_w: int, queries=None, depth_scale: Optional[float] = None):
+        """attention rollout of a float graph on the token grid of camera frames: tokenize_long, then
+        attention_rollout_long_f32 through every layer for the tokens queries = [(ty, tx), ...] (None: the single start
+        vector 1 / S) -> (N, n, tok_h, tok_w) f32 in the order of queries.  Duplicate or out-of-grid queries raise
+        ValueError."""
+        tok_h, tok_w = int(tok_h), int(tok_w)
+        toks = None
+        if queries is not None:
+            toks = []
+            for ty, tx in queries:
+                ty, tx = int(ty), int(tx)
+                if not (0 <= ty < tok_h and 0 <= tx < tok_w):
+                    raise ValueError(f"query ({ty}, {tx}) lies outside the {tok_h} x {tok_w} token grid")
+                toks.append(ty * tok_w + tx)
+            if len(set(toks)) != len(toks):
+                raise ValueError("duplicate queries")
+        y = self.tokenize_long(frames, tok_h, tok_w, depth_scale)
+        v = self.attention_rollout_long_f32(y, toks)
+        return v.reshape(v.shape[0], v.shape[1], tok_h, tok_w)
 
     def encoder_layer_long_f32(self, x, layer: int = 0, out=None):
         """one encoder layer with a float FFN (ITAW0002 / ITAW0003 blob) over a long sequence: x (B,S,E) f32 ->

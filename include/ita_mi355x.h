@@ -53,7 +53,7 @@ int ita_destroy(ita_handle h);
  * A layer with H > 1 runs on the block kernels (ita_mha_kernel<E, H>, then the FFN block) behind the stand-alone tokenizer;
  * every entry point below serves it except those that need the one-head stream kernel, which return
  * ITA_ERR_UNSUPPORTED before any launch: ita_mha_q8, ita_mha_long_q8, ita_mha_long_int8, ita_mha_long_int8_taps,
- * ita_mha_long_int8_stats, ita_mha_long_int8_propagate, ita_encoder_layer_long, ita_debug_encoder_stamps, ita_vitlstm_forward_slots (and ita_mha_long_f32 / ita_mha_long_f32_stats / ita_encoder_layer_long_f32, which take
+ * ita_mha_long_int8_stats, ita_mha_long_int8_propagate, ita_encoder_layer_long, ita_debug_encoder_stamps, ita_vitlstm_forward_slots (and ita_mha_long_f32 / ita_mha_long_f32_stats / ita_mha_long_f32_propagate / ita_encoder_layer_long_f32, which take
  * float layers only).
  * The reference pre-loads weights into the accelerator out of band
  * (docs/HOW-TO-run-the-full-project-workflow.md:55); this is that step. */
@@ -194,9 +194,9 @@ int ita_ffn_f32(ita_handle h, int layer, const float* x_dev, float* y_dev, int b
  * blob: the float graph, models/ITA_single_layer_upsample_shuffle/model.py, nothing quantised).  ita_mha_int8 / _taps,
  * ita_mha_q8, ita_mha_long_q8, ita_mha_long_int8, ita_encoder_layer_long, ita_debug_encoder_stamps and the drop-in
  * ITASelfAttention_workgroup on an F32 layer, and
- * ita_mha_f32 / ita_mha_long_f32 / ita_mha_long_f32_taps / ita_mha_long_f32_stats on an INT8 layer, fail with ITA_ERR_UNSUPPORTED; each message names the
+ * ita_mha_f32 / ita_mha_long_f32 / ita_mha_long_f32_taps / ita_mha_long_f32_stats / ita_mha_long_f32_propagate on an INT8 layer, fail with ITA_ERR_UNSUPPORTED; each message names the
  * sibling entry (ita_mha_long_int8 <-> ita_mha_long_f32, ita_mha_long_int8_taps <-> ita_mha_long_f32_taps,
- * ita_mha_long_int8_stats <-> ita_mha_long_f32_stats,
+ * ita_mha_long_int8_stats <-> ita_mha_long_f32_stats; ita_mha_long_f32_propagate names ita_mha_long_int8_propagate,
  * ita_encoder_layer_long <-> ita_encoder_layer_long_f32). */
 enum { ITA_ATTN_INT8 = 0, ITA_ATTN_F32 = 1 };
 int ita_get_attn_kind(ita_handle h, int layer, int* kind);
@@ -266,6 +266,32 @@ struct ita_mha_long_f32_stats {
 };
 int ita_mha_long_f32_stats(ita_handle h, int layer, const float* x_dev, int batch, int seq_len, float p_min,
                            const struct ita_mha_long_f32_stats* stats, void* stream);
+/* Weighted column sums of the WHOLE seq_len x seq_len probability matrix of ita_mha_long_f32, which is never held -- the
+ * float sibling of ita_mha_long_int8_propagate:
+ *     out[b, r, j] = sum_i w[b, r, i] * p[b, i, j]      w f32 (B, n_w, seq_len), out f32 (B, n_w, seq_len), 1 <= n_w <= 64
+ * with p[b, i, j] = ita_expf(s - m) * (1.0f / l) the probability ita_mha_long_f32_taps defines, each operation rounded on
+ * its own; s, m and l are the production sweep's bits.  col_mass of ita_mha_long_f32_stats is w = all ones up to the order
+ * of the additions, a probability row is w = one-hot.  x (B, seq_len, E) f32 is read only; w and out must not overlap each
+ * other or x.  The weights are not scanned: non-finite weights give non-finite sums.
+ * Numerical contract.  The f32 sums are taken in one fixed order (csrc/ita_long_f32_prop_kernel.h: fmaf chains of the 64
+ * queries of a unit from zero, the units' blocks added in ascending order; no atomics).  Bit-exact: a one-hot weight row
+ * gives the bits of the taps' probability row (0 * p adds +0); a weight row gives the same bits whether it is row 0 of an
+ * n_w = 1 call or row 37 of an n_w = 64 call; the same input gives the same bits on every call, in any batch position, and
+ * alone.  Against the kernels' own probabilities P (the taps' probs of all rows) summed in float64:
+ *     |out - sum_i w P| <= gamma_(S+2) * sum_i |w| P,   gamma_n = n u / (1 - n u),  u = 2^-24
+ * (any fixed-order f32 sum of S terms, one rounding for a product, one to spare: derived, not measured).  Against float64
+ * from the parameters the project's rule holds per case: 3 * e_torch + 4 ulp32(max |truth|), e_torch the error of torch's
+ * CPU f32 w @ softmax(q k^T) on the same inputs.
+ * Launches: one projection launch that writes the K image and a Q image in the same layout (no V), ita_lf32_stats_kernel
+ * for the row maximum and row sum of every query (rows only, into the workspace), and ita_lf32_prop_kernel, the transposed
+ * sweep: kernel launches only.  Workspace: ita_mha_long_f32's plus 8 bytes per token; it grows on demand (not inside a
+ * stream capture: ITA_ERR_INVALID_ARG); once it holds the call there is no host synchronisation and no allocation, and
+ * the call may be captured.  Shape limits of ita_mha_long_f32.  Refusals, all before any launch, out untouched: whatever
+ * ita_mha_long_f32 refuses, with the same status (an int8-attention layer: ITA_ERR_UNSUPPORTED, the message names
+ * ita_mha_long_int8_propagate); ITA_ERR_INVALID_ARG for a NULL x_dev, w_dev or out_dev, a bad layer, n_w outside [1, 64],
+ * w_dev or out_dev off a 16-byte boundary. */
+int ita_mha_long_f32_propagate(ita_handle h, int layer, const float* x_dev, int batch, int seq_len,
+                               const float* w_dev, int n_w, float* out_dev, void* stream);
 /* The long form of ita_encoder_layer for a layer with a float FFN: y = LN2(x1 + ffn(x1)), x1 = LN1(x + attn(x)) on
  * (B, seq_len, E) f32 rows; x_dev may equal y_dev.  Attention + residual + LN1 are the two launches of ita_mha_long_f32
  * (ITAW0003 blob) or of ita_mha_long_int8 (ITAW0002 blob, with that entry's refusals); the float FFN + residual + LN2
