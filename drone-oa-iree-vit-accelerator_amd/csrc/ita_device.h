@@ -219,6 +219,72 @@ __device__ __forceinline__ void dq16_b(const i32x4 (&acc)[4], float mult, float 
   float c[16];
   dq16_b(acc, mult, scale, d, c);
 }
+// v_pk_fma_f32 x, x, s[p:p+1], s[p:p+1] with the SGPR pair {m, K}: x * m + K in both halves (the operand modifiers hipcc
+// itself emits for a splat of each dword)
+#define ITA_PK_MK "op_sel:[0,0,1] op_sel_hi:[1,0,1]"
+// The fused dequantise form of the same block output (out_proj, fc2; ita_weights_load.h: fused_site with dq): the accumulators
+// started at the site's own integer base C, t = fma(acc_bits, m, K) with K = 1.5 * 2^23 - round(C m) in ONE v_pk_fma_f32 per
+// pair -- an integer of [2^23, 2^24), rounded once --, r = t - 1.5 * 2^23 (v_pk_add_f32, exact), the float clamp, the scale:
+// 8 + 8 + 16 + 8 = 2.5 instructions per value instead of 3.5.  Permitted per site by the load-time enumeration of the whole
+// clamp range against the reference's two roundings; beyond that range both forms clamp (the fma is monotone).
+// (m and K travel as one SGPR pair, see pk_requant_round.)
+// Sign of zero: the two-rounding form yields -0.0 for a small negative accumulator (v_rndne_f32 keeps the sign), t - 1.5 * 2^23
+// yields +0.0.  The proof compares codes, where the two are one; d differs in the sign bit only, and the residual x + d only
+// when x is -0.0 as well, which compares equal and which the LayerNorm that follows maps to the same bits.
+__device__ __forceinline__ void dq16_fused(const i32x4 (&acc)[4], float mult, float kf, float scale, float (&d)[16]) {
+  f32x2 x[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) x[k] = (f32x2){__int_as_float(acc[k >> 1][2 * (k & 1)]), __int_as_float(acc[k >> 1][2 * (k & 1) + 1])};
+  const f32x2 c2 = {-ITA_MAGIC_F, -ITA_MAGIC_F}, mk = {mult, kf};
+  asm("s_nop 7\n\ts_nop 1\n\t"
+      "v_pk_fma_f32 %0, %0, %8, %8 " ITA_PK_MK "\n\t"
+      "v_pk_fma_f32 %1, %1, %8, %8 " ITA_PK_MK "\n\t"
+      "v_pk_fma_f32 %2, %2, %8, %8 " ITA_PK_MK "\n\t"
+      "v_pk_fma_f32 %3, %3, %8, %8 " ITA_PK_MK "\n\t"
+      "v_pk_fma_f32 %4, %4, %8, %8 " ITA_PK_MK "\n\t"
+      "v_pk_fma_f32 %5, %5, %8, %8 " ITA_PK_MK "\n\t"
+      "v_pk_fma_f32 %6, %6, %8, %8 " ITA_PK_MK "\n\t"
+      "v_pk_fma_f32 %7, %7, %8, %8 " ITA_PK_MK "\n\t"
+      "v_pk_add_f32 %0, %0, %9\n\t"
+      "v_pk_add_f32 %1, %1, %9\n\t"
+      "v_pk_add_f32 %2, %2, %9\n\t"
+      "v_pk_add_f32 %3, %3, %9\n\t"
+      "v_pk_add_f32 %4, %4, %9\n\t"
+      "v_pk_add_f32 %5, %5, %9\n\t"
+      "v_pk_add_f32 %6, %6, %9\n\t"
+      "v_pk_add_f32 %7, %7, %9"
+      : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7])
+      : "s"(mk), "s"(c2));
+  float f[16];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { f[2 * k] = x[k].x; f[2 * k + 1] = x[k].y; }
+  const float lo = -128.0f, hi = 127.0f;
+  asm("v_med3_f32 %0, %0, %16, %17\n\t"
+      "v_med3_f32 %1, %1, %16, %17\n\t"
+      "v_med3_f32 %2, %2, %16, %17\n\t"
+      "v_med3_f32 %3, %3, %16, %17\n\t"
+      "v_med3_f32 %4, %4, %16, %17\n\t"
+      "v_med3_f32 %5, %5, %16, %17\n\t"
+      "v_med3_f32 %6, %6, %16, %17\n\t"
+      "v_med3_f32 %7, %7, %16, %17\n\t"
+      "v_med3_f32 %8, %8, %16, %17\n\t"
+      "v_med3_f32 %9, %9, %16, %17\n\t"
+      "v_med3_f32 %10, %10, %16, %17\n\t"
+      "v_med3_f32 %11, %11, %16, %17\n\t"
+      "v_med3_f32 %12, %12, %16, %17\n\t"
+      "v_med3_f32 %13, %13, %16, %17\n\t"
+      "v_med3_f32 %14, %14, %16, %17\n\t"
+      "v_med3_f32 %15, %15, %16, %17"
+      : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]), "+v"(f[6]), "+v"(f[7]), "+v"(f[8]), "+v"(f[9]),
+        "+v"(f[10]), "+v"(f[11]), "+v"(f[12]), "+v"(f[13]), "+v"(f[14]), "+v"(f[15])
+      : "s"(lo), "v"(hi));
+  const f32x2 s2 = {scale, scale};
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const f32x2 v = (f32x2){f[2 * k], f[2 * k + 1]} * s2;
+    d[2 * k] = v.x; d[2 * k + 1] = v.y;
+  }
+}
 // ---- round-3 requantisation of biased accumulators: the clamp moves behind the rounding, into the integer domain, where
 // ONE instruction saturates two values (v_sat_pk_u8_i16) -- 2.75 VALU instructions per value instead of 3.0, and 2.25 where a
 // load-time proof allows the single-rounding form:
@@ -251,32 +317,36 @@ __device__ __forceinline__ void pk_requant_round(f32x2 (&x)[NP], float mult, flo
   static_assert(NP == 8 || NP == 4, "");
   const f32x2 c2 = {-ITA_MAGIC_F, -ITA_MAGIC_F};
   if constexpr (MODE == ITA_RQ_FUSED || MODE == ITA_RQ_FUSED_RELU) {
-    // `magic` is the site's K = magic - round(C m); the accumulators were started at the site's C (copied into a VGPR pair
-    // inside the block for the same two reasons as in the fast form below)
-    const f32x2 m2 = {mult, mult}, g2s = {magic, magic};
-    f32x2 g2;
+    // `magic` is the site's K = magic - round(C m); the accumulators were started at the site's C.  The multiplier and K
+    // travel as ONE SGPR pair {m, K} (ItaStreamArgs::mk*): the op_sel bits pick dword 0 for both halves of src1 and dword 1 for
+    // both halves of src2, and one pair read twice is one scalar operand -- no copy of K into VGPRs (ITA_PK_MK)
+    const f32x2 mk = {mult, magic};
     if constexpr (NP == 8) {
+      f32x2 y[8];
       asm("s_nop 7\n\ts_nop 1\n\t"
-        "v_pk_mov_b32 %8, %10, %10\n\t"
-        "v_pk_fma_f32 %0, %0, %9, %8\n\t"
-        "v_pk_fma_f32 %1, %1, %9, %8\n\t"
-        "v_pk_fma_f32 %2, %2, %9, %8\n\t"
-        "v_pk_fma_f32 %3, %3, %9, %8\n\t"
-        "v_pk_fma_f32 %4, %4, %9, %8\n\t"
-        "v_pk_fma_f32 %5, %5, %9, %8\n\t"
-        "v_pk_fma_f32 %6, %6, %9, %8\n\t"
-        "v_pk_fma_f32 %7, %7, %9, %8"
-          : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]), "=&v"(g2)
-          : "s"(m2), "s"(g2s));
+        "v_pk_fma_f32 %0, %9, %8, %8 " ITA_PK_MK "\n\t"
+        "v_pk_fma_f32 %1, %10, %8, %8 " ITA_PK_MK "\n\t"
+        "v_pk_fma_f32 %2, %11, %8, %8 " ITA_PK_MK "\n\t"
+        "v_pk_fma_f32 %3, %12, %8, %8 " ITA_PK_MK "\n\t"
+        "v_pk_fma_f32 %4, %13, %8, %8 " ITA_PK_MK "\n\t"
+        "v_pk_fma_f32 %5, %14, %8, %8 " ITA_PK_MK "\n\t"
+        "v_pk_fma_f32 %6, %15, %8, %8 " ITA_PK_MK "\n\t"
+        "v_pk_fma_f32 %7, %16, %8, %8 " ITA_PK_MK
+          : "=&v"(y[0]), "=&v"(y[1]), "=&v"(y[2]), "=&v"(y[3]), "=&v"(y[4]), "=&v"(y[5]), "=&v"(y[6]), "=&v"(y[7])
+          : "s"(mk), "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(x[4]), "v"(x[5]), "v"(x[6]), "v"(x[7]));
+#pragma unroll
+      for (int k = 0; k < 8; ++k) x[k] = y[k];
     } else {
+      f32x2 y[4];
       asm("s_nop 7\n\ts_nop 1\n\t"
-        "v_pk_mov_b32 %4, %6, %6\n\t"
-        "v_pk_fma_f32 %0, %0, %5, %4\n\t"
-        "v_pk_fma_f32 %1, %1, %5, %4\n\t"
-        "v_pk_fma_f32 %2, %2, %5, %4\n\t"
-        "v_pk_fma_f32 %3, %3, %5, %4"
-          : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "=&v"(g2)
-          : "s"(m2), "s"(g2s));
+        "v_pk_fma_f32 %0, %5, %4, %4 " ITA_PK_MK "\n\t"
+        "v_pk_fma_f32 %1, %6, %4, %4 " ITA_PK_MK "\n\t"
+        "v_pk_fma_f32 %2, %7, %4, %4 " ITA_PK_MK "\n\t"
+        "v_pk_fma_f32 %3, %8, %4, %4 " ITA_PK_MK
+          : "=&v"(y[0]), "=&v"(y[1]), "=&v"(y[2]), "=&v"(y[3])
+          : "s"(mk), "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]));
+#pragma unroll
+      for (int k = 0; k < 4; ++k) x[k] = y[k];
     }
   } else if constexpr (MODE == ITA_RQ_FAST) {
     // (an instruction reads at most one SGPR operand: the magic constant is copied into a VGPR pair inside the block -- as a

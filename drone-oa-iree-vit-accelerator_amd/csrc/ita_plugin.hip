@@ -378,6 +378,7 @@ template <int E, bool FFN, int TOK, bool IO8>
 int launch_stream_kernel(bool fast, int fused, dim3 grid, hipStream_t s, const ItaStreamArgs& a) {
   constexpr int lds = ItaStreamLds<E, FFN, TOK != 0>::TOTAL;
   if constexpr (FFN) {
+    if (fused == 3) return launch<ita_stream_kernel<E, FFN, TOK, false, IO8, true, 3>, lds>(grid, dim3(512), s, a);
     if (fused == 2) return launch<ita_stream_kernel<E, FFN, TOK, false, IO8, true, 2>, lds>(grid, dim3(512), s, a);
   }
   if (fused) return launch<ita_stream_kernel<E, FFN, TOK, false, IO8, true, 1>, lds>(grid, dim3(512), s, a);
@@ -401,10 +402,11 @@ int launch_stream(ita_context* c, int layer, int mode, bool fuse_ln, const Strea
   const dim3 grid(B < c->num_cus ? B : c->num_cus), block(512);
   const bool fast = L.fast_sites == ITA_SITES_ALL;
   // the fused form: its own images, and the constants of its five sites
-  const int fused = (L.fused && !io.stamps) ? (L.fused_relu ? 2 : 1) : 0;   // (2: fc1 as well, the whole-layer flavours)
+  // (2: fc1 as well, 3: and the dequantise sites out_proj and fc2 -- the whole-layer flavours, the others launch 1)
+  const int fused = (L.fused && !io.stamps) ? (L.fused_dq ? 3 : L.fused_relu ? 2 : 1) : 0;
   if (fused) {
-    a.k1 = L.fused_k[5];
-    a.kq = L.fused_k[0]; a.kk = L.fused_k[1]; a.kv = L.fused_k[2]; a.kl = L.fused_k[3]; a.kc = L.fused_k[4];
+    a.mkq = {a.mq, L.fused_k[0]}; a.mkk = {a.mk, L.fused_k[1]}; a.mkv = {a.mv, L.fused_k[2]}; a.mkl = {a.ml, L.fused_k[3]};
+    a.mkc = {a.mc, L.fused_k[4]}; a.mk1 = {a.m1, L.fused_k[5]}; a.mko = {a.mo, L.fused_k[6]}; a.mk2 = {a.m2, L.fused_k[7]};
     a.c_l = L.fused_c[3]; a.c_c = L.fused_c[4];
   }
   if (mode == 2) {
@@ -1427,7 +1429,7 @@ int ita_debug_fused_site(float mult, int* C, float* K) {
 }
 int ita_debug_fused_check(float mult, int form, int C, float* K) {
   float k = 0.0f;
-  const int ok = fused_site_check(mult, form == 1 ? ITA_MAGIC32K_F : form == 2 ? ITA_MAGIC_F : ITA_MAGIC128_F, C, &k) ? 1 : 0;
+  const int ok = fused_site_check(mult, form == 1 ? ITA_MAGIC32K_F : (form == 2 || form == 3) ? ITA_MAGIC_F : ITA_MAGIC128_F, C, &k, form == 3) ? 1 : 0;
   if (K) *K = k;
   return ok;
 }
@@ -1442,6 +1444,41 @@ int ita_debug_layer_fused(ita_handle h, int layer, unsigned* fused_sites, int* f
     if (C6) C6[i] = L.fused_c[i];
     if (K6) K6[i] = L.fused_k[i];
   }
+  return ITA_OK;
+}
+
+int ita_debug_dequant_site(float mult, int dmax, int* C, float* K) {
+  if (!C || !K) return 0;
+  return fused_site(mult, ITA_MAGIC_F, dmax, C, K, true) ? 1 : 0;
+}
+int ita_debug_layer_dequant(ita_handle h, int layer, int* fused_dq, int* C2, float* K2) {
+  if (!h || !h->w.loaded) return fail(ITA_ERR_NO_WEIGHTS, "no weights loaded");
+  if (!fused_dq || layer < 0 || layer >= h->w.hdr.num_layers)
+    return fail(ITA_ERR_INVALID_ARG, "ita_debug_layer_dequant: null output or layer out of range");
+  const Layer& L = h->w.layers[layer];
+  *fused_dq = L.fused_dq ? 1 : 0;
+  for (int i = 0; i < 2; ++i) {
+    if (C2) C2[i] = L.fused_c[6 + i];
+    if (K2) K2[i] = L.fused_k[6 + i];
+  }
+  return ITA_OK;
+}
+
+int ita_debug_x2_planes(ita_handle h, int fill, void* hi, void* lo, int B, int* ld_planes, void* stream) {
+  if (!h || !h->w.loaded) return fail(ITA_ERR_NO_WEIGHTS, "no weights loaded");
+  if (ld_planes) *ld_planes = h->w.ldfold;
+  if (B <= 0 || B > h->ws.cap || !h->ws.x2_hi || !h->ws.x2_lo)
+    return fail(ITA_ERR_INVALID_ARG, "ita_debug_x2_planes: batch beyond the reserved workspace, or no planes");
+  const size_t bytes = (size_t)B * h->w.ldfold * sizeof(_Float16);
+  hipStream_t s = (hipStream_t)stream;
+  if (fill) {
+    HIPCHK(hipMemsetAsync(h->ws.x2_hi, fill & 0xff, bytes, s));
+    HIPCHK(hipMemsetAsync(h->ws.x2_lo, fill & 0xff, bytes, s));
+    return ITA_OK;
+  }
+  if (!hi || !lo) return fail(ITA_ERR_INVALID_ARG, "ita_debug_x2_planes: null output");
+  HIPCHK(hipMemcpyAsync(hi, h->ws.x2_hi, bytes, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemcpyAsync(lo, h->ws.x2_lo, bytes, hipMemcpyDeviceToDevice, s));
   return ITA_OK;
 }
 

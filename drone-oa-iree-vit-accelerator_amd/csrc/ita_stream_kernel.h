@@ -57,14 +57,19 @@ struct ItaStreamArgs {
   // Informational inside the kernel: the launcher picks the FAST instantiation when all six bits are set.
   unsigned fast_sites;
   // the FUSED instantiation (the launcher picks it when every fused site of the layer is proven, ita_weights_load.h:
-  // fused_site): the logits' and the column sums' accumulator bases C_L, C_C, and K_site = magic - round(C_site m_site) of
-  // Q, K, V, logits and context.  The bases of Q, K and V are in the image's biases.  Unused by the other instantiations.
+  // fused_site): the logits' and the column sums' accumulator bases C_L, C_C; each site's K_site = magic - round(C_site m_site)
+  // is the second half of its mk* pair below.  The bases of Q, K and V are in the image's biases.  Unused by the other instantiations.
   int c_l, c_c;
-  float kq, kk, kv, kl, kc, k1;   // k1: fc1's K of the fused ReLU form (FUSED == 2; its base is in the image's b1)
+  // Each site's {multiplier, K} as one 8-byte kernel argument: it arrives as an aligned SGPR pair, the operand of the
+  // site's v_pk_fma_f32 (ita_device.h: ITA_PK_MK).  k1: fc1's fused ReLU form (FUSED >= 2; its base is in the image's b1);
+  // ko, k2: out_proj's and fc2's fused dequantise form (FUSED == 3; bases in bo and b2)
+  f32x2 mkq, mkk, mkv, mkl, mkc, mk1, mko, mk2;
 };
 enum { ITA_SITE_Q = 1, ITA_SITE_K = 2, ITA_SITE_V = 4, ITA_SITE_L = 8, ITA_SITE_C = 16, ITA_SITE_O = 32, ITA_SITES_ALL = 63,
        ITA_SITES_FUSED = 31 /* the sites the fused instantiation changes: all but out_proj */,
-       ITA_SITE_FC1 = 32 /* in the FUSED mask only (the fast mask's bit 5 is out_proj): fc1's fused ReLU form */ };
+       ITA_SITE_FC1 = 32 /* in the FUSED mask only (the fast mask's bit 5 is out_proj): fc1's fused ReLU form */,
+       ITA_SITE_DQ_O = 64, ITA_SITE_DQ_FC2 = 128 /* FUSED mask only: the fused dequantise form of out_proj and fc2 */,
+       ITA_SITES_DQ = 192 };
 
 #define ITA_SCHED_BARRIER() __builtin_amdgcn_sched_barrier(0)
 
@@ -253,19 +258,36 @@ __device__ __forceinline__ i32x4 rq_group(const i32x4 (&acc)[4], float mult, boo
   return rq_pack16_v3<ITA_RQ_EXACT>(acc, mult);
 }
 // block output: d[4t+i] = dequantised int8 code of channel (E/4)kq + 4(et0+t) + i
-__device__ __forceinline__ void dq_group(const i32x4 (&acc)[4], float mult, float scale, float (&d)[16]) {
+// FUSED: the accumulators started at the site's own base and kf is its K (ita_device.h: dq16_fused)
+template <bool FUSED = false>
+__device__ __forceinline__ void dq_group(const i32x4 (&acc)[4], float mult, float scale, float (&d)[16], float kf = 0.0f) {
   if constexpr (ITA_ABLATE & 1) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) d[i] = __int_as_float(acc[i >> 2][i & 3]);
     return;
   }
-  dq16_b(acc, mult, scale, d);
+  if constexpr (FUSED) dq16_fused(acc, mult, kf, scale, d);
+  else dq16_b(acc, mult, scale, d);
 }
 // the same, and the codes it scaled: c[4t+i] = d[4t+i] / scale as integers in [-128, 127] (the long taps kernel stores them)
 __device__ __forceinline__ void dq_group_codes(const i32x4 (&acc)[4], float mult, float scale, float (&d)[16], float (&c)[16]) {
   dq16_b(acc, mult, scale, d, c);
 }
 
+// E = 64 plane stores with the lane exchange: p0 / p1 are the lane's two 16-byte pieces of its 32
+// bytes of a plane row; v_permlane16_swap trades p0 of the odd 16-lane rows for p1 of the even ones, after which the first
+// store holds bytes [0, 16) of the pair's 64 in the even lane and [16, 32) in the odd one (pa = the lane's own offset, less 16
+// in the odd lane), and the second store the next 32 the same way.  Written through, the launch's WRITE_SIZE falls from twice
+// the payload to the payload, and the launch is not slower for the 10 more VALU per wave (profiles/encoder_dequant_fused_ab.txt).
+__device__ __forceinline__ void plane_store_xchg(__amdgpu_buffer_rsrc_t f, int pa, u32x4 p0, u32x4 p1) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const auto r = __builtin_amdgcn_permlane16_swap(p0[c], p1[c], false, false);
+    p0[c] = r[0]; p1[c] = r[1];
+  }
+  ita_store16<true>(f, pa, p0);
+  ita_store16<true>(f, pa + 32, p1);
+}
 // (amdgpu_waves_per_eu(2, 2): the workgroup owns the CU's LDS, so two waves per SIMD is all there will ever be -- without
 // it the scheduler trades instruction-level parallelism for registers it has no use for: the LDS size is dynamic)
 // FAST: every requantisation site of this layer passed the load-time single-rounding proof (ita_plugin.hip: fast_site_ok).
@@ -274,11 +296,12 @@ __device__ __forceinline__ void dq_group_codes(const i32x4 (&acc)[4], float mult
 // round-2 form, 54.0 with the fast form compiled in, 55.3 with the exact one).
 // FUSED (implies FAST at the out_proj site of the int8 I/O form, the only one it leaves alone): Q, K, V, logits and context
 // run the one-fma form on accumulators started at per-site bases, chosen and proven at load time; FUSED == 2: fc1 runs the
-// fused ReLU form as well (its own proof).  A template argument for the same reason.
+// fused ReLU form as well (its own proof); FUSED == 3: out_proj and fc2 run the fused dequantise form on top of that (their
+// own proofs, both or neither).  A template argument for the same reason.
 template <int E, bool FFN, int TOK, bool STAMP = false, bool IO8 = false, bool FAST = false, int FUSED = 0>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void ita_stream_kernel(const ItaStreamArgs a) {
   static_assert(!IO8 || (!FFN && TOK == 0), "int8 I/O is the attention block's form");
-  static_assert(FUSED == 0 || FUSED == 1 || (FUSED == 2 && FFN), "the fused ReLU form is fc1's");
+  static_assert(FUSED == 0 || FUSED == 1 || ((FUSED == 2 || FUSED == 3) && FFN), "the fused ReLU and dequantise forms are the whole layer's");
   static_assert(FUSED == 0 || FAST, "the fused instantiation keeps the fast form at out_proj");
   using L = ItaStreamLds<E, FFN, TOK != 0>;
   constexpr int S = 128, P = 192, F = 256, EC = E / 4, NK = E / 64, NTE = E / 16;
@@ -460,13 +483,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       auto epilogue = [&](int g, const i32x4 (&acc)[4]) {
         const int mat = g / 3, gg = g - 3 * mat;
         if (mat == 0) {
-          qf[gg] = rq_group<false, FUSED != 0>(acc, a.mq, fq, a.kq);
+          qf[gg] = rq_group<false, FUSED != 0>(acc, FUSED ? a.mkq.x : a.mq, fq, a.mkq.y);
         } else if (mat == 1) {
-          *(i32x4*)(lds + L::K + (((4 * gg + kq) * S + token) << 4)) = rq_group<false, FUSED != 0>(acc, a.mk, fk, a.kk);
+          *(i32x4*)(lds + L::K + (((4 * gg + kq) * S + token) << 4)) = rq_group<false, FUSED != 0>(acc, FUSED ? a.mkk.x : a.mk, fk, a.mkk.y);
         } else {
           // V with the roles swapped (A = tokens, B = weights): lane (feature qi, kq) holds keys 16w + 4kq + i of
           // feature 16 dt + qi -- one dword of the V^T slot (key block w>>2, k-group kq), at word w&3
-          const i32x4 p4 = rq_group<false, FUSED != 0>(acc, a.mv, fv, a.kv);
+          const i32x4 p4 = rq_group<false, FUSED != 0>(acc, FUSED ? a.mkv.x : a.mv, fv, a.mkv.y);
 #pragma unroll
           for (int t = 0; t < 4; ++t) {
             const int d = (4 * gg + t) * 16 + qi;
@@ -548,7 +571,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       auto epil = [&](int p, const i32x4 (&acc)[2]) {
         // low 16 bits = rne(logit) + 32768, unclamped: the softmax clamps (ita_softmax_packed16)
         unsigned w4[4];
-        if constexpr (FUSED) lg8_v3<ITA_RQ_FUSED>(acc, a.ml, w4, a.kl);
+        if constexpr (FUSED) lg8_v3<ITA_RQ_FUSED>(acc, a.mkl.x, w4, a.mkl.y);
         else if (fl) lg8_v3<ITA_RQ_FAST>(acc, a.ml, w4);
         else lg8_v3<ITA_RQ_EXACT>(acc, a.ml, w4);
 #pragma unroll
@@ -582,7 +605,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       for (int st = 0; st < 6; ++st) {
         if (st + 1 < 6) ldv(st + 1, vb[(st + 1) & 1]);
         mm_ks(vb[st & 1], pf[st & 1], va[st >> 1]);
-        if (st == 3) cf[0] = rq_group<false, FUSED != 0>(va[0], a.mc, fc, a.kc);
+        if (st == 3) cf[0] = rq_group<false, FUSED != 0>(va[0], FUSED ? a.mkc.x : a.mc, fc, a.mkc.y);
         ITA_SCHED_BARRIER();   // keep the step's loads ahead of the next step's MFMAs
       }
       ITA_SSTAMP(5);
@@ -593,10 +616,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       ld_obias<E>(oa, l_bo, 0, kq);
       // the next frame's pixel window, before this frame's global stores (one in-order vmcnt for loads and stores)
       if constexpr (TOK != 0) { if (more) tok_fill(ol); }
-      cf[1] = rq_group<false, FUSED != 0>(va[1], a.mc, fc, a.kc);
+      cf[1] = rq_group<false, FUSED != 0>(va[1], FUSED ? a.mkc.x : a.mc, fc, a.mkc.y);
       ld_frg_ks<E>(ob[1], lds + L::WO, 0, 1, qi, kq);
       mm_ks(ob[0], cf[0], oa);
-      cf[2] = rq_group<false, FUSED != 0>(va[2], a.mc, fc, a.kc);
+      cf[2] = rq_group<false, FUSED != 0>(va[2], FUSED ? a.mkc.x : a.mc, fc, a.mkc.y);
     }
 
     // ---------------- out_proj + residual + LayerNorm1 (k-step 0 of the first group is already in flight)
@@ -624,7 +647,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         continue;
       }
       float d[16];
-      dq_group(oa, a.mo, a.so, d);
+      dq_group<FUSED == 3>(oa, FUSED == 3 ? a.mko.x : a.mo, a.so, d, a.mko.y);
       if (eg + 1 < EG) ld_obias<E>(oa, l_bo, 4 * (eg + 1), kq);
 #pragma unroll
       for (int j = 0; j < 16; ++j) x1[16 * eg + j] = (FFN || a.fuse_ln) ? xr[16 * eg + j] + d[j] : d[j];
@@ -662,17 +685,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         if (g >= 1) ld_frg_ks<E>(wb[(g - 1) & 1], w2p, 0, g - 1, qi, kq);
         mm_group<NK, false>(ffr[g & 1], x1f, fa[g % 3]);
         if (g >= 2) mm_ks(wb[(g - 2) & 1], hf[g - 2], ya);
-        if (g >= 1) hf[g - 1] = rq_group<true, FUSED == 2>(fa[(g - 1) % 3], a.m1, false, a.k1);
+        if (g >= 1) hf[g - 1] = rq_group<true, FUSED >= 2>(fa[(g - 1) % 3], FUSED >= 2 ? a.mk1.x : a.m1, false, a.mk1.y);
         ITA_SCHED_BARRIER();   // keep the step's loads ahead of the next step's MFMAs
       }
       ld_frg_ks<E>(wb[1], w2p, 0, 3, qi, kq);
       mm_ks(wb[0], hf[2], ya);
-      hf[3] = rq_group<true, FUSED == 2>(fa[3 % 3], a.m1, false, a.k1);
+      hf[3] = rq_group<true, FUSED >= 2>(fa[3 % 3], FUSED >= 2 ? a.mk1.x : a.m1, false, a.mk1.y);
       mm_ks(wb[1], hf[3], ya);
       ITA_SSTAMP(8);
       {
         float d[16];
-        dq_group(ya, a.m2, a.s2, d);
+        dq_group<FUSED == 3>(ya, FUSED == 3 ? a.mk2.x : a.m2, a.s2, d, a.mk2.y);
 #pragma unroll
         for (int j = 0; j < 16; ++j) yv[j] = x1[j] + d[j];
       }
@@ -688,7 +711,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           ITA_SCHED_BARRIER();
         }
         float d[16];
-        dq_group(ya, a.m2, a.s2, d);
+        dq_group<FUSED == 3>(ya, FUSED == 3 ? a.mk2.x : a.m2, a.s2, d, a.mk2.y);
 #pragma unroll
         for (int j = 0; j < 16; ++j) yv[16 * eg + j] = x1[16 * eg + j] + d[j];
       }
@@ -726,11 +749,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         } else {
           // one plane after the other: one resource (four SGPRs) live at a time
           const __amdgpu_buffer_rsrc_t f_hi = ita_rsrc(y_hi + (size_t)b * a.ld_planes);
+          if constexpr (PLANES_WT) {
+            // lanes kq and kq ^ 1 (16 apart) exchange a 16-byte piece, the even one's second against the odd one's first: a
+            // store instruction then covers 32 contiguous bytes per lane pair, two runs per token row instead of four
+            const int pa = po * 2 - 16 * (kq & 1);
+            plane_store_xchg(f_hi, pa, __builtin_bit_cast(u32x4, vh[0]), __builtin_bit_cast(u32x4, vh[1]));
+            const __amdgpu_buffer_rsrc_t f_lo = ita_rsrc(a.y_lo + (size_t)b * a.ld_planes);
+            plane_store_xchg(f_lo, pa, __builtin_bit_cast(u32x4, vl[0]), __builtin_bit_cast(u32x4, vl[1]));
+          } else {
 #pragma unroll
-          for (int i = 0; i < EC / 8; ++i) ita_store16<PLANES_WT>(f_hi, (po + 8 * i) * 2, __builtin_bit_cast(u32x4, vh[i]));
-          const __amdgpu_buffer_rsrc_t f_lo = ita_rsrc(a.y_lo + (size_t)b * a.ld_planes);
+            for (int i = 0; i < EC / 8; ++i) ita_store16<PLANES_WT>(f_hi, (po + 8 * i) * 2, __builtin_bit_cast(u32x4, vh[i]));
+            const __amdgpu_buffer_rsrc_t f_lo = ita_rsrc(a.y_lo + (size_t)b * a.ld_planes);
 #pragma unroll
-          for (int i = 0; i < EC / 8; ++i) ita_store16<PLANES_WT>(f_lo, (po + 8 * i) * 2, __builtin_bit_cast(u32x4, vl[i]));
+            for (int i = 0; i < EC / 8; ++i) ita_store16<PLANES_WT>(f_lo, (po + 8 * i) * 2, __builtin_bit_cast(u32x4, vl[i]));
+          }
         }
       }
     }

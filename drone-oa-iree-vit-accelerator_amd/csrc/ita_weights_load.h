@@ -37,10 +37,13 @@ struct Layer {
   // long-sequence kernels read simg_mha, the stamped diagnostic instantiations the other two.
   // Entry / bit 5 is fc1 (the fused ReLU form, a proof of its own): with it the whole-layer images carry fc1's base in b1
   // and the FUSED == 2 instantiation runs; without it they keep the default there and FUSED == 1 runs.
+  // Entries / bits 6 and 7 are out_proj and fc2 (the fused dequantise form, ita_device.h: dq16_fused): with fc1 and BOTH of
+  // them the whole-layer images carry their bases in bo and b2 and FUSED == 3 runs.  The attention-only image keeps the
+  // default bo: the int8-I/O form, whose out_proj ends in codes, reads the same image.
   unsigned fused_sites = 0;
-  bool fused = false, fused_relu = false;
-  int fused_c[6] = {ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS};
-  float fused_k[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  bool fused = false, fused_relu = false, fused_dq = false;
+  int fused_c[8] = {ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS};
+  float fused_k[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
   DevBuf<char> fimg_enc, fimg_tok, fimg_mha;
 };
 
@@ -210,7 +213,8 @@ void build_tok_tab(const float* conv_w, const float* conv_b, char* tab) {
       }
 }
 
-// cb: the accumulator bases of the Q, K, V and fc1 sites (fused form: Layer::fused_c[0, 1, 2, 5]), or null: ITA_ACC_BIAS
+// cb: the accumulator bases of the Q, K, V, fc1, out_proj and fc2 sites (fused form: Layer::fused_c[0, 1, 2, 5, 6, 7]), or
+// null: ITA_ACC_BIAS
 template <int E, bool FFN, bool TOK>
 int build_stream_image(const StreamHostParams& p, DevBuf<char>& out, const int* cb = nullptr) {
   using L = ItaStreamLds<E, FFN, TOK>;
@@ -243,7 +247,9 @@ int build_stream_image(const StreamHostParams& p, DevBuf<char>& out, const int* 
     for (int i = 0; i < L::NBIAS; ++i) {
       int base = ITA_ACC_BIAS;
       if (cb && i < 3 * P) base = cb[i / P];
-      else if (cb && FFN && i >= 3 * P + E && i < 3 * P + E + F) base = cb[5];
+      else if (cb && FFN && i < 3 * P + E) base = cb[6];
+      else if (cb && FFN && i < 3 * P + E + F) base = cb[5];
+      else if (cb && FFN) base = cb[7];
       bias[i] = (int32_t)((uint32_t)bias[i] + (uint32_t)base);
     }
   };
@@ -333,11 +339,12 @@ unsigned fast_sites_of(const float* ascal) {
 // contraction off): a C is accepted when the clamped code equals that of the reference's two roundings for every value.
 // magic: ITA_MAGIC128_F (codes travel as r + 128, u8 saturation), ITA_MAGIC32K_F (logits: r + 32768, clamped by the
 // integer softmax, which reads nothing of a logit but its clamped value: ita_softmax_packed16) or ITA_MAGIC_F (fc1's fused
-// ReLU form: r itself travels, min with 127 and the u8 saturation clamp it to [0, 127]).
+// ReLU form: r itself travels, min with 127 and the u8 saturation clamp it to [0, 127]; dq, the dequantise sites out_proj and
+// fc2: r = t - 1.5 * 2^23 as a float, exact, clamped to [-128, 127] by v_med3_f32 -- nothing travels in 16 bits).
 constexpr int ITA_FUSED_DMAX = 1 << 18, ITA_FUSED_TRIES = 8;
 // the enumeration for one given C: true when the fused form equals the reference on the whole clamp range; *K is set whenever
 // K is an exact float in [2^23, 2^24)
-bool fused_site_check(float m, float magic, int C, float* K) {
+bool fused_site_check(float m, float magic, int C, float* K, bool dq = false) {
   if (!(m > 0.0f) || !(m < 1.0f)) return false;
   const double lim = 130.0 / (double)m;
   if (lim > 4.0e6) return false;
@@ -353,7 +360,12 @@ bool fused_site_check(float m, float magic, int C, float* K) {
   const float Kf = (float)kd;                                 // an integer below 2^24: exact
   *K = Kf;
   const bool l16 = magic == ITA_MAGIC32K_F, relu = magic == ITA_MAGIC_F;
-  auto code = [l16, relu](float t) {
+  if (dq && !relu) return false;   // the dequantise form is defined against K = 1.5 * 2^23 - round(C m) only
+  auto code = [l16, relu, dq](float t) {
+    if (dq) {    // t is an integer of [2^23, 2^24): the subtraction is exact, then the float clamp
+      const float r = t - ITA_MAGIC_F;
+      return (int)(r < -128.0f ? -128.0f : r > 127.0f ? 127.0f : r);
+    }
     unsigned u;
     memcpy(&u, &t, 4);
     if (relu) {   // low 16 bits = r, signed
@@ -377,7 +389,7 @@ bool fused_site_check(float m, float magic, int C, float* K) {
   return true;
 }
 // the search: *C, *K of the first accepted candidate
-bool fused_site(float m, float magic, int dmax, int* C, float* K) {
+bool fused_site(float m, float magic, int dmax, int* C, float* K, bool dq = false) {
   if (!(m > 0.0f) || !(m < 1.0f) || 130.0 / (double)m > 4.0e6 || dmax < 0) return false;
   if (dmax > ITA_FUSED_DMAX) dmax = ITA_FUSED_DMAX;
   uint32_t mb;
@@ -401,13 +413,14 @@ bool fused_site(float m, float magic, int dmax, int* C, float* K) {
     best[j] = Cand{dist, (int)((long long)ITA_ACC_BIAS + d)};
   }
   for (int i = 0; i < nb; ++i)
-    if (fused_site_check(m, magic, best[i].C, K)) { *C = best[i].C; return true; }
+    if (fused_site_check(m, magic, best[i].C, K, dq)) { *C = best[i].C; return true; }
   return false;
 }
 
 // The fused sites of a layer whose accumulators stream_range_ok admitted: Q, K, V (bases in the image's biases: the base
 // may move only as far as the worst row sum leaves room below 2^22), logits (|sum| <= 192 * 128 * 128) and context
-// (<= 255 * 128).  ITA_FUSED_SITES (diagnostic, read at load time) is ANDed onto the proven mask: it can only turn sites off.
+// (<= 255 * 128); fc1, and the two dequantise sites out_proj and fc2, of a whole layer (bases in b1, bo, b2).
+// ITA_FUSED_SITES (diagnostic, read at load time) is ANDed onto the proven mask: it can only turn sites off.
 void prove_fused(Layer& L, const StreamHostParams& p, int E, bool ffn) {
   auto room = [](const int8_t* w, const int32_t* b, int rows, int k) {
     long long worst = 0;
@@ -425,14 +438,18 @@ void prove_fused(Layer& L, const StreamHostParams& p, int E, bool ffn) {
   unsigned proven = 0;
   for (int i = 0; i < 5; ++i)
     if (fused_site(L.ascal[idx[i]], i == 3 ? ITA_MAGIC32K_F : ITA_MAGIC128_F, dmax[i], &L.fused_c[i], &L.fused_k[i])) proven |= 1u << i;
-  unsigned mask = ITA_SITES_FUSED | ITA_SITE_FC1;
+  unsigned mask = ITA_SITES_FUSED | ITA_SITE_FC1 | ITA_SITES_DQ;
   if (const char* e = getenv("ITA_FUSED_SITES")) mask = (unsigned)strtoul(e, nullptr, 0);
   if (ffn && fused_site(L.fscal[ITA_F_M1], ITA_MAGIC_F, room(p.w1, p.b1, 256, E), &L.fused_c[5], &L.fused_k[5])) proven |= ITA_SITE_FC1;
+  if (ffn && fused_site(L.ascal[ITA_A_MO], ITA_MAGIC_F, room(p.wo, p.bo, E, 192), &L.fused_c[6], &L.fused_k[6], true)) proven |= ITA_SITE_DQ_O;
+  if (ffn && fused_site(L.fscal[ITA_F_M2], ITA_MAGIC_F, room(p.w2, p.b2, E, 256), &L.fused_c[7], &L.fused_k[7], true)) proven |= ITA_SITE_DQ_FC2;
   mask &= proven;
   L.fused_sites = mask;
   L.fused = (mask & ITA_SITES_FUSED) == ITA_SITES_FUSED && L.fast_sites == ITA_SITES_ALL;
   L.fused_relu = L.fused && (mask & ITA_SITE_FC1);
+  L.fused_dq = L.fused_relu && (mask & ITA_SITES_DQ) == ITA_SITES_DQ;
   if (!L.fused_relu) L.fused_c[5] = ITA_ACC_BIAS;   // the images keep fc1's default base
+  if (!L.fused_dq) L.fused_c[6] = L.fused_c[7] = ITA_ACC_BIAS;   // ... and out_proj's and fc2's
 }
 
 // ---- the steps of ita_load_weights, in the order the loader runs them; each returns an ITA_* code, and the loader

@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = (
     "ita_vitlstm_back", "ita_vitlstm_pipelined", "ita_vitlstm_front_ev", "ita_vitlstm_encode", "ita_vitlstm_fold", "ita_vitlstm_tail", "ita_debug_softmax_rows",
     "ita_head_status", "ita_vitlstm_sequence", "ita_ingest", "ita_tokenizer_long", "ita_ingest_wire", "ita_ingest_wire_prepare", "ita_resize_table",
     "ita_debug_fast_site_ok", "ita_debug_layer_forms", "ita_debug_fused_site", "ita_debug_fused_check", "ita_debug_layer_fused",
+    "ita_debug_dequant_site", "ita_debug_layer_dequant", "ita_debug_x2_planes",
     "ITASelfAttention_workgroup", "ITASelfAttention_workgroup_expanded", "ITAFeedForward_workgroup",
 )
 
@@ -214,6 +215,9 @@ def lib():
         L.ita_debug_fused_site.argtypes = [C.c_float, C.POINTER(i), C.POINTER(C.c_float)]
         L.ita_debug_fused_check.argtypes = [C.c_float, i, i, C.POINTER(C.c_float)]
         L.ita_debug_layer_fused.argtypes = [vp, i, C.POINTER(C.c_uint), C.POINTER(i), C.POINTER(i), C.POINTER(C.c_float)]
+        L.ita_debug_dequant_site.argtypes = [C.c_float, i, C.POINTER(i), C.POINTER(C.c_float)]
+        L.ita_debug_layer_dequant.argtypes = [vp, i, C.POINTER(i), C.POINTER(i), C.POINTER(C.c_float)]
+        L.ita_debug_x2_planes.argtypes = [vp, i, vp, vp, i, C.POINTER(i), vp]
         L.ita_validate_blob.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p]
         L.ita_bind_dispatch.argtypes = [vp, i, i]
         L.ita_wire_unpack_packet.argtypes = [vp, C.c_size_t, i, vp]
@@ -306,12 +310,23 @@ def fused_site(mult: float):
     return c.value, k.value
 
 
-def fused_check(mult: float, base: int, logits: bool = False, relu: bool = False):
+def fused_check(mult: float, base: int, logits: bool = False, relu: bool = False, dq: bool = False):
     """ita_debug_fused_check: the enumeration alone, on a given base -> (accepted, K); logits: the 16-bit travel form of
-    the logits, relu: fc1's form (codes 0 .. 127)"""
+    the logits, relu: fc1's form (codes 0 .. 127), dq: the dequantise form of out_proj and fc2 (float clamp to [-128, 127])"""
     k = C.c_float(0.0)
-    ok = lib().ita_debug_fused_check(C.c_float(float(mult)), 1 if logits else 2 if relu else 0, int(base), C.byref(k))
+    ok = lib().ita_debug_fused_check(C.c_float(float(mult)), 3 if dq else 1 if logits else 2 if relu else 0, int(base), C.byref(k))
     return bool(ok), k.value
+
+
+DQ_SITES = ("O", "fc2")    # bits 6 and 7 of the fused mask: the fused dequantise form
+
+
+def dequant_site(mult: float, dmax: int = 1 << 18):
+    """ita_debug_dequant_site: the search of the fused dequantise form, the base within dmax of ACC_BIAS -> (C, K) or None"""
+    c, k = C.c_int(0), C.c_float(0.0)
+    if not lib().ita_debug_dequant_site(C.c_float(float(mult)), int(dmax), C.byref(c), C.byref(k)):
+        return None
+    return c.value, k.value
 
 
 class Engine:
@@ -412,6 +427,28 @@ class Engine:
         c6, k6 = (C.c_int * 6)(), (C.c_float * 6)()
         _chk(lib().ita_debug_layer_fused(self._h, layer, C.byref(m), C.byref(f), c6, k6))
         return dict(fused_sites=m.value, fused=f.value >= 1, fused_relu=f.value == 2, C=list(c6), K=list(k6))
+
+    def layer_dequant(self, layer: int = 0) -> dict:
+        """ita_debug_layer_dequant: fused_dq (the whole-layer flavours run the fused dequantise form at out_proj and fc2),
+        and their C and K"""
+        f = C.c_int(0)
+        c2, k2 = (C.c_int * 2)(), (C.c_float * 2)()
+        _chk(lib().ita_debug_layer_dequant(self._h, layer, C.byref(f), c2, k2))
+        return dict(fused_dq=bool(f.value), C=list(c2), K=list(k2))
+
+    def fill_x2_planes(self, batch: int, byte: int):
+        """ita_debug_x2_planes: set every byte of the first `batch` rows of both x2 planes, padding included"""
+        _chk(lib().ita_debug_x2_planes(self._h, int(byte) & 0xff or 1, None, None, batch, None, _stream_ptr(self.device)))
+
+    def x2_planes(self, batch: int):
+        """ita_debug_x2_planes: (hi, lo) f16 tensors (batch, ld_planes): the planes the encoder handed to the folded GEMM"""
+        torch = _torch()
+        ld = C.c_int(0)
+        lib().ita_debug_x2_planes(self._h, 1, None, None, 0, C.byref(ld), None)   # (refused for batch 0; reports the stride)
+        hi = torch.empty((batch, ld.value), dtype=torch.float16, device=f"cuda:{self.device}")
+        lo = torch.empty_like(hi)
+        _chk(lib().ita_debug_x2_planes(self._h, 0, hi.data_ptr(), lo.data_ptr(), batch, None, _stream_ptr(self.device)))
+        return hi, lo
 
     def attn_kind(self, layer: int = 0) -> int:
         """ATTN_INT8 (ITAW0001 / ITAW0002 blob) or ATTN_F32 (ITAW0003: the float graph's float32 attention)"""

@@ -552,13 +552,27 @@ int ita_debug_layer_forms(ita_handle h, int layer, unsigned* fast_sites, int* st
  * multiplier outside (0, 1) or below 130 / 4e6, or a K outside [2^23, 2^24)).
  * ita_debug_fused_check: the enumeration alone on a given C; form 0: int8 codes, 1: the logits' 16-bit travel form, clamped
  * as the integer softmax clamps it, 2: fc1's ReLU form (codes 0 .. 127); *K (may be null) receives the K it used.
- * ita_debug_layer_fused: fused_sites = bits 0..5 (Q, K, V, logits, context, fc1) proven for this layer and left on by the
+ * ita_debug_layer_fused: fused_sites = bits 0..5 (Q, K, V, logits, context, fc1; 6, 7: see below) proven for this layer and left on by the
  * environment variable ITA_FUSED_SITES (a mask ANDed onto the proven sites when the weights are loaded); fused = 1 when
  * the stream kernels run the fused instantiation (bits 0..4 all set, and fast_sites == 63), 2 when the whole-layer
- * flavours run fc1's fused ReLU form as well (bit 5), else 0; C6 / K6 (may be null): the six bases and constants. */
+ * flavours run fc1's fused ReLU form as well (bit 5), else 0; C6 / K6 (may be null): the six bases and constants of bits 0..5
+ * (those of bits 6 and 7 are reachable only through ita_debug_layer_dequant). */
 int ita_debug_fused_site(float mult, int* C, float* K);
 int ita_debug_fused_check(float mult, int form, int C, float* K);
 int ita_debug_layer_fused(ita_handle h, int layer, unsigned* fused_sites, int* fused, int* C6, float* K6);
+/* The fused dequantise form of the two block outputs, out_proj and fc2 (fused_sites bits 6 and 7): t = fma(C + sum, mult, K),
+ * K = 1.5 * 2^23 - round(C mult), then t - 1.5 * 2^23, the clamp to [-128, 127] and the scale.
+ * ita_debug_fused_check form 3 is its enumeration on a given C.
+ * ita_debug_dequant_site: host only: the search with the base kept within dmax (capped at 2^18) of 0x4B400000.
+ * ita_debug_layer_dequant: fused_dq = 1 when the whole-layer flavours of this layer run the form at both sites (bits 6 and 7
+ * proven and left on, on top of fused == 2); C2 / K2 (may be null): the bases and constants of out_proj and fc2 (the
+ * default base when the form does not run). */
+int ita_debug_dequant_site(float mult, int dmax, int* C, float* K);
+int ita_debug_layer_dequant(ita_handle h, int layer, int* fused_dq, int* C2, float* K2);
+/* Test entry: the first set of f16 hi / lo planes of x2 that the encoder hands to the folded GEMM, rows [0, B) of ld_planes
+ * halves each (B within the reserved workspace).  fill != 0: set every byte of those rows, padding included, to fill & 0xff;
+ * fill == 0: copy them to the device buffers hi and lo (B * ld_planes halves each).  *ld_planes (may be null) is the row stride. */
+int ita_debug_x2_planes(ita_handle h, int fill, void* hi, void* lo, int B, int* ld_planes, void* stream);
 
 /* ---- wire format of the reference's UDP host (ita_wire.h), exported for bindings and tests ------- */
 /* frame_out: [desired_velocity, position_x, quat w, x, y, z]; returns 0, or -1 on a short packet */

@@ -1,0 +1,274 @@
+"""The fused dequantise form of out_proj and fc2 on the GPU (ita_stream_kernel<64, true, TOK, ..., FUSED = 3>): bit equality
+with the oracle under accumulator bases in bo / b2 that are not 0x4B400000.
+
+Crafted blobs, in the style of test_gpu_requant_fused.py: the seed-0 model of the default benchmark, whose eight sites all
+pass their load-time proofs, with up to 40 rows of Wo and of W2 set to zero and a wanted accumulator as the row's bias, so
+that channel's accumulator IS that value (under the fused form: C_site + that value) on every token of every frame:
+  * the two accumulators on either side of every rounding tie (k + 0.5) / m, k = -129, -128, -1, 0, 126, 127 -- the clamp's
+    two edges and zero -- and their negatives ("model": the blob's own multipliers);
+  * with power-of-two multipliers at both sites ("pow2") the ties themselves, a = (k + 0.5) / m, and a - 1, a + 1;
+  * values far beyond the clamp range, +-BIG: "pow2" goes up to the stream_range_ok bound (|a| < 2^22 and |a| m < 32000; the
+    row leaves the base no room, and a power of two needs none), "model" as far as leaves the base the room its proof uses;
+  * "refused": out_proj's multiplier is one whose search fails: the layer keeps the other forms at both sites.
+Flavours: the u8 frames with the tokenizer in front, <64, true, 1> (Engine.forward: tokens, x1, x2 taps, velocities), and
+f32 tokens, <64, true, 0> (Engine.encoder_layer).  x1 and x2 are compared with the oracle bit for bit.  The f16 hi / lo
+planes the kernel hands to the folded GEMM are read back in test_plane_rows_and_padding and, in every case, held to the
+planes ita_split_planes_kernel makes of the same x2 through the bit equality of vel, h and c (forward against Engine.tail fed
+forward's x2).  The velocities: the oracle's tail is float64-accumulated C, the GPU's an f16x3 GEMM and fast LSTM gates, so
+vel, h and c are compared with the oracle within the forward tests' bound of 2e-5, not bit for bit; what is bit for bit is
+every input of the tail (x2 and its planes), batches against each other and forward against tail.  The f32-token flavour has
+no x1 tap: its x2 is compared.  Batches: 1, 3, the CU count + 1 (the persistent workgroups' second round) and
+2 x CU count + 1 (a last frame without a successor for its tokenizer); the large batches cycle the three frames, so every
+frame of them must equal that frame run alone, which the oracle has checked."""
+import functools
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import requant_common as rc
+from conftest import REPO, golden_files
+from drone_oa_iree_vit_accelerator_amd import host, params, synth
+from test_dequant_fused_cpu import MAGIC0, differs, room
+from test_requant_fused_cpu import _k_of, proven
+
+pytestmark = pytest.mark.gpu
+f32 = np.float32
+ORACLE_ATOL = 2e-5        # vel, h, c of forward against the CPU oracle (tests/test_gpu_parity.py, tail mode 1)
+KINDS = ("model", "pow2", "refused")
+WN = {"O": ("attn0.wo", "attn0.bo"), "fc2": ("ffn0.w2", "ffn0.b2")}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def torch_cuda():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    return torch
+
+
+def _cu(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _refused_multiplier(m0):
+    """a multiplier near m0 that passes the single-rounding proof (the layer stays fused) and fails the dequantise search"""
+    rs = np.random.RandomState(21)
+    for _ in range(400):
+        m = f32(m0 * 2.0 ** rs.uniform(-0.5, 0.5))
+        if host.fast_site_ok(m) and host.dequant_site(m) is None:
+            return m
+    raise AssertionError("no refused multiplier found")
+
+
+@functools.lru_cache(maxsize=None)
+def case(kind):
+    """(tensors of the whole model, wanted accumulators per site)"""
+    fx = params.load_fixture(golden_files("vitlstm_E64_seed0_B2.npz")[0])
+    t = {**params.attention_tensors(fx, "attn0.", 0), **params.ffn_tensors(fx, "ffn0.", 0)}
+    t = {k: v.copy() for k, v in t.items()}
+    t.update(params.float_tensors(synth.float_params(0, E=64)))
+    if kind == "pow2":
+        for s in host.DQ_SITES:
+            rc.set_multiplier(t, s, rc.pow2_near(rc.multiplier_of(t, s)))
+    if kind == "refused":
+        rc.set_multiplier(t, "O", _refused_multiplier(rc.multiplier_of(t, "O")))
+    want = {}
+    for s in host.DQ_SITES:
+        m = rc.multiplier_of(t, s)
+        a = rc.tie_neighbours(m)
+        if kind == "pow2":
+            a = sorted(set(a) | {v + d for v in a for d in (-1, 1)})
+            big = min((1 << 22) - 1, int(31999.0 / float(m)))  # the accumulator and travel bounds of stream_range_ok
+        else:
+            big = min((1 << 22) - 1 - (1 << 18), int(31999.0 / float(m)))   # the base keeps its full room
+        assert big < 1 << 22 and big * float(m) > 1000.0
+        a = [v for v in a if abs(v) <= big] + [big, -big, big // 2, -(big // 2)]
+        assert len(a) <= 40
+        wn, bn = WN[s]
+        rows = rc.spread(len(a), 64)
+        t[wn][rows] = 0
+        t[bn][rows] = np.array(a, np.int32)
+        want[s] = a
+    return t, want
+
+
+def blob_of(t):
+    return params.pack_blob(t, E=64, has_tail="tail.conv_w" in t)
+
+
+def expected_dq(t):
+    """the loader's decision for the two sites, on the CPU: {site: (C, K) or None}"""
+    return {s: host.dequant_site(rc.multiplier_of(t, s), room(t[WN[s][0]], t[WN[s][1]])) for s in host.DQ_SITES}
+
+
+def check_forms(eng, t, mask=0xFF):
+    """the engine's decision against the CPU's and the exact re-computation; returns fused_dq"""
+    exp = expected_dq(t)
+    lf, ld = eng.layer_fused(), eng.layer_dequant()
+    assert lf["fused"] and lf["fused_relu"], lf           # the bench model: Q, K, V, logits, context and fc1 are proven
+    for i, s in enumerate(host.DQ_SITES):
+        on = exp[s] is not None and bool(mask >> (6 + i) & 1)
+        assert bool(lf["fused_sites"] >> (6 + i) & 1) == on, (s, lf, exp)
+    want = all(exp[s] is not None for s in host.DQ_SITES) and (mask & 0xC0) == 0xC0
+    assert ld["fused_dq"] == want, (ld, exp)
+    for i, s in enumerate(host.DQ_SITES):
+        if want:
+            m = rc.multiplier_of(t, s)
+            assert (ld["C"][i], ld["K"][i]) == exp[s] and ld["K"][i] == _k_of(m, ld["C"][i], MAGIC0), (s, ld)
+            assert differs(m, ld["C"][i], ld["K"][i]).size == 0, s
+        else:
+            assert ld["C"][i] == host.ACC_BIAS, (s, ld)   # the images keep the default base
+    return want
+
+
+@functools.lru_cache(maxsize=None)
+def reference(kind):
+    """three frames: u8 images with their inputs, three f32 token frames, and the oracle's results on both"""
+    from oracle import oracle
+    oracle.build()
+    t, _ = case(kind)
+    fr = synth.frames(77, 3)
+    rs = np.random.RandomState(9)
+    x = (rs.standard_normal((3, 128, 64)) * 1.5).astype(np.float32)
+    x[2, ::3] *= 20.0                                           # saturating rows
+
+    def layer(tok):
+        x1 = oracle.add_ln(tok, oracle.mha(tok, t), t["norm1_0.w"], t["norm1_0.b"])
+        return x1, oracle.add_ln(x1, oracle.ffn(x1, t), t["norm2_0.w"], t["norm2_0.b"])
+    ov = oracle.forward(blob_of(t), fr["img_u8"], fr["desvel"], fr["quat"])
+    return dict(fr=fr, x=x, x2_tokens=layer(x)[1], layer=layer, fwd=ov)
+
+
+def batches():
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    return [1, 3, cus + 1, 2 * cus + 1]
+
+
+def run_case(kind, mask=0xFF):
+    """every flavour and batch size of one case; returns fused_dq"""
+    import torch
+    t, want = case(kind)
+    ref = reference(kind)
+    eng = host.Engine(blob_of(t), device=0)
+    fused_dq = check_forms(eng, t, mask)
+    # the crafted accumulators are at their sites: the oracle's own accumulators on the first token frame
+    acc_o = rc.ref.mha(ref["x"][:1], t, 1, taps=True)[2]["O"]
+    assert np.isin(np.array(want["O"], np.int64), acc_o).all()
+    acc_2 = rc.ref.ffn(ref["x"][:1], t, taps=True)[2]["fc2"]
+    assert np.isin(np.array(want["fc2"], np.int64), acc_2).all()
+    fr, x = ref["fr"], ref["x"]
+    tok3 = x1_3 = x2_3 = None
+    for B in batches():
+        idx = np.arange(B) % 3
+        img, dv, qt = _cu(fr["img_u8"][idx]), _cu(fr["desvel"][idx]), _cu(fr["quat"][idx])
+        vel, (h, c), tp = eng.forward(img, dv, qt, taps=True)
+        tok, x1, x2 = (tp[k].cpu().numpy() for k in ("tokens", "x1", "x2"))
+        if B == 1:
+            o1, o2 = ref["layer"](tok)
+            np.testing.assert_array_equal(x1, o1, err_msg=f"{kind} u8 x1 B=1")
+            np.testing.assert_array_equal(x2, o2, err_msg=f"{kind} u8 x2 B=1")
+        elif B == 3:
+            o1, o2 = ref["layer"](tok)
+            np.testing.assert_array_equal(x1, o1, err_msg=f"{kind} u8 x1 B=3")
+            np.testing.assert_array_equal(x2, o2, err_msg=f"{kind} u8 x2 B=3")
+            for got, o, name in ((vel, ref["fwd"][0], "vel"), (h, ref["fwd"][1], "h"), (c, ref["fwd"][2], "c")):
+                np.testing.assert_allclose(got.cpu().numpy(), o, atol=ORACLE_ATOL, rtol=0, err_msg=f"{kind} {name}")
+            tok3, x1_3, x2_3, vel3, h3, c3 = tok, x1, x2, vel, h, c
+        else:   # every frame of a large batch equals the same frame of the batch of three
+            assert np.array_equal(tok, tok3[idx]) and np.array_equal(x1, x1_3[idx]), f"{kind} u8 B={B}"
+            bad = np.flatnonzero((x2 != x2_3[idx]).any(axis=(1, 2)))
+            assert bad.size == 0, f"{kind} u8 x2 B={B}: frames {bad[:8]}"
+            li = torch.from_numpy(idx).cuda()
+            assert torch.equal(vel, vel3[li]) and torch.equal(h, h3[:, li]) and torch.equal(c, c3[:, li]), f"{kind} vel B={B}"
+        # the planes: the same x2 split by ita_split_planes_kernel gives the same vel, h, c bit for bit
+        vt, (ht, ct) = eng.tail(tp["x2"], dv, qt)
+        assert torch.equal(vt, vel) and torch.equal(ht, h) and torch.equal(ct, c), f"{kind} planes B={B}"
+        # without taps (y == nullptr: the planes alone)
+        vn, (hn, cn) = eng.forward(img, dv, qt)
+        assert torch.equal(vn, vel) and torch.equal(hn, h) and torch.equal(cn, c), f"{kind} no taps B={B}"
+        # f32 tokens, <64, true, 0>
+        y = eng.encoder_layer(_cu(x[idx])).cpu().numpy()
+        bad = np.flatnonzero((y != ref["x2_tokens"][idx]).any(axis=(1, 2)))
+        assert bad.size == 0, f"{kind} f32 tokens B={B}: frames {bad[:8]}"
+    eng.close()
+    return fused_dq
+
+
+def test_case_selection():
+    """the model and pow2 cases run the form under the CPU's decision, out_proj's base off the default in the model case;
+    the refused case does not"""
+    for kind in KINDS:
+        t, want = case(kind)
+        exp = expected_dq(t)
+        for s in host.DQ_SITES:
+            m = rc.multiplier_of(t, s)
+            assert host.fast_site_ok(m) or s == "fc2", (kind, s)
+            if exp[s] is not None:
+                assert differs(m, *exp[s]).size == 0
+        print(kind, {s: (None if exp[s] is None else exp[s][0] - host.ACC_BIAS) for s in exp},
+              {s: (len(want[s]), max(want[s])) for s in want})
+        if kind == "refused":
+            assert exp["O"] is None
+        else:
+            assert all(v is not None for v in exp.values()), (kind, exp)
+    exp = expected_dq(case("model")[0])
+    assert any(exp[s][0] != host.ACC_BIAS for s in host.DQ_SITES)
+    assert proven(rc.multiplier_of(case("model")[0], "fc1"), relu=True) is not None
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_crafted(kind):
+    assert run_case(kind) == (kind != "refused")
+
+
+def test_plane_rows_and_padding():
+    """the f16 hi / lo planes the E = 64 encoder writes for the folded GEMM, read back (ita_debug_x2_planes): every half of
+    every row of both planes is the f16 split of the x2 tap, bit for bit, at the four batch sizes, with and without the f32
+    rows beside them; the row padding up to ld_planes, filled with a byte pattern before the launch, stays unwritten"""
+    import torch
+    t, _ = case("model")
+    fr = reference("model")["fr"]
+    bs = batches()
+    eng = host.Engine(blob_of(t), device=0, reserve=max(bs))
+    n = 128 * 64
+    for B in bs:
+        idx = np.arange(B) % 3
+        img, dv, qt = _cu(fr["img_u8"][idx]), _cu(fr["desvel"][idx]), _cu(fr["quat"][idx])
+        for taps in (True, False):
+            eng.fill_x2_planes(B, 0xA5)
+            out = eng.forward(img, dv, qt, taps=taps)
+            if taps:
+                x2 = out[2]["x2"].reshape(B, n).clone()
+            hi, lo = eng.x2_planes(B)
+            assert hi.shape[1] > n, hi.shape
+            w_hi = x2.half()
+            w_lo = (x2 - w_hi.float()).half()
+            for got, want, name in ((hi, w_hi, "hi"), (lo, w_lo, "lo")):
+                bad = (got[:, :n].view(torch.int16) != want.view(torch.int16)).nonzero()
+                assert bad.numel() == 0, f"{name} plane, B={B}, taps={taps}: first (frame, half) {bad[0].tolist()} of {bad.shape[0]}"
+                pad = got[:, n:].contiguous().view(torch.uint8)
+                assert bool((pad == 0xA5).all()), f"{name} plane padding written, B={B}, taps={taps}"
+    eng.close()
+
+
+def _fresh(env_mask, code):
+    env = dict(os.environ, ITA_FUSED_SITES=env_mask, PYTHONPATH=os.pathsep.join([os.path.join(REPO, "tests"), REPO]))
+    r = subprocess.run([sys.executable, "-c", code], cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "switch ok" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+
+
+def test_switch_masks_the_two_sites_off():
+    """ITA_FUSED_SITES=63 in a fresh process: the two new bits are off, the layer runs the FUSED == 2 instantiation, and the
+    results are the oracle's, as with them on"""
+    _fresh("63", "import torch; assert torch.cuda.is_available(); import test_gpu_dequant_fused as t; "
+                 "assert t.run_case('model', mask=63) is False; print('switch ok')")
+
+
+def test_switch_cannot_turn_a_refused_site_on():
+    """ITA_FUSED_SITES=255 on the refused case: the mask is ANDed onto the proven bits"""
+    _fresh("255", "import torch; assert torch.cuda.is_available(); import test_gpu_dequant_fused as t; "
+                  "assert t.run_case('refused', mask=255) is False; print('switch ok')")

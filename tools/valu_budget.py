@@ -5,16 +5,18 @@ function (the loop body; inline-asm requantisation blocks are expanded in the as
 Counts are per WAVE and frame; a frame is 8 waves.  usage: python tools/valu_budget.py [extra hipcc flags]
 The single-rounding permission of the requantisation sites is a template argument: the default counts the FAST instantiation
 (all six sites of the layer proven at load time), --exact the two-rounding one, --fused the one-fma one (Q, K, V, logits and
-context proven for per-site accumulator bases), --fused-relu the one with fc1's fused ReLU form as well; -DITA_FORCE_SITES=<mask> fixes the fast form per site.  The last line is the
+context proven for per-site accumulator bases), --fused-relu the one with fc1's fused ReLU form as well, --fused-dq the one
+with the fused dequantise form of out_proj and fc2 on top of that; -DITA_FORCE_SITES=<mask> fixes the fast form per site.  The last line is the
 kernel's register and scratch figures from the code object's metadata."""
 import collections, os, re, subprocess, sys, tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(REPO, "drone-oa-iree-vit-accelerator_amd", "csrc", "ita_plugin.hip")
 # <E = 64, FFN, TOK = 1, no stamps, f32 I/O, FAST, FUSED>: the bench blob runs the fused one
-FLAGS = ("--exact", "--fused", "--fused-relu")
+FLAGS = ("--exact", "--fused", "--fused-relu", "--fused-dq")
 KERNEL = "_Z17ita_stream_kernelILi64ELb1ELi1ELb0ELb0ELb%dELi%dEEv13ItaStreamArgs" % (
-    0 if "--exact" in sys.argv else 1, 2 if "--fused-relu" in sys.argv else 1 if "--fused" in sys.argv else 0)
+    0 if "--exact" in sys.argv else 1,
+    3 if "--fused-dq" in sys.argv else 2 if "--fused-relu" in sys.argv else 1 if "--fused" in sys.argv else 0)
 CLASSES = [
     ("requantise: unbias + scale + round (v_pk_add/mul/fma_f32, v_pk_mov)", r"^v_pk_(add|mul|fma)_f32|^v_pk_mov"),
     ("requantise: float clamp (v_med3_f32)", r"^v_med3_f32"),
