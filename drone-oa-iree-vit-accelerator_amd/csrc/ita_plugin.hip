@@ -28,6 +28,7 @@
 #include "ita_stream_kernel.h"
 #include "ita_long_attn_kernel.h"
 #include "ita_long_stats_kernel.h"
+#include "ita_long_hist_kernel.h"
 #include "ita_long_prop_kernel.h"
 #include "ita_ffn_f32_kernel.h"
 #include "ita_attn_f32_kernel.h"
@@ -1074,6 +1075,42 @@ int ita_mha_long_int8_stats(ita_handle h, int layer, const float* x, int batch, 
     constexpr bool FAST = decltype(fst)::value;
     if (int rc = launch<ita_long_proj_kernel<FAST, E, true>, ItaStreamLds<E, false, false>::TOTAL>(proj_grid, dim3(512), s, a)) return rc;
     return launch<ita_long_stats_kernel<FAST>, ItaLongStatsLds::TOTAL>(grid, dim3(512), s, sa);
+  };
+  return with_E(h->w.hdr.E, [&](auto e) { return fast ? run(e, std::true_type{}) : run(e, std::false_type{}); });
+}
+
+// The production projection launch (f32 form), then ita_long_hist_kernel over its workspace (ita_long_hist_kernel.h): two
+// sweeps, no y.  The kernel ADDS into the outputs: they are set to zero (the range to INT_MAX, INT_MIN) on the stream first,
+// by a kernel (inside a stream capture the call is kernel nodes only)
+int ita_mha_long_int8_hist(ita_handle h, int layer, const float* x, int batch, int seq_len, const ita_mha_long_hist* hist,
+                           void* stream) {
+  if (int rc = check(h, batch)) return rc;
+  if (!x || !hist || layer < 0 || layer >= h->w.hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
+  const Layer& L = h->w.layers[layer];
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = check_long(L, batch, seq_len)) return rc;
+  if (!hist->logits && !hist->shifts && !hist->probs && !hist->logits_out && !hist->acc_range)
+    return fail(ITA_ERR_INVALID_ARG, "ita_mha_long_int8_hist: all five outputs are null");
+  if (misaligned(hist->logits, 8) || misaligned(hist->shifts, 8) || misaligned(hist->probs, 8) || misaligned(hist->logits_out, 8) ||
+      misaligned(hist->acc_range, 4))
+    return fail(ITA_ERR_INVALID_ARG, "logits, shifts, probs and logits_out must be 8-byte aligned, acc_range 4-byte aligned");
+  const size_t ntile = (size_t)batch * (seq_len / 128);
+  if (int rc = ensure_long_ws(h, long_int8_ws(ntile), s)) return rc;
+  ItaLongArgs a = long_args(h, L, ntile, batch, seq_len);
+  a.x = x;
+  ItaLongHistArgs ha{};
+  ha.qfrag = a.qfrag; ha.kimg = a.kimg; ha.ml = a.ml; ha.B = batch; ha.S = seq_len;
+  ha.logits = (unsigned long long*)hist->logits; ha.shifts = (unsigned long long*)hist->shifts;
+  ha.probs = (unsigned long long*)hist->probs; ha.logits_out = (unsigned long long*)hist->logits_out;
+  ha.acc_range = hist->acc_range;
+  if (int rc = launch<ita_long_hist_zero_kernel>(dim3(batch), dim3(256), s, ha)) return rc;
+  const bool fast = L.fast_sites == ITA_SITES_ALL;
+  const dim3 proj_grid(ntile < (size_t)h->num_cus ? (int)ntile : h->num_cus), grid(seq_len / 128, batch);
+  auto run = [&](auto e, auto fst) {
+    constexpr int E = decltype(e)::value;
+    constexpr bool FAST = decltype(fst)::value;
+    if (int rc = launch<ita_long_proj_kernel<FAST, E, true>, ItaStreamLds<E, false, false>::TOTAL>(proj_grid, dim3(512), s, a)) return rc;
+    return launch<ita_long_hist_kernel<FAST>, ItaLongHistLds::TOTAL>(grid, dim3(512), s, ha);
   };
   return with_E(h->w.hdr.E, [&](auto e) { return fast ? run(e, std::true_type{}) : run(e, std::false_type{}); });
 }

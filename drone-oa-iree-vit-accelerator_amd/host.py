@@ -34,7 +34,7 @@ HEAD_TIMEOUT = 1
 
 EXPORTED_SYMBOLS = (
     "ita_abi_version", "ita_create", "ita_destroy", "ita_load_weights", "ita_validate_blob", "ita_reserve", "ita_get_dims",
-    "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_mha_long_int8", "ita_mha_long_int8_taps", "ita_mha_long_int8_stats", "ita_mha_long_int8_propagate", "ita_encoder_layer_long", "ita_ffn_int8", "ita_ffn_int8_taps",
+    "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_mha_long_int8", "ita_mha_long_int8_taps", "ita_mha_long_int8_stats", "ita_mha_long_int8_hist", "ita_mha_long_int8_propagate", "ita_encoder_layer_long", "ita_ffn_int8", "ita_ffn_int8_taps",
     "ita_ffn_f32", "ita_get_ffn_kind", "ita_mha_f32", "ita_get_attn_kind", "ita_mha_long_f32", "ita_mha_long_f32_taps", "ita_mha_long_f32_stats", "ita_mha_long_f32_propagate", "ita_encoder_layer_long_f32",
     "ita_encoder_layer", "ita_tokenizer", "ita_fusion_tail", "ita_vitlstm_forward", "ita_bind_dispatch",
     "ita_profile_begin", "ita_profile_begin_sampled", "ita_profile_end", "ita_set_tail_mode", "ita_debug_encoder_stamps",
@@ -106,6 +106,14 @@ class _MhaLongStats(C.Structure):     # ita_mha_long_stats
 
 
 LONG_STATS = ("row_max", "row_sum", "row_mass", "row_nnz", "col_mass", "col_nnz")
+
+
+class _MhaLongHist(C.Structure):      # ita_mha_long_hist
+    _fields_ = [(n, C.c_void_p) for n in ("logits", "shifts", "probs", "logits_out", "acc_range")]
+
+
+LONG_HIST = ("logits", "logits_out", "acc_range", "shifts", "probs")      # the order of attention_hist_ref.NAMES
+LONG_HIST_STAGES = ("x_q", "Q", "K", "V", "ctx", "out_q")
 LONG_MAX_WEIGHT_ROWS = 64      # ita_mha_long_int8_propagate: n_w in [1, 64]
 ROLLOUT_QMAX = 2097151         # attention rollout: a vector is quantised to 21 bits, three base-128 digits
 ROLLOUT_CHUNK = LONG_MAX_WEIGHT_ROWS // 3      # vectors per ita_mha_long_int8_propagate call
@@ -201,6 +209,7 @@ def lib():
         L.ita_mha_long_int8.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_int8_taps.argtypes = [vp, i, vp, vp, i, i, C.POINTER(_MhaLongTaps), vp]
         L.ita_mha_long_int8_stats.argtypes = [vp, i, vp, i, i, C.POINTER(_MhaLongStats), vp]
+        L.ita_mha_long_int8_hist.argtypes = [vp, i, vp, i, i, C.POINTER(_MhaLongHist), vp]
         L.ita_mha_long_int8_propagate.argtypes = [vp, i, vp, i, i, vp, i, vp, vp]
         L.ita_encoder_layer_long.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_f32.argtypes = [vp, i, vp, vp, i, i, vp]
@@ -846,6 +855,44 @@ class Engine:
         attention_received_long of `layer` -> (N, tok_h, tok_w) int32"""
         y = self._tokens_below(frames, int(tok_h), int(tok_w), layer, depth_scale)
         return self.attention_received_long(y, int(layer)).reshape(y.shape[0], int(tok_h), int(tok_w))
+
+    def _long_hist(self, x, layer, want):
+        """ita_mha_long_int8_hist asking for the outputs named in `want` only -> dict of those"""
+        torch = _torch()
+        x = self._long_f32(x)
+        B, S = x.shape[0], x.shape[1]
+        unknown = [k for k in want if k not in LONG_HIST]
+        if unknown:
+            raise ITAError(f"no such long histogram: {unknown}")
+        spec = dict(logits=((B, 256), torch.int64), logits_out=((B, 2), torch.int64), acc_range=((B, 2), torch.int32),
+                    shifts=((B, 256), torch.int64), probs=((B, 256), torch.int64))
+        t = {k: torch.empty(spec[k][0], dtype=spec[k][1], device=x.device) for k in LONG_HIST if k in want}
+        st = _MhaLongHist(**{k: v.data_ptr() for k, v in t.items()})
+        _chk(lib().ita_mha_long_int8_hist(self._h, layer, x.data_ptr(), B, S, C.byref(st), _stream_ptr(self.device)))
+        return t
+
+    def attention_histograms_long(self, x, layer: int = 0, stages: bool = False):
+        """histograms of the whole S x S matrix of a long sequence in front of and behind the integer softmax, which is
+        never held (ita_mha_long_int8_hist): x (B,S,E) f32 -> dict of logits (B,256) int64 (bin c + 128 counts the int8
+        logit c), logits_out (B,2) int64 (raw logits below -128 and above 127: what the clamp changed), acc_range (B,2)
+        int32 (minimum and maximum of the Q K^T accumulators), shifts (B,256) int64 (row maximum - logit; the softmax
+        resolves 0 .. 15) and probs (B,256) int64 (the uint8 probabilities).  Equal to attention_hist_ref.hist.  With
+        stages=True also (B,256) int64 histograms (bin c + 128) of the int8 stage tensors x_q, Q, K, V, ctx and out_q of
+        mha_long_taps, counted with torch."""
+        torch = _torch()
+        out = self._long_hist(x, layer, LONG_HIST)
+        if stages:
+            _, taps = self._long_taps(x, (), layer, LONG_HIST_STAGES)
+            for k in LONG_HIST_STAGES:
+                v = taps[k].reshape(taps[k].shape[0], -1).to(torch.int64) + 128
+                out[k] = torch.stack([torch.bincount(r, minlength=256) for r in v])
+        return out
+
+    def attention_histograms_frames_long(self, frames, tok_h: int, tok_w: int, layer: int = 0, depth_scale: Optional[float] = None):
+        """the histograms of attention_histograms_long for camera frames: tokenize_long, the encoder layers below `layer`,
+        then attention_histograms_long of `layer` -> its dict"""
+        y = self._tokens_below(frames, int(tok_h), int(tok_w), layer, depth_scale)
+        return self.attention_histograms_long(y, int(layer))
 
     def attention_propagate_long(self, x, w, layer: int = 0):
         """weighted column sums of the whole S x S integer-softmax matrix of a long sequence, which is never held

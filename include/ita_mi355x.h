@@ -53,7 +53,7 @@ int ita_destroy(ita_handle h);
  * A layer with H > 1 runs on the block kernels (ita_mha_kernel<E, H>, then the FFN block) behind the stand-alone tokenizer;
  * every entry point below serves it except those that need the one-head stream kernel, which return
  * ITA_ERR_UNSUPPORTED before any launch: ita_mha_q8, ita_mha_long_q8, ita_mha_long_int8, ita_mha_long_int8_taps,
- * ita_mha_long_int8_stats, ita_mha_long_int8_propagate, ita_encoder_layer_long, ita_debug_encoder_stamps, ita_vitlstm_forward_slots (and ita_mha_long_f32 / ita_mha_long_f32_stats / ita_mha_long_f32_propagate / ita_encoder_layer_long_f32, which take
+ * ita_mha_long_int8_stats, ita_mha_long_int8_hist, ita_mha_long_int8_propagate, ita_encoder_layer_long, ita_debug_encoder_stamps, ita_vitlstm_forward_slots (and ita_mha_long_f32 / ita_mha_long_f32_stats / ita_mha_long_f32_propagate / ita_encoder_layer_long_f32, which take
  * float layers only).
  * The reference pre-loads weights into the accelerator out of band
  * (docs/HOW-TO-run-the-full-project-workflow.md:55); this is that step. */
@@ -150,6 +150,29 @@ typedef struct ita_mha_long_stats {
 } ita_mha_long_stats;
 int ita_mha_long_int8_stats(ita_handle h, int layer, const float* x_dev, int batch, int seq_len,
                             const ita_mha_long_stats* stats, void* stream);
+/* Histograms of the WHOLE seq_len x seq_len matrix of ita_mha_long_int8 (H = 1) in front of and behind its integer softmax,
+ * which is never held: the health of the quantisation, where the statistics above describe the attention map.  x (B,
+ * seq_len, E) f32 is read only, there is no y.  With acc the int32 Q K^T accumulator (it has no bias term), raw = rne(f32(acc)
+ * * f32(ml)), logits = clamp(raw, -128, 127) and p the u8 probabilities, per frame (device pointers, any may be NULL):
+ *   logits (B, 256) s64: bin c + 128 = #{(i, j) : logits[i, j] = c};  logits_out (B, 2) s64: #{raw < -128}, #{raw > 127}, what
+ *   the clamp changed;  acc_range (B, 2) s32: minimum and maximum of acc, that is, which ml would fit;  shifts (B, 256) s64:
+ *   bin s = #{(i, j) : max_j' logits[i, j'] - logits[i, j] = s} (the softmax resolves 0 .. 15 only);  probs (B, 256) s64: bin
+ *   v = #{(i, j) : p[i, j] = v}.  Every histogram of a frame sums to seq_len^2 (2^32 at seq_len = 65 536: no 32-bit word holds a frame's
+ *   total).  Equal, bit for bit, to attention_hist_ref.py.
+ * The production projection launch, then one kernel of two Q K^T sweeps (csrc/ita_long_hist_kernel.h) that counts in LDS
+ * and adds to the outputs with integer atomics, so the result does not depend on the order of arrival: the same bytes on every
+ * call.  The outputs are set to zero on `stream` first, by a small kernel: a captured call is kernel nodes only.
+ * Refusals, all before any launch, outputs untouched: whatever ita_mha_long_int8 refuses, with the same status and words (a
+ * float-attention layer, H > 1, a shape outside the limits); ITA_ERR_INVALID_ARG for a NULL x_dev or hist, a bad layer, all
+ * five pointers NULL, an s64 output off an 8-byte boundary or acc_range off a 4-byte boundary.  Workspace of
+ * ita_mha_long_q8: once it holds the call there is no host synchronisation and no allocation, the call may be captured. */
+typedef struct ita_mha_long_hist {
+  int64_t *logits, *shifts, *probs;   /* (batch, 256) each, may be NULL */
+  int64_t *logits_out;                /* (batch, 2), may be NULL */
+  int32_t *acc_range;                 /* (batch, 2), may be NULL */
+} ita_mha_long_hist;
+int ita_mha_long_int8_hist(ita_handle h, int layer, const float* x_dev, int batch, int seq_len,
+                           const ita_mha_long_hist* hist, void* stream);
 /* Weighted column sums of the WHOLE seq_len x seq_len probability matrix of ita_mha_long_int8 (H = 1), which is never held:
  *     out[b, r, j] = sum_i w[b, r, i] * p[b, i, j]      w s8 (B, n_w, seq_len), out s32 (B, n_w, seq_len), 1 <= n_w <= 64
  * with p[b, i, j] the u8 probability of query i for key j, the bits of ita_mha_long_taps' probs.  col_mass of
