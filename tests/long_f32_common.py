@@ -1,5 +1,5 @@
 """Shared by the long float attention tests (test_long_f32_abi.py, test_gpu_long_f32.py): the ITAW0003 blobs, the inputs,
-the float64 restatement (attn64 of test_gpu_float_graph.py over any S and E, and the whole float layer) and torch's own
+the float64 restatement (attn64 of float_graph_common.py over any S and E, and the whole float layer) and torch's own
 f32 result on the CPU, whose error against float64 sets the tests' bound.  Everything cached here is read-only."""
 import functools
 
@@ -21,7 +21,7 @@ def case(E):
 
 
 def ln_like(B, S, E, seed):
-    """LayerNorm-like activations (_ln_like of test_gpu_float_graph.py): per token zero mean, unit variance, mild affine"""
+    """LayerNorm-like activations (ln_like of float_graph_common.py): per token zero mean, unit variance, mild affine"""
     rs = np.random.RandomState(seed)
     x = rs.standard_normal((B, S, E))
     x = (x - x.mean(-1, keepdims=True)) / x.std(-1, keepdims=True)

@@ -1,7 +1,7 @@
 """Shared by test_long_hist_cpu.py, test_gpu_long_hist.py and test_gpu_long_hist_limits.py: the fixtures, shapes and inputs of
 the long-sequence histogram tests (ita_mha_long_int8_hist) and the definition's results on them, computed once.  CPU only.
 
-Fixtures: the four forms of test_gpu_long_layer.py with its _case / _long_f32 inputs -- exact and FAST at E = 64 and at
+Fixtures: the four forms of test_gpu_long_layer.py with long_cases' long_case / long_f32 inputs -- exact and FAST at E = 64 and at
 E = 128, the FAST E = 128 blob on both layers.  Shapes (S, B): (128, 3) one key tile; (256, 2) / (384, 2) even and odd tile
 counts, so the ring-slot parity differs between the two sweeps; B > 1 the frame strides; (1024, 1) a longer sum."""
 import functools
@@ -10,7 +10,7 @@ import numpy as np
 
 from drone_oa_iree_vit_accelerator_amd import attention_hist_ref as ahr
 import softmax_clamp_common as scc
-from test_gpu_long_layer import _case, _long_f32
+from long_cases import long_case, long_f32
 
 FIXTURES = (("blocks_E64_seed2_B1", 0), ("vitlstm_E64_seed0_B2", 0), ("blocks_E128_seed0_B1", 0),
             ("vit2l_us_E128_s1_B2", 0), ("vit2l_us_E128_s1_B2", 1))
@@ -33,8 +33,9 @@ def _frozen(x, h):
 @functools.lru_cache(maxsize=None)
 def expected(name, l, S, B):
     """(x (B, S, E) f32, attention_hist_ref.hist of it) of one case; read-only"""
-    E, _, t, _, _ = _case(name)
-    x = _long_f32(S + B, B, S, E, t, l)
+    case = long_case(name)
+    E, t = case.E, case.t
+    x = long_f32(S + B, B, S, E, t, l)
     return _frozen(x, ahr.hist(x, t, l))
 
 

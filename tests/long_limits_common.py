@@ -357,13 +357,14 @@ INT8_VOCAB = (512, 256, 5)                      # V, singles, seed
 
 
 def int8_vocab_frame(name, l, S):
-    """(x (1, S, E) f32, reps, cls, counts): the tokens test_gpu_long_layer._long_f32(seed, 1, V, E, t, l) of fixture
+    """(x (1, S, E) f32, reps, cls, counts): the tokens long_cases.long_f32(seed, 1, V, E, t, l) of fixture
     `name` at the positions of vocabulary(S, *INT8_VOCAB)"""
-    from test_gpu_long_layer import _case, _long_f32
+    from long_cases import long_case, long_f32
     V, singles, seed = INT8_VOCAB
-    E, _, t, _, _ = _case(name)
+    case = long_case(name)
+    E, t = case.E, case.t
     idx, reps, cls, counts = vocabulary(S, V, singles, seed)
-    return np.ascontiguousarray(_long_f32(seed, 1, V, E, t, l)[:, idx]), reps, cls, counts
+    return np.ascontiguousarray(long_f32(seed, 1, V, E, t, l)[:, idx]), reps, cls, counts
 
 
 @functools.lru_cache(maxsize=None)
@@ -386,10 +387,10 @@ def int8_vocab_ref(name, l, S=65536):
     statistics of the frame in the class form, from the representatives among those rows).  About two minutes of numpy
     at S = 65536"""
     import long_taps_common as itc
-    from test_gpu_long_layer import _case
+    from long_cases import long_case
     x, reps, cls, counts = int8_vocab_frame(name, l, S)
     rows, at = int8_vocab_rows(S)
-    taps = dict(zip(("logits", "probs", "ctx", "out_q"), itc.mha_rows(x, _case(name)[2], list(rows), l)))
+    taps = dict(zip(("logits", "probs", "ctx", "out_q"), itc.mha_rows(x, long_case(name).t, list(rows), l)))
     _frozen(x, *taps.values())
     return x, rows, taps, class_stats_int8_from({k: taps[k][:, at] for k in ("logits", "probs")}, cls, counts)
 

@@ -12,9 +12,8 @@ import functools
 import numpy as np
 
 from drone_oa_iree_vit_accelerator_amd import attention_propagate_ref as apr
-from drone_oa_iree_vit_accelerator_amd import params
 import long_taps_common as ltc
-from test_gpu_long_taps import _case, _tokens
+from long_cases import long_case, tokens
 
 FIXTURES = ("vitlstm_E64_seed0_B2", "blocks_E128_seed0_B1")
 CRAFTED = ("fast", "exact")
@@ -31,8 +30,8 @@ def blob_case(name):
     if name in CRAFTED:
         E, t, _ = ltc.crafted(name)
         return E, t, ltc.blob(name)
-    E, _, t, blob = _case(name)
-    return E, t, blob
+    c = long_case(name)
+    return c.E, c.t, c.blob
 
 
 def one_hot(S, token, value=1):
@@ -68,7 +67,7 @@ def frames(name, S, B):
     if name in CRAFTED:
         rows = np.tile(ltc.fixture()["x256"][:B], (1, (S + 255) // 256))[:, :S]
         return ltc.frames_for(name, rows)
-    return _tokens(S + B, B, S, E, t)
+    return tokens(S + B, B, S, E, t)
 
 
 @functools.lru_cache(maxsize=None)
@@ -80,18 +79,3 @@ def expected(name, S):
     for a in (x, w, want):
         a.setflags(write=False)
     return x, w, want
-
-
-@functools.lru_cache(maxsize=None)
-def rollout_case(name):
-    """(E, num_layers, block tensors, float parameters, blob) of a rollout fixture; read-only"""
-    from conftest import golden_files
-    from drone_oa_iree_vit_accelerator_amd import synth
-    d = params.load_fixture(golden_files(name + ".npz")[0])
-    E, nl = int(d["meta.E"]), int(d["meta.num_layers"]) if "meta.num_layers" in d else 1
-    fp = synth.float_params(int(d["meta.seed"]), E=E, num_layers=nl, tail=(E == 64))
-    t = {}
-    for l in range(nl):
-        t.update(params.attention_tensors(d, f"attn{l}.", l))
-        t.update(params.ffn_tensors(d, f"ffn{l}.", l))
-    return E, nl, t, fp, params.blob_from_record(d, fp, E=E, num_layers=nl)

@@ -22,6 +22,7 @@ f32 = np.float32
 ATTN_SITES = ("Q", "K", "V", "L", "C", "O")          # bit order of the engine's fast_sites mask
 FFN_SITES = ("fc1", "fc2")
 SITES = ATTN_SITES + FFN_SITES
+MHA_TAPS = ("x_q", "Q", "K", "V", "logits", "probs", "ctx", "out_q")
 LINEAR = {"Q": ("attn0.wq", "attn0.bq"), "K": ("attn0.wk", "attn0.bk"), "V": ("attn0.wv", "attn0.bv"),
           "O": ("attn0.wo", "attn0.bo"), "fc1": ("ffn0.w1", "ffn0.b1"), "fc2": ("ffn0.w2", "ffn0.b2")}
 SCAL = {"Q": ("attn0.scal", ref.MQ), "K": ("attn0.scal", ref.MK), "V": ("attn0.scal", ref.MV), "L": ("attn0.scal", ref.ML),

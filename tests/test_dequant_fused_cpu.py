@@ -13,48 +13,10 @@ import numpy as np
 import requant_common as rc
 from conftest import golden_files
 from drone_oa_iree_vit_accelerator_amd import host, params
-from test_requant_fused_cpu import _amax, _cval, _k_of, _ms, candidates
+from requant_fused_common import DMAX, MAGIC0, amax, candidates, cval, dequant_differs, fma32, in_range, k_of, room
 
 f32 = np.float32
-MAGIC0 = 12582912          # 1.5 * 2^23
-DMAX = 1 << 18
 BENCH = "vitlstm_E64_seed0_B2"
-
-
-def fma32(x, m, K):
-    """fl32(x * m + K) for an int64 array x of 24-bit integers, a float32 m in (0, 1) and an integer K, as float32"""
-    M, s = _ms(m)
-    assert 24 <= s <= 39 and float(K) == int(K)
-    N = x.astype(np.int64) * M + (int(K) << s)
-    q, rem, half = N >> s, N & ((1 << s) - 1), 1 << (s - 1)
-    t = q + (rem > half) + ((rem == half) & ((q & 1) == 1))
-    assert t.min() >= 1 << 23 and t.max() < 1 << 24          # ulp 1: rounding to an integer IS the fma's rounding
-    return t.astype(np.float32)
-
-
-def fused_codes(m, C, K, a):
-    t = fma32(_cval(C) + a, m, K)
-    r = t - f32(MAGIC0)                                      # exact: both are integers below 2^24
-    return np.clip(r, f32(-128.0), f32(127.0)).astype(np.int64)
-
-
-def ref_codes(m, a):
-    return np.clip(np.rint(a.astype(np.float32) * f32(m)), -128, 127).astype(np.int64)
-
-
-def differs(m, C, K):
-    a = np.arange(-_amax(m), _amax(m) + 1, dtype=np.int64)
-    return a[fused_codes(m, C, K, a) != ref_codes(m, a)]
-
-
-def in_range(m):
-    return 0 < float(m) < 1 and 130.0 / float(f32(m)) <= 4.0e6
-
-
-def room(w, b):
-    """how far the base may move: the worst row of sum |w| * 128 + |b| against 2^22 (prove_fused)"""
-    worst = int((np.abs(w.astype(np.int64)).sum(axis=1) * 128 + np.abs(b.astype(np.int64))).max())
-    return (1 << 22) - 1 - worst
 
 
 def fixture_sites():
@@ -79,11 +41,11 @@ def test_fma32_is_fraction_arithmetic():
     for m in (f32(0.0013524714158847928), f32(2.0 ** -7), f32(0.0047836629673838615), f32(3.4e-5)):
         fm = Fraction(float(m))
         for C in (host.ACC_BIAS, host.ACC_BIAS - 247716, host.ACC_BIAS + 1):
-            K = _k_of(m, C, MAGIC0)
-            a = np.array(sorted(set(rc.tie_neighbours(m)) | set(int(v) for v in rs.randint(-_amax(m), _amax(m), 40))), np.int64)
-            t = fma32(_cval(C) + a, m, K)
+            K = k_of(m, C, MAGIC0)
+            a = np.array(sorted(set(rc.tie_neighbours(m)) | set(int(v) for v in rs.randint(-amax(m), amax(m), 40))), np.int64)
+            t = fma32(cval(C) + a, m, K)
             for ai, ti in zip(a, t):
-                assert int(ti) == round(Fraction(_cval(C) + int(ai)) * fm + K), (m, C, ai)   # half-even on the result
+                assert int(ti) == round(Fraction(cval(C) + int(ai)) * fm + K), (m, C, ai)   # half-even on the result
 
 
 def test_fixture_sites_accepted_equal_refused_differ():
@@ -100,17 +62,17 @@ def test_fixture_sites_accepted_equal_refused_differ():
         if got is not None:
             C, K = got
             assert abs(C - host.ACC_BIAS) <= cap, (name, C, dmax)            # the base leaves the worst row its room below 2^22
-            assert K == int(K) and (1 << 23) <= K < (1 << 24) and K == _k_of(m, C, MAGIC0), (name, C, K)
+            assert K == int(K) and (1 << 23) <= K < (1 << 24) and K == k_of(m, C, MAGIC0), (name, C, K)
             assert C == next(c for c in candidates(m, cap) if host.fused_check(m, c, dq=True)[0]), name
-            bad = differs(m, C, K)
+            bad = dequant_differs(m, C, K)
             assert bad.size == 0, (name, m, C, K, bad[:4])
             n_ok += 1
         else:
             # every candidate of the search was refused: each has an accumulator on which the fused form differs
             for c in candidates(m, cap):
                 ok, k = host.fused_check(m, c, dq=True)
-                assert not ok and k == _k_of(m, c, MAGIC0), (name, c)
-                assert differs(m, c, k).size >= 1, (name, c)
+                assert not ok and k == k_of(m, c, MAGIC0), (name, c)
+                assert dequant_differs(m, c, k).size >= 1, (name, c)
             n_ref += 1
     print(f"{len(sites)} out_proj / fc2 sites of the fixtures: {n_ok} accepted, {n_ref} refused, {n_range} outside the multiplier range")
     assert n_ok >= 2
@@ -124,8 +86,8 @@ def test_enumeration_decides_every_candidate_exactly():
         if not in_range(m) or dmax < 0:
             continue
         for c in candidates(m, min(dmax, DMAX)):
-            k = _k_of(m, c, MAGIC0)
-            want = differs(m, c, k).size == 0
+            k = k_of(m, c, MAGIC0)
+            want = dequant_differs(m, c, k).size == 0
             ok, k2 = host.fused_check(m, c, dq=True)
             assert k2 == k and ok == want, (name, c, want)
             n_acc += want
@@ -133,8 +95,8 @@ def test_enumeration_decides_every_candidate_exactly():
         # a base whose C m lies far from an integer
         C = candidates(m, min(dmax, DMAX))[0]
         for dlt in (1, 2, 3):
-            k = _k_of(m, C + dlt, MAGIC0)
-            want = differs(m, C + dlt, k).size == 0
+            k = k_of(m, C + dlt, MAGIC0)
+            want = dequant_differs(m, C + dlt, k).size == 0
             assert host.fused_check(m, C + dlt, dq=True)[0] == want, (name, dlt)
             n_acc += want
             n_rej += not want
@@ -149,7 +111,7 @@ def test_bench_blob_sites_are_accepted():
         m, dmax = sites[f"{BENCH}.0.{s}"]
         got = host.dequant_site(m, dmax)
         assert got is not None, s
-        assert differs(m, *got).size == 0
+        assert dequant_differs(m, *got).size == 0
 
 
 def test_refusals():

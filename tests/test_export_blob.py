@@ -13,6 +13,7 @@ import torch
 
 from conftest import REPO, golden_files
 from drone_oa_iree_vit_accelerator_amd import params, synth
+from float_graph_common import converted_state_dict
 
 
 def _fake_state_dict(d, fp, spectral=True):
@@ -55,30 +56,8 @@ def test_export_from_synthesised_state_dict():
     assert "decoder.weight" in params.float_tensors(got_sn) or True
 
 
-def _converted_state_dict(path):
-    """the reference's converted state_dict as tools/gen_golden.py (gen_checkpoint) recorded it: key order, packed
-    quantized Linears, observer scales; the unchanged float parameters are the fixture seed's synthetic ones"""
-    d = np.load(path)
-    fp = synth.float_params(int(d["meta.seed"]), E=64)
-    assert str(d["meta.params_sha256"]) == synth.digest(fp)
-    sd = {}
-    for k in d["keys"]:
-        k = str(k)
-        if "d." + k in d:
-            sd[k] = getattr(torch, str(d["d." + k]))
-        elif "q." + k + ".int_repr" in d:
-            w = torch._make_per_tensor_quantized_tensor(torch.from_numpy(d["q." + k + ".int_repr"]),
-                                                        float(d["q." + k + ".scale"]), int(d["q." + k + ".zero_point"]))
-            sd[k] = (w, torch.from_numpy(d["q." + k + ".bias"]))
-        elif "t." + k in d:
-            sd[k] = torch.from_numpy(d["t." + k])
-        else:
-            sd[k] = torch.from_numpy(fp[k])
-    return sd
-
-
 def test_cli_on_real_converted_checkpoint(tmp_path):
-    torch.save(_converted_state_dict(golden_files("qatckpt_E64_s0.npz")[0]),
+    torch.save(converted_state_dict(golden_files("qatckpt_E64_s0.npz")[0]),
                str(tmp_path / "model_quantized_final.pth"))     # training/qa_train.py:91-92
     out = tmp_path / "w.itaw"
     r = subprocess.run([sys.executable, os.path.join(REPO, "tools", "export_blob.py"), "--checkpoint",

@@ -12,7 +12,7 @@ import torch
 
 from conftest import REPO, golden_files
 from drone_oa_iree_vit_accelerator_amd import float_twin, params, synth
-from test_float_graph_cpu import _Attention, _Ffn, _Tokenizer, _unpack, _validate, plugin  # noqa: F401
+from float_graph_common import Attention, Ffn, Tokenizer, unpack, validate, plugin  # noqa: F401
 
 GRAPHS = {128: ("floatnt2l_E128_s1_B2.npz", 2), 64: ("floatnt1l_E64_s2_B2.npz", 1)}
 
@@ -50,11 +50,11 @@ def test_blob_without_tail(plugin, E):  # noqa: F811
     assert blob[:8] == b"ITAW0003"
     hdr = np.frombuffer(blob[12:44], np.int32)
     assert int(hdr[0]) == E and int(hdr[5]) == L and int(hdr[6]) == 0   # E, num_layers, has_tail
-    t = _unpack(blob)
+    t = unpack(blob)
     assert not [k for k in t if k.startswith("tail.")]
     assert t["dec.w"].shape == (512, E * 128)
     np.testing.assert_array_equal(t["dec.w"], fp["decoder.weight"])
-    assert _validate(plugin, blob) == (0, "")
+    assert validate(plugin, blob) == (0, "")
 
 
 class _UpsampleShuffleNet(torch.nn.Module):
@@ -63,9 +63,9 @@ class _UpsampleShuffleNet(torch.nn.Module):
 
     def __init__(self, E=128, P=192, F=256):
         super().__init__()
-        self.tokenizer = _Tokenizer(E)
-        self.attention_blocks = torch.nn.ModuleList(_Attention(E, P) for _ in range(2))
-        self.ffn_blocks = torch.nn.ModuleList(_Ffn(E, F) for _ in range(2))
+        self.tokenizer = Tokenizer(E)
+        self.attention_blocks = torch.nn.ModuleList(Attention(E, P) for _ in range(2))
+        self.ffn_blocks = torch.nn.ModuleList(Ffn(E, F) for _ in range(2))
         self.norm1_layers = torch.nn.ModuleList(torch.nn.LayerNorm(E) for _ in range(2))
         self.norm2_layers = torch.nn.ModuleList(torch.nn.LayerNorm(E) for _ in range(2))
         self.decoder = torch.nn.utils.spectral_norm(torch.nn.Linear(E * 128, 512))
@@ -80,9 +80,9 @@ class _SingleLayerNet(torch.nn.Module):
 
     def __init__(self, E=64, P=192, F=256):
         super().__init__()
-        self.tokenizer = _Tokenizer(E)
-        self.attention_block = _Attention(E, P)
-        self.ffn_block = _Ffn(E, F)
+        self.tokenizer = Tokenizer(E)
+        self.attention_block = Attention(E, P)
+        self.ffn_block = Ffn(E, F)
         self.norm1, self.norm2 = torch.nn.LayerNorm(E), torch.nn.LayerNorm(E)
         self.decoder = torch.nn.utils.spectral_norm(torch.nn.Linear(E * 128, 512))
         self.lstm = torch.nn.LSTM(input_size=517, hidden_size=128, num_layers=3)
@@ -131,7 +131,7 @@ def test_export_checkpoint_of_each_model_file(tmp_path, E):
     assert blob == params.blob_from_state_dict(sd, L)
     hdr = np.frombuffer(blob[12:44], np.int32)
     assert int(hdr[0]) == E and int(hdr[6]) == 0
-    assert not [k for k in _unpack(blob) if k.startswith("tail.")]
+    assert not [k for k in unpack(blob) if k.startswith("tail.")]
 
 
 def test_decoder_width_decides_the_tail():

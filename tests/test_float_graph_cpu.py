@@ -1,7 +1,6 @@
 """The float ViT+LSTM graph (models/ITA_single_layer_upsample_shuffle/model.py: float attention with nn.Softmax, float
 FFN, nothing quantised) on the CPU: the ITAW0003 blob format (packing, validation by the built plugin, refusal by
 consumers that only know ITAW0001), the float-checkpoint export, and the unchanged ITAW0001 / ITAW0002 formats."""
-import ctypes as C
 import hashlib
 import os
 import subprocess
@@ -13,6 +12,7 @@ import torch
 
 from conftest import REPO, golden_files
 from drone_oa_iree_vit_accelerator_amd import params, synth
+from float_graph_common import float_state_dict, plugin, repack, unpack, validate  # noqa: F401
 
 ATTN_F32_NAMES = ("attn0.wqf", "attn0.wkf", "attn0.wvf", "attn0.bqf", "attn0.bkf", "attn0.bvf", "attn0.wof", "attn0.bof")
 INT8_ATTN_NAMES = ("attn0.wq", "attn0.wk", "attn0.wv", "attn0.wo", "attn0.bq", "attn0.bk", "attn0.bv", "attn0.bo", "attn0.scal")
@@ -25,53 +25,13 @@ UNCHANGED = {
     ("onlyattn2l_E64_s1_B2.npz", 2): "1d79d2ae0087eca9ff15a77b0ba19c494481780fb7b09e7ed403e7c91d75bc95",
 }
 
-_NP = {0: np.float32, 1: np.int8, 2: np.int32, 3: np.uint8, 4: np.float16}
-
-
-def _unpack(blob):
-    n = np.frombuffer(blob[8:12], np.int32)[0]
-    t = {}
-    for i in range(n):
-        e = blob[64 + 72 * i: 64 + 72 * (i + 1)]
-        nm = e[:32].split(b"\0")[0].decode()
-        dt, nd = np.frombuffer(e[32:40], np.int32)
-        shape = [int(s) for s in np.frombuffer(e[40:56], np.int32)[:nd]]
-        off, nb = (int(v) for v in np.frombuffer(e[56:72], np.int64))
-        t[nm] = np.frombuffer(blob[off:off + nb], _NP[int(dt)]).reshape(shape).copy()
-    return t
-
-
-def _repack(blob, t, magic=None):
-    hdr = np.frombuffer(blob[12:44], np.int32)
-    E, S, P, F, H, L, has_tail = (int(v) for v in hdr[:7])
-    magic = magic or blob[:8]
-    return params.pack_blob(t, E=E, S=S, P=P, F=F, H=H, num_layers=L, has_tail=bool(has_tail),
-                            ffn_f32=magic != b"ITAW0001", attn_f32=magic == b"ITAW0003")
-
-
-@pytest.fixture(scope="module")
-def plugin():
-    from drone_oa_iree_vit_accelerator_amd import host
-    so = host.build_extension()
-    lib = C.CDLL(so)
-    lib.ita_validate_blob.argtypes = [C.c_void_p, C.c_size_t, C.c_char_p]
-    return lib
-
-
-def _validate(lib, blob):
-    bad = C.create_string_buffer(32)
-    buf = C.create_string_buffer(blob, len(blob))
-    rc = lib.ita_validate_blob(buf, len(blob), bad)
-    return rc, bad.value.decode()
-
-
 def test_blob_from_float_params():
     for L in (1, 2):
         fp = synth.float_params(0, E=64, num_layers=L)
         blob = params.blob_from_float_params(fp, L)
         assert blob[:8] == b"ITAW0003"
         assert int(np.frombuffer(blob[32:36], np.int32)[0]) == L
-        t = _unpack(blob)
+        t = unpack(blob)
         assert not any(n in t for n in INT8_ATTN_NAMES + ("ffn0.w1", "ffn0.scal"))
         for i in range(L):
             a, f = f"attention_blocks.{i}.", f"ffn_blocks.{i}."
@@ -87,34 +47,34 @@ def test_blob_from_float_params():
 
 def test_validate_blob(plugin):
     blob = params.blob_from_float_params(synth.float_params(0))
-    assert _validate(plugin, blob) == (0, "")
+    assert validate(plugin, blob) == (0, "")
     blob2 = params.blob_from_float_params(synth.float_params(1, num_layers=2), 2)
-    assert _validate(plugin, blob2) == (0, "")
-    t = _unpack(blob)
-    assert _repack(blob, t) == blob   # the repacker is faithful
+    assert validate(plugin, blob2) == (0, "")
+    t = unpack(blob)
+    assert repack(blob, t) == blob   # the repacker is faithful
     for nm in ATTN_F32_NAMES:
         bad_t = dict(t)
         del bad_t[nm]
-        rc, bad = _validate(plugin, _repack(blob, bad_t))
+        rc, bad = validate(plugin, repack(blob, bad_t))
         assert rc != 0 and bad == nm
         bad_t[nm] = t[nm].reshape(-1)[:-4].copy()
-        rc, bad = _validate(plugin, _repack(blob, bad_t))
+        rc, bad = validate(plugin, repack(blob, bad_t))
         assert rc != 0 and bad == nm
         bad_t[nm] = t[nm].astype(np.float16)
-        rc, bad = _validate(plugin, _repack(blob, bad_t))
+        rc, bad = validate(plugin, repack(blob, bad_t))
         assert rc != 0 and bad == nm
-    t2 = _unpack(blob2)
+    t2 = unpack(blob2)
     del t2["attn1.wkf"]
-    rc, bad = _validate(plugin, _repack(blob2, t2))
+    rc, bad = validate(plugin, repack(blob2, t2))
     assert rc != 0 and bad == "attn1.wkf"
     # an ITAW0003 blob carrying the int8 attention of an ITAW0002 blob instead of the float one
     d = params.load_fixture(golden_files("onlyattn1l_E64_s0_B2.npz")[0])
     b2 = params.blob_from_record(d, synth.float_params(0, E=64), E=64)
-    assert _validate(plugin, b2) == (0, "")
-    rc, bad = _validate(plugin, _repack(b2, _unpack(b2), magic=b"ITAW0003"))
+    assert validate(plugin, b2) == (0, "")
+    rc, bad = validate(plugin, repack(b2, unpack(b2), magic=b"ITAW0003"))
     assert rc != 0 and bad == "attn0.wqf"
     # and the other way round: float attention under the ITAW0002 magic lacks the int8 attention
-    rc, bad = _validate(plugin, _repack(blob, t, magic=b"ITAW0002"))
+    rc, bad = validate(plugin, repack(blob, t, magic=b"ITAW0002"))
     assert rc != 0 and bad == "attn0.wq"
 
 
@@ -123,7 +83,7 @@ def test_int8_formats_unchanged(plugin, name, L):
     d = params.load_fixture(golden_files(name)[0])
     blob = params.blob_from_record(d, synth.float_params(int(d["meta.seed"]), E=64, num_layers=L), E=64, num_layers=L)
     assert hashlib.sha256(blob).hexdigest() == UNCHANGED[(name, L)]
-    assert _validate(plugin, blob) == (0, "")
+    assert validate(plugin, blob) == (0, "")
 
 
 def test_oracle_refuses_float_blob(oracle):
@@ -133,62 +93,9 @@ def test_oracle_refuses_float_blob(oracle):
         oracle.forward(blob, fx["in0.img_u8"], fx["in0.desvel"], fx["in0.quat"])
 
 
-class _Attention(torch.nn.Module):
-    def __init__(self, E, P):
-        super().__init__()
-        self.q_proj, self.k_proj = torch.nn.Linear(E, P), torch.nn.Linear(E, P)
-        self.v_proj, self.out_proj = torch.nn.Linear(E, P), torch.nn.Linear(P, E)
-
-
-class _Ffn(torch.nn.Module):
-    def __init__(self, E, F):
-        super().__init__()
-        self.fc1, self.fc2 = torch.nn.Linear(E, F), torch.nn.Linear(F, E)
-
-
-class _Tokenizer(torch.nn.Module):
-    def __init__(self, E):
-        super().__init__()
-        self.conv = torch.nn.Conv2d(1, E, 7, stride=2, padding=3)
-        self.norm = torch.nn.LayerNorm(E)
-
-
-class _FloatNet(torch.nn.Module):
-    """the float model's parameter tree under its state_dict names (models/ITA_single_layer_upsample_shuffle/model.py),
-    decoder and nn_fc2 under spectral_norm as declared there"""
-
-    def __init__(self, L, E=64, P=192, F=256):
-        super().__init__()
-        self.tokenizer = _Tokenizer(E)
-        self.attention_blocks = torch.nn.ModuleList(_Attention(E, P) for _ in range(L))
-        self.ffn_blocks = torch.nn.ModuleList(_Ffn(E, F) for _ in range(L))
-        self.norms1 = torch.nn.ModuleList(torch.nn.LayerNorm(E) for _ in range(L))
-        self.norms2 = torch.nn.ModuleList(torch.nn.LayerNorm(E) for _ in range(L))
-        self.down_sample = torch.nn.Conv2d(E // 4 + E, 9, 3, padding=1)
-        self.decoder = torch.nn.utils.spectral_norm(torch.nn.Linear(4608, 512))
-        self.lstm = torch.nn.LSTM(input_size=517, hidden_size=128, num_layers=3)
-        self.nn_fc2 = torch.nn.utils.spectral_norm(torch.nn.Linear(128, 3))
-
-
-def _float_state_dict(L, seed):
-    fp = synth.float_params(seed, E=64, num_layers=L)
-    torch.manual_seed(seed)
-    net = _FloatNet(L)
-    with torch.no_grad():
-        for k, v in net.state_dict().items():
-            src = k.replace("weight_orig", "weight")
-            if src in fp and not k.endswith(("weight_u", "weight_v")):
-                assert tuple(v.shape) == fp[src].shape, k
-                v.copy_(torch.from_numpy(fp[src]))
-    sd = net.state_dict()
-    assert "decoder.weight_orig" in sd and "decoder.weight_u" in sd and "decoder.weight" not in sd
-    assert "attention_blocks.0.q_proj.weight" in sd
-    return sd
-
-
 @pytest.mark.parametrize("L", [1, 2])
 def test_export_float_checkpoint(tmp_path, L):
-    sd = _float_state_dict(L, 3)
+    sd = float_state_dict(L, 3)
     ck = tmp_path / "model_000205.pth"
     torch.save(sd, str(ck))
     out = tmp_path / "w.itaw"
@@ -198,7 +105,7 @@ def test_export_float_checkpoint(tmp_path, L):
     blob = out.read_bytes()
     assert blob[:8] == b"ITAW0003"
     assert blob == params.blob_from_state_dict(sd, L)
-    t = _unpack(blob)
+    t = unpack(blob)
     want_dec = params.fold_spectral_norm(sd, "decoder")
     np.testing.assert_array_equal(t["dec.w"], want_dec)
     assert not np.array_equal(want_dec, sd["decoder.weight_orig"].numpy())   # the fold is not the identity

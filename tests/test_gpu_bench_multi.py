@@ -13,7 +13,7 @@ import sys
 import pytest
 
 from conftest import REPO
-from test_gpu_bench_dump import check_dump
+from bench_dump_common import check_dump
 
 pytestmark = pytest.mark.gpu
 

@@ -31,8 +31,8 @@ import pytest
 import requant_common as rc
 from conftest import REPO, golden_files
 from drone_oa_iree_vit_accelerator_amd import host, params, synth
-from test_dequant_fused_cpu import MAGIC0, differs, room
-from test_requant_fused_cpu import _k_of, proven
+from gpu_support import cu
+from requant_fused_common import MAGIC0, dequant_differs, k_of, proven, room
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -46,11 +46,6 @@ def torch_cuda():
     import torch
     assert torch.cuda.is_available(), "GPU tests need a GPU"
     return torch
-
-
-def _cu(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _refused_multiplier(m0):
@@ -117,8 +112,8 @@ def check_forms(eng, t, mask=0xFF):
     for i, s in enumerate(host.DQ_SITES):
         if want:
             m = rc.multiplier_of(t, s)
-            assert (ld["C"][i], ld["K"][i]) == exp[s] and ld["K"][i] == _k_of(m, ld["C"][i], MAGIC0), (s, ld)
-            assert differs(m, ld["C"][i], ld["K"][i]).size == 0, s
+            assert (ld["C"][i], ld["K"][i]) == exp[s] and ld["K"][i] == k_of(m, ld["C"][i], MAGIC0), (s, ld)
+            assert dequant_differs(m, ld["C"][i], ld["K"][i]).size == 0, s
         else:
             assert ld["C"][i] == host.ACC_BIAS, (s, ld)   # the images keep the default base
     return want
@@ -164,7 +159,7 @@ def run_case(kind, mask=0xFF):
     tok3 = x1_3 = x2_3 = None
     for B in batches():
         idx = np.arange(B) % 3
-        img, dv, qt = _cu(fr["img_u8"][idx]), _cu(fr["desvel"][idx]), _cu(fr["quat"][idx])
+        img, dv, qt = cu(fr["img_u8"][idx]), cu(fr["desvel"][idx]), cu(fr["quat"][idx])
         vel, (h, c), tp = eng.forward(img, dv, qt, taps=True)
         tok, x1, x2 = (tp[k].cpu().numpy() for k in ("tokens", "x1", "x2"))
         if B == 1:
@@ -191,7 +186,7 @@ def run_case(kind, mask=0xFF):
         vn, (hn, cn) = eng.forward(img, dv, qt)
         assert torch.equal(vn, vel) and torch.equal(hn, h) and torch.equal(cn, c), f"{kind} no taps B={B}"
         # f32 tokens, <64, true, 0>
-        y = eng.encoder_layer(_cu(x[idx])).cpu().numpy()
+        y = eng.encoder_layer(cu(x[idx])).cpu().numpy()
         bad = np.flatnonzero((y != ref["x2_tokens"][idx]).any(axis=(1, 2)))
         assert bad.size == 0, f"{kind} f32 tokens B={B}: frames {bad[:8]}"
     eng.close()
@@ -208,7 +203,7 @@ def test_case_selection():
             m = rc.multiplier_of(t, s)
             assert host.fast_site_ok(m) or s == "fc2", (kind, s)
             if exp[s] is not None:
-                assert differs(m, *exp[s]).size == 0
+                assert dequant_differs(m, *exp[s]).size == 0
         print(kind, {s: (None if exp[s] is None else exp[s][0] - host.ACC_BIAS) for s in exp},
               {s: (len(want[s]), max(want[s])) for s in want})
         if kind == "refused":
@@ -237,7 +232,7 @@ def test_plane_rows_and_padding():
     n = 128 * 64
     for B in bs:
         idx = np.arange(B) % 3
-        img, dv, qt = _cu(fr["img_u8"][idx]), _cu(fr["desvel"][idx]), _cu(fr["quat"][idx])
+        img, dv, qt = cu(fr["img_u8"][idx]), cu(fr["desvel"][idx]), cu(fr["quat"][idx])
         for taps in (True, False):
             eng.fill_x2_planes(B, 0xA5)
             out = eng.forward(img, dv, qt, taps=taps)

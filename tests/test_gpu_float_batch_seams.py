@@ -20,10 +20,9 @@ import numpy as np
 import pytest
 
 from drone_oa_iree_vit_accelerator_amd import host, synth
-from test_float_graph_cpu import _unpack
-from test_gpu_float_e128 import _ln_like, _setup as _setup_notail
-from test_gpu_float_graph import _setup as _setup_float
-from test_gpu_only_attn import _setup as _setup_only_attn
+from gpu_support import cu
+from float_graph_common import ln_like, setup_float, setup_notail, unpack
+from only_attn_common import setup_only_attn
 
 pytestmark = pytest.mark.gpu
 
@@ -35,16 +34,11 @@ FLOAT_ATTN = ("itaw3_e64", "itaw3_e128")
 def _family(name):
     """(blob, E, layers)"""
     if name == "itaw3_e64":
-        return _setup_float(1)[2], 64, 1
+        return setup_float(1)[2], 64, 1
     if name == "itaw3_e128":
-        _, _, blob, L = _setup_notail(128)
+        _, _, blob, L = setup_notail(128)
         return blob, 128, L
-    return _setup_only_attn(1)[2], 64, 1
-
-
-def _cu(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    return setup_only_attn(1)[2], 64, 1
 
 
 def _cus():
@@ -117,9 +111,9 @@ def test_mha_f32_past_one_frame_per_workgroup(family):
     _, B1, B2 = _batches()
     eng = host.Engine(blob, device=0)
     for B in (B1, B2):
-        x = _ln_like(B, 100 + B, E)
+        x = ln_like(B, 100 + B, E)
         for l in range(L):
-            run = lambda a: eng.mha_f32(_cu(a), l).cpu().numpy()
+            run = lambda a: eng.mha_f32(cu(a), l).cpu().numpy()
             _assert_frames_equal(run(x), _chunked(run, x), f"mha_f32 {family} B={B} layer {l}")
     eng.close()
 
@@ -128,17 +122,17 @@ def test_mha_f32_past_one_frame_per_workgroup(family):
 @pytest.mark.parametrize("family", FAMILIES)
 def test_ffn_f32_past_one_tile_per_workgroup(oracle, family):
     blob, E, L = _family(family)
-    t = _unpack(blob)
+    t = unpack(blob)
     eng = host.Engine(blob, device=0)
     for B in _batches():
-        x = _ln_like(B, 200 + B, E)
+        x = ln_like(B, 200 + B, E)
         x[0, 0, :8] = 0.0
         pick = _pick8(B)
         assert pick.size == 8 and pick[0] == 0 and pick[-1] == B - 1
         if B == _batches()[2]:
             assert ((pick >= _cus()) & (pick < 2 * _cus())).any() and (pick >= 2 * _cus()).any()
         for l in range(L):
-            run = lambda a: eng.ffn_f32(_cu(a), l).cpu().numpy()
+            run = lambda a: eng.ffn_f32(cu(a), l).cpu().numpy()
             y = run(x)
             _assert_frames_equal(y, _chunked(run, x), f"ffn_f32 {family} B={B} layer {l}")
             hid = np.maximum(oracle.linear_f32(x[pick], t[f"ffn{l}.w1f"], t[f"ffn{l}.b1f"]), np.float32(0))
@@ -154,13 +148,13 @@ def test_encoder_layer_past_one_frame_per_workgroup(family):
     B0, B1, B2 = _batches()
     eng = host.Engine(blob, device=0)
     for B in (B0, B1, B2):
-        x = _ln_like(B, 300 + B, E)
+        x = ln_like(B, 300 + B, E)
         for l in range(L):
-            run = lambda a: eng.encoder_layer(_cu(a), l).cpu().numpy()
+            run = lambda a: eng.encoder_layer(cu(a), l).cpu().numpy()
             want = _chunked(run, x)
             _assert_frames_equal(run(x), want, f"encoder_layer {family} B={B} layer {l}")
             if B == B2:   # in place: y aliases x across the iterations
-                xx = _cu(x)
+                xx = cu(x)
                 host._chk(host.lib().ita_encoder_layer(eng._h, l, xx.data_ptr(), xx.data_ptr(), B, host._stream_ptr(eng.device)))
                 _assert_frames_equal(xx.cpu().numpy(), want, f"encoder_layer in place {family} B={B} layer {l}")
     eng.close()
@@ -186,7 +180,7 @@ def test_forward_past_one_frame_per_workgroup(family):
     img, dv, qt, h0, c0 = _step_inputs(31, B1)
 
     def run(img, dv, qt, h0, c0):
-        v, (h, c), tp = eng.forward(_cu(img), _cu(dv), _cu(qt), (_cu(h0), _cu(c0)), taps=True)
+        v, (h, c), tp = eng.forward(cu(img), cu(dv), cu(qt), (cu(h0), cu(c0)), taps=True)
         torch.cuda.synchronize()
         return dict(vel=v.cpu().numpy(), h=h.cpu().numpy(), c=c.cpu().numpy(), x1=tp["x1"].cpu().numpy(), x2=tp["x2"].cpu().numpy())
 
@@ -199,7 +193,7 @@ def test_forward_past_one_frame_per_workgroup(family):
             ax = 1 if k in ("h", "c") else 0
             want = np.concatenate([p[k] for p in parts], axis=ax)
             _assert_frames_equal(got[k], want, f"forward {family} tail mode {mode} B={B1}: {k}", frame_axis=ax, tokens=k in ("x1", "x2"))
-        v, (h, c) = eng.forward(_cu(img), _cu(dv), _cu(qt), (_cu(h0), _cu(c0)))
+        v, (h, c) = eng.forward(cu(img), cu(dv), cu(qt), (cu(h0), cu(c0)))
         for k, g in (("vel", v), ("h", h), ("c", c)):
             _assert_frames_equal(g.cpu().numpy(), got[k], f"forward without taps {family} tail mode {mode} B={B1}: {k}",
                                  frame_axis=1 if k != "vel" else 0, tokens=False)
@@ -219,9 +213,9 @@ def test_forward_slots_past_one_frame_per_workgroup(family):
     perm = np.random.RandomState(B1).permutation(NS)
     slots, rest = perm[:B1].astype(np.int32), np.sort(perm[B1:])
     assert rest.size == 5 and not (slots == np.arange(B1)).all()
-    sh, sc = _cu(h0.copy()), _cu(c0.copy())
-    vel = eng.forward_slots(_cu(img), _cu(dv), _cu(qt), sh, sc, _cu(slots))
-    v2, (h2, c2) = eng.forward(_cu(img), _cu(dv), _cu(qt), (_cu(h0[:, slots]), _cu(c0[:, slots])))
+    sh, sc = cu(h0.copy()), cu(c0.copy())
+    vel = eng.forward_slots(cu(img), cu(dv), cu(qt), sh, sc, cu(slots))
+    v2, (h2, c2) = eng.forward(cu(img), cu(dv), cu(qt), (cu(h0[:, slots]), cu(c0[:, slots])))
     torch.cuda.synchronize()
     _assert_frames_equal(vel.cpu().numpy(), v2.cpu().numpy(), f"forward_slots {family} B={B1}: vel", tokens=False)
     sh, sc = sh.cpu().numpy(), sc.cpu().numpy()
@@ -241,7 +235,7 @@ def test_graphed_step_past_one_frame_per_workgroup(family):
     st = (torch.zeros((3, B1, 128), device="cuda"), torch.zeros((3, B1, 128), device="cuda"))
     for t in range(3):
         fr = synth.frames(600 + t, B1)
-        img, dv, qt = _cu(fr["img_u8"]), _cu(fr["desvel"]), _cu(fr["quat"])
+        img, dv, qt = cu(fr["img_u8"]), cu(fr["desvel"]), cu(fr["quat"])
         g.img.copy_(img); g.desvel.copy_(dv.reshape(B1)); g.quat.copy_(qt)
         vg = g().clone()
         ve, st = eng.forward(img, dv, qt, st)

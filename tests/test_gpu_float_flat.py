@@ -14,16 +14,12 @@ import numpy as np
 import pytest
 
 from drone_oa_iree_vit_accelerator_amd import host
+from gpu_support import cu
 import float_flat_common as fc
 import long_f32_common as lc
 from long_f32_common import LAYERS
 
 pytestmark = pytest.mark.gpu
-
-
-def _cu(a):
-    import torch
-    return torch.from_numpy(np.array(a)).cuda()
 
 
 @pytest.fixture(scope="module")
@@ -62,7 +58,7 @@ KIND = pytest.mark.parametrize("kind", fc.KINDS)
 @KIND
 def test_mha_f32_flat_rows(engine, kind, E, s):
     S, B = fc.SHORT
-    x = _cu(lc.inputs(kind, E, S, B))
+    x = cu(lc.inputs(kind, E, S, B))
     for l in range(LAYERS[E]):
         want, e_torch = fc.attn_ref(kind, E, S, B, l, s)
         _check(engine(E, l, s).mha_f32(x, l).cpu().numpy(), want, e_torch, f"mha_f32 s={fc.label(s)} {kind} E={E} S={S} B={B} layer {l}")
@@ -73,7 +69,7 @@ def test_mha_f32_flat_rows(engine, kind, E, s):
 @KIND
 def test_encoder_layer_flat_rows(engine, kind, E, s):
     S, B = fc.SHORT
-    x = _cu(lc.inputs(kind, E, S, B))
+    x = cu(lc.inputs(kind, E, S, B))
     for l in range(LAYERS[E]):
         want, e_torch = fc.layer_ref(kind, E, S, B, l, s)
         _check(engine(E, l, s).encoder_layer(x, l).cpu().numpy(), want, e_torch,
@@ -86,7 +82,7 @@ def test_encoder_layer_flat_rows(engine, kind, E, s):
 @KIND
 def test_mha_long_f32_flat_rows(engine, kind, E, s, S, B):
     """every 64-key unit contributes to every row's running sum; on the ramped rows the maximum keeps moving as well"""
-    x = _cu(lc.inputs(kind, E, S, B))
+    x = cu(lc.inputs(kind, E, S, B))
     for l in range(LAYERS[E]):
         want, e_torch = fc.attn_ref(kind, E, S, B, l, s)
         _check(engine(E, l, s).mha_long_f32(x, l).cpu().numpy(), want, e_torch,
@@ -100,7 +96,7 @@ def test_scale_zero_rows_bit_equal(engine, kind, E):
     same V in the same key order.  A row that differs from row 0 belongs to a wave that read K or V while another wave
     was still writing it (or that walked the keys in another order)."""
     S, B = fc.SHORT
-    x = _cu(lc.inputs(kind, E, S, B))
+    x = cu(lc.inputs(kind, E, S, B))
     for l in range(LAYERS[E]):
         y = engine(E, l, 0.0).mha_f32(x, l).cpu().numpy()
         assert np.isfinite(y).all()
@@ -117,7 +113,7 @@ def test_duplicated_tokens_stock_weights(engine, E):
     import torch
     fp, _, twin = lc.case(E)
     xn = fc.duplicated(E)
-    x = _cu(xn)
+    x = cu(xn)
     eng = engine(E, 0, 1.0)
     for l in range(LAYERS[E]):
         want = lc.attn64(xn, fp, l)
@@ -146,7 +142,7 @@ def test_poisoned_frame_stays_alone(engine, E, poison):
     clean = lc.ln_like(B, 128, E, 900 + E)
     bad = clean.copy()
     bad[0, 37, 5] = poison
-    xc, xb = _cu(clean), _cu(bad)
+    xc, xb = cu(clean), cu(bad)
     for l in range(LAYERS[E]):
         for name, fn in (("mha_f32", eng.mha_f32), ("encoder_layer", eng.encoder_layer)):
             want, got = fn(xc, l).cpu().numpy(), fn(xb, l).cpu().numpy()

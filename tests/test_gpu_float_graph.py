@@ -9,43 +9,10 @@ import pytest
 
 from conftest import golden_files
 from drone_oa_iree_vit_accelerator_amd import float_twin, host, params, synth
-from test_float_graph_cpu import _float_state_dict
+from gpu_support import cu
+from float_graph_common import attn64, float_state_dict, ln_like, setup_float as _setup
 
 pytestmark = pytest.mark.gpu
-
-FIX = {1: golden_files("floattwin_E64_s0_B2.npz")[0], 2: golden_files("floattwin2l_E64_s1_B2.npz")[0]}
-
-
-def _setup(L):
-    d = params.load_fixture(FIX[L])
-    fp = synth.float_params(int(d["meta.seed"]), E=64, num_layers=L)
-    assert str(d["meta.params_sha256"]) == synth.digest(fp)
-    return d, fp, params.blob_from_float_params(fp, L)
-
-
-def _cu(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _ln_like(B, seed):
-    """LayerNorm-like activations: per token zero mean, unit variance, then a mild affine"""
-    rs = np.random.RandomState(seed)
-    x = rs.standard_normal((B, 128, 64))
-    x = (x - x.mean(-1, keepdims=True)) / x.std(-1, keepdims=True)
-    return (x * (1.0 + 0.1 * rs.standard_normal(64)) + 0.1 * rs.standard_normal(64)).astype(np.float32)
-
-
-def attn64(x, fp, i):
-    """ITASelfAttention.forward (models/ITA/layers.py:67-88) in float64: one head, no 1/sqrt(d)"""
-    g = lambda k: fp[f"attention_blocks.{i}.{k}"].astype(np.float64)
-    x = x.astype(np.float64)
-    q, k, v = (x @ g(f"{n}.weight").T + g(f"{n}.bias") for n in ("q_proj", "k_proj", "v_proj"))
-    s = q @ k.transpose(0, 2, 1)
-    p = np.exp(s - s.max(-1, keepdims=True))
-    p /= p.sum(-1, keepdims=True)
-    return (p @ v) @ g("out_proj.weight").T + g("out_proj.bias")
-
 
 def test_mha_f32_against_float64():
     """On the reference's tokens (|logit| <= 109) within 1e-5 of float64.  The random activations reach |logit| ~ 230,
@@ -59,13 +26,13 @@ def test_mha_f32_against_float64():
         twin = float_twin.FloatTwin(fp, num_layers=L)
         assert [eng.attn_kind(l) for l in range(L)] == [host.ATTN_F32] * L
         assert [eng.ffn_kind(l) for l in range(L)] == [host.FFN_F32] * L
-        cases = [("tokens", d["s0.tok.out"])] + [(f"ln B={B}", _ln_like(B, B)) for B in (1, 3, 37, 1024)]
+        cases = [("tokens", d["s0.tok.out"])] + [(f"ln B={B}", ln_like(B, B, 64)) for B in (1, 3, 37, 1024)]
         for name, x in cases:
             B = x.shape[0]
             frames = np.arange(B) if B < 64 else np.random.RandomState(B).choice(B, 24, replace=False)
             for l in range(L):
-                y = eng.mha_f32(_cu(x), l).cpu().numpy()
-                assert np.array_equal(eng.mha(_cu(x), l).cpu().numpy(), y)
+                y = eng.mha_f32(cu(x), l).cpu().numpy()
+                assert np.array_equal(eng.mha(cu(x), l).cpu().numpy(), y)
                 want = attn64(x[frames], fp, l)
                 err = np.abs(y[frames] - want).max()
                 terr = np.abs(twin._attention(torch.from_numpy(x[frames]), l).numpy() - want).max()
@@ -80,16 +47,16 @@ def test_mha_f32_against_float64():
 def test_frames_independent_and_runs_repeatable():
     _, _, blob = _setup(1)
     eng = host.Engine(blob, device=0)
-    x = _ln_like(37, 5)
-    y = eng.mha_f32(_cu(x), 0).cpu().numpy()
-    assert np.array_equal(eng.mha_f32(_cu(x), 0).cpu().numpy(), y)
-    z = eng.encoder_layer(_cu(x), 0).cpu().numpy()
-    assert np.array_equal(eng.encoder_layer(_cu(x), 0).cpu().numpy(), z)
+    x = ln_like(37, 5, 64)
+    y = eng.mha_f32(cu(x), 0).cpu().numpy()
+    assert np.array_equal(eng.mha_f32(cu(x), 0).cpu().numpy(), y)
+    z = eng.encoder_layer(cu(x), 0).cpu().numpy()
+    assert np.array_equal(eng.encoder_layer(cu(x), 0).cpu().numpy(), z)
     for b in (0, 17, 36):
-        assert np.array_equal(eng.mha_f32(_cu(x[b:b + 1]), 0).cpu().numpy()[0], y[b]), b
-        assert np.array_equal(eng.encoder_layer(_cu(x[b:b + 1]), 0).cpu().numpy()[0], z[b]), b
+        assert np.array_equal(eng.mha_f32(cu(x[b:b + 1]), 0).cpu().numpy()[0], y[b]), b
+        assert np.array_equal(eng.encoder_layer(cu(x[b:b + 1]), 0).cpu().numpy()[0], z[b]), b
     # in place (y aliases x)
-    xx = _cu(x)
+    xx = cu(x)
     host.lib().ita_encoder_layer(eng._h, 0, xx.data_ptr(), xx.data_ptr(), 37, host._stream_ptr(eng.device))
     assert np.array_equal(xx.cpu().numpy(), z)
     eng.close()
@@ -99,14 +66,14 @@ def test_frames_independent_and_runs_repeatable():
 def test_layers_from_reference_tokens(L):
     d, fp, blob = _setup(L)
     eng = host.Engine(blob, device=0)
-    x = _cu(d["s0.tok.out"])
+    x = cu(d["s0.tok.out"])
     for l in range(L):
         x = eng.encoder_layer(x, l)
         want = d[f"s0.x2_{l}"] if L > 1 else d["s0.x2"]
         err = np.abs(x.cpu().numpy() - want).max()
         assert err <= 2e-5, (l, err)
     # the forward's x1 tap (LayerNorm1 output of the last layer) from the u8 frames
-    _, _, tp = eng.forward(_cu(d["in0.img_u8"]), _cu(d["in0.desvel"]), _cu(d["in0.quat"]), taps=True)
+    _, _, tp = eng.forward(cu(d["in0.img_u8"]), cu(d["in0.desvel"]), cu(d["in0.quat"]), taps=True)
     assert np.abs(tp["x1"].cpu().numpy() - d["s0.x1"]).max() <= 2e-5
     eng.close()
 
@@ -124,8 +91,8 @@ def test_forward_against_reference_and_float_twin(L):
     tv1, tst1 = twin.forward(fr["img_u8"], fr["desvel"], fr["quat"], hidden=hid)
     for mode in (0, 1):
         eng.set_tail_mode(mode)
-        v0, st, tp = eng.forward(_cu(d["in0.img_u8"]), _cu(d["in0.desvel"]), _cu(d["in0.quat"]), taps=True)
-        v1, st1 = eng.forward(_cu(d["in1.img_u8"]), _cu(d["in1.desvel"]), _cu(d["in1.quat"]), st)
+        v0, st, tp = eng.forward(cu(d["in0.img_u8"]), cu(d["in0.desvel"]), cu(d["in0.quat"]), taps=True)
+        v1, st1 = eng.forward(cu(d["in1.img_u8"]), cu(d["in1.desvel"]), cu(d["in1.quat"]), st)
         torch.cuda.synchronize()
         assert np.abs(tp["tokens"].cpu().numpy() - d["s0.tok.out"]).max() <= 2e-5
         for k in ("x1", "x2") + (("dec",) if mode == 0 else ()):
@@ -135,8 +102,8 @@ def test_forward_against_reference_and_float_twin(L):
             err = np.abs(g.cpu().numpy() - d[k]).max()
             assert err <= 5e-4, (mode, k, err)
         # FloatTwin on the CPU, 64 frames, zero and given state
-        g0, gst, gtp = eng.forward(_cu(fr["img_u8"]), _cu(fr["desvel"]), _cu(fr["quat"]), taps=True)
-        g1, gst1 = eng.forward(_cu(fr["img_u8"]), _cu(fr["desvel"]), _cu(fr["quat"]), (_cu(hid[0]), _cu(hid[1])))
+        g0, gst, gtp = eng.forward(cu(fr["img_u8"]), cu(fr["desvel"]), cu(fr["quat"]), taps=True)
+        g1, gst1 = eng.forward(cu(fr["img_u8"]), cu(fr["desvel"]), cu(fr["quat"]), (cu(hid[0]), cu(hid[1])))
         assert np.abs(gtp["tokens"].cpu().numpy() - ttp["tokens"].numpy()).max() <= 2e-5
         for k in ("x1", "x2") + (("dec",) if mode == 0 else ()):
             err = np.abs(gtp[k].cpu().numpy() - ttp[k].numpy()).max()
@@ -152,7 +119,7 @@ def test_profiler_stages():
     fr = synth.frames(3, 8)
     eng.profile_begin(4)
     for _ in range(3):
-        eng.forward(_cu(fr["img_u8"]), _cu(fr["desvel"]), _cu(fr["quat"]))
+        eng.forward(cu(fr["img_u8"]), cu(fr["desvel"]), cu(fr["quat"]))
     ms, n = eng.profile_end()
     assert n == 3 and ms["mha"] > 0 and ms["ffn"] > 0
     eng.close()
@@ -165,14 +132,14 @@ def test_serving_forms_equal_eager_forward():
     # forward_slots with the state updated in place
     B, NS = 5, 16
     fr = synth.frames(21, B)
-    img, dv, qt = _cu(fr["img_u8"]), _cu(fr["desvel"]), _cu(fr["quat"])
+    img, dv, qt = cu(fr["img_u8"]), cu(fr["desvel"]), cu(fr["quat"])
     rs = np.random.RandomState(0)
     h0 = (0.1 * rs.standard_normal((3, NS, 128))).astype(np.float32)
     c0 = (0.1 * rs.standard_normal((3, NS, 128))).astype(np.float32)
     slots = np.array([7, 0, 15, 3, 9], np.int32)
-    sh, sc = _cu(h0.copy()), _cu(c0.copy())
-    vel = eng.forward_slots(img, dv, qt, sh, sc, _cu(slots))
-    v2, (h2, c2) = eng.forward(img, dv, qt, (_cu(h0[:, slots]), _cu(c0[:, slots])))
+    sh, sc = cu(h0.copy()), cu(c0.copy())
+    vel = eng.forward_slots(img, dv, qt, sh, sc, cu(slots))
+    v2, (h2, c2) = eng.forward(img, dv, qt, (cu(h0[:, slots]), cu(c0[:, slots])))
     assert torch.equal(vel, v2)
     assert torch.equal(sh[:, slots.tolist()], h2) and torch.equal(sc[:, slots.tolist()], c2)
     # front / back on two streams
@@ -180,19 +147,19 @@ def test_serving_forms_equal_eager_forward():
     frames = [synth.frames(400 + t, B) for t in range(T)]
     ref, hid = [], None
     for t in range(T):
-        v, hid = eng.forward(_cu(frames[t]["img_u8"]), _cu(frames[t]["desvel"]), _cu(frames[t]["quat"]), hid)
+        v, hid = eng.forward(cu(frames[t]["img_u8"]), cu(frames[t]["desvel"]), cu(frames[t]["quat"]), hid)
         ref.append((v.clone(), hid[0].clone(), hid[1].clone()))
     sf, sb = torch.cuda.Stream(), torch.cuda.Stream()
     state = [(torch.zeros((3, B, 128), device="cuda"), torch.zeros((3, B, 128), device="cuda")) for _ in range(2)]
     torch.cuda.synchronize()
     for t in range(T):
         ev = torch.cuda.Event()
-        eng.front(_cu(frames[t]["img_u8"]), 0, stream=sf)
+        eng.front(cu(frames[t]["img_u8"]), 0, stream=sf)
         ev.record(sf)
         sb.wait_event(ev)
         out = torch.empty((B, 3), device="cuda")
         dst = state[(t + 1) & 1]
-        eng.back(_cu(frames[t]["desvel"]).reshape(B), _cu(frames[t]["quat"]), state[t & 1], (out, dst[0], dst[1]), 0, stream=sb)
+        eng.back(cu(frames[t]["desvel"]).reshape(B), cu(frames[t]["quat"]), state[t & 1], (out, dst[0], dst[1]), 0, stream=sb)
         sb.synchronize()
         assert torch.equal(out, ref[t][0]) and torch.equal(dst[0], ref[t][1]) and torch.equal(dst[1], ref[t][2]), t
     del out, dst
@@ -200,9 +167,9 @@ def test_serving_forms_equal_eager_forward():
     g = eng.graphed_step(B)
     st = (torch.zeros((3, B, 128), device="cuda"), torch.zeros((3, B, 128), device="cuda"))
     for t in range(T):
-        g.img.copy_(_cu(frames[t]["img_u8"])); g.desvel.copy_(_cu(frames[t]["desvel"]).reshape(B)); g.quat.copy_(_cu(frames[t]["quat"]))
+        g.img.copy_(cu(frames[t]["img_u8"])); g.desvel.copy_(cu(frames[t]["desvel"]).reshape(B)); g.quat.copy_(cu(frames[t]["quat"]))
         vg = g().clone()
-        ve, st = eng.forward(_cu(frames[t]["img_u8"]), _cu(frames[t]["desvel"]), _cu(frames[t]["quat"]), st)
+        ve, st = eng.forward(cu(frames[t]["img_u8"]), cu(frames[t]["desvel"]), cu(frames[t]["quat"]), st)
         assert torch.equal(vg, ve) and torch.equal(g.h, st[0]) and torch.equal(g.c, st[1]), t
     del g
     eng.close()
@@ -225,7 +192,7 @@ def test_pipelined_steps_equal_sequential_forward(stages):
     eng2 = host.Engine(blob, device=0)
     st = None
     for t in range(n):
-        v, st = eng2.forward(_cu(frs[t]["img_u8"]), _cu(frs[t]["desvel"]), _cu(frs[t]["quat"]), st)
+        v, st = eng2.forward(cu(frs[t]["img_u8"]), cu(frs[t]["desvel"]), cu(frs[t]["quat"]), st)
         assert torch.equal(got[t], v), t
     assert torch.equal(ps.h, st[0]) and torch.equal(ps.c, st[1])
     del ps
@@ -233,15 +200,15 @@ def test_pipelined_steps_equal_sequential_forward(stages):
 
 
 def test_float_checkpoint_runs():
-    sd = _float_state_dict(1, 3)
+    sd = float_state_dict(1, 3)
     blob = params.blob_from_state_dict(sd, 1)
     fp = synth.float_params(3, E=64)
     fp["decoder.weight"] = params.fold_spectral_norm(sd, "decoder")
     fp["nn_fc2.weight"] = params.fold_spectral_norm(sd, "nn_fc2")
     fr = synth.frames(9, 16)
     eng, eng2 = host.Engine(blob, device=0), host.Engine(params.blob_from_float_params(fp), device=0)
-    v, _ = eng.forward(_cu(fr["img_u8"]), _cu(fr["desvel"]), _cu(fr["quat"]))
-    v2, _ = eng2.forward(_cu(fr["img_u8"]), _cu(fr["desvel"]), _cu(fr["quat"]))
+    v, _ = eng.forward(cu(fr["img_u8"]), cu(fr["desvel"]), cu(fr["quat"]))
+    v2, _ = eng2.forward(cu(fr["img_u8"]), cu(fr["desvel"]), cu(fr["quat"]))
     assert np.abs(v.cpu().numpy() - v2.cpu().numpy()).max() <= 1e-5
     tv, _ = float_twin.FloatTwin(fp).forward(fr["img_u8"], fr["desvel"], fr["quat"])
     assert np.abs(v.cpu().numpy() - tv.numpy()).max() <= 5e-4
@@ -256,11 +223,11 @@ def test_refusals_between_attention_kinds():
     L = host.lib()
     ef, e8 = host.Engine(blob, device=0), host.Engine(b8, device=0)
     assert ef.attn_kind(0) == host.ATTN_F32 and e8.attn_kind(0) == host.ATTN_INT8
-    x = _cu(_ln_like(2, 1))
+    x = cu(ln_like(2, 1, 64))
     y = torch.empty_like(x)
     xq = torch.zeros((2, 128, 64), dtype=torch.int8, device="cuda")
     yq = torch.empty_like(xq)
-    img = _cu(fx["in0.img_u8"])
+    img = cu(fx["in0.img_u8"])
     stamps = torch.zeros(4096, dtype=torch.int64, device="cuda")
     s = host._stream_ptr(0)
     assert L.ita_mha_int8(ef._h, 0, x.data_ptr(), y.data_ptr(), 2, s) == -4

@@ -10,6 +10,7 @@ import pytest
 import heads_common as hc
 from conftest import golden_files
 from drone_oa_iree_vit_accelerator_amd import host, mha_heads_ref, params, synth
+from gpu_support import cu
 
 pytestmark = pytest.mark.gpu
 
@@ -23,11 +24,6 @@ def torch_cuda():
     import torch
     assert torch.cuda.is_available(), "GPU tests need a GPU"
     return torch
-
-
-def _cu(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 @functools.lru_cache(maxsize=None)
@@ -56,7 +52,7 @@ def test_attention_block_equals_the_definition(torch_cuda, path):
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     for B in (1, 3, cus + 3):
         idx = np.arange(B) % len(x)
-        xb = _cu(x[idx])
+        xb = cu(x[idx])
         gy, gt = eng.mha(xb, taps=True)
         assert tuple(gt["logits"].shape) == (B, H, 128, 128) and tuple(gt["probs"].shape) == (B, H, 128, 128)
         for k in TAPS:
@@ -91,7 +87,7 @@ def test_crafted_heads_do_not_leak(torch_cuda):
     assert (k2[..., 0::2] == 127).all() and (k2[..., 1::2] == -128).all()
     assert len(np.unique(taps["probs"][:, 0])) > 2 and len(np.unique(taps["probs"][:, 3])) > 2   # the other heads: real rows
     eng = host.Engine(blob, device=0)
-    gy, gt = eng.mha(_cu(x), taps=True)
+    gy, gt = eng.mha(cu(x), taps=True)
     assert (gt["probs"][:, 1] == 1).all().item()
     for k in TAPS:
         np.testing.assert_array_equal(gt[k].cpu().numpy(), taps[k], err_msg=k)
@@ -115,8 +111,8 @@ def test_whole_forward_two_steps_and_sequence(torch_cuda, oracle, path):
         o0 = hc.forward(oracle, imgs[0], t, fp, nl, H, fr[0]["desvel"], fr[0]["quat"])
         for mode in (0, 1):
             eng.set_tail_mode(mode)
-            v0, st0 = eng.forward(_cu(imgs[0]), _cu(fr[0]["desvel"]), _cu(fr[0]["quat"]))
-            v1, st1 = eng.forward(_cu(imgs[1]), _cu(fr[1]["desvel"]), _cu(fr[1]["quat"]), st0)
+            v0, st0 = eng.forward(cu(imgs[0]), cu(fr[0]["desvel"]), cu(fr[0]["quat"]))
+            v1, st1 = eng.forward(cu(imgs[1]), cu(fr[1]["desvel"]), cu(fr[1]["quat"]), st0)
             got = (v0, st0[0], st0[1], v1, st1[0], st1[1])
             # the second step from the state the engine carried (in mode 0 that is the oracle's own, bit for bit)
             o1 = hc.forward(oracle, imgs[1], t, fp, nl, H, fr[1]["desvel"], fr[1]["quat"], st0[0].cpu().numpy(), st0[1].cpu().numpy())
@@ -129,21 +125,21 @@ def test_whole_forward_two_steps_and_sequence(torch_cuda, oracle, path):
                     np.testing.assert_allclose(g, w, atol=2e-5, rtol=0, err_msg=f"{name} f32={f32}")
     # against the reference's own outputs, from its image: the suite's end-to-end bound on the velocity
     eng.set_tail_mode(1)
-    v, _ = eng.forward(_cu(d["in0.img_u8"]), _cu(d["in0.desvel"]), _cu(d["in0.quat"]))
+    v, _ = eng.forward(cu(d["in0.img_u8"]), cu(d["in0.desvel"]), cu(d["in0.quat"]))
     np.testing.assert_allclose(v.cpu().numpy(), d["s0.vel"], atol=5e-4, rtol=0)
     # the sequence form and the encoder's taps
     img = np.stack([f["img_u8"] for f in fr]); dv = np.stack([f["desvel"].reshape(2) for f in fr]); qt = np.stack([f["quat"] for f in fr])
     rs = np.random.RandomState(1)
     h0, c0 = ((0.3 * rs.standard_normal((3, 2, 128))).astype(np.float32) for _ in range(2))
-    st, vels = (_cu(h0), _cu(c0)), []
+    st, vels = (cu(h0), cu(c0)), []
     for s in range(3):
-        vs, st = eng.forward(_cu(img[s]), _cu(dv[s]), _cu(qt[s]), st)
+        vs, st = eng.forward(cu(img[s]), cu(dv[s]), cu(qt[s]), st)
         vels.append(vs)
-    sv, (sh, sc) = eng.forward_sequence(_cu(img), _cu(dv), _cu(qt), (_cu(h0), _cu(c0)))
+    sv, (sh, sc) = eng.forward_sequence(cu(img), cu(dv), cu(qt), (cu(h0), cu(c0)))
     torch.cuda.synchronize()
     assert eng.head_status() == 0
     assert torch.equal(sv, torch.stack(vels)) and torch.equal(sh, st[0]) and torch.equal(sc, st[1])
-    _, _, tp = eng.forward(_cu(img[0]), _cu(dv[0]), _cu(qt[0]), taps=True)
+    _, _, tp = eng.forward(cu(img[0]), cu(dv[0]), cu(qt[0]), taps=True)
     tok = oracle.tokenizer(img[0], fp["tokenizer.conv.weight"], fp["tokenizer.conv.bias"], fp["tokenizer.norm.weight"],
                            fp["tokenizer.norm.bias"])
     np.testing.assert_array_equal(tp["tokens"].cpu().numpy(), tok)
@@ -162,7 +158,7 @@ def test_whole_forward_two_steps_and_sequence(torch_cuda, oracle, path):
     idx = np.arange(cus + 3) % 5
     eng.close()
     eng = host.Engine(blob, device=0)      # (the first engine's workspace is pinned at six frames)
-    _, _, tp = eng.forward(_cu(img5[idx]), _cu(f5["desvel"][idx]), _cu(f5["quat"][idx]), taps=True)
+    _, _, tp = eng.forward(cu(img5[idx]), cu(f5["desvel"][idx]), cu(f5["quat"][idx]), taps=True)
     np.testing.assert_array_equal(tp["x1"].cpu().numpy(), x1[idx])
     np.testing.assert_array_equal(tp["x2"].cpu().numpy(), x2[idx])
     eng.close()
@@ -178,21 +174,21 @@ def test_split_forms_equal_forward(torch_cuda):
     zero = lambda: (torch.zeros((3, B, 128), device="cuda"), torch.zeros((3, B, 128), device="cuda"))
     ref, st = [], zero()
     for f in fr:
-        v, st = eng.forward(_cu(f["img_u8"]), _cu(f["desvel"]), _cu(f["quat"]), st)
+        v, st = eng.forward(cu(f["img_u8"]), cu(f["desvel"]), cu(f["quat"]), st)
         ref.append((v.clone(), st[0].clone(), st[1].clone()))
-    _, _, tp = eng.forward(_cu(fr[0]["img_u8"]), _cu(fr[0]["desvel"]), _cu(fr[0]["quat"]), taps=True)
-    vt, (ht, ct) = eng.tail(tp["x2"], _cu(fr[0]["desvel"]), _cu(fr[0]["quat"]))
+    _, _, tp = eng.forward(cu(fr[0]["img_u8"]), cu(fr[0]["desvel"]), cu(fr[0]["quat"]), taps=True)
+    vt, (ht, ct) = eng.tail(tp["x2"], cu(fr[0]["desvel"]), cu(fr[0]["quat"]))
     assert torch.equal(vt, ref[0][0]) and torch.equal(ht, ref[0][1]) and torch.equal(ct, ref[0][2])
     for split in (False, True):
         st = zero()
         for s, f in enumerate(fr):
             if split:
-                eng.encode(_cu(f["img_u8"]), 0)
+                eng.encode(cu(f["img_u8"]), 0)
                 eng.fold(B, 0, 0)
             else:
-                eng.front(_cu(f["img_u8"]), 0)
+                eng.front(cu(f["img_u8"]), 0)
             out = (torch.empty((B, 3), device="cuda"), *zero())
-            eng.back(_cu(f["desvel"]).reshape(B), _cu(f["quat"]), st, out, 0)
+            eng.back(cu(f["desvel"]).reshape(B), cu(f["quat"]), st, out, 0)
             torch.cuda.synchronize()
             assert all(torch.equal(a, b) for a, b in zip(out, ref[s])), (split, s)
             st = out[1:]
@@ -200,7 +196,7 @@ def test_split_forms_equal_forward(torch_cuda):
     vels = [torch.empty((B, 3), device="cuda") for _ in range(T)]
     sf, sb = torch.cuda.Stream(), torch.cuda.Stream()
     torch.cuda.synchronize()
-    eng.pipelined([_cu(f["img_u8"]) for f in fr], [_cu(f["desvel"]).reshape(B) for f in fr], [_cu(f["quat"]) for f in fr],
+    eng.pipelined([cu(f["img_u8"]) for f in fr], [cu(f["desvel"]).reshape(B) for f in fr], [cu(f["quat"]) for f in fr],
                   (h, c), vels, sf, sb)
     torch.cuda.synchronize()
     assert all(torch.equal(vels[s], ref[s][0]) for s in range(T)) and torch.equal(h, ref[-1][1]) and torch.equal(c, ref[-1][2])
@@ -237,7 +233,7 @@ def test_refusals_and_reload(torch_cuda, oracle):
     fr = synth.frames(3, 2)
     sh, sc = torch.zeros((3, 4, 128), device="cuda"), torch.zeros((3, 4, 128), device="cuda")
     with pytest.raises(host.ITAError, match=UNSUPPORTED):
-        eng.forward_slots(_cu(fr["img_u8"]), _cu(fr["desvel"]), _cu(fr["quat"]), sh, sc, torch.tensor([2, 0], device="cuda"))
+        eng.forward_slots(cu(fr["img_u8"]), cu(fr["desvel"]), cu(fr["quat"]), sh, sc, torch.tensor([2, 0], device="cuda"))
     torch.cuda.synchronize()
     assert float(sh.abs().max()) == 0.0 and float(sc.abs().max()) == 0.0        # nothing ran
     # (the long-sequence entry refuses E = 64 before it looks at the image, so its head-count refusal can only be reached
@@ -248,7 +244,7 @@ def test_refusals_and_reload(torch_cuda, oracle):
     e128.close()
     # the handle still runs after the refusals
     x, y, *_ = _block_case(GRAPHS[0])
-    np.testing.assert_array_equal(eng.mha(_cu(x[:2])).cpu().numpy(), y[:2])
+    np.testing.assert_array_equal(eng.mha(cu(x[:2])).cpu().numpy(), y[:2])
     # loads that stay refused: the float graph with two heads, a head count the kernel is not built for, and the
     # attention-only graph (int8 attention, float FFN) with more than one head
     set_h = lambda b, h: b[:28] + np.int32(h).tobytes() + b[32:]
@@ -267,12 +263,12 @@ def test_refusals_and_reload(torch_cuda, oracle):
     t1 = params.attention_tensors(d1, "attn0.", 0)
     x1 = d1["s0.attn0.x_q.in"]
     want, wt = oracle.mha(x1, t1, taps=True)
-    np.testing.assert_array_equal(eng.mha(_cu(x1)).cpu().numpy(), want)
-    np.testing.assert_array_equal(eng.mha_q8(_cu(wt["x_q"])).cpu().numpy(), wt["out_q"])      # needs the stream image
-    gy, gt = eng.mha(_cu(x1), taps=True)
+    np.testing.assert_array_equal(eng.mha(cu(x1)).cpu().numpy(), want)
+    np.testing.assert_array_equal(eng.mha_q8(cu(wt["x_q"])).cpu().numpy(), wt["out_q"])      # needs the stream image
+    gy, gt = eng.mha(cu(x1), taps=True)
     assert tuple(gt["logits"].shape) == (2, 128, 128)
     np.testing.assert_array_equal(gt["probs"].cpu().numpy(), wt["probs"])
-    vel, (h, c) = eng.forward(_cu(d1["in0.img_u8"]), _cu(d1["in0.desvel"]), _cu(d1["in0.quat"]))
+    vel, (h, c) = eng.forward(cu(d1["in0.img_u8"]), cu(d1["in0.desvel"]), cu(d1["in0.quat"]))
     ovel, oh, oc = oracle.forward(blob1, d1["in0.img_u8"], d1["in0.desvel"], d1["in0.quat"])
     np.testing.assert_allclose(vel.cpu().numpy(), ovel, atol=2e-5, rtol=0)
     np.testing.assert_allclose(h.cpu().numpy(), oh, atol=2e-5, rtol=0)

@@ -18,27 +18,20 @@ import pytest
 
 from conftest import golden_files
 from drone_oa_iree_vit_accelerator_amd import host, params, synth
+from gpu_support import cu, engine_pool
 import long_f32_common as lc
 from long_f32_common import SHAPES, LAYERS
-from test_gpu_long_layer import _long_f32 as quantiser_safe_tokens
-from test_only_attn_cpu import _fp as only_attn_fp, _tensors as only_attn_tensors
+from long_cases import long_f32 as quantiser_safe_tokens
+from only_attn_common import fp as only_attn_fp, tensors as only_attn_tensors
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = 12345.0
 
 
-def _cu(a):
-    import torch
-    return torch.from_numpy(np.array(a)).cuda()
-
-
 @pytest.fixture(scope="module")
 def engines():
-    e = {E: host.Engine(lc.case(E)[1], device=0) for E in LAYERS}
-    yield e
-    for eng in e.values():
-        eng.close()
+    yield from engine_pool(lambda E: lc.case(E)[1])
 
 
 def _check(got, want, e_torch, what):
@@ -55,9 +48,9 @@ def _check(got, want, e_torch, what):
 @pytest.mark.parametrize("E", [64, 128])
 @pytest.mark.parametrize("kind", ["plain", "ramp", "ramp_rev"])
 def test_mha_long_f32_against_float64(engines, kind, E, S, B):
-    eng = engines[E]
+    eng = engines(E)
     assert [eng.attn_kind(l) for l in range(LAYERS[E])] == [host.ATTN_F32] * LAYERS[E]
-    x = _cu(lc.inputs(kind, E, S, B))
+    x = cu(lc.inputs(kind, E, S, B))
     for l in range(LAYERS[E]):
         want, e_torch = lc.attn_ref(kind, E, S, B, l)
         _check(eng.mha_long_f32(x, l).cpu().numpy(), want, e_torch, f"mha_long_f32 {kind} E={E} S={S} B={B} layer {l}")
@@ -73,13 +66,13 @@ def test_mha_long_f32_one_dominant_key(engines, kind, E, S, B):
     Measured on an MI355X: err / e_torch 0.20 .. 1.87 over the 24 (kind, E, S, B, layer) cases.  (With Q, K and the
     logits summed as one fmaf chain each, the kernel's first form, it was 0.72 .. 3.22 and spike_last, E = 128, S = 256,
     layer 1 missed the bound: the block sums of ita_long_f32_kernel.h are there for this test.)"""
-    eng = engines[E]
+    eng = engines(E)
     fp = lc.case(E)[0]
     xn = lc.inputs(kind, E, S, B)
     pos = S - 1 if kind == "spike_last" else 0
     for l in range(LAYERS[E]):
         want, e_torch = lc.attn_ref(kind, E, S, B, l)
-        got = eng.mha_long_f32(_cu(xn), l).cpu().numpy()
+        got = eng.mha_long_f32(cu(xn), l).cpu().numpy()
         _check(got, want, e_torch, f"mha_long_f32 {kind} E={E} S={S} B={B} layer {l}")
         p, v = lc.probs64(xn, fp, l)
         onehot = p[:, :, pos] > 1.0 - 1e-6
@@ -93,9 +86,9 @@ def test_mha_long_f32_one_dominant_key(engines, kind, E, S, B):
 @pytest.mark.parametrize("E", [64, 128])
 def test_runs_repeatable_and_frames_independent(engines, E):
     import torch
-    eng = engines[E]
+    eng = engines(E)
     for S, B in ((256, 2), (384, 2), (128, 3)):
-        x = _cu(lc.inputs("ramp", E, S, B))
+        x = cu(lc.inputs("ramp", E, S, B))
         y = eng.mha_long_f32(x)
         assert torch.equal(y, eng.mha_long_f32(x)), (S, B)
         assert torch.equal(eng.mha_long_f32(x.flip(0).contiguous()).flip(0), y), (S, B)
@@ -115,8 +108,8 @@ def test_duplicated_sequence(engines, kind, E, S, B):
     0 .. S - 1 (bit-equal), and softmax over the doubled keys is the softmax over S keys: both halves within the rule's
     bound of the S-length float64 result"""
     import torch
-    eng = engines[E]
-    x = _cu(lc.inputs(kind, E, S, B))
+    eng = engines(E)
+    x = cu(lc.inputs(kind, E, S, B))
     xx = torch.cat([x, x], dim=1).contiguous()
     for l in range(LAYERS[E]):
         y = eng.mha_long_f32(xx, l)
@@ -129,9 +122,9 @@ def test_duplicated_sequence(engines, kind, E, S, B):
 @pytest.mark.parametrize("E", [64, 128])
 def test_one_tile_beside_mha_f32(engines, E):
     """no bit-equality (the summation order differs): both within the bound of float64 on the same rows"""
-    eng = engines[E]
+    eng = engines(E)
     for kind in ("plain", "ramp"):
-        x = _cu(lc.inputs(kind, E, 128, 3))
+        x = cu(lc.inputs(kind, E, 128, 3))
         for l in range(LAYERS[E]):
             want, e_torch = lc.attn_ref(kind, E, 128, 3, l)
             _check(eng.mha_long_f32(x, l).cpu().numpy(), want, e_torch, f"mha_long_f32 {kind} E={E} S=128 layer {l}")
@@ -145,9 +138,9 @@ def test_encoder_layer_long_f32_against_float64(engines, E, S, B):
     """LN2(x1 + ffn(x1)), x1 = LN1(x + attn(x)) against float64, bound from the same composition in torch f32 on the CPU;
     out aliasing x gives the bit-identical result"""
     import torch
-    eng = engines[E]
+    eng = engines(E)
     for kind in ("plain", "ramp"):
-        x = _cu(lc.inputs(kind, E, S, B))
+        x = cu(lc.inputs(kind, E, S, B))
         for l in range(LAYERS[E]):
             want, e_torch = lc.layer_ref(kind, E, S, B, l)
             got = eng.encoder_layer_long_f32(x, l)
@@ -159,9 +152,9 @@ def test_encoder_layer_long_f32_against_float64(engines, E, S, B):
 
 def test_encode_long_f32_is_the_layers_chained(engines):
     import torch
-    eng = engines[128]
+    eng = engines(128)
     assert eng.num_layers == 2
-    x = _cu(lc.inputs("ramp", 128, 384, 2))
+    x = cu(lc.inputs("ramp", 128, 384, 2))
     keep = x.clone()
     got = eng.encode_long_f32(x)
     assert torch.equal(x, keep), "encode_long_f32 changed its input"
@@ -184,7 +177,7 @@ def test_encoder_layer_long_f32_only_attn_equals_oracle(oracle, fixture, S, B):
     for l in range(L):
         assert eng.ffn_kind(l) == host.FFN_F32 and eng.attn_kind(l) == host.ATTN_INT8
         x = quantiser_safe_tokens(S + B + l, B, S, 64, t, l)
-        xc = _cu(x)
+        xc = cu(x)
         got = eng.encoder_layer_long_f32(xc, l)
         x1 = oracle.add_ln(x, oracle.mha(x, t, l), t[f"norm1_{l}.w"], t[f"norm1_{l}.b"])
         hid = np.maximum(oracle.linear_f32(x1, t[f"ffn{l}.w1f"], t[f"ffn{l}.b1f"]), np.float32(0))
@@ -222,23 +215,23 @@ def test_refusals_before_any_launch(engines):
     assert "ita_encoder_layer_long" in host.lib().ita_error_string().decode()
     e1.close(); e2.close()
     for E in (64, 128):
-        eng = engines[E]
+        eng = engines(E)
         for entry in ("ita_mha_long_f32", "ita_encoder_layer_long_f32"):
             for seq_len in (0, 200, 65664):
                 assert _status(eng, entry, seq_len) == -4, (E, entry, seq_len)
         # the same handle still runs a valid call correctly
         want, e_torch = lc.attn_ref("plain", E, 256, 2, 0)
-        _check(eng.mha_long_f32(_cu(lc.inputs("plain", E, 256, 2))).cpu().numpy(), want, e_torch, f"after refusals E={E}")
+        _check(eng.mha_long_f32(cu(lc.inputs("plain", E, 256, 2))).cpu().numpy(), want, e_torch, f"after refusals E={E}")
         with pytest.raises(host.ITAError, match="expected"):
-            eng.mha_long_f32(_cu(np.zeros((1, 128, E + 4), np.float32)))
+            eng.mha_long_f32(cu(np.zeros((1, 128, E + 4), np.float32)))
 
 
 # ---- 9: camera frames
 @pytest.mark.parametrize("E", [64, 128])
 def test_encode_frames_long_f32_is_tokenize_then_encode(engines, E):
     import torch
-    eng = engines[E]
-    frames = _cu(np.random.RandomState(E).randint(0, 256, (2, 97, 131)).astype(np.uint8))
+    eng = engines(E)
+    frames = cu(np.random.RandomState(E).randint(0, 256, (2, 97, 131)).astype(np.uint8))
     for th, tw in ((8, 16), (16, 16)):
         got = eng.encode_frames_long_f32(frames, th, tw)
         assert tuple(got.shape) == (2, th * tw, E) and bool(torch.isfinite(got).all())

@@ -17,20 +17,13 @@ import pytest
 from drone_oa_iree_vit_accelerator_amd import attention_propagate_f32_ref as apr
 from drone_oa_iree_vit_accelerator_amd import attention_rollout_f32_ref as arr
 from drone_oa_iree_vit_accelerator_amd import host
+from gpu_support import INVALID, UNSUPPORTED, Canaries, captured_replays, cu, engine_pool, refused
+from long_cases import long_case
 import long_f32_common as lc
 import long_f32_propagate_common as pc
 import long_f32_taps_common as ltc
 
 pytestmark = pytest.mark.gpu
-
-INVALID, UNSUPPORTED = "ita status -1", "ita status -4"
-CANARY = 0x77
-
-
-def _cu(a):
-    import torch
-    return torch.from_numpy(np.array(a)).cuda()
-
 
 def _bits(t):
     import torch
@@ -45,16 +38,12 @@ def _same(a, b):
 @pytest.fixture(scope="module")
 def engines():
     """(kind, E) -> Engine: the stock blob of E, or the flat one; opened on first use"""
-    made = {}
+    yield from engine_pool(lambda kind, E: pc.case(kind, E)[1], lambda kind, E: ("flat" if kind == "flat" else "stock", E))
 
-    def get(kind, E):
-        key = ("flat" if kind == "flat" else "stock", E)
-        if key not in made:
-            made[key] = host.Engine(pc.case(kind, E)[1], device=0)
-        return made[key]
-    yield get
-    for eng in made.values():
-        eng.close()
+
+def _call(eng, x, B, S, w, n_w, out, layer=0):
+    """the raw C entry on device pointers (or None)"""
+    host._chk(host.lib().ita_mha_long_f32_propagate(eng._h, layer, x, B, S, w, n_w, out, host._stream_ptr(eng.device)))
 
 
 def _all_probs(eng, x):
@@ -69,11 +58,11 @@ def _all_probs(eng, x):
 def test_propagate_against_own_probabilities_and_float64(engines, kind, S, B, E):
     import torch
     eng = engines(kind, E)
-    x, w = _cu(pc.inputs(kind, E, S, B)), _cu(pc.weights(S, B))
+    x, w = cu(pc.inputs(kind, E, S, B)), cu(pc.weights(S, B))
     got = eng.attention_propagate_long_f32(x, w)
     assert got.dtype == torch.float32 and tuple(got.shape) == (B, 64, S)
-    assert torch.equal(x, _cu(pc.inputs(kind, E, S, B))), "x was written to"
-    assert torch.equal(w, _cu(pc.weights(S, B))), "w was written to"
+    assert torch.equal(x, cu(pc.inputs(kind, E, S, B))), "x was written to"
+    assert torch.equal(w, cu(pc.weights(S, B))), "w was written to"
     g = got.cpu().numpy()
     assert np.isfinite(g).all()
 
@@ -101,17 +90,15 @@ def test_group_edges_and_canaries(engines, E):
     import torch
     kind, S, B = "ramp", 256, 2
     eng = engines(kind, E)
-    x, w = _cu(pc.inputs(kind, E, S, B)), _cu(pc.weights(S, B))
+    x, w = cu(pc.inputs(kind, E, S, B)), cu(pc.weights(S, B))
     full = eng.attention_propagate_long_f32(x, w)
     for R in pc.RS:
         wr = w[:, :R].contiguous()
-        buf = torch.full((4 * B * 64 * S + 4096,), CANARY, dtype=torch.int8, device="cuda")
-        host._chk(host.lib().ita_mha_long_f32_propagate(eng._h, 0, x.data_ptr(), B, S, wr.data_ptr(), R, buf.data_ptr(),
-                                                        host._stream_ptr(eng.device)))
+        c = Canaries({"out": ((B, R, S), torch.float32)}, pad=4 * B * (64 - R) * S + 4096)
+        _call(eng, x.data_ptr(), B, S, wr.data_ptr(), R, c.ptr("out"))
         torch.cuda.synchronize()
-        n = 4 * B * R * S
-        assert _same(buf[:n].view(torch.float32).reshape(B, R, S), full[:, :R].contiguous()), R
-        assert bool((buf[n:] == CANARY).all()), f"R = {R}: written behind the last row"
+        assert _same(c.views()["out"], full[:, :R].contiguous()), R
+        c.assert_untouched(written=("out",))
     # (R, S) weights: the same for every frame
     got = eng.attention_propagate_long_f32(x, w[1, :17])
     for b in range(B):
@@ -125,7 +112,7 @@ def test_group_edges_and_canaries(engines, E):
 @pytest.mark.parametrize("S,B", [(128, 3), (256, 2), (384, 2)])
 def test_same_bits_on_every_call_and_in_every_batch(engines, S, B, E):
     eng = engines("ramp", E)
-    x, w = _cu(pc.inputs("ramp", E, S, B)), _cu(pc.weights(S, B)[:, :17])
+    x, w = cu(pc.inputs("ramp", E, S, B)), cu(pc.weights(S, B)[:, :17])
     got = eng.attention_propagate_long_f32(x, w)
     assert _same(eng.attention_propagate_long_f32(x, w), got), "a second call gives other bits"
     flipped = eng.attention_propagate_long_f32(x.flip(0).contiguous(), w.flip(0).contiguous())
@@ -141,7 +128,7 @@ def test_production_path_undisturbed(engines, E):
     import torch
     S, B = 256, 2
     eng = engines("plain", E)
-    x, w = _cu(pc.inputs("plain", E, S, B)), _cu(pc.weights(S, B))
+    x, w = cu(pc.inputs("plain", E, S, B)), cu(pc.weights(S, B))
     y0 = eng.mha_long_f32(x)
     st0 = eng.attention_stats_long_f32(x)
     p0 = eng.attention_propagate_long_f32(x, w)
@@ -155,25 +142,10 @@ def test_captured_call_replays(engines):
     import torch
     S, B, E, R = 256, 2, 64, 17
     eng = engines("plain", E)
-    x, w = _cu(pc.inputs("plain", E, S, B)), _cu(pc.weights(S, B)[:, :R])
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        eager = eng.attention_propagate_long_f32(x, w)       # outside the capture: the workspace holds the call
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    out = torch.full((B, R, S), float("nan"), dtype=torch.float32, device="cuda")
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        host._chk(host.lib().ita_mha_long_f32_propagate(eng._h, 0, x.data_ptr(), B, S, w.data_ptr(), R, out.data_ptr(),
-                                                        host._stream_ptr(eng.device)))
-    for replay in range(2):
-        g.replay()
-        torch.cuda.synchronize()
-        assert _same(out, eager), replay
-        out.fill_(float("nan"))
-        torch.cuda.synchronize()
-    del g
+    x, w = cu(pc.inputs("plain", E, S, B)), cu(pc.weights(S, B)[:, :R])
+    c = Canaries({"out": ((B, R, S), torch.float32)})
+    captured_replays(lambda: {"out": eng.attention_propagate_long_f32(x, w)},
+                     lambda: _call(eng, x.data_ptr(), B, S, w.data_ptr(), R, c.ptr("out")), c, ("out",))
 
 
 def _refused(eng, status, S=256, seq_len=None, n_w=4, null=None, skew=None, layer=0):
@@ -181,25 +153,20 @@ def _refused(eng, status, S=256, seq_len=None, n_w=4, null=None, skew=None, laye
     import torch
     x = torch.zeros((1, S, eng.E), dtype=torch.float32, device="cuda")
     w = torch.ones((4 * S + 16,), dtype=torch.float32, device="cuda")
-    out = torch.full((4 * 4 * S + 32,), CANARY, dtype=torch.int8, device="cuda")
-    args = dict(x=x.data_ptr(), w=w.data_ptr() + (4 if skew == "w" else 0), out=out.data_ptr() + (4 if skew == "out" else 0))
+    c = Canaries({"out": ((1, 4, S), torch.float32)}, pad=32)
+    args = dict(x=x.data_ptr(), w=w.data_ptr() + (4 if skew == "w" else 0), out=c.ptr("out", 4 if skew == "out" else 0))
     if null:
         args[null] = None
-    with pytest.raises(host.ITAError, match=status):
-        host._chk(host.lib().ita_mha_long_f32_propagate(eng._h, layer, args["x"], 1, S if seq_len is None else seq_len, args["w"],
-                                                        n_w, args["out"], host._stream_ptr(eng.device)))
-    torch.cuda.synchronize()
-    assert bool((out == CANARY).all()), "a refused call wrote to out"
+    refused(lambda: _call(eng, args["x"], 1, S if seq_len is None else seq_len, args["w"], n_w, args["out"], layer), c, status)
 
 
 def test_refusals_before_any_launch(engines):
-    from test_gpu_long_taps import _case as int8_case
     for name in ("vitlstm_E64_seed0_B2", "onlyattn1l_E64_s0_B2"):          # ITAW0001, ITAW0002: int8 attention
-        ei = host.Engine(int8_case(name)[3], device=0)
+        ei = host.Engine(long_case(name).blob, device=0)
         assert ei.attn_kind(0) == host.ATTN_INT8
         _refused(ei, UNSUPPORTED)
         assert "ita_mha_long_int8_propagate" in host.lib().ita_error_string().decode()
-        x = _cu(np.zeros((1, 256, ei.E), np.float32))
+        x = cu(np.zeros((1, 256, ei.E), np.float32))
         with pytest.raises(host.ITAError, match="attention_rollout_long"):
             ei.attention_rollout_long_f32(x, [0])
         ei.close()
@@ -216,8 +183,8 @@ def test_refusals_before_any_launch(engines):
     _refused(eng, INVALID, skew="out")
     # the handle still runs, and a good call is what the kernels' own probabilities say
     S, B = 128, 3
-    x = _cu(pc.inputs("plain", 64, S, B))
-    got = eng.attention_propagate_long_f32(x, _cu(pc.weights(S, B))).cpu().numpy()
+    x = cu(pc.inputs("plain", 64, S, B))
+    got = eng.attention_propagate_long_f32(x, cu(pc.weights(S, B))).cpu().numpy()
     assert pc.compare_taps(got, _all_probs(eng, x), pc.weights(S, B))[0] == []
 
 
@@ -252,7 +219,7 @@ def test_rollout_against_float64(engines, E, first_layer):
     S, B = 256, 2
     eng = engines("plain", E)
     assert eng.num_layers == lc.LAYERS[E]
-    x = _cu(lc.inputs("plain", E, S, B))
+    x = cu(lc.inputs("plain", E, S, B))
     for rows in ([200, 5, 130], None):          # key tiles 1, 0, 1; the single vector 1 / S
         got = eng.attention_rollout_long_f32(x, rows, first_layer)
         n = 3 if rows else 1
@@ -263,7 +230,7 @@ def test_rollout_against_float64(engines, E, first_layer):
         err = float(np.abs(g - want).max())
         print(f"rollout E={E} first_layer={first_layer} rows={rows}: error / bound {err / bound:.4f} (bound {bound:.3e}, e_torch {e:.3e})")
         assert err <= bound
-    assert torch.equal(x, _cu(lc.inputs("plain", E, S, B))), "x was written to"
+    assert torch.equal(x, cu(lc.inputs("plain", E, S, B))), "x was written to"
     for bad in ([3, 3], [S], [-1]):
         with pytest.raises(ValueError):
             eng.attention_rollout_long_f32(x, bad)
@@ -275,7 +242,7 @@ def test_rollout_of_more_rows_than_a_call_takes(engines):
     """70 rows run as 64 + 6: bit for bit the rows computed in two calls"""
     S, B, E = 256, 2, 128
     eng = engines("plain", E)
-    x = _cu(lc.inputs("plain", E, S, B))
+    x = cu(lc.inputs("plain", E, S, B))
     rows = [int(r) for r in np.random.RandomState(7).permutation(S)[:70]]
     many = eng.attention_rollout_long_f32(x, rows)
     assert tuple(many.shape) == (B, 70, S)
@@ -289,7 +256,7 @@ def test_attention_rollout_map_long_f32(engines, E):
     with the queries out of order"""
     import torch
     eng = engines("plain", E)
-    frames = _cu(np.random.RandomState(4).randint(0, 256, size=(2, 120, 180)).astype(np.uint8))
+    frames = cu(np.random.RandomState(4).randint(0, 256, size=(2, 120, 180)).astype(np.uint8))
     queries = [(15, 15), (0, 0), (3, 9)]
     got = eng.attention_rollout_map_long_f32(frames, 16, 16, queries)
     assert tuple(got.shape) == (2, 3, 16, 16) and got.dtype == torch.float32

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from drone_oa_iree_vit_accelerator_amd import host
+from gpu_support import cu
 import long_f32_common as lc
 import long_f32_taps_common as ltc
 import long_limits_common as ll
@@ -23,11 +24,6 @@ pytestmark = pytest.mark.gpu
 
 VOCAB = (192, 64, 3)                # V, singles, seed: the float statistics' vocabulary frames
 R = 16
-
-
-def _cu(a):
-    import torch
-    return torch.from_numpy(np.array(a)).cuda()
 
 
 def _bound(t, r):
@@ -66,8 +62,8 @@ def test_propagate_at_8192_against_float64(kind, E):
     S = 8192
     w, t, bound, e = _ref_8192(kind, E)
     eng = host.Engine(lc.case(E)[1], device=0)
-    x = _cu(lc.inputs(kind, E, S, 1))
-    got = eng.attention_propagate_long_f32(x, _cu(w))
+    x = cu(lc.inputs(kind, E, S, 1))
+    got = eng.attention_propagate_long_f32(x, cu(w))
     g = got.cpu().numpy()
     err = float(np.abs(g - t).max())
     print(f"propagate {kind} E={E} S={S}: |gpu - float64| = {err:.3e}, e_torch {e:.3e}, bound {bound:.3e}, err / bound {err / bound:.2f}")
@@ -108,12 +104,12 @@ def test_propagate_at_65536_on_a_vocabulary_frame(E):
     V, singles, seed = VOCAB
     w, t, bound, e = _ref_65536(E)
     eng = host.Engine(lc.case(E)[1], device=0)
-    x = _cu(ll.vocab_f32_frame(E, S, V, singles, seed))
-    got = eng.attention_propagate_long_f32(x, _cu(w))
+    x = cu(ll.vocab_f32_frame(E, S, V, singles, seed))
+    got = eng.attention_propagate_long_f32(x, cu(w))
     g = got.cpu().numpy()
     err = float(np.abs(g - t).max())
     print(f"propagate vocabulary E={E} S={S}: |gpu - float64| = {err:.3e}, e_torch {e:.3e}, bound {bound:.3e}, err / bound {err / bound:.2f}")
     assert np.isfinite(g).all() and err <= bound
     assert torch.equal(got[:, 3].view(torch.int32), eng.attention_rows_long_f32(x, [S - 1])[:, 0].view(torch.int32)), "the one-hot row"
-    assert torch.equal(got.view(torch.int32), eng.attention_propagate_long_f32(x, _cu(w)).view(torch.int32))
+    assert torch.equal(got.view(torch.int32), eng.attention_propagate_long_f32(x, cu(w)).view(torch.int32))
     eng.close()

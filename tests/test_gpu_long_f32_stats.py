@@ -11,69 +11,47 @@ Worst error / bound against float64 measured on the MI355X over all cases: col_m
 row_gap 0.27 (ramp, E = 64, S = 256); the CPU model of the kernel gives the same figures on every case."""
 import numpy as np
 import pytest
+import torch
 
 from drone_oa_iree_vit_accelerator_amd import attention_stats_f32_ref as asr
 from drone_oa_iree_vit_accelerator_amd import host
+from gpu_support import INVALID, UNSUPPORTED, Canaries, captured_replays, cu, engine_pool, refused, same_bits, to_numpy
+from long_cases import long_case
 import long_f32_common as lc
 import long_f32_stats_common as sc
 
 pytestmark = pytest.mark.gpu
 
 STATS = host.LONG_F32_STATS
-INVALID, UNSUPPORTED = "ita status -1", "ita status -4"
 ROW_TAPS = ("logits", "row_max", "row_sum")
-
-
-def _cu(a):
-    import torch
-    return torch.from_numpy(np.array(a)).cuda()
-
-
-def _np(t):
-    return {k: v.cpu().numpy() for k, v in t.items()}
 
 
 @pytest.fixture(scope="module")
 def engines():
     """(kind, E) -> Engine: the stock blob of E, or the flat one; opened on first use"""
-    made = {}
-
-    def get(kind, E):
-        key = ("flat" if kind == "flat" else "stock", E)
-        if key not in made:
-            made[key] = host.Engine(sc.case(kind, E)[1], device=0)
-        return made[key]
-    yield get
-    for eng in made.values():
-        eng.close()
+    yield from engine_pool(lambda kind, E: sc.case(kind, E)[1], lambda kind, E: ("flat" if kind == "flat" else "stock", E))
 
 
 def _taps_of_all_rows(eng, x):
     """logits (B, S, S), row_max, row_sum (B, S) of every query row, in taps calls of at most 1024 rows"""
     S = x.shape[1]
-    parts = [_np(eng._long_f32_taps(x, list(range(r0, min(r0 + host.LONG_MAX_ROWS, S))), 0, ROW_TAPS)[1])
+    parts = [to_numpy(eng._long_f32_taps(x, list(range(r0, min(r0 + host.LONG_MAX_ROWS, S))), 0, ROW_TAPS)[1])
              for r0 in range(0, S, host.LONG_MAX_ROWS)]
     return {k: np.concatenate([p[k] for p in parts], axis=1) for k in ROW_TAPS}
-
-
-def _same_bits(a, b):
-    import torch
-    return all(a[k].dtype == b[k].dtype and torch.equal(a[k].view(torch.int32), b[k].view(torch.int32)) for k in STATS)
 
 
 @pytest.mark.parametrize("E", [64, 128])
 @pytest.mark.parametrize("kind,S,B", sc.CASES)
 def test_stats_against_own_probabilities_and_float64(engines, kind, S, B, E):
-    import torch
     eng = engines(kind, E)
-    x = _cu(sc.inputs(kind, E, S, B))
+    x = cu(sc.inputs(kind, E, S, B))
     got = eng.attention_stats_long_f32(x)
     assert tuple(got) == STATS + ("row_entropy",)
     for k, v in got.items():
         assert tuple(v.shape) == (B, S) and v.dtype == (torch.int32 if k.endswith("_nnz") else torch.float32), k
-    assert torch.equal(x, _cu(sc.inputs(kind, E, S, B))), "x was written to"
+    assert torch.equal(x, cu(sc.inputs(kind, E, S, B))), "x was written to"
     assert torch.equal(got["row_entropy"], torch.log(got["row_sum"]) + got["row_gap"])
-    g = _np(got)
+    g = to_numpy(got)
     assert all(np.isfinite(g[k]).all() for k in g) and (g["row_gap"] >= 0).all()
 
     # 1. against the kernels' own probabilities
@@ -85,7 +63,7 @@ def test_stats_against_own_probabilities_and_float64(engines, kind, S, B, E):
     occurring = float(np.sort(inside)[len(inside) // 2])       # a boundary that sits on a value P holds
     assert (P == np.float32(occurring)).any()
     for p_min in (1.0 / 16, occurring):
-        c = _np(eng._long_f32_stats(x, 0, ("row_nnz", "col_nnz"), p_min))
+        c = to_numpy(eng._long_f32_stats(x, 0, ("row_nnz", "col_nnz"), p_min))
         keep = P >= np.float32(p_min)
         np.testing.assert_array_equal(c["row_nnz"], keep.sum(-1), err_msg=f"row_nnz at p_min = {p_min!r}")
         np.testing.assert_array_equal(c["col_nnz"], keep.sum(-2), err_msg=f"col_nnz at p_min = {p_min!r}")
@@ -105,24 +83,18 @@ def test_stats_against_own_probabilities_and_float64(engines, kind, S, B, E):
 @pytest.mark.parametrize("S,B", [(128, 3), (256, 2), (384, 2)])
 def test_same_bits_on_every_call_and_in_every_batch(engines, S, B, E):
     eng = engines("ramp", E)
-    x = _cu(sc.inputs("ramp", E, S, B))
+    x = cu(sc.inputs("ramp", E, S, B))
     got = eng._long_f32_stats(x, 0, STATS, sc.P_MIN)
-    assert _same_bits(eng._long_f32_stats(x, 0, STATS, sc.P_MIN), got), "a second call gives other bits"
+    assert same_bits(eng._long_f32_stats(x, 0, STATS, sc.P_MIN), got, STATS), "a second call gives other bits"
     flipped = eng._long_f32_stats(x.flip(0).contiguous(), 0, STATS, sc.P_MIN)
-    assert _same_bits({k: v.flip(0) for k, v in flipped.items()}, got), "a frame's result depends on its place in the batch"
+    assert same_bits({k: v.flip(0) for k, v in flipped.items()}, got, STATS), "a frame's result depends on its place in the batch"
     for b in range(B):
         alone = eng._long_f32_stats(x[b:b + 1].contiguous(), 0, STATS, sc.P_MIN)
-        assert _same_bits(alone, {k: v[b:b + 1] for k, v in got.items()}), f"frame {b} alone differs from frame {b} in the batch"
+        assert same_bits(alone, {k: v[b:b + 1] for k, v in got.items()}, STATS), f"frame {b} alone differs from frame {b} in the batch"
 
 
-def _canaries(B, S, pad=0):
-    import torch
-    return {k: torch.full((4 * B * S + pad,), 0x77, dtype=torch.int8, device="cuda") for k in STATS}
-
-
-def _views(c, B, S):
-    import torch
-    return {k: v[:4 * B * S].view(torch.int32 if k.endswith("_nnz") else torch.float32).reshape(B, S) for k, v in c.items()}
+def _canaries(B, S):
+    return Canaries({k: ((B, S), torch.int32 if k.endswith("_nnz") else torch.float32) for k in STATS})
 
 
 def _call(eng, x, st, S=None, p_min=sc.P_MIN):
@@ -134,83 +106,54 @@ def _call(eng, x, st, S=None, p_min=sc.P_MIN):
 @pytest.mark.parametrize("E", [64, 128])
 def test_each_statistic_alone(engines, E):
     """asked for alone a statistic has the bits of the full call, and what is not asked for is not written"""
-    import torch
     S, B = 384, 2
     eng = engines("plain", E)
-    x = _cu(sc.inputs("plain", E, S, B))
+    x = cu(sc.inputs("plain", E, S, B))
     full = eng._long_f32_stats(x, 0, STATS, sc.P_MIN)
     assert torch.equal(eng.attention_received_long_f32(x), full["col_mass"])
     for want in [(k,) for k in STATS] + [("row_max", "row_sum"), ("row_gap", "row_nnz"), ("col_mass", "col_nnz")]:
         c = _canaries(B, S)
-        _call(eng, x, host._MhaLongF32Stats(**{k: c[k].data_ptr() for k in want}))
+        _call(eng, x, host._MhaLongF32Stats(**c.ptrs(want)))
         torch.cuda.synchronize()
-        v = _views(c, B, S)
-        for k in STATS:
-            if k in want:
-                assert torch.equal(v[k].view(torch.int32), full[k].view(torch.int32)), (want, k)
-            else:
-                assert bool((c[k] == 0x77).all()), f"{k} was written by a call that asked for {want}"
+        assert same_bits(c.views(), full, want), want
+        c.assert_untouched(written=want)
 
 
 @pytest.mark.parametrize("E", [64, 128])
 def test_production_path_undisturbed(engines, E):
     """the statistics share the handle's workspace with mha_long_f32 and its taps: neither disturbs the other"""
-    import torch
     S, B = 256, 2
     eng = engines("plain", E)
-    x = _cu(sc.inputs("plain", E, S, B))
+    x = cu(sc.inputs("plain", E, S, B))
     y0 = eng.mha_long_f32(x)
     st0 = eng._long_f32_stats(x, 0, STATS, sc.P_MIN)
     assert torch.equal(eng.mha_long_f32(x), y0)
-    assert _same_bits(eng._long_f32_stats(x, 0, STATS, sc.P_MIN), st0)
+    assert same_bits(eng._long_f32_stats(x, 0, STATS, sc.P_MIN), st0, STATS)
     y1, _ = eng.mha_long_f32_taps(x, [0, 200])
     assert torch.equal(y1, y0)
-    assert _same_bits(eng._long_f32_stats(x, 0, STATS, sc.P_MIN), st0)
+    assert same_bits(eng._long_f32_stats(x, 0, STATS, sc.P_MIN), st0, STATS)
 
 
 def test_captured_call_replays(engines):
-    import torch
     S, B, E = 256, 2, 64
     eng = engines("plain", E)
-    x = _cu(sc.inputs("plain", E, S, B))
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        eager = eng._long_f32_stats(x, 0, STATS, sc.P_MIN)       # outside the capture: the workspace holds the call
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
+    x = cu(sc.inputs("plain", E, S, B))
     c = _canaries(B, S)
-    st = host._MhaLongF32Stats(**{k: v.data_ptr() for k, v in c.items()})
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        _call(eng, x, st)
-    for replay in range(2):
-        g.replay()
-        torch.cuda.synchronize()
-        assert _same_bits(_views(c, B, S), eager), replay
-        for v in c.values():
-            v.fill_(0x77)
-        torch.cuda.synchronize()
-    del g
+    st = host._MhaLongF32Stats(**c.ptrs())
+    captured_replays(lambda: eng._long_f32_stats(x, 0, STATS, sc.P_MIN), lambda: _call(eng, x, st), c, STATS)
 
 
 def _refused(eng, status, S=256, seq_len=None, null_x=False, want=STATS, skew=None, p_min=sc.P_MIN):
     """the call must raise with `status` and leave the canary-filled outputs untouched"""
-    import torch
     x = torch.zeros((1, S, eng.E), dtype=torch.float32, device="cuda")
-    c = _canaries(1, S, pad=16)
-    st = host._MhaLongF32Stats(**{k: c[k].data_ptr() + (2 if k == skew else 0) for k in want})
-    with pytest.raises(host.ITAError, match=status):
-        _call(eng, None if null_x else x, st, S if seq_len is None else seq_len, p_min)
-    torch.cuda.synchronize()
-    for k, v in c.items():
-        assert bool((v == 0x77).all()), f"a refused call wrote to {k}"
+    c = _canaries(1, S)
+    st = host._MhaLongF32Stats(**{k: c.ptr(k, 2 if k == skew else 0) for k in want})
+    refused(lambda: _call(eng, None if null_x else x, st, S if seq_len is None else seq_len, p_min), c, status)
 
 
 def test_refusals_before_any_launch(engines):
-    from test_gpu_long_taps import _case as int8_case
     for name in ("vitlstm_E64_seed0_B2", "onlyattn1l_E64_s0_B2"):          # ITAW0001, ITAW0002: int8 attention
-        ei = host.Engine(int8_case(name)[3], device=0)
+        ei = host.Engine(long_case(name).blob, device=0)
         assert ei.attn_kind(0) == host.ATTN_INT8
         _refused(ei, UNSUPPORTED)
         assert "ita_mha_long_int8_stats" in host.lib().ita_error_string().decode()
@@ -225,20 +168,19 @@ def test_refusals_before_any_launch(engines):
         _refused(eng, INVALID, p_min=p_min)
     # the handle still runs, and a good call is what the kernels' own probabilities say
     S, B = 128, 3
-    x = _cu(sc.inputs("plain", 64, S, B))
+    x = cu(sc.inputs("plain", 64, S, B))
     tp = _taps_of_all_rows(eng, x)
     ref = asr.stats_from_taps(tp["logits"], tp["row_max"], tp["row_sum"], sc.P_MIN)
-    assert sc.compare(_np(eng._long_f32_stats(x, 0, STATS, sc.P_MIN)), ref, S) == []
+    assert sc.compare(to_numpy(eng._long_f32_stats(x, 0, STATS, sc.P_MIN)), ref, S) == []
 
 
 @pytest.mark.parametrize("E,layer", [(64, 0), (128, 1)])
 def test_attention_received_map_long_f32(engines, E, layer):
     """u8 frames 120 x 180 on a 16 x 16 token grid (S = 256): the composition of tokenize_long, the float encoder layers
     below `layer` and attention_received_long_f32"""
-    import torch
     eng = engines("plain", E)
     assert eng.num_layers == lc.LAYERS[E] > layer
-    frames = _cu(np.random.RandomState(4).randint(0, 256, size=(2, 120, 180)).astype(np.uint8))
+    frames = cu(np.random.RandomState(4).randint(0, 256, size=(2, 120, 180)).astype(np.uint8))
     got = eng.attention_received_map_long_f32(frames, 16, 16, layer=layer)
     assert tuple(got.shape) == (2, 16, 16) and got.dtype == torch.float32
     y = eng.tokenize_long(frames, 16, 16)

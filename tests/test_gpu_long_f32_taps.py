@@ -14,6 +14,8 @@ import numpy as np
 import pytest
 
 from drone_oa_iree_vit_accelerator_amd import host
+from gpu_support import INVALID, UNSUPPORTED, Canaries, cu, engine_pool, refused, to_numpy
+from long_cases import long_case
 import long_f32_common as lc
 import long_f32_taps_common as ltc
 
@@ -22,25 +24,12 @@ pytestmark = pytest.mark.gpu
 MODELS = [(64, 0), (128, 0), (128, 1)]
 KINDS = ("plain", "ramp", "spike_first")
 TENSOR, ROW = host.LONG_F32_TENSOR_TAPS, host.LONG_ROW_TAPS
-INVALID, UNSUPPORTED = "ita status -1", "ita status -4"
-SENTINEL, CANARY, PAD = 12345.0, 77.0, 16
-
-
-def _cu(a):
-    import torch
-    return torch.from_numpy(np.array(a)).cuda()
-
-
-def _np(t):
-    return {k: v.cpu().numpy() for k, v in t.items()}
+SENTINEL, PAD = 12345.0, 64       # PAD: bytes behind every tap buffer
 
 
 @pytest.fixture(scope="module")
 def engines():
-    e = {E: host.Engine(lc.case(E)[1], device=0) for E in lc.LAYERS}
-    yield e
-    for eng in e.values():
-        eng.close()
+    yield from engine_pool(lambda E: lc.case(E)[1])
 
 
 def _probs_from_taps(g):
@@ -68,14 +57,14 @@ def _call(eng, x, y, st, S=None, layer=0):
 @pytest.mark.parametrize("kind", KINDS)
 def test_taps_against_float64(engines, kind, E, layer, S, B):
     import torch
-    eng = engines[E]
-    x = _cu(lc.inputs(kind, E, S, B))
+    eng = engines(E)
+    x = cu(lc.inputs(kind, E, S, B))
     rows = ltc.rows_for(kind, E, S, B, layer)
     y, got = eng.mha_long_f32_taps(x, rows, layer)
     assert set(got) == set(TENSOR + ROW)
     want_y = eng.mha_long_f32(x, layer)
     assert torch.equal(y, want_y)
-    g = _np(got)
+    g = to_numpy(got)
     for k in TENSOR:
         assert g[k].shape == (B, S, eng.P) and g[k].dtype == np.float32, k
     assert g["logits"].shape == g["probs"].shape == (B, len(rows), S) and g["row_max"].shape == g["row_sum"].shape == (B, len(rows))
@@ -101,11 +90,11 @@ def test_taps_against_float64(engines, kind, E, layer, S, B):
 def test_row_counts(engines, E, layer):
     """no rows with the four tensors, one row, all 128 rows of one tile"""
     import torch
-    eng, kind, (S, B) = engines[E], "plain", lc.SHAPES[0]
-    x = _cu(lc.inputs(kind, E, S, B))
+    eng, kind, (S, B) = engines(E), "plain", lc.SHAPES[0]
+    x = cu(lc.inputs(kind, E, S, B))
     want_y = eng.mha_long_f32(x, layer)
     _, full = eng.mha_long_f32_taps(x, range(S), layer)
-    g = _np(full)
+    g = to_numpy(full)
     _check_bounds(g, kind, E, S, B, layer, range(S))
     np.testing.assert_array_equal(g["row_max"], g["logits"].max(-1))
     np.testing.assert_array_equal(g["probs"], _probs_from_taps(g))
@@ -123,11 +112,11 @@ def test_the_most_rows(engines):
     import torch
     E, kind, layer, (S, B) = 64, "plain", 0, lc.SHAPES[3]
     assert (S, B) == (1024, 1)
-    eng = engines[E]
-    x = _cu(lc.inputs(kind, E, S, B))
+    eng = engines(E)
+    x = cu(lc.inputs(kind, E, S, B))
     y, got = eng._long_f32_taps(x, range(S), layer, ROW)
     assert torch.equal(y, eng.mha_long_f32(x, layer))
-    g = _np(got)
+    g = to_numpy(got)
     _check_bounds(g, kind, E, S, B, layer, range(S))
     np.testing.assert_array_equal(g["row_max"], g["logits"].max(-1))
     np.testing.assert_array_equal(g["probs"], _probs_from_taps(g))
@@ -137,33 +126,33 @@ def test_the_most_rows(engines):
         assert torch.equal(few[k], got[k][:, list(rows)]), k
 
 
-def _buffers(eng, B, S, n, want):
-    """name -> flat canary-filled f32 buffer of the tap's size plus PAD words"""
+def _canaries(eng, B, S, n, want, y=False):
+    """canary-filled f32 buffers of the taps in `want`, PAD bytes behind each; y: one for the (B, S, E) output as well"""
     import torch
-    size = dict(Q=B * S * eng.P, K=B * S * eng.P, V=B * S * eng.P, ctx=B * S * eng.P, logits=B * max(n, 1) * S,
-                probs=B * max(n, 1) * S, row_max=B * max(n, 1), row_sum=B * max(n, 1))
-    return {k: torch.full((size[k] + PAD,), CANARY, dtype=torch.float32, device="cuda") for k in want}, size
+    shape = dict(Q=(B, S, eng.P), K=(B, S, eng.P), V=(B, S, eng.P), ctx=(B, S, eng.P), logits=(B, max(n, 1), S),
+                 probs=(B, max(n, 1), S), row_max=(B, max(n, 1)), row_sum=(B, max(n, 1)), y=(B, S, eng.E))
+    return Canaries({k: (shape[k], torch.float32) for k in tuple(want) + (("y",) if y else ())}, pad=PAD)
 
 
 @pytest.mark.parametrize("E,layer", MODELS)
 def test_canaries_and_frame_independence(engines, E, layer):
     import torch
-    eng, kind, (S, B) = engines[E], "ramp", lc.SHAPES[1]
+    eng, kind, (S, B) = engines(E), "ramp", lc.SHAPES[1]
     assert B == 2
-    x = _cu(lc.inputs(kind, E, S, B))
+    x = cu(lc.inputs(kind, E, S, B))
     rows = ltc.rows_for(kind, E, S, B, layer)
     y, got = eng.mha_long_f32_taps(x, rows, layer)
-    t, size = _buffers(eng, B, S, len(rows), TENSOR + ROW)
-    st = host._MhaLongF32Taps(**{k: v.data_ptr() for k, v in t.items()})
+    c = _canaries(eng, B, S, len(rows), TENSOR + ROW)
+    st = host._MhaLongF32Taps(**c.ptrs())
     arr = (host.C.c_int * len(rows))(*rows)
     st.rows, st.n_rows = arr, len(rows)
     y1 = torch.empty_like(x)
     _call(eng, x, y1, st, layer=layer)
     torch.cuda.synchronize()
     assert torch.equal(y1, y)
-    for k, v in t.items():
-        assert bool((v[size[k]:] == CANARY).all()), f"the {k} tap wrote behind its end"
-        assert torch.equal(v[:size[k]].reshape(got[k].shape), got[k]), k
+    c.assert_untouched(written=TENSOR + ROW)
+    for k, v in c.views().items():
+        assert torch.equal(v.reshape(got[k].shape), got[k]), k
     # frame 1 of the batch equals the same frame run alone
     ya, ta = eng.mha_long_f32_taps(x[1:2].contiguous(), rows, layer)
     assert torch.equal(ya, y[1:2])
@@ -175,8 +164,8 @@ def test_canaries_and_frame_independence(engines, E, layer):
 def test_attention_map_long_f32(engines, E, layer):
     """2 frames of 97 x 131 -> an 8 x 16 token grid, queries out of order: tokenize_long, the layers below, the rows"""
     import torch
-    eng = engines[E]
-    frames = _cu(np.random.RandomState(4).randint(0, 256, size=(2, 97, 131)).astype(np.uint8))
+    eng = engines(E)
+    frames = cu(np.random.RandomState(4).randint(0, 256, size=(2, 97, 131)).astype(np.uint8))
     th, tw, queries = 8, 16, [(5, 11), (0, 3), (7, 15)]
     toks = [ty * tw + tx for ty, tx in queries]
     got = eng.attention_map_long_f32(frames, th, tw, queries, layer=layer)
@@ -195,34 +184,27 @@ def test_attention_map_long_f32(engines, E, layer):
 
 
 def _refused(eng, status, S=256, rows=(0, 5), n_rows=None, want=TENSOR + ROW, seq_len=None, skew=0):
-    """the call must raise with `status` and leave the sentinel-filled output and taps untouched; skew: bytes added to
-    every tap pointer (the buffers are PAD words larger)"""
+    """the call must raise with `status` and leave the canary-filled output and taps untouched; skew: bytes added to
+    every tap pointer (the buffers are PAD bytes larger)"""
     import torch
     B, n = 1, len(rows)
-    y = torch.full((B, S, eng.E), SENTINEL, dtype=torch.float32, device="cuda")
-    x = torch.zeros_like(y)
-    t, _ = _buffers(eng, B, S, n, want)
-    st = host._MhaLongF32Taps(**{k: v.data_ptr() + skew for k, v in t.items()})
+    x = torch.zeros((B, S, eng.E), dtype=torch.float32, device="cuda")
+    c = _canaries(eng, B, S, n, want, y=True)
+    st = host._MhaLongF32Taps(**{k: c.ptr(k, skew) for k in want})
     arr = (host.C.c_int * max(n, 1))(*rows)
     st.rows, st.n_rows = (arr if n else None), (n if n_rows is None else n_rows)
-    with pytest.raises(host.ITAError, match=status):
-        _call(eng, x, y, st, seq_len)
-    torch.cuda.synchronize()
-    assert bool((y == SENTINEL).all()), "a refused call wrote to its output"
-    for k, v in t.items():
-        assert bool((v == CANARY).all()), f"a refused call wrote to the {k} tap"
+    refused(lambda: _call(eng, x, c.views()["y"], st, seq_len), c, status)
 
 
 def test_refusals_before_any_launch(engines):
     import torch
-    from test_gpu_long_taps import _case as int8_case
     for name in ("vitlstm_E64_seed0_B2", "onlyattn1l_E64_s0_B2"):          # ITAW0001, ITAW0002: int8 attention
-        ei = host.Engine(int8_case(name)[3], device=0)
+        ei = host.Engine(long_case(name).blob, device=0)
         assert ei.attn_kind(0) == host.ATTN_INT8
         _refused(ei, UNSUPPORTED)
         assert "ita_mha_long_int8_taps" in host.lib().ita_error_string().decode()
         ei.close()
-    eng = engines[64]
+    eng = engines(64)
     _refused(eng, UNSUPPORTED, S=256, seq_len=200)                       # not a multiple of 128
     _refused(eng, INVALID, rows=(0, 5), n_rows=-1)
     _refused(eng, INVALID, rows=(0, 5), n_rows=1025)
@@ -241,17 +223,17 @@ def test_refusals_before_any_launch(engines):
         _refused(eng, INVALID, rows=(0, 5), want=(k,), skew=2)
     # the handle then still runs a valid call correctly
     kind, (S, B) = "plain", lc.SHAPES[1]
-    x = _cu(lc.inputs(kind, 64, S, B))
+    x = cu(lc.inputs(kind, 64, S, B))
     rows = ltc.rows_for(kind, 64, S, B, 0)
     y, got = eng.mha_long_f32_taps(x, rows)
     assert torch.equal(y, eng.mha_long_f32(x))
-    _check_bounds(_np(got), kind, 64, S, B, 0, rows)
+    _check_bounds(to_numpy(got), kind, 64, S, B, 0, rows)
 
 
 def test_refused_inside_a_stream_capture(engines):
     import torch
-    eng, kind, (S, B) = engines[64], "plain", lc.SHAPES[1]
-    xc = _cu(lc.inputs(kind, 64, S, B))
+    eng, kind, (S, B) = engines(64), "plain", lc.SHAPES[1]
+    xc = cu(lc.inputs(kind, 64, S, B))
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
@@ -261,14 +243,14 @@ def test_refused_inside_a_stream_capture(engines):
     y = torch.full_like(xc, SENTINEL)
     yg = torch.empty_like(xc)
     g = torch.cuda.CUDAGraph()
-    refused = None
+    message = None
     with torch.cuda.graph(g):
         host._chk(host.lib().ita_mha_long_f32(eng._h, 0, xc.data_ptr(), yg.data_ptr(), B, S, host._stream_ptr(eng.device)))
         try:
             _call(eng, xc, y, host._MhaLongF32Taps())
         except host.ITAError as e:
-            refused = str(e)
-    assert refused is not None and INVALID in refused and "capture" in refused, refused
+            message = str(e)
+    assert message is not None and INVALID in message and "capture" in message, message
     g.replay()
     torch.cuda.synchronize()
     assert torch.equal(yg, out)
@@ -277,4 +259,4 @@ def test_refused_inside_a_stream_capture(engines):
     rows = ltc.rows_for(kind, 64, S, B, 0)
     y2, got = eng.mha_long_f32_taps(xc, rows)
     assert torch.equal(y2, out)
-    _check_bounds(_np(got), kind, 64, S, B, 0, rows)
+    _check_bounds(to_numpy(got), kind, 64, S, B, 0, rows)

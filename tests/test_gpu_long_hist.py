@@ -7,29 +7,26 @@ The crafted frames of softmax_clamp_common have raw logits in about +-600, so th
 logits histogram are large; the S = 8192 case is held to the blockwise definition."""
 import numpy as np
 import pytest
+import torch
 
 from drone_oa_iree_vit_accelerator_amd import attention_hist_ref as ahr
 from drone_oa_iree_vit_accelerator_amd import attention_stats_ref as asr
 from drone_oa_iree_vit_accelerator_amd import host, params, synth
 from drone_oa_iree_vit_accelerator_amd import mha_heads_ref as ref
+from gpu_support import INVALID, UNSUPPORTED, Canaries, captured_replays, cu, refused, to_numpy
 from heads_common import FIX_HEADS_2L, case as heads_case
+from long_cases import long_case
 import long_hist_common as lhc
 import softmax_clamp_common as scc
-from test_gpu_long_layer import _case, _cu
 
 pytestmark = pytest.mark.gpu
 
 NAMES = lhc.NAMES
-INVALID, UNSUPPORTED = "ita status -1", "ita status -4"
 I64 = ("logits", "shifts", "probs", "logits_out")
 
 
-def _np(t):
-    return {k: v.cpu().numpy() for k, v in t.items()}
-
-
 def _equal(got, want, msg):
-    g = _np(got)
+    g = to_numpy(got)
     assert tuple(k for k in g if k in NAMES) == NAMES
     for k in NAMES:
         assert g[k].dtype == want[k].dtype and g[k].shape == want[k].shape, (msg, k, g[k].dtype, g[k].shape)
@@ -42,40 +39,22 @@ def _call(eng, x, st, S=None, B=None, layer=0):
                                                 host.C.byref(st) if st is not None else None, host._stream_ptr(eng.device)))
 
 
-def _nbytes(k, B):
-    return B * lhc.WIDTH[k] * (4 if k == "acc_range" else 8)
-
-
-def _canaries(B, pad=16):
-    """byte buffers of 0x77, `pad` bytes longer than the output: the sentinel behind it"""
-    import torch
-    return {k: torch.full((_nbytes(k, B) + pad,), 0x77, dtype=torch.int8, device="cuda") for k in NAMES}
-
-
-def _views(c, B):
-    import torch
-    return {k: c[k][:_nbytes(k, B)].view(torch.int32 if k == "acc_range" else torch.int64).reshape(B, lhc.WIDTH[k]) for k in c}
-
-
-def _sentinels_whole(c, B, written=NAMES):
-    for k, v in c.items():
-        tail = v[_nbytes(k, B):] if k in written else v
-        assert bool((tail == 0x77).all()), f"bytes behind (or of an output not asked for) {k} were written"
+def _canaries(B):
+    return Canaries({k: ((B, lhc.WIDTH[k]), torch.int32 if k == "acc_range" else torch.int64) for k in NAMES})
 
 
 @pytest.mark.parametrize("S,B", lhc.SHAPES)
 @pytest.mark.parametrize("name,l", lhc.FIXTURES)
 def test_hist_equals_the_definition(name, l, S, B):
-    import torch
-    _, _, _, _, blob = _case(name)
+    blob = long_case(name).blob
     x, want = lhc.expected(name, l, S, B)
     eng = host.Engine(blob, device=0)
     forms = eng.layer_forms(l)
     assert forms["attn_image"] and forms["fast"] == lhc.FAST[name], (name, forms)
-    xc = _cu(x)
+    xc = cu(x)
     got = eng.attention_histograms_long(xc, l)
     _equal(got, want, f"{name} layer {l} S={S}")
-    assert torch.equal(xc, _cu(x)), "x was written to"
+    assert torch.equal(xc, cu(x)), "x was written to"
     # the same bytes twice, and whatever the batch position of a frame
     again = eng.attention_histograms_long(xc, l)
     assert all(torch.equal(again[k], got[k]) for k in NAMES)
@@ -85,20 +64,20 @@ def test_hist_equals_the_definition(name, l, S, B):
     # each single pointer gives that output alone, through the C entry into canary-filled buffers
     for k in NAMES:
         c = _canaries(B)
-        _call(eng, xc, host._MhaLongHist(**{k: c[k].data_ptr()}), layer=l)
+        _call(eng, xc, host._MhaLongHist(**c.ptrs((k,))), layer=l)
         torch.cuda.synchronize()
-        assert torch.equal(_views(c, B)[k], got[k]), k
-        _sentinels_whole(c, B, written=(k,))
+        assert torch.equal(c.views()[k], got[k]), k
+        c.assert_untouched(written=(k,))
     eng.close()
 
 
 def test_stage_histograms():
-    import torch
     name, l, S, B = "vit2l_us_E128_s1_B2", 1, 256, 2
-    _, _, t, _, blob = _case(name)
+    case = long_case(name)
+    t, blob = case.t, case.blob
     x, want = lhc.expected(name, l, S, B)
     eng = host.Engine(blob, device=0)
-    got = eng.attention_histograms_long(_cu(x), l, stages=True)
+    got = eng.attention_histograms_long(cu(x), l, stages=True)
     assert tuple(got) == NAMES + host.LONG_HIST_STAGES
     _equal(got, want, "with stages")
     _, tp = ref.mha(x, t, 1, l)
@@ -117,7 +96,7 @@ def test_crafted_clamp_frames(form, S):
     eng = host.Engine(scc.blob(form), device=0)
     forms = eng.layer_forms(0)
     assert forms["attn_image"] and forms["fast"] == (form == "fast"), forms
-    g = _np(eng.attention_histograms_long(_cu(x)))
+    g = to_numpy(eng.attention_histograms_long(cu(x)))
     np.testing.assert_array_equal(g["logits_out"], np.stack([(raw < -128).sum((-2, -1)), (raw > 127).sum((-2, -1))], axis=1))
     for k in ("logits", "shifts", "probs", "logits_out"):
         np.testing.assert_array_equal(g[k], want[k], err_msg=k)
@@ -129,12 +108,12 @@ def test_crafted_clamp_frames(form, S):
 def test_frames_entry():
     """u8 frames 60 x 90 -> an 8 x 16 token grid, layers 0 and 1 of the two-layer E = 128 blob: the composition of
     tokenize_long, encoder_layer_long and attention_histograms_long"""
-    import torch
     name = "vit2l_us_E128_s1_B2"
-    _, nl, t, _, blob = _case(name)
+    case = long_case(name)
+    nl, t, blob = case.num_layers, case.t, case.blob
     assert nl == 2
     eng = host.Engine(blob, device=0)
-    frames = _cu(np.random.RandomState(4).randint(0, 256, size=(2, 60, 90)).astype(np.uint8))
+    frames = cu(np.random.RandomState(4).randint(0, 256, size=(2, 60, 90)).astype(np.uint8))
     for layer in (0, 1):
         got = eng.attention_histograms_frames_long(frames, 8, 16, layer=layer)
         y = eng.tokenize_long(frames, 8, 16)
@@ -148,55 +127,34 @@ def test_frames_entry():
 
 def test_captured_call_replays():
     """one call captured on one stream: every replay sets the outputs to zero again"""
-    import torch
     name, l, S, B = "vitlstm_E64_seed0_B2", 0, 256, 2
-    _, _, _, _, blob = _case(name)
+    blob = long_case(name).blob
     eng = host.Engine(blob, device=0)
     x, want = lhc.expected(name, l, S, B)
-    xc = _cu(x)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        eager = eng.attention_histograms_long(xc)         # outside the capture: the workspace exists
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    _equal(eager, want, "eager")
+    xc = cu(x)
     c = _canaries(B)
-    st = host._MhaLongHist(**{k: v.data_ptr() for k, v in c.items()})
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        _call(eng, xc, st)
-    for replay in range(2):
-        g.replay()
-        torch.cuda.synchronize()
-        got = _views(c, B)
-        for k in NAMES:
-            assert torch.equal(got[k], eager[k]), (replay, k)
-    _sentinels_whole(c, B)
-    del g
+    st = host._MhaLongHist(**c.ptrs())
+    eager = captured_replays(lambda: eng.attention_histograms_long(xc), lambda: _call(eng, xc, st), c, NAMES)
+    _equal(eager, want, "eager")
     eng.close()
 
 
 def test_8192_keys():
     name, l, S, B = lhc.BIG
-    _, _, _, _, blob = _case(name)
+    blob = long_case(name).blob
     x, want = lhc.expected(name, l, S, B)
     lhc.conditions(want)
     eng = host.Engine(blob, device=0)
-    _equal(eng.attention_histograms_long(_cu(x), l), want, f"{name} S={S}")
+    _equal(eng.attention_histograms_long(cu(x), l), want, f"{name} S={S}")
     eng.close()
 
 
 def _refused(eng, status, S=256, seq_len=None, null_x=False, null_st=False, want=NAMES, skew=None):
     """the call must raise with `status` and leave the canary-filled outputs untouched"""
-    import torch
     x = torch.zeros((1, S, eng.E), dtype=torch.float32, device="cuda")
     c = _canaries(1)
-    st = host._MhaLongHist(**{k: c[k].data_ptr() + (4 if k == skew else 0) for k in want})
-    with pytest.raises(host.ITAError, match=status):
-        _call(eng, None if null_x else x, None if null_st else st, S if seq_len is None else seq_len, 1)
-    torch.cuda.synchronize()
-    _sentinels_whole(c, 1, written=())
+    st = host._MhaLongHist(**{k: c.ptr(k, 4 if k == skew else 0) for k in want})
+    refused(lambda: _call(eng, None if null_x else x, None if null_st else st, S if seq_len is None else seq_len, 1), c, status)
 
 
 def test_refusals_before_any_launch():
@@ -211,7 +169,8 @@ def test_refusals_before_any_launch():
     eh.close()
 
     name = "vitlstm_E64_seed0_B2"
-    E, _, t, _, blob = _case(name)
+    case = long_case(name)
+    E, t, blob = case.E, case.t, case.blob
     eng = host.Engine(blob, device=0)
     _refused(eng, UNSUPPORTED, seq_len=200)
     _refused(eng, UNSUPPORTED, seq_len=0)
@@ -221,8 +180,8 @@ def test_refusals_before_any_launch():
     for k in I64:
         _refused(eng, INVALID, skew=k)
     x, want = lhc.expected(name, 0, 256, 2)
-    _equal(eng.attention_histograms_long(_cu(x)), want, "after the refusals")
-    st = eng.attention_stats_long(_cu(x))
+    _equal(eng.attention_histograms_long(cu(x)), want, "after the refusals")
+    st = eng.attention_stats_long(cu(x))
     ws = asr.stats(x, t)
     for k in host.LONG_STATS:
         np.testing.assert_array_equal(st[k].cpu().numpy(), ws[k], err_msg=f"attention_stats_long after the refusals: {k}")

@@ -7,9 +7,10 @@ import pytest
 
 from drone_oa_iree_vit_accelerator_amd import attention_hist_ref as ahr
 from drone_oa_iree_vit_accelerator_amd import host
+from gpu_support import cu, to_numpy
+from long_cases import long_case
 import long_hist_common as lhc
 import long_limits_common as llc
-from test_gpu_long_layer import _case, _cu
 
 pytestmark = pytest.mark.gpu
 
@@ -18,7 +19,8 @@ S = 65536
 
 @pytest.mark.parametrize("name,l", llc.INT8_MODELS)
 def test_65536_keys_against_the_class_form(name, l):
-    _, _, t, _, blob = _case(name)
+    case = long_case(name)
+    t, blob = case.t, case.blob
     x, reps, cls, counts = llc.int8_vocab_frame(name, l, S)
     assert x.shape[:2] == (1, S) and len(reps) == 512 and int(counts.sum()) == S
     want = ahr.hist_from_classes(x[0, reps], counts, t, l)
@@ -26,7 +28,7 @@ def test_65536_keys_against_the_class_form(name, l):
         assert int(want[k].sum()) == 1 << 32, k
     assert max(int(want[k].max()) for k in ("logits", "shifts", "probs")) > 1 << 31
     eng = host.Engine(blob, device=0)
-    got = {k: v.cpu().numpy() for k, v in eng.attention_histograms_long(_cu(x), l).items()}
+    got = to_numpy(eng.attention_histograms_long(cu(x), l))
     eng.close()
     assert tuple(got) == lhc.NAMES
     for k in lhc.NAMES:

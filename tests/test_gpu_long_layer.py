@@ -15,59 +15,21 @@ selects, i.e. which instantiation of ita_long_proj_kernel / ita_long_attn_kernel
 test_long_f32_quantiser_edges gives the f32 entries ties, saturating and zero tokens on the FAST and the exact one of each E;
 so both forms run at both E, in the int8 form (E = 128 exact: tests/test_gpu_parity.py; E = 128 FAST: vit2l_us here) and
 in the f32 form."""
-import functools
-
 import numpy as np
 import pytest
 
 from conftest import golden_files
 from drone_oa_iree_vit_accelerator_amd import host, params, synth
 from heads_common import FIX_HEADS_2L, case as heads_case
-from test_only_attn_cpu import _fp as only_attn_fp
+from gpu_support import UNSUPPORTED, Canaries, cu, refused
+from long_cases import long_case, long_f32, long_inputs
+from only_attn_common import fp as only_attn_fp
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(128, 3), (256, 2), (384, 2), (1024, 1)]
-INV_SX = 0
 E64_BLOCKS, E64_VIT = "blocks_E64_seed2_B1", ["vitlstm_E64_seed0_B2", "vitlstm_E64_seed1_B2", "vitlstm_E64_seed2_B2"]
 E128_BLOCKS, E128_VIT, E128_FAST = ["blocks_E128_seed0_B1", "blocks_E128_seed1_B1"], "vit2l_E128_s0_B2", "vit2l_us_E128_s1_B2"
-
-
-@functools.lru_cache(maxsize=None)
-def _case(name):
-    """(E, num_layers, block tensors of every layer, float parameters or None, blob) of one fixture; read-only"""
-    d = params.load_fixture(golden_files(name + ".npz")[0])
-    E = int(d["meta.E"])
-    nl = int(d["meta.num_layers"]) if "meta.num_layers" in d else 1
-    fp = None
-    if name.startswith("vit"):
-        fp = synth.float_params(int(d["meta.seed"]), E=E, num_layers=nl, tail=(E == 64))
-    t = {}
-    for l in range(nl):
-        t.update(params.attention_tensors(d, f"attn{l}.", l))
-        t.update(params.ffn_tensors(d, f"ffn{l}.", l))
-    return E, nl, t, fp, params.blob_from_record(d, fp, E=E, num_layers=nl)
-
-
-def _cu(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _long_inputs(seed, B, S, E):
-    """structured codes: blocks of 32 similar tokens (all-noise rows make the integer softmax degenerate)"""
-    rs = np.random.RandomState(seed)
-    base = rs.standard_normal((B, S // 32, E)).repeat(32, axis=1) * 18.0
-    x = base + rs.standard_normal((B, S, E)) * 9.0
-    return np.clip(np.rint(x), -128, 127).astype(np.int8)
-
-
-def _long_f32(seed, B, S, E, t, l=0):
-    """f32 tokens that quantise to those codes: (codes + u) * s_x, u uniform in (-0.4, 0.4), s_x = 1 / scal[INV_SX]"""
-    codes = _long_inputs(seed, B, S, E).astype(np.float32)
-    u = np.random.RandomState(seed + 1000).uniform(-0.4, 0.4, size=codes.shape).astype(np.float32)
-    s_x = np.float32(1.0) / np.float32(t[f"attn{l}.scal"][INV_SX])
-    return ((codes + u) * s_x).astype(np.float32)
 
 
 def _layer(oracle, x, t, fp, l):
@@ -80,37 +42,40 @@ def _layer(oracle, x, t, fp, l):
 def test_mha_long_q8_e64_equals_oracle(oracle, S, B):
     """ita_long_*_kernel<FAST | exact, 64, int8>: the whole output against oracle.mha_q8; at S = 128 also ita_mha_q8"""
     for name in (E64_BLOCKS, E64_VIT[0], E64_VIT[1]):
-        E, _, t, _, blob = _case(name)
+        case = long_case(name)
+        E, t, blob = case.E, case.t, case.blob
         eng = host.Engine(blob, device=0)
-        xq = _long_inputs(S + B, B, S, E)
-        got = eng.mha_long_q8(_cu(xq)).cpu().numpy()
+        xq = long_inputs(S + B, B, S, E)
+        got = eng.mha_long_q8(cu(xq)).cpu().numpy()
         want = oracle.mha_q8(xq, t)
         np.testing.assert_array_equal(got, want, err_msg=name)
         assert len({r.tobytes() for r in got[0]}) > S // 4, name
         if S == 128:
-            np.testing.assert_array_equal(eng.mha_q8(_cu(xq)).cpu().numpy(), want, err_msg=name)
+            np.testing.assert_array_equal(eng.mha_q8(cu(xq)).cpu().numpy(), want, err_msg=name)
         eng.close()
 
 
 @pytest.mark.parametrize("S,B", [(128, 3), (384, 2)])
 def test_mha_long_q8_e128_fast_form(oracle, S, B):
     """ita_long_*_kernel<FAST, 128, int8>, which no blocks_E128 fixture selects: both layers of vit2l_us_E128_s1"""
-    E, nl, t, _, blob = _case(E128_FAST)
+    case = long_case(E128_FAST)
+    E, nl, t, blob = case.E, case.num_layers, case.t, case.blob
     eng = host.Engine(blob, device=0)
-    xq = _long_inputs(S + B, B, S, E)
+    xq = long_inputs(S + B, B, S, E)
     for l in range(nl):
-        np.testing.assert_array_equal(eng.mha_long_q8(_cu(xq), l).cpu().numpy(), oracle.mha_q8(xq, t, l), err_msg=f"layer {l}")
+        np.testing.assert_array_equal(eng.mha_long_q8(cu(xq), l).cpu().numpy(), oracle.mha_q8(xq, t, l), err_msg=f"layer {l}")
     eng.close()
 
 
 def test_mha_long_q8_e64_config5_size(oracle):
     """S = 8192 at E = 64: 16 sampled rows against oracle.mha_q8_rows, two runs bit-identical"""
     import torch
-    E, _, t, _, blob = _case(E64_VIT[0])
+    case = long_case(E64_VIT[0])
+    E, t, blob = case.E, case.t, case.blob
     eng = host.Engine(blob, device=0)
     S = 8192
-    xq = _long_inputs(99, 1, S, E)
-    x = _cu(xq)
+    xq = long_inputs(99, 1, S, E)
+    x = cu(xq)
     a1, a2 = eng.mha_long_q8(x), eng.mha_long_q8(x)
     assert torch.equal(a1, a2)
     rows = [0, 1, 127, 128, 129, 1000, 2047, 2048, 4095, 4096, 5000, 6143, 7000, 8063, 8064, 8191]
@@ -128,10 +93,11 @@ def test_mha_long_f32_equals_oracle(oracle, E, S, B):
     import torch
     names = (E64_BLOCKS, E64_VIT[0]) if E == 64 else (*E128_BLOCKS, E128_FAST)
     for name in names:
-        _, _, t, _, blob = _case(name)
+        case = long_case(name)
+        t, blob = case.t, case.blob
         eng = host.Engine(blob, device=0)
-        x = _long_f32(S + B, B, S, E, t)
-        xc = _cu(x)
+        x = long_f32(S + B, B, S, E, t)
+        xc = cu(x)
         got = eng.mha_long(xc)
         np.testing.assert_array_equal(got.cpu().numpy(), oracle.mha(x, t), err_msg=name)
         assert torch.equal(got, eng.mha_long(xc)), name
@@ -148,11 +114,12 @@ def test_encoder_layer_long_equals_oracle(oracle, E, S, B):
     encoder_layer; with out aliasing x; two runs bit-identical; a frame does not depend on its batch position"""
     import torch
     for name in (E64_VIT if E == 64 else [E128_VIT]):
-        _, nl, t, fp, blob = _case(name)
+        case = long_case(name)
+        nl, t, fp, blob = case.num_layers, case.t, case.fp, case.blob
         eng = host.Engine(blob, device=0)
         for l in range(nl):
-            x = _long_f32(S + B + l, B, S, E, t, l)
-            xc = _cu(x)
+            x = long_f32(S + B + l, B, S, E, t, l)
+            xc = cu(x)
             got = eng.encoder_layer_long(xc, l)
             np.testing.assert_array_equal(got.cpu().numpy(), _layer(oracle, x, t, fp, l), err_msg=f"{name} layer {l}")
             assert torch.equal(got, eng.encoder_layer_long(xc, l)), name
@@ -170,17 +137,18 @@ QUANT_EDGES = [(E64_VIT[0], True), (E64_VIT[1], False), (E128_VIT, False), (E128
 
 @pytest.mark.parametrize("name,fast", QUANT_EDGES)
 def test_long_f32_quantiser_edges(oracle, name, fast):
-    """the long kernels' f32 input at the quantiser's edges, which _long_f32's offsets of (-0.4, 0.4) never reach: zero
+    """the long kernels' f32 input at the quantiser's edges, which long_f32's offsets of (-0.4, 0.4) never reach: zero
     tokens, saturating +-50 tokens, a 1e30 token, exact ties 0.5 s and 1.5 s (to even: 0 and 2), a token scaled by 30, among
     ordinary ones at S = 256; mha_long, encoder_layer_long and the statistics against the oracle composition, on the FAST
     and on the exact fixture of each E"""
     from drone_oa_iree_vit_accelerator_amd import attention_stats_ref as asr
-    E, _, t, fp, blob = _case(name)
+    case = long_case(name)
+    E, t, fp, blob = case.E, case.t, case.fp, case.blob
     eng = host.Engine(blob, device=0)
     forms = eng.layer_forms(0)
     assert forms["fast"] == fast and forms["attn_image"], (name, forms)
     S, B = 256, 2
-    x = _long_f32(S + B, B, S, E, t)
+    x = long_f32(S + B, B, S, E, t)
     s = np.float32(float(params.load_fixture(golden_files(name + ".npz")[0])["attn0.quant.scale"]))
     x[0, 0:3], x[0, 3:6], x[0, 6:9] = 0.0, 50.0, -50.0
     x[0, 130] = 1e30
@@ -193,9 +161,9 @@ def test_long_f32_quantiser_edges(oracle, name, fast):
     assert (xq[0, 140] == 0).all() and (xq[0, 141] == 2).all() and (xq[1, 201] == 2).all()      # ties to even
     assert (xq[0, 130] == 127).all() and (xq[0, 3:6] == 127).all() and (xq[0, 6:9] == -128).all() and (xq[0, 0:3] == 0).all()
     assert (np.abs(xq[0, 150].astype(np.int32)) >= 127).sum() > E // 2
-    xc = _cu(x)
+    xc = cu(x)
     np.testing.assert_array_equal(eng.mha_long(xc).cpu().numpy(), oy, err_msg=name)
-    np.testing.assert_array_equal(eng.mha_long_q8(_cu(xq)).cpu().numpy(), otaps["out_q"], err_msg=name)
+    np.testing.assert_array_equal(eng.mha_long_q8(cu(xq)).cpu().numpy(), otaps["out_q"], err_msg=name)
     want = _layer(oracle, x, t, fp, 0)
     got = eng.encoder_layer_long(xc, 0).cpu().numpy()
     print(f"{name}: the 1e30 token's row: oracle {want[0, 130, :4]}, engine {got[0, 130, :4]}")
@@ -209,12 +177,13 @@ def test_long_f32_quantiser_edges(oracle, name, fast):
 def test_encode_long_is_the_layers_chained(oracle):
     """the two-layer E = 128 blob: encode_long equals layer 0 then layer 1, and the oracle's chain"""
     import torch
-    E, nl, t, fp, blob = _case(E128_VIT)
+    case = long_case(E128_VIT)
+    E, nl, t, fp, blob = case.E, case.num_layers, case.t, case.fp, case.blob
     assert nl == 2
     eng = host.Engine(blob, device=0)
     S, B = 384, 2
-    x = _long_f32(7, B, S, E, t)
-    xc = _cu(x)
+    x = long_f32(7, B, S, E, t)
+    xc = cu(x)
     keep = xc.clone()
     got = eng.encode_long(xc)
     assert torch.equal(xc, keep), "encode_long changed its input"
@@ -224,14 +193,11 @@ def test_encode_long_is_the_layers_chained(oracle):
 
 
 def _refused(eng, call):
-    """call(out) must raise ITAError UNSUPPORTED and leave the sentinel-filled output untouched"""
+    """call(x, out) must raise ITAError UNSUPPORTED and leave the canary-filled output untouched"""
     import torch
-    out = torch.full((1, 256, eng.E), 12345.0, dtype=torch.float32, device="cuda")
-    x = torch.zeros_like(out)
-    with pytest.raises(host.ITAError, match="ita status -4"):
-        call(x, out)
-    torch.cuda.synchronize()
-    assert bool((out == 12345.0).all()), "a refused call wrote to its output"
+    x = torch.zeros((1, 256, eng.E), dtype=torch.float32, device="cuda")
+    c = Canaries({"out": (x.shape, torch.float32)})
+    refused(lambda: call(x, c.views()["out"]), c, UNSUPPORTED)
 
 
 def _mha_long_into(eng):
@@ -262,8 +228,8 @@ def test_refusals_before_any_launch(oracle):
     assert eo.ffn_kind(0) == host.FFN_F32
     _refused(eo, lambda x, out: eo.encoder_layer_long(x, 0, out=out))
     t = params.attention_tensors(d, "attn0.", 0)
-    xq = _long_inputs(5, 2, 256, 64)
-    np.testing.assert_array_equal(eo.mha_long_q8(_cu(xq)).cpu().numpy(), oracle.mha_q8(xq, t))
-    x = _long_f32(5, 2, 256, 64, t)
-    np.testing.assert_array_equal(eo.mha_long(_cu(x)).cpu().numpy(), oracle.mha(x, t))
+    xq = long_inputs(5, 2, 256, 64)
+    np.testing.assert_array_equal(eo.mha_long_q8(cu(xq)).cpu().numpy(), oracle.mha_q8(xq, t))
+    x = long_f32(5, 2, 256, 64, t)
+    np.testing.assert_array_equal(eo.mha_long(cu(x)).cpu().numpy(), oracle.mha(x, t))
     eo.close()

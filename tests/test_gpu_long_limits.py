@@ -26,13 +26,14 @@ import pytest
 
 from drone_oa_iree_vit_accelerator_amd import host
 from drone_oa_iree_vit_accelerator_amd import mha_heads_ref as mref
+from gpu_support import cu, engine_pool
 import float_flat_common as fc
 import long_f32_common as lc
 import long_f32_stats_common as lsc
 import long_f32_taps_common as ltc
 import long_limits_common as ll
 import long_taps_common as itc
-from test_gpu_long_layer import _case, _long_f32, _long_inputs
+from long_cases import long_case, long_f32, long_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -42,11 +43,6 @@ VOCAB_F32 = (192, 64, 3)            # V, singles, seed of the float statistics' 
 FRAMES, DISTINCT = 45000, 61
 
 
-def _cu(a):
-    import torch
-    return torch.from_numpy(np.array(a)).cuda()
-
-
 def _idx(rows):
     import torch
     return torch.tensor(list(rows), dtype=torch.long, device="cuda")
@@ -54,10 +50,7 @@ def _idx(rows):
 
 @pytest.fixture(scope="module")
 def engines():
-    e = {E: host.Engine(lc.case(E)[1], device=0) for E in lc.LAYERS}
-    yield e
-    for eng in e.values():
-        eng.close()
+    yield from engine_pool(lambda E: lc.case(E)[1])
 
 
 @pytest.fixture(scope="module")
@@ -78,7 +71,7 @@ def _attention_and_layer(eng, kind, E, S, B, layer, s, what):
     """mha_long_f32 and encoder_layer_long_f32 (also with out aliasing x) on the sampled rows; returns the attention"""
     import torch
     rows, want_a, e_a, want_l, e_l = ll.ref(kind, E, S, B, layer, s)
-    x, at = _cu(lc.inputs(kind, E, S, B)), _idx(rows)
+    x, at = cu(lc.inputs(kind, E, S, B)), _idx(rows)
     y = eng.mha_long_f32(x, layer)
     assert bool(torch.isfinite(y).all()), what
     _check(y[:, at].cpu().numpy(), want_a, e_a, f"mha_long_f32 {what}")
@@ -96,7 +89,7 @@ def _attention_and_layer(eng, kind, E, S, B, layer, s, what):
 @pytest.mark.parametrize("E,layer", ll.MODELS)
 @pytest.mark.parametrize("kind", ll.KINDS)
 def test_attention_and_layer_against_float64(engines, kind, E, layer, S, B):
-    _attention_and_layer(engines[E], kind, E, S, B, layer, 1, f"{kind} E={E} layer {layer} S={S} B={B}")
+    _attention_and_layer(engines(E), kind, E, S, B, layer, 1, f"{kind} E={E} layer {layer} S={S} B={B}")
 
 
 @pytest.mark.parametrize("S,B", ll.SIZES)
@@ -120,9 +113,9 @@ def test_flat_rows_against_float64(E, layer, s, S, B):
 def test_frames_and_repeats(engines, E, layer):
     """bit for bit: frame b of a B = 2 call is the B = 1 call on that frame; two runs agree (S = 8192 and 65536)"""
     import torch
-    eng = engines[E]
+    eng = engines(E)
     for S, B in ll.SIZES:
-        x = _cu(lc.inputs("ramp", E, S, B))
+        x = cu(lc.inputs("ramp", E, S, B))
         for f in (eng.mha_long_f32, eng.encoder_layer_long_f32):
             y = f(x, layer)
             assert torch.equal(y, f(x, layer)), (f.__name__, S)
@@ -139,7 +132,7 @@ def _probs_from_taps(g, n):
 
 def _check_taps(eng, kind, E, S, B, layer, rows, want):
     import torch
-    x = _cu(lc.inputs(kind, E, S, B))
+    x = cu(lc.inputs(kind, E, S, B))
     y, got = eng._long_f32_taps(x, rows, layer, want)
     assert torch.equal(y, eng.mha_long_f32(x, layer))
     g = {k: v.cpu().numpy() for k, v in got.items()}
@@ -160,15 +153,15 @@ def _check_taps(eng, kind, E, S, B, layer, rows, want):
 @pytest.mark.parametrize("E,layer", ll.MODELS)
 @pytest.mark.parametrize("kind", ["plain", "ramp"])
 def test_taps_against_float64(engines, kind, E, layer, S, B):
-    _check_taps(engines[E], kind, E, S, B, layer, ll.rows_for(S), TENSOR + ROW)
+    _check_taps(engines(E), kind, E, S, B, layer, ll.rows_for(S), TENSOR + ROW)
 
 
 def test_taps_the_most_rows_at_the_longest_sequence(engines):
     """1024 rows of S = 65536, row 65535 among them: the row table's last entry, 256 MiB of logits"""
     import torch
     S, rows = 65536, ll.many_rows(65536)
-    got = _check_taps(engines[64], "plain", 64, S, 1, 0, rows, ROW)
-    few = engines[64]._long_f32_taps(_cu(lc.inputs("plain", 64, S, 1)), ll.rows_for(S), 0, ROW)[1]
+    got = _check_taps(engines(64), "plain", 64, S, 1, 0, rows, ROW)
+    few = engines(64)._long_f32_taps(cu(lc.inputs("plain", 64, S, 1)), ll.rows_for(S), 0, ROW)[1]
     at = _idx([rows.index(r) for r in ll.rows_for(S)])
     for k in ROW:
         assert torch.equal(few[k], got[k][:, at]), k
@@ -184,7 +177,7 @@ def test_stats_at_8192_against_float64(kind, s, E):
     S = 8192
     t, bounds = ll.stats_ref(kind, E, S, s)
     eng = host.Engine(fc.case(E, 0, s)[1], device=0)
-    x = _cu(lc.inputs(kind, E, S, 1))
+    x = cu(lc.inputs(kind, E, S, 1))
     st = eng.attention_stats_long_f32(x)
     for k in ("col_mass", "row_gap"):
         g = st[k].cpu().numpy()
@@ -212,7 +205,7 @@ def test_stats_at_65536_on_a_vocabulary_frame(s, E):
     V, singles, seed = VOCAB_F32
     _, reps, cls, counts = ll.vocabulary(S, V, singles, seed)
     eng = host.Engine(fc.case(E, 0, s)[1], device=0)
-    x = _cu(ll.vocab_f32_frame(E, S, V, singles, seed))
+    x = cu(ll.vocab_f32_frame(E, S, V, singles, seed))
     st = eng.attention_stats_long_f32(x)
     again = eng.attention_stats_long_f32(x)
     assert all(torch.equal(st[k], again[k]) for k in st)
@@ -245,18 +238,19 @@ def test_int8_sampled_rows_at_65536(oracle, name, l):
     encoder_layer_long against the oracle composition on those rows (LayerNorm and the FFN are per token)"""
     import torch
     S = 65536
-    E, _, t, fp, blob = _case(name)
+    case = long_case(name)
+    E, t, fp, blob = case.E, case.t, case.fp, case.blob
     rows = ll.rows_for(S)
     at = _idx(rows)
-    xq = _long_inputs(S + l, 1, S, E)
-    x = _long_f32(S + l, 1, S, E, t, l)
+    xq = long_inputs(S + l, 1, S, E)
+    x = long_f32(S + l, 1, S, E, t, l)
     want_q = oracle.mha_q8_rows(xq[0], t, rows, l)
     assert len({r.tobytes() for r in want_q}) > len(rows) // 2
     eng = host.Engine(blob, device=0)
-    got_q = eng.mha_long_q8(_cu(xq), l)
+    got_q = eng.mha_long_q8(cu(xq), l)
     np.testing.assert_array_equal(got_q[0, at].cpu().numpy(), want_q, err_msg=name)
-    assert torch.equal(got_q, eng.mha_long_q8(_cu(xq), l))
-    xc = _cu(x)
+    assert torch.equal(got_q, eng.mha_long_q8(cu(xq), l))
+    xc = cu(x)
     want_a = want_q.astype(np.float32) * np.float32(t[f"attn{l}.scal"][mref.SO])
     np.testing.assert_array_equal(eng.mha_long(xc, l)[0, at].cpu().numpy(), want_a, err_msg=name)
     if fp is not None:
@@ -277,8 +271,8 @@ def test_int8_taps_and_stats_at_65536(int8_refs, name, l):
     among them) against long_taps_common.mha_rows, attention_stats_long against the class form; every output bit for bit"""
     x, rows, want, stats = int8_refs[(name, l)]
     S = x.shape[1]
-    eng = host.Engine(_case(name)[4], device=0)
-    xc, at = _cu(x), _idx(rows)
+    eng = host.Engine(long_case(name).blob, device=0)
+    xc, at = cu(x), _idx(rows)
     _, tp = eng.mha_long_taps(xc, rows, l)
     for k in ("logits", "probs"):
         np.testing.assert_array_equal(tp[k].cpu().numpy(), want[k], err_msg=f"{name} layer {l} {k}")
@@ -323,10 +317,11 @@ def test_int8_workspace_past_4_gib(oracle):
     """mha_long_q8, E = 64, S = 256: 90 000 tiles, Q fragments, K and V images of 2.2 GB each, the V image past 2^32 bytes"""
     import torch
     _room(10, "the int8 case")
-    E, _, t, _, blob = _case("blocks_E64_seed2_B1")
-    base = _long_inputs(61, DISTINCT, 256, E)
+    case = long_case("blocks_E64_seed2_B1")
+    E, t, blob = case.E, case.t, case.blob
+    base = long_inputs(61, DISTINCT, 256, E)
     eng = host.Engine(blob, device=0)
-    big, small, pick = _gathered(_cu(base), eng.mha_long_q8)
+    big, small, pick = _gathered(cu(base), eng.mha_long_q8)
     np.testing.assert_array_equal(small.cpu().numpy(), oracle.mha_q8(base, t))
     assert len({f.tobytes() for f in small.cpu().numpy()}) == DISTINCT
     assert tuple(big.shape) == (FRAMES, 256, E)
@@ -343,7 +338,7 @@ def test_float_workspace_past_4_gib():
     kind, E, S = "plain", 64, 128
     want, e_torch = lc.attn_ref(kind, E, S, DISTINCT, 0)
     eng = host.Engine(lc.case(E)[1], device=0)
-    big, small, pick = _gathered(_cu(lc.inputs(kind, E, S, DISTINCT)), eng.mha_long_f32)
+    big, small, pick = _gathered(cu(lc.inputs(kind, E, S, DISTINCT)), eng.mha_long_f32)
     _check(small.cpu().numpy(), want, e_torch, f"mha_long_f32 {kind} E={E} S={S} B={DISTINCT}")
     assert tuple(big.shape) == (FRAMES, S, E)
     _same_frames(big.view(torch.int32), small.view(torch.int32), pick)

@@ -13,12 +13,10 @@ from drone_oa_iree_vit_accelerator_amd import attention_rollout_ref as arr
 from drone_oa_iree_vit_accelerator_amd import host, params, synth
 from heads_common import FIX_HEADS_2L, case as heads_case
 import long_propagate_common as lpc
-from test_gpu_long_taps import _cu, _tokens
+from gpu_support import INVALID, UNSUPPORTED, Canaries, cu, refused
+from long_cases import long_case, tokens
 
 pytestmark = pytest.mark.gpu
-
-INVALID, UNSUPPORTED = "ita status -1", "ita status -4"
-
 
 def _engine(name):
     _, _, blob = lpc.blob_case(name)
@@ -37,16 +35,16 @@ def test_propagate_equals_the_definition(name, S):
     x, w, want = lpc.expected(name, S)
     eng = _engine(name)
     for B in lpc.BATCHES:
-        xc = _cu(x[:B])
+        xc = cu(x[:B])
         for R in lpc.ROWS:
-            got = eng.attention_propagate_long(xc, _cu(w[:B, :R]))
+            got = eng.attention_propagate_long(xc, cu(w[:B, :R]))
             assert got.dtype == torch.int32 and tuple(got.shape) == (B, R, S)
             np.testing.assert_array_equal(got.cpu().numpy(), want[:B, :R], err_msg=f"{name} S={S} B={B} R={R}")
-        assert torch.equal(xc, _cu(x[:B])), "x was written to"
+        assert torch.equal(xc, cu(x[:B])), "x was written to"
     # (R, S) weights: the same for every frame
-    got = eng.attention_propagate_long(_cu(x), _cu(w[1, :17]))
+    got = eng.attention_propagate_long(cu(x), cu(w[1, :17]))
     for b in range(3):
-        one = eng.attention_propagate_long(_cu(x[b:b + 1]), _cu(w[1:2, :17]))
+        one = eng.attention_propagate_long(cu(x[b:b + 1]), cu(w[1:2, :17]))
         assert torch.equal(got[b:b + 1], one), b
     eng.close()
 
@@ -58,7 +56,7 @@ def test_frames_and_repeats(name):
     S = 384
     x, w, want = lpc.expected(name, S)
     eng = _engine(name)
-    xc, wc = _cu(x), _cu(w)
+    xc, wc = cu(x), cu(w)
     got = eng.attention_propagate_long(xc, wc)
     for b in range(3):
         assert torch.equal(eng.attention_propagate_long(xc[b:b + 1].contiguous(), wc[b:b + 1].contiguous()), got[b:b + 1]), b
@@ -75,7 +73,7 @@ def test_identities_at_long_sequences(name, S):
     import torch
     E, t, _ = lpc.blob_case(name)
     eng = _engine(name)
-    xc = _cu(_tokens(S + 1, 1, S, E, t))
+    xc = cu(tokens(S + 1, 1, S, E, t))
     fixed = {0, 127, 128, 129, S // 2 - 1, S // 2, S - 129, S - 128, S - 1}
     extra = [int(r) for r in np.random.RandomState(S).permutation(S) if int(r) not in fixed][:16 - len(fixed)]
     rows = sorted(fixed | set(extra))
@@ -84,7 +82,7 @@ def test_identities_at_long_sequences(name, S):
     w[0, 0], w[0, 1] = 1, -1
     for n, r in enumerate(rows):
         w[0, 2 + n, r] = 1
-    got = eng.attention_propagate_long(xc, _cu(w))
+    got = eng.attention_propagate_long(xc, cu(w))
     received = eng.attention_received_long(xc)
     assert torch.equal(got[:, 0], received) and torch.equal(got[:, 1], -received)
     assert int(received.max()) > 0
@@ -103,16 +101,11 @@ def _refused(eng, status, S=256, seq_len=None, n_w=4, null=None, skew=None):
     import torch
     x = torch.zeros((1, S, eng.E), dtype=torch.float32, device="cuda")
     w = torch.ones((4 * S + 16,), dtype=torch.int8, device="cuda")
-    out = torch.full((4 * 4 * S + 32,), 0x77, dtype=torch.int8, device="cuda")
-    args = dict(x=x, w=w.data_ptr() + (2 if skew == "w" else 0), out=out.data_ptr() + (4 if skew == "out" else 0))
+    c = Canaries({"out": ((1, 4, S), torch.int32)}, pad=32)
+    args = dict(x=x, w=w.data_ptr() + (2 if skew == "w" else 0), out=c.ptr("out", 4 if skew == "out" else 0))
     if null:
         args[null] = None
-    with pytest.raises(host.ITAError, match=status):
-        host._chk(host.lib().ita_mha_long_int8_propagate(eng._h, 0, x.data_ptr() if args["x"] is not None else None, 1,
-                                                         S if seq_len is None else seq_len, args["w"], n_w, args["out"],
-                                                         host._stream_ptr(eng.device)))
-    torch.cuda.synchronize()
-    assert bool((out == 0x77).all()), "a refused call wrote to out"
+    refused(lambda: _call(eng, args["x"], args["w"], args["out"], n_w, S if seq_len is None else seq_len), c, status)
 
 
 def test_refusals_before_any_launch():
@@ -137,7 +130,7 @@ def test_refusals_before_any_launch():
     _refused(eng, INVALID, skew="w")
     _refused(eng, INVALID, skew="out")
     x, w, want = lpc.expected(name, 256)
-    np.testing.assert_array_equal(eng.attention_propagate_long(_cu(x), _cu(w)).cpu().numpy(), want, err_msg="after the refusals")
+    np.testing.assert_array_equal(eng.attention_propagate_long(cu(x), cu(w)).cpu().numpy(), want, err_msg="after the refusals")
     eng.close()
 
 
@@ -148,7 +141,7 @@ def test_captured_call_replays():
     name, S, B, R = "vitlstm_E64_seed0_B2", 256, 3, 17
     x, w, want = lpc.expected(name, S)
     eng = _engine(name)
-    xc, wc = _cu(x), _cu(w[:, :R])
+    xc, wc = cu(x), cu(w[:, :R])
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
@@ -156,21 +149,24 @@ def test_captured_call_replays():
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
     np.testing.assert_array_equal(eager.cpu().numpy(), want[:, :R], err_msg="eager")
-    out = torch.full((B, R, S), 0x77777777, dtype=torch.int32, device="cuda")
+    c = Canaries({"out": ((B, R, S), torch.int32)})
+    out = c.views()["out"]
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
         _call(eng, xc, wc, out, R, B=B)
     g.replay()
     torch.cuda.synchronize()
     np.testing.assert_array_equal(out.cpu().numpy(), want[:, :R], err_msg="first replay")
+    c.assert_untouched(written=("out",))
     # the frames in another order, other weight rows
     order = [2, 0, 1]
-    xc.copy_(_cu(x[order]))
-    wc.copy_(_cu(w[order, 40:40 + R]))
-    out.fill_(0x77777777)
+    xc.copy_(cu(x[order]))
+    wc.copy_(cu(w[order, 40:40 + R]))
+    c.refill()
     g.replay()
     torch.cuda.synchronize()
     np.testing.assert_array_equal(out.cpu().numpy(), want[order, 40:40 + R], err_msg="second replay")
+    c.assert_untouched(written=("out",))
     del g
     eng.close()
 
@@ -178,12 +174,13 @@ def test_captured_call_replays():
 @pytest.mark.parametrize("name", lpc.ROLLOUT_BLOBS)
 def test_rollout_equals_the_definition(oracle, name):
     import torch
-    E, nl, t, fp, blob = lpc.rollout_case(name)
+    case = long_case(name)
+    E, nl, t, fp, blob = case.E, case.num_layers, case.t, case.fp, case.blob
     assert nl == (2 if name.startswith("vit2l") else 1)
     S, B = 256, 2
-    x = _tokens(S + B, B, S, E, t)
+    x = tokens(S + B, B, S, E, t)
     eng = host.Engine(blob, device=0)
-    xc = _cu(x)
+    xc = cu(x)
     for rows in ((0, 100, 255), None):
         got = eng.attention_rollout_long(xc, rows)
         want = arr.rollout(oracle, x, t, fp, nl, rows)
@@ -202,7 +199,7 @@ def test_rollout_equals_the_definition(oracle, name):
         eng.attention_rollout_long(xc, [3, 3])
     with pytest.raises(ValueError):
         eng.attention_rollout_long(xc, [S])
-    assert torch.equal(xc, _cu(x)), "x was written to"
+    assert torch.equal(xc, cu(x)), "x was written to"
     eng.close()
 
 
@@ -210,9 +207,8 @@ def test_attention_rollout_map_long():
     """u8 frames 60 x 90 -> an 8 x 16 token grid on the two-layer E = 128 blob: tokenize_long plus attention_rollout_long,
     reshaped, with the queries out of order"""
     import torch
-    E, nl, t, fp, blob = lpc.rollout_case("vit2l_E128_s0_B2")
-    eng = host.Engine(blob, device=0)
-    frames = _cu(np.random.RandomState(4).randint(0, 256, size=(2, 60, 90)).astype(np.uint8))
+    eng = host.Engine(long_case("vit2l_E128_s0_B2").blob, device=0)
+    frames = cu(np.random.RandomState(4).randint(0, 256, size=(2, 60, 90)).astype(np.uint8))
     queries = [(7, 15), (0, 0), (3, 9)]
     got = eng.attention_rollout_map_long(frames, 8, 16, queries)
     assert tuple(got.shape) == (2, 3, 8, 16) and got.dtype == torch.float64

@@ -1,6 +1,6 @@
 """Long-sequence attention statistics on the MI355X: ita_mha_long_int8_stats (Engine.attention_stats_long,
 attention_received_long, attention_received_map_long) against the numpy definition attention_stats_ref, every comparison
-an equality.  Cases and fixtures are those of test_gpu_long_taps.py.
+an equality.  Cases and fixtures are long_cases.py's, as in test_gpu_long_taps.py.
 
 Shapes (S, B): (128, 2) one key tile; (256, 2) two; (384, 2) an odd tile count, the ring-slot parity flips between the
 sweeps and the column table's slot with it; (1024, 1) eight query tiles adding into one column; (2048, 1) many tiles.  The
@@ -11,35 +11,33 @@ import functools
 
 import numpy as np
 import pytest
+import torch
 
 from drone_oa_iree_vit_accelerator_amd import attention_stats_ref as asr
 from drone_oa_iree_vit_accelerator_amd import host, params, synth
 from heads_common import FIX_HEADS_2L, case as heads_case
+from gpu_support import INVALID, UNSUPPORTED, Canaries, captured_replays, cu, refused, to_numpy
+from long_cases import FIXTURES, TWO_LAYER, long_case, tap_rows, tokens
 import long_taps_common as ltc
-from test_gpu_long_taps import FIXTURES, TWO_LAYER, _case, _cu, _rows, _tokens
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(128, 2), (256, 2), (384, 2), (1024, 1)]
 STATS = host.LONG_STATS
-INVALID, UNSUPPORTED = "ita status -1", "ita status -4"
 
 
 @functools.lru_cache(maxsize=None)
 def _expected(name, S, B):
     """(x, the definition's statistics) of one case: computed once, read-only"""
-    E, _, t, _ = _case(name)
-    x = _tokens(S + B, B, S, E, t)
+    case = long_case(name)
+    E, t = case.E, case.t
+    x = tokens(S + B, B, S, E, t)
     return x, asr.stats(x, t)
-
-
-def _np(t):
-    return {k: v.cpu().numpy() for k, v in t.items()}
 
 
 def _equal(got, want, msg):
     assert tuple(got) == STATS
-    g = _np(got)
+    g = to_numpy(got)
     for k in STATS:
         assert g[k].dtype == want[k].dtype and g[k].shape == want[k].shape, (msg, k, g[k].dtype, g[k].shape)
         np.testing.assert_array_equal(g[k], want[k], err_msg=f"{msg} {k}")
@@ -51,31 +49,25 @@ def _call(eng, x, st, S=None, B=None):
                                                  host.C.byref(st) if st is not None else None, host._stream_ptr(eng.device)))
 
 
-def _canaries(B, S, pad=0):
-    import torch
-    return {k: torch.full((B * S * (1 if k == "row_max" else 4) + pad,), 0x77, dtype=torch.int8, device="cuda") for k in STATS}
-
-
-def _views(t, B, S):
-    import torch
-    return {k: (v[:B * S] if k == "row_max" else v[:4 * B * S].view(torch.int32)).reshape(B, S) for k, v in t.items()}
+def _canaries(B, S):
+    return Canaries({k: ((B, S), torch.int8 if k == "row_max" else torch.int32) for k in STATS})
 
 
 @pytest.mark.parametrize("S,B", SHAPES)
 @pytest.mark.parametrize("name", list(FIXTURES))
 def test_stats_equal_the_definition(name, S, B):
-    import torch
-    E, _, t, blob = _case(name)
+    case = long_case(name)
+    E, t, blob = case.E, case.t, case.blob
     x, want = _expected(name, S, B)
     eng = host.Engine(blob, device=0)
     forms = eng.layer_forms(0)
     assert forms["attn_image"] and (FIXTURES[name] is None or forms["fast"] == FIXTURES[name]), (name, forms)
-    xc = _cu(x)
+    xc = cu(x)
     got = eng.attention_stats_long(xc)
     _equal(got, want, f"{name} S={S}")
-    assert torch.equal(xc, _cu(x)), "x was written to"
+    assert torch.equal(xc, cu(x)), "x was written to"
     # the taps entry's row maximum and row sum at its rows
-    rows = _rows(S)
+    rows = tap_rows(S)
     _, tp = eng._long_taps(xc, rows, 0, ("row_max", "row_sum"))
     for k in ("row_max", "row_sum"):
         assert torch.equal(got[k][:, rows], tp[k]), k
@@ -93,17 +85,19 @@ def test_stats_equal_the_definition(name, S, B):
     if (name, S) == ("vitlstm_E64_seed1_B2", 384):
         # through the C entry into canary-filled outputs: the column arrays are zeroed by the call, not by the caller
         c = _canaries(B, S)
-        _call(eng, xc, host._MhaLongStats(**{k: v.data_ptr() for k, v in c.items()}))
-        _equal(_views(c, B, S), want, "canary-filled outputs")
+        _call(eng, xc, host._MhaLongStats(**c.ptrs()))
+        _equal(c.views(), want, "canary-filled outputs")
+        c.assert_untouched(written=STATS)
     eng.close()
 
 
 @pytest.mark.parametrize("name", ["vitlstm_E64_seed0_B2", "blocks_E128_seed0_B1"])
 def test_many_tiles(name):
-    E, _, t, blob = _case(name)
+    case = long_case(name)
+    E, t, blob = case.E, case.t, case.blob
     x, want = _expected(name, 2048, 1)
     eng = host.Engine(blob, device=0)
-    _equal(eng.attention_stats_long(_cu(x)), want, f"{name} S=2048")
+    _equal(eng.attention_stats_long(cu(x)), want, f"{name} S=2048")
     eng.close()
 
 
@@ -130,7 +124,7 @@ def test_crafted_rows_256_keys(form):
     assert d["y256"].shape == (118, 256) and int((d["y256"].astype(np.int64).sum(-1) == 0).sum()) == 12
     x = ltc.frames_for(form, d["x256"])
     eng = _crafted_engine(form)
-    g = _np(eng.attention_stats_long(_cu(x)))
+    g = to_numpy(eng.attention_stats_long(cu(x)))
     for b in range(len(x)):
         _equal_row_form(g, b, d["y256"][b], d["x256"][b], 256, f"{form} frame {b}")
     assert int((g["row_mass"][:, 0] == 0).sum()) == 12
@@ -145,7 +139,7 @@ def test_crafted_rows_8192_keys(form):
     x = ltc.frames_for(form, d["x8192"])
     eng = _crafted_engine(form)
     for b in range(len(x)):
-        g = _np(eng.attention_stats_long(_cu(x[b:b + 1])))
+        g = to_numpy(eng.attention_stats_long(cu(x[b:b + 1])))
         _equal_row_form(g, 0, d["y8192"][b], d["x8192"][b], 8192, f"{form} row {b}")
         assert g["col_mass"].max() == 8192 * int(d["y8192"][b].max())
     eng.close()
@@ -154,12 +148,13 @@ def test_crafted_rows_8192_keys(form):
 @pytest.mark.parametrize("name", ["vitlstm_E64_seed0_B2", "blocks_E128_seed0_B1"])
 def test_random_tokens_8192(name):
     S = 8192
-    E, _, t, blob = _case(name)
+    case = long_case(name)
+    E, t, blob = case.E, case.t, case.blob
     eng = host.Engine(blob, device=0)
-    xc = _cu(_tokens(S + 1, 1, S, E, t))
+    xc = cu(tokens(S + 1, 1, S, E, t))
     rows = list(range(3, S, 8))
     assert len(rows) == 1024
-    g = _np(eng.attention_stats_long(xc))
+    g = to_numpy(eng.attention_stats_long(xc))
     _, tp = eng._long_taps(xc, rows, 0, ("logits", "probs"))
     lg, pr = tp["logits"].cpu().numpy(), tp["probs"].cpu().numpy().astype(np.int64)
     np.testing.assert_array_equal(g["row_max"][:, rows], lg.max(-1))
@@ -176,12 +171,12 @@ def test_random_tokens_8192(name):
 def test_attention_received_map_long():
     """u8 frames 60 x 90 -> an 8 x 16 and 120 x 180 -> a 16 x 16 token grid, layers 0 and 1 of the two-layer E = 128 blob: the
     composition of tokenize_long, encoder_layer_long and attention_received_long"""
-    import torch
-    E, nl, t, blob = _case(TWO_LAYER)
+    case = long_case(TWO_LAYER)
+    E, nl, t, blob = case.E, case.num_layers, case.t, case.blob
     assert (E, nl) == (128, 2)
     eng = host.Engine(blob, device=0)
     for (H, W), (th, tw) in (((60, 90), (8, 16)), ((120, 180), (16, 16))):
-        frames = _cu(np.random.RandomState(4).randint(0, 256, size=(2, H, W)).astype(np.uint8))
+        frames = cu(np.random.RandomState(4).randint(0, 256, size=(2, H, W)).astype(np.uint8))
         for layer in (0, 1):
             got = eng.attention_received_map_long(frames, th, tw, layer=layer)
             assert tuple(got.shape) == (2, th, tw) and got.dtype == torch.int32
@@ -198,15 +193,10 @@ def test_attention_received_map_long():
 
 def _refused(eng, status, S=256, seq_len=None, null=False, want=STATS, skew=None):
     """the call must raise with `status` and leave the canary-filled outputs untouched"""
-    import torch
     x = torch.zeros((1, S, eng.E), dtype=torch.float32, device="cuda")
-    c = _canaries(1, S, pad=16)
-    st = host._MhaLongStats(**{k: c[k].data_ptr() + (2 if k == skew else 0) for k in want})
-    with pytest.raises(host.ITAError, match=status):
-        _call(eng, x, None if null else st, seq_len)
-    torch.cuda.synchronize()
-    for k, v in c.items():
-        assert bool((v == 0x77).all()), f"a refused call wrote to {k}"
+    c = _canaries(1, S)
+    st = host._MhaLongStats(**{k: c.ptr(k, 2 if k == skew else 0) for k in want})
+    refused(lambda: _call(eng, x, None if null else st, seq_len), c, status)
 
 
 def test_refusals_before_any_launch_or_memset():
@@ -221,7 +211,7 @@ def test_refusals_before_any_launch_or_memset():
     eh.close()
 
     name = "vitlstm_E64_seed0_B2"
-    _, _, _, blob = _case(name)
+    blob = long_case(name).blob
     eng = host.Engine(blob, device=0)
     _refused(eng, UNSUPPORTED, seq_len=200)
     _refused(eng, UNSUPPORTED, seq_len=0)
@@ -229,35 +219,19 @@ def test_refusals_before_any_launch_or_memset():
     _refused(eng, INVALID, want=())
     _refused(eng, INVALID, skew="col_mass")
     x, want = _expected(name, 256, 2)
-    _equal(eng.attention_stats_long(_cu(x)), want, "after the refusals")
+    _equal(eng.attention_stats_long(cu(x)), want, "after the refusals")
     eng.close()
 
 
 def test_captured_call_replays():
     """one call captured on one stream: every replay zeroes the column arrays again"""
-    import torch
     name = "vitlstm_E64_seed0_B2"
-    _, _, _, blob = _case(name)
+    blob = long_case(name).blob
     eng = host.Engine(blob, device=0)
     x, want = _expected(name, 256, 2)
-    xc = _cu(x)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        eager = eng.attention_stats_long(xc)         # outside the capture: the workspace exists
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    _equal(eager, want, "eager")
+    xc = cu(x)
     c = _canaries(2, 256)
-    st = host._MhaLongStats(**{k: v.data_ptr() for k, v in c.items()})
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        _call(eng, xc, st)
-    for replay in range(2):
-        g.replay()
-        torch.cuda.synchronize()
-        got = _views(c, 2, 256)
-        for k in STATS:
-            assert torch.equal(got[k], eager[k]), (replay, k)
-    del g
+    st = host._MhaLongStats(**c.ptrs())
+    eager = captured_replays(lambda: eng.attention_stats_long(xc), lambda: _call(eng, xc, st), c, STATS)
+    _equal(eager, want, "eager")
     eng.close()

@@ -18,64 +18,25 @@ import functools
 import numpy as np
 import pytest
 
-from conftest import golden_files
 from drone_oa_iree_vit_accelerator_amd import host, params, synth
 from drone_oa_iree_vit_accelerator_amd import mha_heads_ref as ref
 from heads_common import FIX_HEADS_2L, case as heads_case
-from test_only_attn_cpu import _fp as only_attn_fp
+from gpu_support import INVALID, UNSUPPORTED, Canaries, cu, refused, to_numpy
+from long_cases import FIXTURES, TWO_LAYER, long_case, tap_rows, tokens
 import long_taps_common as ltc
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(256, 2), (384, 2), (128, 2)]
-# name -> does the layer run the FAST (single-rounding) instantiation
-FIXTURES = {"vitlstm_E64_seed0_B2": True, "vitlstm_E64_seed1_B2": False, "blocks_E128_seed0_B1": False,
-            "vit2l_us_E128_s1_B2": True, "onlyattn1l_E64_s0_B2": None}
-TWO_LAYER = "vit2l_E128_s0_B2"
 TENSOR, ROW = host.LONG_TENSOR_TAPS, host.LONG_ROW_TAPS
-INVALID, UNSUPPORTED = "ita status -1", "ita status -4"
-
-
-@functools.lru_cache(maxsize=None)
-def _case(name):
-    """(E, num_layers, attention tensors of every layer, blob) of one fixture; read-only"""
-    d = params.load_fixture(golden_files(name + ".npz")[0])
-    E = int(d["meta.E"])
-    nl = int(d["meta.num_layers"]) if "meta.num_layers" in d else 1
-    if name.startswith("onlyattn"):
-        fp = only_attn_fp(d)
-    else:
-        fp = synth.float_params(int(d["meta.seed"]), E=E, num_layers=nl, tail=(E == 64)) if name.startswith("vit") else None
-    t = {}
-    for l in range(nl):
-        t.update(params.attention_tensors(d, f"attn{l}.", l))
-    return E, nl, t, params.blob_from_record(d, fp, E=E, num_layers=nl)
-
-
-def _cu(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _tokens(seed, B, S, E, t, l=0):
-    """f32 tokens in blocks of 32 similar ones (all-noise rows make the integer softmax degenerate), off the code grid"""
-    rs = np.random.RandomState(seed)
-    base = rs.standard_normal((B, S // 32, E)).repeat(32, axis=1) * 18.0
-    codes = np.clip(np.rint(base + rs.standard_normal((B, S, E)) * 9.0), -128, 127).astype(np.float32)
-    u = rs.uniform(-0.4, 0.4, size=codes.shape).astype(np.float32)
-    return ((codes + u) * (np.float32(1.0) / np.float32(t[f"attn{l}.scal"][ref.INV_SX]))).astype(np.float32)
-
-
-def _rows(S):
-    return sorted({0, 1, 15, 16, 17, 127, 128 % S, S - 1})
 
 
 @functools.lru_cache(maxsize=None)
 def _expected(name, S, B):
     """(x, the definition's (out, taps)) of one case: computed once, read-only"""
-    E, _, t, _ = _case(name)
-    x = _tokens(S + B, B, S, E, t)
-    return x, ref.mha(x, t, 1, 0)
+    c = long_case(name)
+    x = tokens(S + B, B, S, c.E, c.t)
+    return x, ref.mha(x, c.t, 1, 0)
 
 
 def _want(tp, rows):
@@ -86,25 +47,20 @@ def _want(tp, rows):
     return w
 
 
-def _np(t):
-    return {k: v.cpu().numpy() for k, v in t.items()}
-
-
 @pytest.mark.parametrize("S,B", SHAPES)
 @pytest.mark.parametrize("name", list(FIXTURES))
 def test_taps_equal_the_definition(name, S, B):
     import torch
-    E, _, t, blob = _case(name)
     x, (out, tp) = _expected(name, S, B)
-    rows = _rows(S)
-    eng = host.Engine(blob, device=0)
+    rows = tap_rows(S)
+    eng = host.Engine(long_case(name).blob, device=0)
     forms = eng.layer_forms(0)
     assert forms["attn_image"] and (FIXTURES[name] is None or forms["fast"] == FIXTURES[name]), (name, forms)
-    xc = _cu(x)
+    xc = cu(x)
     y, got = eng.mha_long_taps(xc, rows)
     assert set(got) == set(TENSOR + ROW)
     want = _want(tp, rows)
-    g = _np(got)
+    g = to_numpy(got)
     for k in TENSOR + ROW:
         assert g[k].dtype == want[k].dtype and g[k].shape == want[k].shape, (k, g[k].dtype, g[k].shape)
         np.testing.assert_array_equal(g[k], want[k], err_msg=f"{name} S={S} tap {k}")
@@ -149,8 +105,8 @@ def test_crafted_softmax_rows_256_keys(form):
     eng = host.Engine(ltc.blob(form), device=0)
     forms = eng.layer_forms(0)
     assert forms["attn_image"] and forms["fast"] == (form == "fast"), forms
-    _, got = eng.mha_long_taps(_cu(x), rows)
-    g = _np(got)
+    _, got = eng.mha_long_taps(cu(x), rows)
+    g = to_numpy(got)
     for j in range(len(rows)):
         np.testing.assert_array_equal(g["logits"][:, j], d["x256"])
         np.testing.assert_array_equal(g["probs"][:, j], d["y256"])
@@ -178,8 +134,8 @@ def test_crafted_softmax_rows_8192_keys(form):
     forms = eng.layer_forms(0)
     assert forms["attn_image"] and forms["fast"] == (form == "fast"), forms
     for b in range(len(x)):
-        _, got = eng.mha_long_taps(_cu(x[b:b + 1]), rows)
-        g = _np(got)
+        _, got = eng.mha_long_taps(cu(x[b:b + 1]), rows)
+        g = to_numpy(got)
         for j in range(len(rows)):
             np.testing.assert_array_equal(g["logits"][0, j], d["x8192"][b], err_msg=f"row {b}")
             np.testing.assert_array_equal(g["probs"][0, j], d["y8192"][b], err_msg=f"row {b}")
@@ -201,21 +157,15 @@ def _refused(eng, status, S=256, rows=(0, 5), n_rows=None, want=TENSOR + ROW, se
     tap pointer (the buffers are that much larger)"""
     import torch
     B, n = 1, len(rows)
-    y = torch.full((B, S, eng.E), 12345.0, dtype=torch.float32, device="cuda")
-    x = torch.zeros_like(y)
+    x = torch.zeros((B, S, eng.E), dtype=torch.float32, device="cuda")
     shapes = dict(x_q=(B, S, eng.E), out_q=(B, S, eng.E), Q=(B, S, eng.P), K=(B, S, eng.P), V=(B, S, eng.P), ctx=(B, S, eng.P),
                   logits=(B, max(n, 1), S), probs=(B, max(n, 1), S), row_max=(B, max(n, 1)), row_sum=(B, max(n, 1)))
     dt = dict(probs=torch.uint8, row_sum=torch.int32)
-    t = {k: torch.full((np.prod(shapes[k]) + 16,), 77, dtype=dt.get(k, torch.int8), device="cuda") for k in want}
-    st = host._MhaLongTaps(**{k: v.data_ptr() + skew for k, v in t.items()})
+    c = Canaries({"y": (x.shape, torch.float32), **{k: (shapes[k], dt.get(k, torch.int8)) for k in want}})
+    st = host._MhaLongTaps(**{k: c.ptr(k, skew) for k in want})
     arr = (host.C.c_int * max(n, 1))(*rows)
     st.rows, st.n_rows = (arr if n else None), (n if n_rows is None else n_rows)
-    with pytest.raises(host.ITAError, match=status):
-        _call(eng, x, y, st, seq_len)
-    torch.cuda.synchronize()
-    assert bool((y == 12345.0).all()), "a refused call wrote to its output"
-    for k, v in t.items():
-        assert bool((v == 77).all()), f"a refused call wrote to the {k} tap"
+    refused(lambda: _call(eng, x, c.views()["y"], st, seq_len), c, status)
 
 
 def test_refusals_before_any_launch():
@@ -232,8 +182,7 @@ def test_refusals_before_any_launch():
     eh.close()
 
     name = "vitlstm_E64_seed0_B2"
-    E, _, t, blob = _case(name)
-    eng = host.Engine(blob, device=0)
+    eng = host.Engine(long_case(name).blob, device=0)
     _refused(eng, UNSUPPORTED, S=256, seq_len=200)                       # not a multiple of 128
     _refused(eng, INVALID, rows=(0, 5), n_rows=-1)
     _refused(eng, INVALID, rows=(0, 5), n_rows=1025)
@@ -248,16 +197,16 @@ def test_refusals_before_any_launch():
     _refused(eng, INVALID, rows=(0, 5), want=("probs",), skew=1)         # probs 4-byte aligned
     # the most rows there may be are served, and the handle still computes mha_long
     x, (out, tp) = _expected(name, 256, 2)
-    xc = _cu(np.concatenate([x, x, x, x], axis=1))                       # S = 1024
+    xc = cu(np.concatenate([x, x, x, x], axis=1))                        # S = 1024
     many = list(range(1024))
     probs = eng.attention_rows_long(xc, many)
     assert tuple(probs.shape) == (2, 1024, 1024)
-    np.testing.assert_array_equal(eng.mha_long(_cu(x)).cpu().numpy(), out)
-    y, got = eng.mha_long_taps(_cu(x), [3])
+    np.testing.assert_array_equal(eng.mha_long(cu(x)).cpu().numpy(), out)
+    y, got = eng.mha_long_taps(cu(x), [3])
     np.testing.assert_array_equal(got["probs"].cpu().numpy(), tp["probs"][:, [3]])
     # taps == NULL behaves as all-null taps
     y0 = torch.empty_like(y)
-    _call(eng, _cu(x), y0, None)
+    _call(eng, cu(x), y0, None)
     assert torch.equal(y0, y)
     eng.close()
 
@@ -265,10 +214,9 @@ def test_refusals_before_any_launch():
 def test_refused_inside_a_stream_capture():
     import torch
     name = "vitlstm_E64_seed0_B2"
-    E, _, t, blob = _case(name)
-    eng = host.Engine(blob, device=0)
+    eng = host.Engine(long_case(name).blob, device=0)
     x, (out, _) = _expected(name, 256, 2)
-    xc = _cu(x)
+    xc = cu(x)
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
@@ -278,14 +226,14 @@ def test_refused_inside_a_stream_capture():
     y = torch.full_like(xc, 12345.0)
     yg = torch.empty_like(xc)
     g = torch.cuda.CUDAGraph()
-    refused = None
+    message = None
     with torch.cuda.graph(g):
         host._chk(host.lib().ita_mha_long_int8(eng._h, 0, xc.data_ptr(), yg.data_ptr(), 2, 256, host._stream_ptr(eng.device)))
         try:
             _call(eng, xc, y, host._MhaLongTaps())
         except host.ITAError as e:
-            refused = str(e)
-    assert refused is not None and INVALID in refused and "capture" in refused, refused
+            message = str(e)
+    assert message is not None and INVALID in message and "capture" in message, message
     g.replay()
     torch.cuda.synchronize()
     np.testing.assert_array_equal(yg.cpu().numpy(), out)
@@ -297,10 +245,10 @@ def test_refused_inside_a_stream_capture():
 def test_attention_map_long():
     """20 x 30 u8 frames -> an 8 x 32 token grid, two queries in descending order, layers 0 and 1 of the two-layer E = 128
     blob: the composition of tokenize_long, encoder_layer_long and the definition's probabilities"""
-    E, nl, t, blob = _case(TWO_LAYER)
-    assert (E, nl) == (128, 2)
-    eng = host.Engine(blob, device=0)
-    frames = _cu(np.random.RandomState(4).randint(0, 256, size=(2, 20, 30)).astype(np.uint8))
+    c = long_case(TWO_LAYER)
+    assert (c.E, c.num_layers) == (128, 2)
+    eng = host.Engine(c.blob, device=0)
+    frames = cu(np.random.RandomState(4).randint(0, 256, size=(2, 20, 30)).astype(np.uint8))
     th, tw, queries = 8, 32, [(5, 17), (2, 3)]
     toks = [ty * tw + tx for ty, tx in queries]
     for layer in (0, 1):
@@ -309,7 +257,7 @@ def test_attention_map_long():
         y = eng.tokenize_long(frames, th, tw)
         for l in range(layer):
             y = eng.encoder_layer_long(y, l)
-        _, tp = ref.mha(y.cpu().numpy(), t, 1, layer)
+        _, tp = ref.mha(y.cpu().numpy(), c.t, 1, layer)
         np.testing.assert_array_equal(got.cpu().numpy(), tp["probs"][:, toks].reshape(2, 2, th, tw), err_msg=f"layer {layer}")
         assert len(np.unique(got.cpu().numpy())) > 2
     with pytest.raises(ValueError):

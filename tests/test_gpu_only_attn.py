@@ -9,23 +9,10 @@ import pytest
 
 from conftest import golden_files
 from drone_oa_iree_vit_accelerator_amd import host, params, synth
-from test_only_attn_cpu import _fp, _tensors, composed
+from gpu_support import cu
+from only_attn_common import composed, setup_only_attn as _setup, tensors
 
 pytestmark = pytest.mark.gpu
-
-FIX = {1: golden_files("onlyattn1l_E64_s0_B2.npz")[0], 2: golden_files("onlyattn2l_E64_s1_B2.npz")[0]}
-
-
-def _setup(L):
-    d = params.load_fixture(FIX[L])
-    fp = _fp(d)
-    return d, fp, params.blob_from_record(d, fp, E=64, num_layers=L)
-
-
-def _cu(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
 
 def _x(B, seed):
     """LayerNorm-like activations (what the FFN sees), with exact zeros and negative values for the ReLU"""
@@ -36,27 +23,27 @@ def _x(B, seed):
 @pytest.mark.parametrize("L", [1, 2])
 def test_ffn_f32_and_layer_bit_equal(oracle, L):
     d, fp, blob = _setup(L)
-    t = _tensors(d, fp)
+    t = tensors(d, fp)
     eng = host.Engine(blob, device=0)
     assert [eng.ffn_kind(l) for l in range(L)] == [host.FFN_F32] * L
     for B in (1, 3, 37, 1024):
         x = _x(B, B)
         frames = np.arange(B) if B < 64 else np.random.RandomState(B).choice(B, 24, replace=False)
         for l in range(L):
-            y = eng.ffn_f32(_cu(x), l).cpu().numpy()
-            assert np.array_equal(eng.ffn(_cu(x), l).cpu().numpy(), y)
+            y = eng.ffn_f32(cu(x), l).cpu().numpy()
+            assert np.array_equal(eng.ffn(cu(x), l).cpu().numpy(), y)
             xs = x[frames]
             hid = np.maximum(oracle.linear_f32(xs, t[f"ffn{l}.w1f"], t[f"ffn{l}.b1f"]), np.float32(0))
             want = oracle.linear_f32(hid, t[f"ffn{l}.w2f"], t[f"ffn{l}.b2f"])
             np.testing.assert_array_equal(y[frames], want, err_msg=f"ffn_f32 B={B} layer {l}")
             # the whole layer: attention + LN1 (int8 blocks) then the float FFN + LN2
-            z = eng.encoder_layer(_cu(x), l).cpu().numpy()
+            z = eng.encoder_layer(cu(x), l).cpu().numpy()
             x1 = oracle.add_ln(xs, oracle.mha(xs, t, l), t[f"norm1_{l}.w"], t[f"norm1_{l}.b"])
             hid = np.maximum(oracle.linear_f32(x1, t[f"ffn{l}.w1f"], t[f"ffn{l}.b1f"]), np.float32(0))
             want = oracle.add_ln(x1, oracle.linear_f32(hid, t[f"ffn{l}.w2f"], t[f"ffn{l}.b2f"]), t[f"norm2_{l}.w"], t[f"norm2_{l}.b"])
             np.testing.assert_array_equal(z[frames], want, err_msg=f"encoder_layer B={B} layer {l}")
     # in place (y aliases x)
-    xx = _cu(_x(5, 77))
+    xx = cu(_x(5, 77))
     want = eng.encoder_layer(xx.clone(), 0)
     host.lib().ita_encoder_layer(eng._h, 0, xx.data_ptr(), xx.data_ptr(), 5, host._stream_ptr(eng.device))
     assert np.array_equal(xx.cpu().numpy(), want.cpu().numpy())
@@ -75,8 +62,8 @@ def test_forward_against_composed_oracle_and_reference(oracle, L, kind):
     ov1, oh1, oc1, _ = composed(oracle, d, fp, img1, d["in1.desvel"], d["in1.quat"], oh0, oc0)
     for mode in (0, 1):
         eng.set_tail_mode(mode)
-        v0, st, tp = eng.forward(_cu(img0), _cu(d["in0.desvel"]), _cu(d["in0.quat"]), taps=True)
-        v1, st1 = eng.forward(_cu(img1), _cu(d["in1.desvel"]), _cu(d["in1.quat"]), st)
+        v0, st, tp = eng.forward(cu(img0), cu(d["in0.desvel"]), cu(d["in0.quat"]), taps=True)
+        v1, st1 = eng.forward(cu(img1), cu(d["in1.desvel"]), cu(d["in1.quat"]), st)
         torch.cuda.synchronize()
         for k in ("tokens", "x1", "x2"):
             np.testing.assert_array_equal(tp[k].cpu().numpy(), otp[k], err_msg=f"{k} mode {mode}")
@@ -102,7 +89,7 @@ def test_profiler_stages():
     fr = synth.frames(3, 8)
     eng.profile_begin(4)
     for _ in range(3):
-        eng.forward(_cu(fr["img_u8"]), _cu(fr["desvel"]), _cu(fr["quat"]))
+        eng.forward(cu(fr["img_u8"]), cu(fr["desvel"]), cu(fr["quat"]))
     ms, n = eng.profile_end()
     assert n == 3 and ms["mha"] > 0 and ms["ffn"] > 0
     eng.close()
@@ -115,17 +102,17 @@ def test_serving_forms_equal_eager_forward():
     # forward_slots with the state updated in place
     B, NS = 5, 16
     fr = synth.frames(21, B)
-    img, dv, qt = _cu(fr["img_u8"]), _cu(fr["desvel"]), _cu(fr["quat"])
+    img, dv, qt = cu(fr["img_u8"]), cu(fr["desvel"]), cu(fr["quat"])
     rs = np.random.RandomState(0)
     h0 = (0.1 * rs.standard_normal((3, NS, 128))).astype(np.float32)
     c0 = (0.1 * rs.standard_normal((3, NS, 128))).astype(np.float32)
     slots = np.array([7, 0, 15, 3, 9], np.int32)
-    sh, sc = _cu(h0.copy()), _cu(c0.copy())
-    vel = eng.forward_slots(img, dv, qt, sh, sc, _cu(slots))
-    v2, (h2, c2) = eng.forward(img, dv, qt, (_cu(h0[:, slots]), _cu(c0[:, slots])))
+    sh, sc = cu(h0.copy()), cu(c0.copy())
+    vel = eng.forward_slots(img, dv, qt, sh, sc, cu(slots))
+    v2, (h2, c2) = eng.forward(img, dv, qt, (cu(h0[:, slots]), cu(c0[:, slots])))
     assert torch.equal(vel, v2)
     assert torch.equal(sh[:, slots.tolist()], h2) and torch.equal(sc[:, slots.tolist()], c2)
-    hh, cc = _cu(h0[:, slots]), _cu(c0[:, slots])
+    hh, cc = cu(h0[:, slots]), cu(c0[:, slots])
     v3, _ = eng.forward(img, dv, qt, (hh, cc), out=(torch.empty_like(v2), hh, cc))
     assert torch.equal(v3, v2) and torch.equal(hh, h2) and torch.equal(cc, c2)
     # front / back on two streams
@@ -133,19 +120,19 @@ def test_serving_forms_equal_eager_forward():
     frames = [synth.frames(400 + t, B) for t in range(T)]
     ref, hid = [], None
     for t in range(T):
-        v, hid = eng.forward(_cu(frames[t]["img_u8"]), _cu(frames[t]["desvel"]), _cu(frames[t]["quat"]), hid)
+        v, hid = eng.forward(cu(frames[t]["img_u8"]), cu(frames[t]["desvel"]), cu(frames[t]["quat"]), hid)
         ref.append((v.clone(), hid[0].clone(), hid[1].clone()))
     sf, sb = torch.cuda.Stream(), torch.cuda.Stream()
     state = [(torch.zeros((3, B, 128), device="cuda"), torch.zeros((3, B, 128), device="cuda")) for _ in range(2)]
     torch.cuda.synchronize()
     for t in range(T):
         ev = torch.cuda.Event()
-        eng.front(_cu(frames[t]["img_u8"]), 0, stream=sf)
+        eng.front(cu(frames[t]["img_u8"]), 0, stream=sf)
         ev.record(sf)
         sb.wait_event(ev)
         out = torch.empty((B, 3), device="cuda")
         dst = state[(t + 1) & 1]
-        eng.back(_cu(frames[t]["desvel"]).reshape(B), _cu(frames[t]["quat"]), state[t & 1], (out, dst[0], dst[1]), 0, stream=sb)
+        eng.back(cu(frames[t]["desvel"]).reshape(B), cu(frames[t]["quat"]), state[t & 1], (out, dst[0], dst[1]), 0, stream=sb)
         sb.synchronize()
         assert torch.equal(out, ref[t][0]) and torch.equal(dst[0], ref[t][1]) and torch.equal(dst[1], ref[t][2]), t
     del out, dst
@@ -153,9 +140,9 @@ def test_serving_forms_equal_eager_forward():
     g = eng.graphed_step(B)
     st = (torch.zeros((3, B, 128), device="cuda"), torch.zeros((3, B, 128), device="cuda"))
     for t in range(T):
-        g.img.copy_(_cu(frames[t]["img_u8"])); g.desvel.copy_(_cu(frames[t]["desvel"]).reshape(B)); g.quat.copy_(_cu(frames[t]["quat"]))
+        g.img.copy_(cu(frames[t]["img_u8"])); g.desvel.copy_(cu(frames[t]["desvel"]).reshape(B)); g.quat.copy_(cu(frames[t]["quat"]))
         vg = g().clone()
-        ve, st = eng.forward(_cu(frames[t]["img_u8"]), _cu(frames[t]["desvel"]), _cu(frames[t]["quat"]), st)
+        ve, st = eng.forward(cu(frames[t]["img_u8"]), cu(frames[t]["desvel"]), cu(frames[t]["quat"]), st)
         assert torch.equal(vg, ve) and torch.equal(g.h, st[0]) and torch.equal(g.c, st[1]), t
     del g
     eng.close()
@@ -178,7 +165,7 @@ def test_pipelined_steps_equal_sequential_forward(stages):
     eng2 = host.Engine(blob, device=0)
     st = None
     for t in range(n):
-        v, st = eng2.forward(_cu(frs[t]["img_u8"]), _cu(frs[t]["desvel"]), _cu(frs[t]["quat"]), st)
+        v, st = eng2.forward(cu(frs[t]["img_u8"]), cu(frs[t]["desvel"]), cu(frs[t]["quat"]), st)
         assert torch.equal(got[t], v), t
     assert torch.equal(ps.h, st[0]) and torch.equal(ps.c, st[1])
     del ps
@@ -232,7 +219,7 @@ def test_refusals_between_ffn_kinds():
     L = host.lib()
     e32, e8 = host.Engine(blob, device=0), host.Engine(b8, device=0)
     assert e32.ffn_kind(0) == host.FFN_F32 and e8.ffn_kind(0) == host.FFN_INT8
-    x = _cu(_x(2, 1))
+    x = cu(_x(2, 1))
     y = torch.empty_like(x)
     s = host._stream_ptr(0)
     assert L.ita_ffn_int8(e32._h, 0, x.data_ptr(), y.data_ptr(), 2, s) == -4

@@ -14,12 +14,11 @@ import pytest
 import requant_common as rc
 from conftest import golden_files
 from drone_oa_iree_vit_accelerator_amd import host, params
+from gpu_support import UNSUPPORTED, cu, refused_untouched
 
 pytestmark = pytest.mark.gpu
 
-MHA_TAPS = ("x_q", "Q", "K", "V", "logits", "probs", "ctx", "out_q")
-FFN_TAPS = ("x_q", "h", "out_q")
-UNSUPPORTED = -4
+MHA_TAPS, FFN_TAPS = rc.MHA_TAPS, ("x_q", "h", "out_q")
 
 
 @pytest.fixture(scope="module")
@@ -29,27 +28,12 @@ def torch_cuda():
     return torch
 
 
-def _cu(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _refused_untouched(eng, fn, x_q, seq_len=None):
-    """the int8 entry returns ITA_ERR_UNSUPPORTED before any launch: the sentinel-filled output is untouched"""
-    import torch
-    out = torch.full_like(x_q, 77)
-    args = (eng._h, 0, x_q.data_ptr(), out.data_ptr(), x_q.shape[0]) + ((seq_len,) if seq_len else ())
-    status = fn(*args, host._stream_ptr(eng.device))
-    torch.cuda.synchronize()
-    return status == UNSUPPORTED and bool((out == 77).all())
-
-
 def _routes(eng, c, stream):
     """every route that accepts the case's blob against the definition -> the names of the routes that differ.
     stream: the blob has its stream images, so the tap-less routes run on the stream kernels and the int8 entries
     accept it; else everything runs on the block kernels and the int8 entries must refuse."""
     exp = c.expect()
-    x = _cu(c.x)
+    x = cu(c.x)
     bad = []
 
     def same(name, got, want):
@@ -70,18 +54,18 @@ def _routes(eng, c, stream):
     same("ffn", eng.ffn(x), fout)
     same("encoder_layer", eng.encoder_layer(x), exp["x2"])
     lout, ltaps, _ = exp["long"]
-    xq, xlq = _cu(taps["x_q"]), _cu(ltaps["x_q"])
+    xq, xlq = cu(taps["x_q"]), cu(ltaps["x_q"])
     if stream:
         same("mha_q8", eng.mha_q8(xq), taps["out_q"])
         same("mha_long_q8", eng.mha_long_q8(xlq), ltaps["out_q"])
-        same("mha_long", eng.mha_long(_cu(exp["x_long"])), lout)
+        same("mha_long", eng.mha_long(cu(exp["x_long"])), lout)
     else:
-        if not _refused_untouched(eng, host.lib().ita_mha_q8, xq):
+        if not refused_untouched(eng, host.lib().ita_mha_q8, xq):
             bad.append("mha_q8 refusal")
-        if not _refused_untouched(eng, host.lib().ita_mha_long_q8, xlq, 256):
+        if not refused_untouched(eng, host.lib().ita_mha_long_q8, xlq, 256):
             bad.append("mha_long_q8 refusal")
-        with pytest.raises(host.ITAError, match=f"ita status {UNSUPPORTED}"):
-            eng.mha_long(_cu(exp["x_long"]))
+        with pytest.raises(host.ITAError, match=UNSUPPORTED):
+            eng.mha_long(cu(exp["x_long"]))
     return bad
 
 
@@ -175,9 +159,9 @@ def test_stream_kernel_inputs(torch_cuda, oracle, E, name, fast):
     x[5], x[6] = np.float32(0.5) * s, np.float32(1.5) * s
     oy, otaps = oracle.mha(x, t, taps=True)
     assert (otaps["x_q"][5] == 0).all() and (otaps["x_q"][6] == 2).all() and (otaps["x_q"][4, 5] == 127).all()   # ties to even
-    xc = _cu(x)
+    xc = cu(x)
     np.testing.assert_array_equal(eng.mha(xc).cpu().numpy(), oy)
-    np.testing.assert_array_equal(eng.mha_q8(_cu(otaps["x_q"])).cpu().numpy(), otaps["out_q"])
+    np.testing.assert_array_equal(eng.mha_q8(cu(otaps["x_q"])).cpu().numpy(), otaps["out_q"])
     np.testing.assert_array_equal(eng.ffn(xc).cpu().numpy(), oracle.ffn(x, t))
     x1 = oracle.add_ln(x, oy, t["norm1_0.w"], t["norm1_0.b"])
     x2 = oracle.add_ln(x1, oracle.ffn(x1, t), t["norm2_0.w"], t["norm2_0.b"])

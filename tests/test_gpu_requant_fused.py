@@ -5,7 +5,7 @@ switch ITA_FUSED_SITES=0 in a fresh process, at one and three frames (both colum
 Crafted blobs: requant_common's rounding cases put the neighbours of every rounding tie of a site into its accumulators
 by a zero weight row and the wanted value as the bias, so under the fused form the accumulator is C_site + that value;
 the travel_in range cases drive a row to the +-2^15 edge of the 16-bit travel format.  Which of them run fused is
-decided here on the CPU the way the loader decides it (test_requant_fused_cpu.proven) and asserted on the engine.
+decided here on the CPU the way the loader decides it (requant_fused_common.proven) and asserted on the engine.
 Flavours: E = 64 with the tokenizer in front (forward), the E = 64 and E = 128 layers (encoder_layer), ita_mha_int8
 and ita_mha_q8."""
 import os
@@ -18,7 +18,8 @@ import pytest
 import requant_common as rc
 from conftest import REPO, golden_files
 from drone_oa_iree_vit_accelerator_amd import host, params, synth
-from test_requant_fused_cpu import _differs, _k_of, proven
+from gpu_support import cu
+from requant_fused_common import differs, k_of, proven
 
 pytestmark = pytest.mark.gpu
 
@@ -33,11 +34,6 @@ def torch_cuda():
     import torch
     assert torch.cuda.is_available(), "GPU tests need a GPU"
     return torch
-
-
-def _cu(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _case(kind, E, site, j):
@@ -67,14 +63,14 @@ def _check_forms(eng, t, off=False):
         assert bool(lf["fused_sites"] >> i & 1) == (sites[s] is not None), (s, lf, sites)
         if sites[s] is not None:
             m, lg = rc.multiplier_of(t, s), s == "L"
-            assert lf["C"][i] == sites[s] and lf["K"][i] == _k_of(m, sites[s], 12615680 if lg else 12583040), (s, lf)
-            assert _differs(m, lf["C"][i], lf["K"][i], lg).size == 0, s
+            assert lf["C"][i] == sites[s] and lf["K"][i] == k_of(m, sites[s], 12615680 if lg else 12583040), (s, lf)
+            assert differs(m, lf["C"][i], lf["K"][i], lg).size == 0, s
     # fc1's fused ReLU form: its own proof, on top of a fused layer with a whole-layer image
     m1 = rc.multiplier_of(t, "fc1")
     c1 = proven(m1, relu=True)
     assert lf["fused_relu"] == (want and c1 is not None and eng.layer_forms()["layer_image"]), (lf, c1)
     if lf["fused_relu"]:
-        assert lf["C"][5] == c1 and lf["K"][5] == _k_of(m1, c1, 12582912) and _differs(m1, c1, lf["K"][5], relu=True).size == 0
+        assert lf["C"][5] == c1 and lf["K"][5] == k_of(m1, c1, 12582912) and differs(m1, c1, lf["K"][5], relu=True).size == 0
     else:
         assert lf["C"][5] == host.ACC_BIAS
     return want
@@ -103,13 +99,13 @@ def test_crafted(kind, E, site, j):
     forms = eng.layer_forms()
     assert forms["attn_image"] and forms["layer_image"]
     print(f"{c.name}: m = {float(c.m)!r}, fused {fused}, bases {[C - host.ACC_BIAS for C in eng.layer_fused()['C']]}")
-    x = _cu(c.x)
+    x = cu(c.x)
     out, taps, _ = exp["mha"]
     np.testing.assert_array_equal(eng.mha(x).cpu().numpy(), out)
-    np.testing.assert_array_equal(eng.mha_q8(_cu(taps["x_q"])).cpu().numpy(), taps["out_q"])
+    np.testing.assert_array_equal(eng.mha_q8(cu(taps["x_q"])).cpu().numpy(), taps["out_q"])
     np.testing.assert_array_equal(eng.encoder_layer(x).cpu().numpy(), exp["x2"])
     # the long kernels read the same layer's default-base image
-    np.testing.assert_array_equal(eng.mha_long_q8(_cu(exp["long"][1]["x_q"])).cpu().numpy(), exp["long"][1]["out_q"])
+    np.testing.assert_array_equal(eng.mha_long_q8(cu(exp["long"][1]["x_q"])).cpu().numpy(), exp["long"][1]["out_q"])
     eng.close()
 
 
@@ -137,11 +133,11 @@ def run_flavours(off=False):
             x = (rs.standard_normal((B, 128, E)) * 1.5).astype(np.float32)
             x[B - 1, ::3] *= 20.0                                   # saturating rows in the last frame
             oy, otaps = oracle.mha(x, t, taps=True)
-            np.testing.assert_array_equal(eng.mha(_cu(x)).cpu().numpy(), oy, err_msg=f"{name} mha B={B}")
-            np.testing.assert_array_equal(eng.mha_q8(_cu(otaps["x_q"])).cpu().numpy(), otaps["out_q"], err_msg=f"{name} q8 B={B}")
+            np.testing.assert_array_equal(eng.mha(cu(x)).cpu().numpy(), oy, err_msg=f"{name} mha B={B}")
+            np.testing.assert_array_equal(eng.mha_q8(cu(otaps["x_q"])).cpu().numpy(), otaps["out_q"], err_msg=f"{name} q8 B={B}")
             x1 = oracle.add_ln(x, oy, t["norm1_0.w"], t["norm1_0.b"])
             x2 = oracle.add_ln(x1, oracle.ffn(x1, t), t["norm2_0.w"], t["norm2_0.b"])
-            np.testing.assert_array_equal(eng.encoder_layer(_cu(x)).cpu().numpy(), x2, err_msg=f"{name} layer B={B}")
+            np.testing.assert_array_equal(eng.encoder_layer(cu(x)).cpu().numpy(), x2, err_msg=f"{name} layer B={B}")
         eng.close()
     # E = 64 with the tokenizer in front: the whole model's blob, x2 of forward against the oracle on the kernel's own tokens
     fx = params.load_fixture(golden_files("vitlstm_E64_seed0_B2.npz")[0])

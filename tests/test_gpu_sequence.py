@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import REPO, golden_files
+from gpu_support import cu
 
 pytestmark = pytest.mark.gpu
 
@@ -34,11 +35,6 @@ def _whole(eng, T, B):
     assert eng._reserved // B >= T, f"workspace of {eng._reserved} frames: {eng._reserved // B} steps per launch, wanted {T}"
 
 
-def _cu(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def _inputs(seed, T, B, zero_state=False):
     """time-major u8 frames, desvel, quat of T steps x B streams and a non-zero initial state"""
     from drone_oa_iree_vit_accelerator_amd import synth
@@ -56,10 +52,10 @@ def _steps(eng, img, dv, qt, h0, c0, T=None):
     """the reference: T calls of Engine.forward, state carried -> (vel (T,B,3), h, c)"""
     import torch
     T = img.shape[0] if T is None else T
-    st = (_cu(h0), _cu(c0))
+    st = (cu(h0), cu(c0))
     vels = []
     for t in range(T):
-        v, st = eng.forward(_cu(img[t]), _cu(dv[t]), _cu(qt[t]), st)
+        v, st = eng.forward(cu(img[t]), cu(dv[t]), cu(qt[t]), st)
         vels.append(v)
     torch.cuda.synchronize()
     assert eng.head_status() == 0
@@ -70,7 +66,7 @@ def _steps(eng, img, dv, qt, h0, c0, T=None):
 
 def _sequence(eng, img, dv, qt, h0, c0, **kw):
     import torch
-    vel, (h, c) = eng.forward_sequence(_cu(img), _cu(dv), _cu(qt), (_cu(h0), _cu(c0)), **kw)
+    vel, (h, c) = eng.forward_sequence(cu(img), cu(dv), cu(qt), (cu(h0), cu(c0)), **kw)
     torch.cuda.synchronize()
     assert eng.head_status() == 0
     return vel.cpu().numpy(), h.cpu().numpy(), c.cpu().numpy()
@@ -163,9 +159,9 @@ def test_lengths():
     lens = [12, 7, 1, 0, 12]
     img, dv, qt, h0, c0 = _inputs(33, T, B)
     vel = torch.full((T, B, 3), -77.0, device="cuda")
-    h, c = _cu(h0), _cu(c0)
+    h, c = cu(h0), cu(c0)
     hin, cin = h.clone(), c.clone()
-    out = eng.forward_sequence(_cu(img), _cu(dv), _cu(qt), (hin, cin), lengths=torch.tensor(lens), out=(vel, h, c))
+    out = eng.forward_sequence(cu(img), cu(dv), cu(qt), (hin, cin), lengths=torch.tensor(lens), out=(vel, h, c))
     torch.cuda.synchronize()
     assert eng.head_status() == 0
     assert out[0] is vel and out[1][0] is h and out[1][1] is c
@@ -190,9 +186,9 @@ def test_in_place(T, B):
     _whole(eng, T, B)
     img, dv, qt, h0, c0 = _inputs(5, T, B)
     ref = _sequence(eng, img, dv, qt, h0, c0)
-    h, c = _cu(h0), _cu(c0)
+    h, c = cu(h0), cu(c0)
     vel = torch.empty((T, B, 3), device="cuda")
-    eng.forward_sequence(_cu(img), _cu(dv), _cu(qt), (h, c), out=(vel, h, c))
+    eng.forward_sequence(cu(img), cu(dv), cu(qt), (h, c), out=(vel, h, c))
     torch.cuda.synchronize()
     assert eng.head_status() == 0
     _assert_equal((vel.cpu().numpy(), h.cpu().numpy(), c.cpu().numpy()), ref, "in place")
@@ -206,8 +202,8 @@ def test_hidden_not_modified():
     eng, _ = _engine(reserve=6)
     _whole(eng, 3, 2)
     img, dv, qt, h0, c0 = _inputs(6, 3, 2)
-    h, c = _cu(h0), _cu(c0)
-    eng.forward_sequence(_cu(img), _cu(dv), _cu(qt), (h, c))
+    h, c = cu(h0), cu(c0)
+    eng.forward_sequence(cu(img), cu(dv), cu(qt), (h, c))
     torch.cuda.synchronize()
     np.testing.assert_array_equal(h.cpu().numpy(), h0)
     np.testing.assert_array_equal(c.cpu().numpy(), c0)
@@ -273,7 +269,7 @@ def test_interleaved_with_the_step_path():
     _assert_equal(_sequence(eng, *x2), r2, "sequence 1")
     g = eng.graphed_step(B)
     for t in range(3):
-        g.img.copy_(_cu(x3[0][t])); g.desvel.copy_(_cu(x3[1][t])); g.quat.copy_(_cu(x3[2][t]))
+        g.img.copy_(cu(x3[0][t])); g.desvel.copy_(cu(x3[1][t])); g.quat.copy_(cu(x3[2][t]))
         g()
         torch.cuda.synchronize()
         np.testing.assert_array_equal(g.vel.cpu().numpy(), r3[0][t], err_msg=f"graph step {t}")
@@ -330,9 +326,9 @@ def test_tail_mode_0_is_refused():
     eng.set_tail_mode(0)
     img, dv, qt, h0, c0 = _inputs(3, 2, 2)
     vel = torch.full((2, 2, 3), -5.0, device="cuda")
-    h, c = _cu(h0), _cu(c0)
+    h, c = cu(h0), cu(c0)
     with pytest.raises(host.ITAError) as ei:
-        eng.forward_sequence(_cu(img), _cu(dv), _cu(qt), (h, c), out=(vel, h, c))
+        eng.forward_sequence(cu(img), cu(dv), cu(qt), (h, c), out=(vel, h, c))
     assert str(ei.value).startswith("ita status -4:")   # ITA_ERR_UNSUPPORTED
     assert host.lib().ita_last_error() == -4
     torch.cuda.synchronize()

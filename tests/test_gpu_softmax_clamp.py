@@ -21,19 +21,15 @@ import numpy as np
 import pytest
 
 from drone_oa_iree_vit_accelerator_amd import host
+from gpu_support import UNSUPPORTED, cu, refused_untouched
 import long_taps_common as ltc
+from requant_common import MHA_TAPS
 import softmax_clamp_common as scc
-from test_gpu_requant_edges import MHA_TAPS, UNSUPPORTED, _refused_untouched
 
 pytestmark = pytest.mark.gpu
 
 FORMS = list(scc.FORMS)
 TENSOR, ROW, STATS = host.LONG_TENSOR_TAPS, host.LONG_ROW_TAPS, host.LONG_STATS
-
-
-def _cu(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _engine(form, H=1):
@@ -60,7 +56,7 @@ def test_block_kernel_taps(form):
     """mha(x, taps=True): ita_mha_kernel<E, 1>, all eight taps and the output; logits are the clamped codes"""
     e = scc.expect(form, "s128")
     eng = _engine(form)
-    y, tp = eng.mha(_cu(e["x"]), taps=True)
+    y, tp = eng.mha(cu(e["x"]), taps=True)
     _equal(tp["logits"], np.clip(e["raw"][:, 0], -128, 127).astype(np.int8), f"{form} logits against the wanted rows")
     for k in MHA_TAPS:
         _equal(tp[k], e["taps"][k], f"{form} tap {k}")
@@ -73,9 +69,9 @@ def test_stream_kernel(form):
     """mha(x), mha_q8(x_q) and encoder_layer(x): ita_softmax_packed16 in the attention image and in the whole-layer image"""
     e = scc.expect(form, "s128")
     eng = _engine(form)
-    xc = _cu(e["x"])
+    xc = cu(e["x"])
     _equal(eng.mha(xc), e["out"], f"{form} mha")
-    _equal(eng.mha_q8(_cu(e["taps"]["x_q"])), e["taps"]["out_q"], f"{form} mha_q8")
+    _equal(eng.mha_q8(cu(e["taps"]["x_q"])), e["taps"]["out_q"], f"{form} mha_q8")
     _equal(eng.encoder_layer(xc), e["x2"], f"{form} encoder_layer")
     eng.close()
 
@@ -86,7 +82,7 @@ def test_two_heads(form):
     block kernels; the int8 entries and the long entry refuse it, as a blob without stream images"""
     e = scc.expect(form, "h2")
     eng = _engine(form, H=2)
-    xc = _cu(e["x"])
+    xc = cu(e["x"])
     y, tp = eng.mha(xc, taps=True)
     _equal(tp["logits"], np.clip(e["raw"], -128, 127).astype(np.int8), f"{form} logits against the wanted rows")
     for k in MHA_TAPS:
@@ -94,10 +90,10 @@ def test_two_heads(form):
     _equal(y, e["out"], form)
     _equal(eng.mha(xc), e["out"], f"{form} H = 2 mha")
     _equal(eng.encoder_layer(xc), e["x2"], f"{form} H = 2 encoder_layer")
-    xq = _cu(e["taps"]["x_q"])
-    assert _refused_untouched(eng, host.lib().ita_mha_q8, xq)
-    assert _refused_untouched(eng, host.lib().ita_mha_long_q8, xq, 128)
-    with pytest.raises(host.ITAError, match=f"ita status {UNSUPPORTED}"):
+    xq = cu(e["taps"]["x_q"])
+    assert refused_untouched(eng, host.lib().ita_mha_q8, xq)
+    assert refused_untouched(eng, host.lib().ita_mha_long_q8, xq, 128)
+    with pytest.raises(host.ITAError, match=UNSUPPORTED):
         eng.mha_long(xc)
     eng.close()
 
@@ -111,8 +107,8 @@ def test_long_kernels(form, S):
     e = scc.expect(form, f"long{S}")
     tp = e["taps"]
     eng = _engine(form)
-    xc = _cu(e["x"])
-    _equal(eng.mha_long_q8(_cu(tp["x_q"])), tp["out_q"], f"{form} S={S} mha_long_q8")
+    xc = cu(e["x"])
+    _equal(eng.mha_long_q8(cu(tp["x_q"])), tp["out_q"], f"{form} S={S} mha_long_q8")
     y = eng.mha_long(xc)
     _equal(y, e["out"], f"{form} S={S} mha_long")
     rows = list(range(S))
@@ -140,13 +136,13 @@ def test_long_batch_position_and_repeat():
     form, S = "exact", 384
     e = scc.expect(form, f"long{S}")
     eng = _engine(form)
-    xc = _cu(e["x"])
+    xc = cu(e["x"])
     xf = xc.flip(0).contiguous()
     rows = list(range(0, S, 3))
     y = eng.mha_long(xc)
     _equal(y, e["out"], "first call")
     assert torch.equal(eng.mha_long(xf).flip(0), y) and torch.equal(eng.mha_long(xc), y)
-    xq = _cu(e["taps"]["x_q"])
+    xq = cu(e["taps"]["x_q"])
     q = eng.mha_long_q8(xq)
     assert torch.equal(eng.mha_long_q8(xq.flip(0).contiguous()).flip(0), q) and torch.equal(eng.mha_long_q8(xq), q)
     _, t1 = eng.mha_long_taps(xc, rows)

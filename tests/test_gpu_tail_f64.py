@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 
 import tail_f64_common as tc
-from drone_oa_iree_vit_accelerator_amd import host, synth
+from drone_oa_iree_vit_accelerator_amd import synth
+from gpu_support import cu, engine_pool
 
 pytestmark = pytest.mark.gpu
 
@@ -23,15 +24,7 @@ def engines():
     """one engine per parameter set (loading a blob builds the fold), shared by the tests below and left in tail mode 1"""
     import torch
     assert torch.cuda.is_available(), "GPU tests need a GPU"
-    cache = {}
-
-    def get(key, fp):
-        if key not in cache:
-            cache[key] = host.Engine(tc.blob(fp), device=0)
-        return cache[key]
-    yield get
-    for e in cache.values():
-        e.close()
+    yield from engine_pool(lambda key, fp: tc.blob(fp), lambda key, fp: key)
 
 
 def _engine(engines, name):
@@ -39,14 +32,9 @@ def _engine(engines, name):
     return engines("seed0" if name[0] == "A" else name, cs["fp"])
 
 
-def _cu(a):
-    import torch
-    return torch.from_numpy(np.array(a, order="C")).cuda()   # a copy: the cases' arrays are read-only
-
-
 def _tail(eng, x2, dv, q, h_in, c_in):
     import torch
-    vel, (h, c) = eng.tail(_cu(x2), _cu(dv), _cu(q), (_cu(h_in), _cu(c_in)))
+    vel, (h, c) = eng.tail(cu(x2), cu(dv), cu(q), (cu(h_in), cu(c_in)))
     torch.cuda.synchronize()
     assert eng.head_status() == 0
     return dict(vel=vel.cpu().numpy(), h=h.cpu().numpy(), c=c.cpu().numpy())
@@ -134,8 +122,8 @@ def test_forward_path_planes(engines, name):
         eng = _engine(engines, name)
     B = len(cs["x2"])
     fr = synth.frames(70, B)
-    dv, q, hid = _cu(cs["desvel"]), _cu(cs["quat"]), (_cu(cs["h_in"]), _cu(cs["c_in"]))
-    vel, (h, c), tp = eng.forward(_cu(fr["img_u8"]), dv, q, hid, taps=True)
+    dv, q, hid = cu(cs["desvel"]), cu(cs["quat"]), (cu(cs["h_in"]), cu(cs["c_in"]))
+    vel, (h, c), tp = eng.forward(cu(fr["img_u8"]), dv, q, hid, taps=True)
     vel2, (h2, c2) = eng.tail(tp["x2"], dv, q, hid)
     torch.cuda.synchronize()
     assert eng.head_status() == 0
@@ -164,16 +152,16 @@ def test_sequence_equals_steps_saturated(engines):
     dv, q = fr["desvel"].reshape(T, B), fr["quat"].reshape(T, B, 4)
     h0, c0 = cs["h_in"][:, :B], np.ascontiguousarray(cs["c_in"][:, 3:8])        # c_in of -1, +-20, +-50
     vel = torch.full((T, B, 3), -77.0, device="cuda")
-    h, c = _cu(h0), _cu(c0)
-    eng.forward_sequence(_cu(img), _cu(dv), _cu(q), (h.clone(), c.clone()), lengths=torch.tensor(lens), out=(vel, h, c))
+    h, c = cu(h0), cu(c0)
+    eng.forward_sequence(cu(img), cu(dv), cu(q), (h.clone(), c.clone()), lengths=torch.tensor(lens), out=(vel, h, c))
     torch.cuda.synchronize()
     assert eng.head_status() == 0
     vel, h, c = vel.cpu().numpy(), h.cpu().numpy(), c.cpu().numpy()
     assert np.isfinite(vel).all() and np.isfinite(h).all() and np.isfinite(c).all()
     for b, n in enumerate(lens):
-        st = (_cu(h0[:, b:b + 1]), _cu(c0[:, b:b + 1]))
+        st = (cu(h0[:, b:b + 1]), cu(c0[:, b:b + 1]))
         for t in range(n):
-            v, st = eng.forward(_cu(img[t, b:b + 1]), _cu(dv[t, b:b + 1]), _cu(q[t, b:b + 1]), st)
+            v, st = eng.forward(cu(img[t, b:b + 1]), cu(dv[t, b:b + 1]), cu(q[t, b:b + 1]), st)
             np.testing.assert_array_equal(_bits(vel[t, b]), _bits(v.cpu().numpy()[0]), err_msg=f"vel stream {b} step {t}")
         assert eng.head_status() == 0
         np.testing.assert_array_equal(_bits(h[:, b]), _bits(st[0].cpu().numpy()[:, 0]), err_msg=f"h stream {b}")
@@ -187,9 +175,9 @@ def test_recurrence(engines):
     import torch
     cs, steps = tc.recurrence()
     eng = engines("R1", cs["fp"])
-    x2 = [_cu(cs["x2"][i]) for i in range(4)]
-    side = [(_cu(dv), _cu(q)) for dv, q in cs["side"]]
-    st = (_cu(cs["h_in"]), _cu(cs["c_in"]))
+    x2 = [cu(cs["x2"][i]) for i in range(4)]
+    side = [(cu(dv), cu(q)) for dv, q in cs["side"]]
+    st = (cu(cs["h_in"]), cu(cs["c_in"]))
     outs = []
     for t in range(tc.R1_STEPS):
         vel, st = eng.tail(x2[t % 4], *side[t % 4], st)

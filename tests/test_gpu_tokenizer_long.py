@@ -12,7 +12,8 @@ import pytest
 from conftest import golden_files
 from drone_oa_iree_vit_accelerator_amd import host, params, synth
 from drone_oa_iree_vit_accelerator_amd import tokenizer_long_ref as tl
-from test_tokenizer_long_cpu import composed, tok_params
+from gpu_support import cu, engine_pool
+from tokenizer_long_common import composed, tok_params
 
 pytestmark = pytest.mark.gpu
 
@@ -48,10 +49,7 @@ def _blob(E):
 
 @pytest.fixture(scope="module")
 def engines(torch_cuda):
-    e = {E: host.Engine(_blob(E), device=0) for E in (64, 128)}
-    yield e
-    for eng in e.values():
-        eng.close()
+    yield from engine_pool(_blob)
 
 
 def _frames(dtype, shape, seed):
@@ -62,12 +60,6 @@ def _frames(dtype, shape, seed):
         a = rs.randint(0, 65536, size=shape).astype(np.uint16)
         return a.view(np.int16) if dtype == "i16" else a
     return rs.uniform(0, 1, size=shape).astype(np.float32)
-
-
-def _cu(torch, a):
-    if a.dtype == np.uint16:       # uploaded as the same bits
-        return torch.from_numpy(np.ascontiguousarray(a).view(np.int16)).cuda().view(torch.uint16)
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _guarded(torch, eng, frames, th, tw, n, depth_scale=None):
@@ -96,13 +88,13 @@ def test_anchor_equals_the_fixed_tokenizer(torch_cuda, engines, E, B):
     """60 x 90 -> 8 x 16: f32 frames give Engine.tokenizer's bits on the same frames; u8 frames give those of the frames
     divided by 255 (f32(code) / 255.0f, correctly rounded: divided on the host) -- not those of the u8 wire form, which
     folds the division into the conv weights and agrees to ~1e-6 only.  300 frames: more than there are CUs."""
-    torch, eng = torch_cuda, engines[E]
+    torch, eng = torch_cuda, engines(E)
     u8 = _frames("u8", (B, 60, 90), 100 + B)
-    f32 = _cu(torch, u8.astype(np.float32) / np.float32(255.0))
+    f32 = cu(u8.astype(np.float32) / np.float32(255.0))
     want = eng.tokenizer(f32)
     assert torch.equal(eng.tokenize_long(f32, 8, 16), want)
-    assert torch.equal(eng.tokenize_long(_cu(torch, u8), 8, 16), want)
-    wire = eng.tokenizer(_cu(torch, u8))
+    assert torch.equal(eng.tokenize_long(cu(u8), 8, 16), want)
+    wire = eng.tokenizer(cu(u8))
     assert float((wire - want).abs().max()) <= 2e-5
 
 
@@ -111,13 +103,13 @@ def test_anchor_equals_the_fixed_tokenizer(torch_cuda, engines, E, B):
 @pytest.mark.parametrize("E", [64, 128])
 def test_shapes_equal_the_definition(torch_cuda, engines, oracle, E, shape, grid):
     f = _frames("f32", (2,) + shape, shape[0] * 4099 + shape[1])
-    _same_bits(_guarded(torch_cuda, engines[E], _cu(torch_cuda, f), *grid, 2), composed(oracle, f, *grid, E))
+    _same_bits(_guarded(torch_cuda, engines(E), cu(f), *grid, 2), composed(oracle, f, *grid, E))
 
 
 def test_config5_shape(torch_cuda, engines, oracle):
     """480 x 720 -> 64 x 128 = 8192 tokens, E = 128, u8 frames"""
     f = _frames("u8", (2, 480, 720), 5)
-    _same_bits(_guarded(torch_cuda, engines[128], _cu(torch_cuda, f), 64, 128, 2), composed(oracle, f, 64, 128, 128))
+    _same_bits(_guarded(torch_cuda, engines(128), cu(f), 64, 128, 2), composed(oracle, f, 64, 128, 128))
 
 
 @pytest.mark.parametrize("shape", [(97, 131), (61, 93)], ids=["97x131-direct", "61x93-window"])
@@ -131,7 +123,7 @@ def test_every_dtype(torch_cuda, engines, oracle, E, dtype, shape):
     if scale:
         v = tl.pixel_values(f, scale)
         assert (v == 1.0).any() and (v < 1.0).any()
-    _same_bits(_guarded(torch_cuda, engines[E], _cu(torch_cuda, f), 8, 16, 2, depth_scale=scale), composed(oracle, f, 8, 16, E, scale))
+    _same_bits(_guarded(torch_cuda, engines(E), cu(f), 8, 16, 2, depth_scale=scale), composed(oracle, f, 8, 16, E, scale))
 
 
 def test_inf_where_only_a_pad_slot_could_reach(torch_cuda, engines, oracle):
@@ -151,7 +143,7 @@ def test_inf_where_only_a_pad_slot_could_reach(torch_cuda, engines, oracle):
     want = composed(oracle, f, th, tw, 64)
     assert np.isfinite(want).all()
     for E in (64, 128):
-        got = _guarded(torch_cuda, engines[E], _cu(torch_cuda, f), th, tw, 2)
+        got = _guarded(torch_cuda, engines(E), cu(f), th, tw, 2)
         assert np.isfinite(got).all()
         _same_bits(got, composed(oracle, f, th, tw, E))
 
@@ -161,22 +153,22 @@ def test_inf_where_only_a_pad_slot_could_reach(torch_cuda, engines, oracle):
 def test_cropped_misaligned_view_is_read_through_its_strides(torch_cuda, engines, oracle, dtype):
     """a crop of a larger buffer whose first pixel lies one pixel behind an aligned address: no copy is made (the view's
     own strides reach the C entry) and the tokens are those of the contiguous copy"""
-    torch, eng = torch_cuda, engines[64]
+    torch, eng = torch_cuda, engines(64)
     big = _frames(dtype, (3, 140, 201), 31)
-    view = _cu(torch, big)[:, 7:7 + 97, 34:34 + 131]
+    view = cu(big)[:, 7:7 + 97, 34:34 + 131]
     px = view.element_size()
     assert not view.is_contiguous() and (view.data_ptr() // px) % 2 == 1
     assert eng._frame_strides(view) == (201, 140 * 201)
     got = _guarded(torch, eng, view, 8, 16, 3)
-    _same_bits(got, eng.tokenize_long(_cu(torch, big[:, 7:7 + 97, 34:34 + 131]), 8, 16).cpu().numpy())
+    _same_bits(got, eng.tokenize_long(cu(big[:, 7:7 + 97, 34:34 + 131]), 8, 16).cpu().numpy())
     _same_bits(got, composed(oracle, big[:, 7:7 + 97, 34:34 + 131], 8, 16, 64))
 
 
 # ---- determinism, batch independence, streams
 @pytest.mark.parametrize("E", [64, 128])
 def test_frames_do_not_depend_on_their_batch_or_stream(torch_cuda, engines, E):
-    torch, eng = torch_cuda, engines[E]
-    f = _cu(torch, _frames("u8", (5, 120, 180), 41))
+    torch, eng = torch_cuda, engines(E)
+    f = cu(_frames("u8", (5, 120, 180), 41))
     a = eng.tokenize_long(f, 16, 32)
     assert torch.equal(a, eng.tokenize_long(f, 16, 32))
     assert torch.equal(eng.tokenize_long(f[3:4], 16, 32), a[3:4])
@@ -192,9 +184,9 @@ def test_frames_do_not_depend_on_their_batch_or_stream(torch_cuda, engines, E):
 # ---- the chain
 def test_encode_frames_long_is_tokenize_then_encode(torch_cuda, engines):
     """the int8 E = 128 two-layer blob: encode_frames_long = encode_long(tokenize_long), and ita_fusion_tail_large takes it"""
-    torch, eng = torch_cuda, engines[128]
+    torch, eng = torch_cuda, engines(128)
     assert eng.num_layers == 2 and eng.attn_kind(0) == host.ATTN_INT8 and eng.ffn_kind(0) == host.FFN_INT8
-    f = _cu(torch, _frames("u8", (2, 120, 180), 43))
+    f = cu(_frames("u8", (2, 120, 180), 43))
     got = eng.encode_frames_long(f, 16, 32)
     assert tuple(got.shape) == (2, 512, 128)
     assert torch.equal(got, eng.encode_long(eng.tokenize_long(f, 16, 32)))
@@ -215,10 +207,10 @@ def _call(eng, src, dtype, H, W, rs, fs, scale, th, tw, out, batch):
 def test_refusals_before_any_launch(torch_cuda, engines, oracle):
     """every INVALID_ARG and UNSUPPORTED case of the entry returns its status and leaves a canary-filled output as it
     was; the handle then runs normally"""
-    torch, eng = torch_cuda, engines[64]
+    torch, eng = torch_cuda, engines(64)
     H, W, th, tw = 20, 30, 8, 16
     f = _frames("u8", (2, H, W), 47)
-    src = _cu(torch, f)
+    src = cu(f)
     out = torch.full((2 * 1024 * 64,), CANARY, dtype=torch.float32, device="cuda")   # room for 2 x 1024 tokens of E = 64
     s, o, ds = src.data_ptr(), out.data_ptr(), 1.0 / 65535.0
     ok = dict(src=s, dtype=host.PIXEL_U8, H=H, W=W, rs=W, fs=H * W, scale=ds, th=th, tw=tw, out=o, batch=2)
@@ -265,8 +257,8 @@ def test_a_handle_without_weights_is_refused(torch_cuda):
 def test_profiling_counts_a_call_as_the_tokenizer_stage(torch_cuda, engines):
     """between profile_begin(only_stage="tokenizer") and profile_end every sampled call is one forward with a tokenizer time
     and nothing else; with all stages selected the call, which is no whole forward, is not counted; the tokens do not change"""
-    torch, eng = torch_cuda, engines[64]
-    f = _cu(torch, _frames("u8", (2, 120, 180), 53))
+    torch, eng = torch_cuda, engines(64)
+    f = cu(_frames("u8", (2, 120, 180), 53))
     want = eng.tokenize_long(f, 16, 32)
     eng.profile_begin(8, every_n=2, only_stage="tokenizer")
     got = [eng.tokenize_long(f, 16, 32) for _ in range(4)]

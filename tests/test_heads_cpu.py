@@ -111,8 +111,8 @@ def test_blob_header_carries_the_head_count(tmp_path):
         b = params.pack_blob(t, E=64, H=H)
         assert lib.ita_validate_blob(b, len(b), bad) != 0, H
     # the command line: a state dict does not hold the head count
-    from test_export_blob import _converted_state_dict
-    torch.save(_converted_state_dict(golden_files("qatckpt_E64_s0.npz")[0]), str(tmp_path / "ckpt.pth"))
+    from float_graph_common import converted_state_dict
+    torch.save(converted_state_dict(golden_files("qatckpt_E64_s0.npz")[0]), str(tmp_path / "ckpt.pth"))
     out = tmp_path / "w.itaw"
     r = subprocess.run([sys.executable, os.path.join(REPO, "tools", "export_blob.py"), "--checkpoint", str(tmp_path / "ckpt.pth"),
                         "--out", str(out), "--heads", "3", "--unsafe-load"], capture_output=True, text=True)

@@ -21,7 +21,7 @@ from drone_oa_iree_vit_accelerator_amd import mha_heads_ref as ref
 import long_hist_common as lhc
 import long_limits_common as llc
 import softmax_clamp_common as scc
-from test_gpu_long_layer import _case, _long_f32
+from long_cases import long_case, long_f32
 
 LLVM = "/opt/rocm/lib/llvm/bin"
 
@@ -34,8 +34,9 @@ def _shapes(h, B):
 @pytest.mark.parametrize("name", ["vitlstm_E64_seed0_B2", "blocks_E128_seed0_B1"])
 def test_hist_is_the_count_of_the_definitions_tensors(name):
     S, B = 256, 2
-    E, _, t, _, _ = _case(name)
-    x = _long_f32(S + B, B, S, E, t)
+    case = long_case(name)
+    E, t = case.E, case.t
+    x = long_f32(S + B, B, S, E, t)
     _, tp, acc = ref.mha(x, t, 1, 0, taps=True)
     st = asr.stats(x, t)
     for block in (512, 96):          # one block, and blocks that do not divide S
@@ -58,10 +59,11 @@ def test_hist_is_the_count_of_the_definitions_tensors(name):
 def test_class_form_equals_the_whole_matrix(name, l):
     """an S = 512 frame drawn from 48 distinct tokens, 16 of them single"""
     S, V, singles, seed = 512, 48, 16, 9
-    E, _, t, _, _ = _case(name)
+    case = long_case(name)
+    E, t = case.E, case.t
     idx, reps, cls, counts = llc.vocabulary(S, V, singles, seed)
     assert int((counts == 1).sum()) == 16 and counts.sum() == S
-    x = np.ascontiguousarray(_long_f32(seed, 1, 64, E, t, l)[:, :V][:, idx])    # (_long_f32 builds blocks of 32 tokens)
+    x = np.ascontiguousarray(long_f32(seed, 1, 64, E, t, l)[:, :V][:, idx])    # (_long_f32 builds blocks of 32 tokens)
     want = ahr.hist(x, t, l)
     got = ahr.hist_from_classes(x[0, reps], counts, t, l)
     _shapes(got, 1)

@@ -110,10 +110,10 @@ def test_float_class_form_is_the_definition(E, s):
 @pytest.mark.parametrize("name,l", ll.INT8_MODELS)
 def test_int8_class_form_is_the_definition(name, l):
     """S = 1024: the class form equals attention_stats_ref.stats exactly, dtypes and shapes included"""
-    from test_gpu_long_layer import _case
+    from long_cases import long_case
     x, rows, taps, st = ll.int8_vocab_ref(name, l, 1024)
     assert len(rows) == 1024 and taps["logits"].shape == (1, 1024, 1024)
-    want = asr.stats(x, _case(name)[2], l)
+    want = asr.stats(x, long_case(name).t, l)
     assert set(st) == set(asr.NAMES)
     for k, v in want.items():
         assert st[k].dtype == v.dtype and st[k].shape == v.shape, k

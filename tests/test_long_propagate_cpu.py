@@ -20,6 +20,7 @@ from drone_oa_iree_vit_accelerator_amd import attention_rollout_ref as arr
 from drone_oa_iree_vit_accelerator_amd import attention_stats_ref as asr
 from drone_oa_iree_vit_accelerator_amd import host
 from drone_oa_iree_vit_accelerator_amd import mha_heads_ref as ref
+from long_cases import long_case
 import long_propagate_common as lpc
 import long_taps_common as ltc
 
@@ -89,7 +90,8 @@ def test_digit_planes_reproduce_the_wide_product():
 
 def test_one_layer_rollout_of_a_one_hot(oracle):
     name = "vitlstm_E64_seed0_B2"
-    E, nl, t, fp, _ = lpc.rollout_case(name)
+    case = long_case(name)
+    nl, t, fp = case.num_layers, case.t, case.fp
     assert nl == 1
     S, B, rows = 256, 2, (0, 100, 255)
     x = lpc.frames(name, S, B)

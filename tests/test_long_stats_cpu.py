@@ -18,7 +18,7 @@ from drone_oa_iree_vit_accelerator_amd import attention_stats_ref as asr
 from drone_oa_iree_vit_accelerator_amd import host
 from drone_oa_iree_vit_accelerator_amd import mha_heads_ref as ref
 import long_taps_common as ltc
-from test_gpu_long_taps import _case, _tokens
+from long_cases import long_case, tokens
 
 LLVM = "/opt/rocm/lib/llvm/bin"
 STATS = ("row_max", "row_sum", "row_mass", "row_nnz", "col_mass", "col_nnz")
@@ -27,8 +27,9 @@ STATS = ("row_max", "row_sum", "row_mass", "row_nnz", "col_mass", "col_nnz")
 @pytest.mark.parametrize("name", ["vitlstm_E64_seed0_B2", "blocks_E128_seed0_B1"])
 def test_stats_are_the_sums_of_the_definitions_probabilities(name):
     S, B = 256, 2
-    E, _, t, _ = _case(name)
-    x = _tokens(S + B, B, S, E, t)
+    case = long_case(name)
+    E, t = case.E, case.t
+    x = tokens(S + B, B, S, E, t)
     _, tp = ref.mha(x, t, 1, 0)
     p, lg = tp["probs"].astype(np.int64), tp["logits"]
     for block in (512, 96):          # one block, and blocks that do not divide S

@@ -1,7 +1,6 @@
 """The attention-only QAT graph (models/ITA_single_layer_upsample_shuffle/QAT_only_attn/model.py: int8 attention,
 float32 FFN + residual + LayerNorm2) on the CPU: its oracle composition against the reference's fixtures, the
 ITAW0002 blob format (export, validation, refusal by consumers that only know the int8 FFN)."""
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -12,41 +11,10 @@ import torch
 
 from conftest import REPO, golden_files
 from drone_oa_iree_vit_accelerator_amd import params, synth
+from float_graph_common import converted_state_dict, plugin, unpack, validate  # noqa: F401
+from only_attn_common import composed, fp as only_attn_fp, tensors
 
 FIX = golden_files("onlyattn*l_E64_*.npz")
-
-
-def _fp(d):
-    return synth.float_params(int(d["meta.seed"]), E=64, num_layers=int(d["meta.num_layers"]))
-
-
-def _tensors(d, fp):
-    """blob-name keyed tensors of the attention-only graph (what blob_from_record packs)"""
-    L = int(d["meta.num_layers"])
-    t = {}
-    for i in range(L):
-        t.update(params.attention_tensors(d, f"attn{i}.", i))
-    t.update(params.float_tensors(fp, L))
-    return t
-
-
-def composed(oracle, d, fp, image, desvel, quat, h_in=None, c_in=None):
-    """oracle.tokenizer -> per layer mha + add_ln (LN1), linear_f32 / ReLU / linear_f32 + add_ln (LN2) -> tail ->
-    linear_f32 -> head_from_dec.  Returns (vel, h, c, taps)."""
-    L = int(d["meta.num_layers"])
-    t = _tensors(d, fp)
-    x = oracle.tokenizer(image, t["tok.conv_w"], t["tok.conv_b"], t["tok.ln_w"], t["tok.ln_b"])
-    tp = {"tokens": x}
-    for i in range(L):
-        x1 = oracle.add_ln(x, oracle.mha(x, t, i), t[f"norm1_{i}.w"], t[f"norm1_{i}.b"])
-        hid = np.maximum(oracle.linear_f32(x1, t[f"ffn{i}.w1f"], t[f"ffn{i}.b1f"]), np.float32(0))
-        x = oracle.add_ln(x1, oracle.linear_f32(hid, t[f"ffn{i}.w2f"], t[f"ffn{i}.b2f"]), t[f"norm2_{i}.w"], t[f"norm2_{i}.b"])
-        tp[f"x1_{i}"], tp[f"x2_{i}"] = x1, x
-    tp["x1"], tp["x2"] = tp[f"x1_{L - 1}"], x
-    tp["feat"] = oracle.tail(x, t["tail.conv_w"], t["tail.conv_b"])
-    tp["dec"] = oracle.linear_f32(tp["feat"], t["dec.w"], t["dec.b"])
-    vel, h, c = oracle.head_from_dec(tp["dec"], desvel, quat, fp, h_in, c_in)
-    return vel, h, c, tp
 
 
 def test_fixtures_present():
@@ -58,12 +26,12 @@ def test_fixtures_present():
 @pytest.mark.parametrize("path", FIX, ids=lambda p: os.path.basename(p)[:-4])
 def test_composition_matches_reference(oracle, path):
     d = params.load_fixture(path)
-    fp = _fp(d)
+    fp = only_attn_fp(d)
     assert str(d["meta.params_sha256"]) == synth.digest(fp)
     vel0, h0, c0, tp = composed(oracle, d, fp, d["in0.img_u8"], d["in0.desvel"], d["in0.quat"])
     assert np.abs(tp["tokens"] - d["s0.tok.out"]).max() <= 2e-5
     # the int8 codes of every attention block are the reference's (same input codes, same probabilities)
-    t = _tensors(d, fp)
+    t = tensors(d, fp)
     x = tp["tokens"]
     for i in range(int(d["meta.num_layers"])):
         _, q = oracle.mha(x, t, i, taps=True)
@@ -82,7 +50,7 @@ def test_composition_matches_reference(oracle, path):
 
 def _only_attn_blob(path=None):
     d = params.load_fixture(path or golden_files("onlyattn1l_E64_s0_B2.npz")[0])
-    return d, params.blob_from_record(d, _fp(d), E=64, num_layers=int(d["meta.num_layers"]))
+    return d, params.blob_from_record(d, only_attn_fp(d), E=64, num_layers=int(d["meta.num_layers"]))
 
 
 def test_blob_magic_and_tensors():
@@ -108,29 +76,8 @@ def _names(blob):
     return [blob[64 + 72 * i: 64 + 72 * i + 32].split(b"\0")[0].decode() for i in range(n)]
 
 
-def _converted_state_dict(path):
-    """gen_only_attn_checkpoint's record -> the converted model's state_dict (float parameters: the seed's synthetic ones)"""
-    d = np.load(path)
-    fp = synth.float_params(int(d["meta.seed"]), E=64)
-    assert str(d["meta.params_sha256"]) == synth.digest(fp)
-    sd = {}
-    for k in d["keys"]:
-        k = str(k)
-        if "d." + k in d:
-            sd[k] = getattr(torch, str(d["d." + k]))
-        elif "q." + k + ".int_repr" in d:
-            w = torch._make_per_tensor_quantized_tensor(torch.from_numpy(d["q." + k + ".int_repr"]),
-                                                        float(d["q." + k + ".scale"]), int(d["q." + k + ".zero_point"]))
-            sd[k] = (w, torch.from_numpy(d["q." + k + ".bias"]))
-        elif "t." + k in d:
-            sd[k] = torch.from_numpy(d["t." + k])
-        else:
-            sd[k] = torch.from_numpy(fp[k])
-    return sd
-
-
 def test_export_converted_checkpoint(tmp_path):
-    sd = _converted_state_dict(golden_files("onlyattn_qatckpt_E64_s0.npz")[0])
+    sd = converted_state_dict(golden_files("onlyattn_qatckpt_E64_s0.npz")[0])
     assert "ffn_blocks.0.fc1.weight" in sd and "ffn_blocks.0.fc1._packed_params._packed_params" not in sd
     _, want = _only_attn_blob()      # same seed, same calibration frames
     assert params.blob_from_state_dict(sd) == want
@@ -145,7 +92,7 @@ def test_export_converted_checkpoint(tmp_path):
 
 def _retensor(blob, name, dtype=None, shrink=False, drop=False):
     """the same tensors repacked with one of them changed (ITAW0002 kept)"""
-    t = _unpack(blob)
+    t = unpack(blob)
     if drop:
         del t[name]
     elif shrink:
@@ -156,58 +103,26 @@ def _retensor(blob, name, dtype=None, shrink=False, drop=False):
                             ffn_f32=blob[:8] == b"ITAW0002")
 
 
-_NP = {0: np.float32, 1: np.int8, 2: np.int32, 3: np.uint8, 4: np.float16}
-
-
-def _unpack(blob):
-    n = np.frombuffer(blob[8:12], np.int32)[0]
-    t = {}
-    for i in range(n):
-        e = blob[64 + 72 * i: 64 + 72 * (i + 1)]
-        nm = e[:32].split(b"\0")[0].decode()
-        dt, nd = np.frombuffer(e[32:40], np.int32)
-        shape = [int(s) for s in np.frombuffer(e[40:56], np.int32)[:nd]]
-        off, nb = (int(v) for v in np.frombuffer(e[56:72], np.int64))
-        t[nm] = np.frombuffer(blob[off:off + nb], _NP[int(dt)]).reshape(shape).copy()
-    return t
-
-
-@pytest.fixture(scope="module")
-def plugin():
-    from drone_oa_iree_vit_accelerator_amd import host
-    so = host.build_extension()
-    lib = C.CDLL(so)
-    lib.ita_validate_blob.argtypes = [C.c_void_p, C.c_size_t, C.c_char_p]
-    return lib
-
-
-def _validate(lib, blob):
-    bad = C.create_string_buffer(32)
-    buf = C.create_string_buffer(blob, len(blob))
-    rc = lib.ita_validate_blob(buf, len(blob), bad)
-    return rc, bad.value.decode()
-
-
 def test_validate_blob(plugin):
     _, blob = _only_attn_blob()
-    assert _validate(plugin, blob) == (0, "")
+    assert validate(plugin, blob) == (0, "")
     _, blob2 = _only_attn_blob(golden_files("onlyattn2l_E64_s1_B2.npz")[0])
-    assert _validate(plugin, blob2) == (0, "")
-    assert _unpack(blob) and _retensor(blob, "ffn0.w1f", np.float32) == blob   # the repacker is faithful
+    assert validate(plugin, blob2) == (0, "")
+    assert unpack(blob) and _retensor(blob, "ffn0.w1f", np.float32) == blob   # the repacker is faithful
     for nm in ("ffn0.w1f", "ffn0.b1f", "ffn0.w2f", "ffn0.b2f"):
-        rc, bad = _validate(plugin, _retensor(blob, nm, shrink=True))
+        rc, bad = validate(plugin, _retensor(blob, nm, shrink=True))
         assert rc != 0 and bad == nm
-        rc, bad = _validate(plugin, _retensor(blob, nm, dtype=np.float16))
+        rc, bad = validate(plugin, _retensor(blob, nm, dtype=np.float16))
         assert rc != 0 and bad == nm
-        rc, bad = _validate(plugin, _retensor(blob, nm, drop=True))
+        rc, bad = validate(plugin, _retensor(blob, nm, drop=True))
         assert rc != 0 and bad == nm
-    rc, bad = _validate(plugin, _retensor(blob2, "ffn1.w2f", drop=True))
+    rc, bad = validate(plugin, _retensor(blob2, "ffn1.w2f", drop=True))
     assert rc != 0 and bad == "ffn1.w2f"
     # an int8 blob still needs its int8 FFN
     fx = params.load_fixture(golden_files("vitlstm_E64_seed0_B2.npz")[0])
     b8 = params.blob_from_record(fx, synth.float_params(0, E=64), E=64)
-    assert _validate(plugin, b8) == (0, "")
-    rc, bad = _validate(plugin, _retensor(b8, "ffn0.w2", drop=True))
+    assert validate(plugin, b8) == (0, "")
+    rc, bad = validate(plugin, _retensor(b8, "ffn0.w2", drop=True))
     assert rc != 0 and bad == "ffn0.w2"
 
 

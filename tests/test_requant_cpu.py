@@ -8,26 +8,12 @@ import numpy as np
 import pytest
 
 import requant_common as rc
+from requant_fused_common import fixture_multipliers
 from conftest import golden_files
 from drone_oa_iree_vit_accelerator_amd import host, mha_heads_ref as ref, params
 
 f32 = np.float32
 FIX_H1 = golden_files("blocks_E64_*.npz") + golden_files("blocks_E128_*.npz") + golden_files("vitlstm_E64_seed0_*.npz")
-
-
-def _fixture_multipliers():
-    """every attn*.scal[1..6] and ffn*.scal[1..2] of every fixture that holds int8 blocks"""
-    out = {}
-    for path in golden_files("*.npz"):
-        d = params.load_fixture(path)
-        for l in range(16):
-            if f"attn{l}.q_proj.w_q" in d:
-                for j, m in enumerate(params.attention_tensors(d, f"attn{l}.", l)[f"attn{l}.scal"][1:7]):
-                    out[f"{path.rsplit('/', 1)[-1][:-4]}.attn{l}.{rc.ATTN_SITES[j]}"] = f32(m)
-            if f"ffn{l}.fc1.w_q" in d:
-                for j, m in enumerate(params.ffn_tensors(d, f"ffn{l}.", l)[f"ffn{l}.scal"][1:3]):
-                    out[f"{path.rsplit('/', 1)[-1][:-4]}.ffn{l}.{rc.FFN_SITES[j]}"] = f32(m)
-    return out
 
 
 def test_fl32_is_float32_rounding():
@@ -41,7 +27,7 @@ def test_fl32_is_float32_rounding():
 
 
 def test_fast_site_ok_equals_the_exact_definition():
-    fx = _fixture_multipliers()
+    fx = fixture_multipliers()
     assert len(fx) >= 100
     rs = np.random.RandomState(0)
     sweep = [f32(3e-5 * (1.0 / 3e-5) ** u) for u in rs.uniform(0.0, 1.0, 220)]

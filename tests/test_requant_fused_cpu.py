@@ -6,7 +6,7 @@ C + a, and t = fma(C + a, m, K) with K = magic - round(C m) is the only float op
 then hold r + 128 and the u8 saturation clamps.  The definition it is held to is the reference's two roundings,
 clamp(rne(fl32(a m))) (requant_common).  Everything here is integer arithmetic: m = M 2^-s, so the exact value under
 the fma's single rounding is ((C + a) M + K 2^s) / 2^s, an integer K plus N / 2^s, rounded to nearest, ties to the
-even RESULT (the parity of K counts).  _fma_codes does that on int64 arrays; test_exact_codes_are_fraction_arithmetic
+even RESULT (the parity of K counts).  fma_codes does that on int64 arrays; test_exact_codes_are_fraction_arithmetic
 holds it to Fraction arithmetic."""
 from fractions import Fraction
 
@@ -15,86 +15,14 @@ import pytest
 
 import requant_common as rc
 from drone_oa_iree_vit_accelerator_amd import host
-from test_requant_cpu import _fixture_multipliers
+from requant_fused_common import (DMAX, MAGIC0, MAGIC32K, MAGIC128, amax, candidates, cval, differs, fixture_multipliers, fma_codes,
+                                  k_of, ms, proven, ref_codes)
 
 f32 = np.float32
-MAGIC128, MAGIC32K, MAGIC0 = 12583040, 12615680, 12582912         # 1.5 * 2^23 + 128, + 32768, + 0 (fc1's ReLU form)
-DMAX = 1 << 18
-
-
-def _ms(m):
-    """m = M 2^-s, M the 24-bit mantissa"""
-    bits = int(f32(m).view(np.uint32))
-    ex = bits >> 23
-    assert 0 < ex < 255
-    return (bits & 0x7FFFFF) | 0x800000, 150 - ex
-
-
-def _cval(C):
-    """the float value of the int32 pattern C (exponent field 150: 2^23 + mantissa)"""
-    assert 0x4B000000 <= C < 0x4B800000
-    return C - 0x4B000000 + (1 << 23)
-
-
-def _amax(m):
-    return int(130.0 / float(f32(m))) + 2
-
-
-def _fma_codes(m, C, K, a, logits=False, relu=False):
-    """u8 code (or, logits: the clamped signed logit; relu: min(r, 127) saturated at 0) of fma(C + a, m, K) for the int64
-    array a, exactly"""
-    M, s = _ms(m)
-    assert float(K) == int(K) and 24 <= s <= 39
-    K = int(K)
-    N = (_cval(C) + a.astype(np.int64)) * M                      # < 2^48
-    q, rem, half = N >> s, N & ((1 << s) - 1), 1 << (s - 1)
-    r = q + (rem > half) + ((rem == half) & (((q + K) & 1) == 1))
-    t = K + r
-    assert t.min() >= 1 << 23 and t.max() < 1 << 24               # ulp 1: the rounding above is the fma's
-    low = t & 0xFFFF                                              # (t - 2^23 is the mantissa; 2^23 has no low bits)
-    if logits:
-        return np.clip(low - 32768, -128, 127)
-    if relu:
-        return np.clip(np.where(low >= 32768, low - 65536, low), 0, 127)
-    return np.clip(np.where(low >= 32768, low - 65536, low), 0, 255)
-
-
-def _ref_codes(m, a, logits=False, relu=False):
-    """the definition: clamp(rne(fl32(a m))), as the code the u8 saturation yields (+ 128), or the clamped logit, or (relu)
-    the code clamped to [0, 127]"""
-    r = np.clip(np.rint(a.astype(np.float32) * f32(m)), 0 if relu else -128, 127).astype(np.int64)
-    return r if logits or relu else r + 128
-
-
-def _differs(m, C, K, logits=False, relu=False):
-    a = np.arange(-_amax(m), _amax(m) + 1, dtype=np.int64)
-    return a[_fma_codes(m, C, K, a, logits, relu) != _ref_codes(m, a, logits, relu)]
-
-
-def _k_of(m, C, magic=MAGIC128):
-    M, s = _ms(m)
-    return magic - int(round(Fraction(_cval(C) * M, 1 << s)))
-
-
-def candidates(m, dmax=DMAX, n=8):
-    """the search's candidates, best first: the n bases within dmax of ACC_BIAS whose C m lies closest to an integer
-    (ties: the lower base first), in integer arithmetic"""
-    M, s = _ms(m)
-    d = np.arange(-dmax, dmax + 1, dtype=np.int64)
-    fr = ((_cval(host.ACC_BIAS) + d) * M) & ((1 << s) - 1)
-    dist = np.minimum(fr, (1 << s) - fr)
-    return [host.ACC_BIAS + int(d[i]) for i in np.argsort(dist, kind="stable")[:n]]
-
-
-def proven(m, logits=False, relu=False, dmax=DMAX):
-    """what the loader decides for a site: the first candidate the enumeration accepts, or None"""
-    if not (0 < float(m) < 1) or 130.0 / float(f32(m)) > 4.0e6:
-        return None
-    return next((C for C in candidates(m, dmax) if host.fused_check(m, C, logits, relu)[0]), None)
 
 
 def _sweep():
-    fx = _fixture_multipliers()
+    fx = fixture_multipliers()
     rs = np.random.RandomState(0)
     sweep = [f32(3e-5 * (1.0 / 3e-5) ** u) for u in rs.uniform(0.0, 1.0, 220)]
     sweep = [m for m in sweep if 3.3e-5 <= m < 1]
@@ -109,20 +37,20 @@ def _sweep():
 
 
 def test_exact_codes_are_fraction_arithmetic():
-    """_fma_codes against Fraction arithmetic and requant_common's float32 rounding, around ties and at random"""
+    """fma_codes against Fraction arithmetic and requant_common's float32 rounding, around ties and at random"""
     rs = np.random.RandomState(3)
     for m in (f32(0.0013524714158847928), f32(2.0 ** -7), f32(0.0047836629673838615), f32(3.4e-5)):
         fm = Fraction(float(m))
         for C in (host.ACC_BIAS, host.ACC_BIAS - 247716, host.ACC_BIAS + 1):
-            K = _k_of(m, C)
-            a = np.array(sorted(set(rc.tie_neighbours(m)) | set(int(v) for v in rs.randint(-_amax(m), _amax(m), 40))), np.int64)
-            got = _fma_codes(m, C, K, a)
+            K = k_of(m, C)
+            a = np.array(sorted(set(rc.tie_neighbours(m)) | set(int(v) for v in rs.randint(-amax(m), amax(m), 40))), np.int64)
+            got = fma_codes(m, C, K, a)
             for ai, g in zip(a, got):
-                exact = Fraction(_cval(C) + int(ai)) * fm + K
+                exact = Fraction(cval(C) + int(ai)) * fm + K
                 t = round(exact)                                   # half-even on the result, as the fma in [2^23, 2^24)
                 low = t & 0xFFFF
                 assert g == max(0, min(255, low - 65536 if low >= 32768 else low)), (m, C, ai)
-            ref = _ref_codes(m, a)
+            ref = ref_codes(m, a)
             for ai, r in zip(a, ref):
                 assert r == rc.clamp8(round(rc.fl32(Fraction(int(ai)) * fm))) + 128, (m, ai)
 
@@ -139,9 +67,9 @@ def test_accepted_sites_equal_the_definition_exactly():
             continue
         C, K = got
         assert abs(C - host.ACC_BIAS) <= DMAX, (m, C)
-        assert K == int(K) and (1 << 23) <= K < (1 << 24) and K == _k_of(m, C), (m, C, K)
-        assert _amax(m) + abs(C - host.ACC_BIAS) < 1 << 22
-        bad = _differs(m, C, K)
+        assert K == int(K) and (1 << 23) <= K < (1 << 24) and K == k_of(m, C), (m, C, K)
+        assert amax(m) + abs(C - host.ACC_BIAS) < 1 << 22
+        bad = differs(m, C, K)
         assert bad.size == 0, (m, C, K, bad[:4])
         ok, k2 = host.fused_check(m, C)
         assert ok and k2 == K
@@ -156,12 +84,12 @@ def test_accepted_sites_equal_the_definition_exactly():
 def test_search_takes_the_best_candidates_in_order():
     """the base the search returns is the first of the eight closest-to-integer bases that the enumeration accepts, and
     the candidates' distances are as small as the form needs (C m within about 1e-5 of an integer)"""
-    fx = _fixture_multipliers()
+    fx = fixture_multipliers()
     for name in sorted(fx)[::7]:
         m = fx[name]
         cs = candidates(m)
-        M, s = _ms(m)
-        eps = [abs(Fraction(_cval(C) * M, 1 << s) - round(Fraction(_cval(C) * M, 1 << s))) for C in cs]
+        M, s = ms(m)
+        eps = [abs(Fraction(cval(C) * M, 1 << s) - round(Fraction(cval(C) * M, 1 << s))) for C in cs]
         assert eps == sorted(eps) and eps[-1] < Fraction(1, 20000), (name, [float(e) for e in eps])
         got = host.fused_site(m)
         assert (got[0] if got else None) == proven(m), name
@@ -174,7 +102,7 @@ def test_refusals():
         assert host.fused_check(m, host.ACC_BIAS)[0] is False, m
     # a base from which C + a leaves [2^23, 2^24) within the clamp range
     m = f32(3.4e-5)
-    assert host.fused_check(m, host.ACC_BIAS + (1 << 22) - _amax(m) + 5)[0] is False
+    assert host.fused_check(m, host.ACC_BIAS + (1 << 22) - amax(m) + 5)[0] is False
     assert host.fused_check(f32(2.0 ** -7), host.ACC_BIAS - (1 << 22) - 1)[0] is False
     # K outside [2^23, 2^24): m = 0.5 puts round(C m) above magic - 2^23
     assert host.fused_check(f32(0.5), host.ACC_BIAS)[0] is False
@@ -184,19 +112,19 @@ def test_refusals():
 def test_enumeration_rejects_a_base_that_differs(logits):
     """for accepted (m, C): neighbouring bases whose C m lies far from an integer make some accumulator round
     differently; the enumeration must reject exactly those (decided here by the exact re-computation)"""
-    fx = _fixture_multipliers()
+    fx = fixture_multipliers()
     magic = MAGIC32K if logits else MAGIC128
     n_rej = n_acc = 0
     for name in ("vitlstm_E64_seed0_B2.attn0.Q", "vitlstm_E64_seed0_B2.attn0.L", "blocks_E128_seed0_B1.attn0.C"):
         m = fx[name]
         C, _ = host.fused_site(m)
-        assert _differs(m, C, _k_of(m, C, magic), logits).size == 0
+        assert differs(m, C, k_of(m, C, magic), logits).size == 0
         assert host.fused_check(m, C, logits)[0]
         for d in range(1, 25):
             C2 = C + d
-            want = _differs(m, C2, _k_of(m, C2, magic), logits).size == 0
+            want = differs(m, C2, k_of(m, C2, magic), logits).size == 0
             ok, k = host.fused_check(m, C2, logits)
-            assert k == _k_of(m, C2, magic)
+            assert k == k_of(m, C2, magic)
             assert ok == want, (name, C2, want)
             n_rej += not want
             n_acc += want
@@ -208,13 +136,13 @@ def test_relu_form_enumeration_is_exact():
     """fc1's fused ReLU form (K = 1.5 * 2^23 - round(C m), codes clamped to [0, 127]): on every fixture's fc1 multiplier the
     enumeration accepts a candidate exactly when the exact re-computation finds no differing accumulator, negative ones
     included (they must saturate to 0)"""
-    fx = _fixture_multipliers()
+    fx = fixture_multipliers()
     n_ok = n_bad = 0
     for name in sorted(k for k in fx if k.endswith(".fc1")):
         m = fx[name]
         for C in candidates(m):
-            K = _k_of(m, C, MAGIC0)
-            want = _differs(m, C, K, relu=True).size == 0
+            K = k_of(m, C, MAGIC0)
+            want = differs(m, C, K, relu=True).size == 0
             ok, k = host.fused_check(m, C, relu=True)
             assert k == K and ok == want, (name, C, want)
             n_ok += want
@@ -228,7 +156,7 @@ def test_bench_blob_sites_are_accepted():
     """the seed-0 blob of the default benchmark: all five fused sites of its encoder layer are accepted, and its six
     sites pass the single-rounding proof too, so the layer runs the fused instantiation (asserted on the engine in
     test_gpu_requant_fused.py)"""
-    fx = _fixture_multipliers()
+    fx = fixture_multipliers()
     for s in rc.ATTN_SITES:
         assert host.fast_site_ok(fx[f"vitlstm_E64_seed0_B2.attn0.{s}"]), s
     for s in host.FUSED_SITES:

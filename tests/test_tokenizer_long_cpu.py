@@ -7,7 +7,6 @@ functions with exactly the chains the definition names:
 (linear_f32: one ascending-k fmaf chain started from the bias; add_ln with y = 0: x + 0 = x exactly, then the project's
 LayerNorm).  tests/test_gpu_tokenizer_long.py compares the kernel with the same composition.  No GPU call is made here."""
 import ctypes
-import functools
 import inspect
 import os
 import re
@@ -18,25 +17,10 @@ import pytest
 from conftest import REPO, golden_files
 from drone_oa_iree_vit_accelerator_amd import host, synth
 from drone_oa_iree_vit_accelerator_amd import tokenizer_long_ref as tl
+from tokenizer_long_common import composed, tok_params
 
 # grids of the fixtures, the GPU test's table and BASELINE config 5
 GRIDS = [(8, 16), (8, 32), (16, 32), (64, 128)]
-
-
-@functools.lru_cache(maxsize=None)
-def tok_params(E, seed=0):
-    """(conv_w (E, 49), conv_b, ln_w, ln_b) of synth.float_params(seed, E); read-only"""
-    fp = synth.float_params(seed, E=E)
-    return (fp["tokenizer.conv.weight"].reshape(E, 49), fp["tokenizer.conv.bias"], fp["tokenizer.norm.weight"],
-            fp["tokenizer.norm.bias"])
-
-
-def composed(oracle, frames, tok_h, tok_w, E, depth_scale=None, seed=0):
-    """the definition's tokens (B, tok_h * tok_w, E) float32"""
-    cw, cb, lw, lb = tok_params(E, seed)
-    pb = tl.blend_patches(frames, tok_h, tok_w, depth_scale)
-    pre = oracle.linear_f32(pb.reshape(-1, 49), cw, cb)
-    return oracle.add_ln(pre, np.zeros_like(pre), lw, lb).reshape(pb.shape[0], tok_h * tok_w, E)
 
 
 def test_params_match_the_fixtures_digest():
