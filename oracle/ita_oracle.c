@@ -174,9 +174,12 @@ int ita_oracle_tokenizer(const float* img, int B, int E, const float* cw, const 
  *     S0 = sum a0 w0,  S1 = sum (a0 w1 + a1 w0),  S2 = sum (a0 w2 + a1 w1),  S3 = sum a1 w2
  *     L = S0 + 256 S1,  H = S2 + 256 S3                      (sum B256 * Wq = 65536 H + L, both below 2^31)
  *     pre[c] = fmaf((float)H, 65536 s_c, fmaf((float)L, s_c, bias[c])),   s_c = 2^-e_c / 65280.0f
- * Same linear map as ita_oracle_tokenizer on pixel / 255.0f, closer to the exact result than its 49-step f32 chain (three
- * f32 roundings instead of forty-nine), and (why it exists) the f32 conv -- v_mfma_f32_16x16x4_f32 runs at the f32 vector
- * rate and blocks the SIMD's VALU -- becomes 24 int8 MFMAs per wave.  The two entry points agree to ~1e-6, not bit for bit. */
+ * Same linear map as ita_oracle_tokenizer on pixel / 255.0f, with three f32 roundings of the sum instead of forty-nine but a
+ * 23-bit weight and the f32 rounding of s_c in front of them: measured against float64 (tests/test_tokenizer_edges_cpu.py) it is
+ * the closer one on the stock weights, where every channel has one e_c (8.2e-7 against 9.6e-7 at E = 64), and on integer
+ * weights (1.0e-6 against 1.9e-6), and the farther one where the channels' scales spread over binades (3.1e-6 against 2.8e-6);
+ * both stay under 3.2e-6.  Why it exists: the f32 conv -- v_mfma_f32_16x16x4_f32 runs at the f32 vector rate and blocks the
+ * SIMD's VALU -- becomes 24 int8 MFMAs per wave.  The two entry points agree to ~1e-6, not bit for bit. */
 void ita_oracle_tok_quant_weights(const float* cw, int E, int32_t* wq /*[E][49]*/, float* sc /*[E]*/) {
   for (int c = 0; c < E; ++c) {
     float mx = 0.0f;
