@@ -27,6 +27,7 @@
 #include "ita_int8_kernels.h"
 #include "ita_stream_kernel.h"
 #include "ita_long_attn_kernel.h"
+#include "ita_long_heads_kernel.h"
 #include "ita_long_stats_kernel.h"
 #include "ita_long_hist_kernel.h"
 #include "ita_long_prop_kernel.h"
@@ -899,7 +900,9 @@ int check_long(const Layer& L, int batch, int seq_len, bool taps = false) {
                                             "here: ita_mha_long_f32_taps reads a float layer out"
                                           : "this layer's attention is float32 (ITAW0003 blob): no int8 long attention");
   if (int rc = check_long_shape(batch, seq_len)) return rc;
-  if (!L.simg_mha) return fail(ITA_ERR_UNSUPPORTED, "this layer has no attention image (accumulator range, or more than one head)");
+  if (!L.simg_mha)
+    return fail(ITA_ERR_UNSUPPORTED, "this layer has no attention image (accumulator range, or more than one head: the "
+                                     "ita_mha_long_heads_* entries and ita_encoder_layer_long_heads run H > 1)");
   return ITA_OK;
 }
 
@@ -1030,6 +1033,86 @@ int ita_mha_long_int8_taps(ita_handle h, int layer, const float* x, float* y, in
   if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
   const ita_mha_long_taps none{};
   return launch_long(h, layer, nullptr, nullptr, x, y, false, batch, seq_len, (hipStream_t)stream, taps ? taps : &none);
+}
+
+namespace {
+
+// H = 2, 3, 4 or 6 heads on long sequences (ita_long_heads_kernel.h): launch_long's refusals, workspace and projection
+// launch, with the layer's own image (Layer::limg_mha) and ita_long_heads_attn_kernel<.., H, ..> behind it.  An H = 1 blob
+// goes to launch_long: a caller need not branch on the head count.
+int launch_long_heads(ita_context* h, int layer, const int8_t* xq, int8_t* yq, const float* x, float* y, bool fuse_ln, int batch,
+                      int seq_len, hipStream_t s, const ita_mha_long_taps* taps = nullptr) {
+  if (h->w.hdr.H == 1) return launch_long(h, layer, xq, yq, x, y, fuse_ln, batch, seq_len, s, taps);
+  const Layer& L = h->w.layers[layer];
+  if (L.attn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's attention is float32 (ITAW0003 blob): no int8 long attention");
+  if (int rc = check_long_shape(batch, seq_len)) return rc;
+  if (!L.limg_mha) return fail(ITA_ERR_UNSUPPORTED, "this layer has no long multi-head attention image (accumulator range)");
+  if (fuse_ln && !L.n1w) return fail(ITA_ERR_BAD_BLOB, "norm1 parameters missing from the blob");
+  if (taps)
+    if (int rc = check_long_taps(*taps, seq_len, s)) return rc;
+  const size_t ntile = (size_t)batch * (seq_len / 128);
+  if (int rc = ensure_long_ws(h, long_int8_ws(ntile), s)) return rc;
+  ItaLongArgs a = long_args(h, L, ntile, batch, seq_len);
+  a.image = L.limg_mha;
+  a.xq = xq; a.yq = yq; a.x = x; a.y = y; a.fuse_ln = fuse_ln ? 1 : 0;
+  const dim3 proj_grid(ntile < (size_t)h->num_cus ? (int)ntile : h->num_cus), attn_grid(seq_len / 128, batch);
+  ItaLongTapArgs tp{};
+  if (taps) {   // logits / probs: (B, H, n_rows, S); row_max / row_sum: (B, H, n_rows)
+    tp.xq = taps->x_q; tp.Q = taps->Q; tp.K = taps->K; tp.V = taps->V; tp.ctx = taps->ctx; tp.outq = taps->out_q;
+    tp.logits = taps->logits; tp.probs = taps->probs; tp.row_max = taps->row_max; tp.row_sum = taps->row_sum;
+    tp.n_rows = taps->n_rows;
+    if (taps->n_rows > 0) {
+      if (int rc = upload_long_rows(h, taps->rows, taps->n_rows, seq_len, s)) return rc;
+      tp.rowidx = h->long_rows;
+    }
+  }
+  auto run = [&](auto e, auto hh, auto f32, auto fst) {
+    constexpr int E = decltype(e)::value, H = decltype(hh)::value;
+    constexpr bool F32 = decltype(f32)::value, FAST = decltype(fst)::value;
+    if constexpr (F32) {
+      if (taps) {
+        if (int rc = launch<ita_long_proj_taps_kernel<FAST, E>, ItaStreamLds<E, false, false>::TOTAL>(proj_grid, dim3(512), s, a, tp)) return rc;
+        return launch<ita_long_heads_attn_taps_kernel<FAST, E, H>, ItaLongLds::TOTAL>(attn_grid, dim3(512), s, a, tp);
+      }
+    }
+    if (int rc = launch<ita_long_proj_kernel<FAST, E, F32>, ItaStreamLds<E, false, false>::TOTAL>(proj_grid, dim3(512), s, a)) return rc;
+    if constexpr (ita_long_heads_two_waves<FAST, E, H>)
+      return launch<ita_long_heads_attn_w2_kernel<FAST, E, H, F32>, ItaLongLds::TOTAL>(attn_grid, dim3(512), s, a);
+    else
+      return launch<ita_long_heads_attn_kernel<FAST, E, H, F32>, ItaLongLds::TOTAL>(attn_grid, dim3(512), s, a);
+  };
+  auto forms = [&](auto e, auto hh) {
+    if (x) return L.long_fast ? run(e, hh, std::true_type{}, std::true_type{}) : run(e, hh, std::true_type{}, std::false_type{});
+    return L.long_fast ? run(e, hh, std::false_type{}, std::true_type{}) : run(e, hh, std::false_type{}, std::false_type{});
+  };
+  return with_E(h->w.hdr.E, [&](auto e) {
+    switch (h->w.hdr.H) {   // (check_blob admits these four besides 1)
+      case 2: return forms(e, std::integral_constant<int, 2>{});
+      case 3: return forms(e, std::integral_constant<int, 3>{});
+      case 4: return forms(e, std::integral_constant<int, 4>{});
+      case 6: return forms(e, std::integral_constant<int, 6>{});
+    }
+    return fail(ITA_ERR_UNSUPPORTED, "the long multi-head attention kernel is built for H in {2,3,4,6}");
+  });
+}
+
+}  // namespace
+
+int ita_mha_long_heads_q8(ita_handle h, int layer, const int8_t* x_q, int8_t* out_q, int batch, int seq_len, void* stream) {
+  if (int rc = check_layer_io(h, layer, x_q, out_q, batch)) return rc;
+  return launch_long_heads(h, layer, x_q, out_q, nullptr, nullptr, false, batch, seq_len, (hipStream_t)stream);
+}
+
+int ita_mha_long_heads_int8(ita_handle h, int layer, const float* x, float* y, int batch, int seq_len, void* stream) {
+  if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
+  return launch_long_heads(h, layer, nullptr, nullptr, x, y, false, batch, seq_len, (hipStream_t)stream);
+}
+
+int ita_mha_long_heads_int8_taps(ita_handle h, int layer, const float* x, float* y, int batch, int seq_len,
+                                 const ita_mha_long_taps* taps, void* stream) {
+  if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
+  const ita_mha_long_taps none{};
+  return launch_long_heads(h, layer, nullptr, nullptr, x, y, false, batch, seq_len, (hipStream_t)stream, taps ? taps : &none);
 }
 
 namespace {
@@ -1171,6 +1254,20 @@ int ita_encoder_layer_long(ita_handle h, int layer, const float* x, float* y, in
   if (L.ffn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's FFN is float32 (ITAW0002 blob): no long-sequence encoder layer");
   if (!L.n1w || !L.n2w) return fail(ITA_ERR_BAD_BLOB, "LayerNorm parameters missing from the blob");
   if (int rc = launch_long(h, layer, nullptr, nullptr, x, y, true, batch, seq_len, (hipStream_t)stream)) return rc;
+  return launch_ffn(h, layer, y, y, batch * (seq_len / 128), true, nullptr, (hipStream_t)stream);
+}
+
+// the same layer with H = 2, 3, 4 or 6 heads: launch_long_heads, then the same FFN launch (an H = 1 blob: the entry above)
+int ita_encoder_layer_long_heads(ita_handle h, int layer, const float* x, float* y, int batch, int seq_len, void* stream) {
+  if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
+  if (h->w.hdr.H == 1) return ita_encoder_layer_long(h, layer, x, y, batch, seq_len, stream);
+  const Layer& L = h->w.layers[layer];
+  if (L.attn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's attention is float32 (ITAW0003 blob): no int8 long attention");
+  if (int rc = check_long_shape(batch, seq_len)) return rc;
+  if (!L.limg_mha) return fail(ITA_ERR_UNSUPPORTED, "this layer has no long multi-head attention image (accumulator range)");
+  if (L.ffn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's FFN is float32 (ITAW0002 blob): no long-sequence encoder layer");
+  if (!L.n1w || !L.n2w) return fail(ITA_ERR_BAD_BLOB, "LayerNorm parameters missing from the blob");
+  if (int rc = launch_long_heads(h, layer, nullptr, nullptr, x, y, true, batch, seq_len, (hipStream_t)stream)) return rc;
   return launch_ffn(h, layer, y, y, batch * (seq_len / 128), true, nullptr, (hipStream_t)stream);
 }
 

@@ -45,6 +45,10 @@ struct Layer {
   int fused_c[8] = {ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS, ITA_ACC_BIAS};
   float fused_k[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
   DevBuf<char> fimg_enc, fimg_tok, fimg_mha;
+  // H > 1 only: the attention image (simg_mha's bytes) of the long-sequence multi-head kernels (ita_long_heads_kernel.h)
+  // and their FAST / EXACT selection; read by the ita_*_long_heads entries and by nothing else
+  DevBuf<char> limg_mha;
+  bool long_fast = false;
 };
 
 // Everything one ita_load_weights call produces.  Raw pointers point into dblob; every DevBuf is a buffer derived from
@@ -559,7 +563,6 @@ int build_stream_images(Weights& w) {
   for (int i = 0; i < hdr.num_layers; ++i) {
     Layer& L = w.layers[i];
     if (L.attn_f32) continue;   // no int8 attention: no stream images (ita_attn_f32_kernel + ita_ffn_f32_kernel)
-    if (hdr.H != 1) continue;   // the stream kernels have one head: a multi-head layer runs on the block kernels
     StreamHostParams sp{};
     sp.wq = hptr<int8_t>(w, NM("attn%d.wq")); sp.wk = hptr<int8_t>(w, NM("attn%d.wk")); sp.wv = hptr<int8_t>(w, NM("attn%d.wv"));
     sp.wo = hptr<int8_t>(w, NM("attn%d.wo")); sp.w1 = hptr<int8_t>(w, NM("ffn%d.w1")); sp.w2 = hptr<int8_t>(w, NM("ffn%d.w2"));
@@ -570,6 +573,14 @@ int build_stream_images(Weights& w) {
     sp.tlw = hptr<float>(w, "tok.ln_w"); sp.tlb = hptr<float>(w, "tok.ln_b");
     sp.conv_w = hptr<float>(w, "tok.conv_w"); sp.conv_b = hptr<float>(w, "tok.conv_b");
     int rc = ITA_OK;
+    if (hdr.H != 1) {   // the stream kernels have one head: a multi-head layer runs on the block kernels, and on long sequences
+                        // on ita_long_heads_attn_kernel, whose image this is (stream_range_ok bounds all 192 features: a head sums fewer)
+      if (!stream_range_ok(sp, hdr.E, false, L.ascal, L.fscal)) continue;
+      L.long_fast = fast_sites_of(L.ascal) == ITA_SITES_ALL;
+      rc = hdr.E == 64 ? build_stream_image<64, false, false>(sp, L.limg_mha) : build_stream_image<128, false, false>(sp, L.limg_mha);
+      if (rc) return rc;
+      continue;
+    }
     // a float-FFN layer gets the attention image only: its FFN is ita_ffn_f32_kernel (no simg_enc / simg_tok)
     const bool lns = !L.ffn_f32 && sp.n1w && sp.n1b && sp.n2w && sp.n2b && stream_range_ok(sp, hdr.E, true, L.ascal, L.fscal);
     if (!stream_range_ok(sp, hdr.E, false, L.ascal, L.fscal)) continue;   // no images: this layer runs on the block kernels

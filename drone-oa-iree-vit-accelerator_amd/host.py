@@ -34,7 +34,8 @@ HEAD_TIMEOUT = 1
 
 EXPORTED_SYMBOLS = (
     "ita_abi_version", "ita_create", "ita_destroy", "ita_load_weights", "ita_validate_blob", "ita_reserve", "ita_get_dims",
-    "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_mha_long_int8", "ita_mha_long_int8_taps", "ita_mha_long_int8_stats", "ita_mha_long_int8_hist", "ita_mha_long_int8_propagate", "ita_encoder_layer_long", "ita_ffn_int8", "ita_ffn_int8_taps",
+    "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_mha_long_int8", "ita_mha_long_int8_taps", "ita_mha_long_int8_stats", "ita_mha_long_int8_hist", "ita_mha_long_int8_propagate", "ita_encoder_layer_long",
+    "ita_mha_long_heads_q8", "ita_mha_long_heads_int8", "ita_mha_long_heads_int8_taps", "ita_encoder_layer_long_heads", "ita_ffn_int8", "ita_ffn_int8_taps",
     "ita_ffn_f32", "ita_get_ffn_kind", "ita_mha_f32", "ita_get_attn_kind", "ita_mha_long_f32", "ita_mha_long_f32_taps", "ita_mha_long_f32_stats", "ita_mha_long_f32_propagate", "ita_encoder_layer_long_f32",
     "ita_encoder_layer", "ita_tokenizer", "ita_fusion_tail", "ita_vitlstm_forward", "ita_bind_dispatch",
     "ita_profile_begin", "ita_profile_begin_sampled", "ita_profile_end", "ita_set_tail_mode", "ita_debug_encoder_stamps",
@@ -212,6 +213,10 @@ def lib():
         L.ita_mha_long_int8_hist.argtypes = [vp, i, vp, i, i, C.POINTER(_MhaLongHist), vp]
         L.ita_mha_long_int8_propagate.argtypes = [vp, i, vp, i, i, vp, i, vp, vp]
         L.ita_encoder_layer_long.argtypes = [vp, i, vp, vp, i, i, vp]
+        L.ita_mha_long_heads_q8.argtypes = [vp, i, vp, vp, i, i, vp]
+        L.ita_mha_long_heads_int8.argtypes = [vp, i, vp, vp, i, i, vp]
+        L.ita_mha_long_heads_int8_taps.argtypes = [vp, i, vp, vp, i, i, C.POINTER(_MhaLongTaps), vp]
+        L.ita_encoder_layer_long_heads.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_f32.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_f32_taps.argtypes = [vp, i, vp, vp, i, i, C.POINTER(_MhaLongF32Taps), vp]
         L.ita_mha_long_f32_stats.argtypes = [vp, i, vp, i, i, C.c_float, C.POINTER(_MhaLongF32Stats), vp]
@@ -765,6 +770,17 @@ class Engine:
                                    _stream_ptr(self.device)))
         return out
 
+    def mha_long_heads_q8(self, x_q, layer: int = 0):
+        """mha_long_q8 for a blob with H = 2, 3, 4 or 6 heads (ita_mha_long_heads_q8): matmul1, the integer softmax over all S
+        keys and matmul2 per head of P / H features; an H = 1 blob runs mha_long_q8's kernels"""
+        torch = _torch()
+        assert x_q.dtype == torch.int8 and x_q.is_cuda and x_q.dim() == 3 and x_q.shape[2] == self.E
+        x_q = x_q.contiguous()
+        out = torch.empty_like(x_q)
+        _chk(lib().ita_mha_long_heads_q8(self._h, layer, x_q.data_ptr(), out.data_ptr(), x_q.shape[0], x_q.shape[1],
+                                         _stream_ptr(self.device)))
+        return out
+
     def _long_f32(self, x):
         if x.dim() != 3 or x.shape[2] != self.E:
             raise ITAError(f"expected (B, S, {self.E}) tokens, got {tuple(x.shape)}")
@@ -780,8 +796,18 @@ class Engine:
                                      _stream_ptr(self.device)))
         return y
 
-    def _long_taps(self, x, rows, layer, want):
-        """ita_mha_long_int8_taps asking for the taps named in `want` only -> (y, dict of those taps)"""
+    def mha_long_heads(self, x, layer: int = 0):
+        """mha_long for a blob with H = 2, 3, 4 or 6 heads (ita_mha_long_heads_int8); an H = 1 blob runs mha_long's kernels"""
+        torch = _torch()
+        x = self._long_f32(x)
+        y = torch.empty_like(x)
+        _chk(lib().ita_mha_long_heads_int8(self._h, layer, x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1],
+                                           _stream_ptr(self.device)))
+        return y
+
+    def _long_taps(self, x, rows, layer, want, heads: bool = False):
+        """ita_mha_long_int8_taps asking for the taps named in `want` only -> (y, dict of those taps); heads: through
+        ita_mha_long_heads_int8_taps, whose row taps carry a head axis when the blob has H > 1"""
         torch = _torch()
         x = self._long_f32(x)
         B, S = x.shape[0], x.shape[1]
@@ -792,6 +818,8 @@ class Engine:
         spec = dict(x_q=((B, S, self.E), i8), Q=((B, S, self.P), i8), K=((B, S, self.P), i8), V=((B, S, self.P), i8),
                     ctx=((B, S, self.P), i8), out_q=((B, S, self.E), i8), logits=((B, n, S), i8), probs=((B, n, S), u8),
                     row_max=((B, n), i8), row_sum=((B, n), i32))
+        if heads and self.H > 1:
+            spec.update({k: ((B, self.H) + shape[1:], dt) for k, (shape, dt) in spec.items() if k in LONG_ROW_TAPS})
         unknown = [k for k in want if k not in spec]
         if unknown:
             raise ITAError(f"no such long tap: {unknown}")
@@ -799,8 +827,8 @@ class Engine:
         st = _MhaLongTaps(**{k: v.data_ptr() for k, v in t.items()})
         arr = (C.c_int * max(n, 1))(*rows)
         st.rows, st.n_rows = (arr if n else None), n
-        _chk(lib().ita_mha_long_int8_taps(self._h, layer, x.data_ptr(), y.data_ptr(), B, S, C.byref(st),
-                                          _stream_ptr(self.device)))
+        entry = lib().ita_mha_long_heads_int8_taps if heads else lib().ita_mha_long_int8_taps
+        _chk(entry(self._h, layer, x.data_ptr(), y.data_ptr(), B, S, C.byref(st), _stream_ptr(self.device)))
         return y, t
 
     def mha_long_taps(self, x, rows=(), layer: int = 0):
@@ -815,6 +843,17 @@ class Engine:
         """what the tokens `rows` of a long sequence attend to: x (B,S,E) f32 -> the integer softmax's uint8 probabilities
         (B, len(rows), S) of those query rows (the reference's attn_weights); rows strictly increasing, at most 1024"""
         return self._long_taps(x, rows, layer, ("probs",))[1]["probs"]
+
+    def mha_long_heads_taps(self, x, rows=(), layer: int = 0):
+        """mha_long_taps for a blob with H = 2, 3, 4 or 6 heads (ita_mha_long_heads_int8_taps): the same stage tensors;
+        logits and probs (B,H,n,S), row_max and row_sum (B,H,n).  An H = 1 blob gives mha_long_taps' shapes."""
+        rows = list(rows)
+        return self._long_taps(x, rows, layer, LONG_TENSOR_TAPS + (LONG_ROW_TAPS if rows else ()), heads=True)
+
+    def attention_rows_long_heads(self, x, rows, layer: int = 0):
+        """attention_rows_long per head: x (B,S,E) f32 -> uint8 probabilities (B, H, len(rows), S) of those query rows"""
+        probs = self._long_taps(x, rows, layer, ("probs",), heads=True)[1]["probs"]
+        return probs if probs.dim() == 4 else probs[:, None]
 
     def attention_map_long(self, frames, tok_h: int, tok_w: int, queries, layer: int = 0, depth_scale: Optional[float] = None):
         """attention maps of chosen tokens over the token grid of camera frames: tokenize_long, the encoder layers below
@@ -1031,6 +1070,26 @@ class Engine:
         y = self.encoder_layer_long(x, 0)
         for layer in range(1, self.num_layers):
             self.encoder_layer_long(y, layer, out=y)
+        return y
+
+    def encoder_layer_long_heads(self, x, layer: int = 0, out=None):
+        """encoder_layer_long for a blob with H = 2, 3, 4 or 6 heads (ita_encoder_layer_long_heads); out as there.  An
+        H = 1 blob runs encoder_layer_long's kernels"""
+        torch = _torch()
+        x = self._long_f32(x)
+        if out is None:
+            out = torch.empty_like(x)
+        elif not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.shape != x.shape:
+            raise ITAError(f"out must be a contiguous f32 GPU tensor of shape {tuple(x.shape)}")
+        _chk(lib().ita_encoder_layer_long_heads(self._h, layer, x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1],
+                                                _stream_ptr(self.device)))
+        return out
+
+    def encode_long_heads(self, x):
+        """all num_layers encoder layers in order over a long sequence, any head count: (B,S,E) f32 -> (B,S,E) f32"""
+        y = self.encoder_layer_long_heads(x, 0)
+        for layer in range(1, self.num_layers):
+            self.encoder_layer_long_heads(y, layer, out=y)
         return y
 
     def tokenize_long(self, frames, tok_h: int, tok_w: int, depth_scale: Optional[float] = None, out=None):

@@ -108,6 +108,28 @@ def mha(x: np.ndarray, t: Dict[str, np.ndarray], H: int = 1, i: int = 0, taps: b
     return (out, tp, acc) if taps else (out, tp)
 
 
+def mha_blocked(x: np.ndarray, t: Dict[str, np.ndarray], H: int = 1, i: int = 0, block: int = 256):
+    """mha for long sequences, head by head in blocks of `block` query rows: no (H, S, S) tensor is held.  Returns
+    (out_q (B, S, E) int8, row_sum (B, H, S) int64: the sum of 256 >> (max - logit) each softmax row is divided by).
+    The same functions as mha, on slices (tests/test_long_heads_cpu.py holds the two equal)."""
+    g = lambda k: t[f"attn{i}.{k}"]
+    sc = np.asarray(g("scal"), np.float32)
+    x = np.asarray(x)
+    x_q = x if x.dtype == np.int8 else quantize(x, sc[INV_SX])
+    Q, K, V = (split_heads(linear_q(x_q, g("w" + k), g("b" + k), sc[m]), H).astype(np.int32)
+               for k, m in (("q", MQ), ("k", MK), ("v", MV)))
+    B, _, S, D = Q.shape
+    ctx = np.empty((B, S, H, D), np.int8)
+    row_sum = np.empty((B, H, S), np.int64)
+    for h in range(H):
+        for r in range(0, S, block):
+            logits = requant(Q[:, h, r:r + block] @ K[:, h].transpose(0, 2, 1), sc[ML]).astype(np.int32)
+            shift = logits.max(-1, keepdims=True) - logits
+            row_sum[:, h, r:r + block] = np.where(shift > 31, 0, 256 >> np.minimum(shift, 31)).sum(-1)
+            ctx[:, r:r + block, h] = requant(softmax_int(logits).astype(np.int32) @ V[:, h], sc[MC])
+    return linear_q(ctx.reshape(B, S, H * D), g("wo"), g("bo"), sc[MO]), row_sum
+
+
 F_INV_SX, M1, M2, S2 = range(4)   # indices of ffn{i}.scal
 
 

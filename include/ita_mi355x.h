@@ -54,7 +54,8 @@ int ita_destroy(ita_handle h);
  * every entry point below serves it except those that need the one-head stream kernel, which return
  * ITA_ERR_UNSUPPORTED before any launch: ita_mha_q8, ita_mha_long_q8, ita_mha_long_int8, ita_mha_long_int8_taps,
  * ita_mha_long_int8_stats, ita_mha_long_int8_hist, ita_mha_long_int8_propagate, ita_encoder_layer_long, ita_debug_encoder_stamps, ita_vitlstm_forward_slots (and ita_mha_long_f32 / ita_mha_long_f32_stats / ita_mha_long_f32_propagate / ita_encoder_layer_long_f32, which take
- * float layers only).
+ * float layers only).  On long sequences an H > 1 layer runs through ita_mha_long_heads_q8, ita_mha_long_heads_int8,
+ * ita_mha_long_heads_int8_taps and ita_encoder_layer_long_heads.
  * The reference pre-loads weights into the accelerator out of band
  * (docs/HOW-TO-run-the-full-project-workflow.md:55); this is that step. */
 int ita_load_weights(ita_handle h, const void* blob, size_t nbytes);
@@ -197,6 +198,23 @@ int ita_mha_long_int8_propagate(ita_handle h, int layer, const float* x_dev, int
  * ita_mha_long_q8; in addition a float-FFN layer (ITAW0002 blob: ita_encoder_layer_long_f32 runs it) is ITA_ERR_UNSUPPORTED and a blob without the layer's
  * norm parameters ITA_ERR_BAD_BLOB -- all before any launch. */
 int ita_encoder_layer_long(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_len, void* stream);
+
+/* The long-sequence entries for a blob with H = 2, 3, 4 or 6 heads (csrc/ita_long_heads_kernel.h): ita_mha_long_q8,
+ * ita_mha_long_int8, ita_mha_long_int8_taps and ita_encoder_layer_long with matmul1, the integer softmax over all seq_len
+ * keys and matmul2 run per head of P / H features, the contexts concatenated, one logit and one context multiplier for
+ * all heads (mha_heads_ref.mha at any seq_len, bit for bit).  Same shapes, same workspace bytes and growth, same capture
+ * rules as the H = 1 entries; x_dev may equal y_dev.  With H heads the taps' logits and probs are
+ * (B, H, n_rows, seq_len) and row_max and row_sum (B, H, n_rows); the stage tensors are unchanged.
+ * Refusals, all before any launch, outputs and taps untouched: whatever the H = 1 sibling refuses for shape, layer index,
+ * NULL pointers, rows and alignment, with the same status; ITA_ERR_UNSUPPORTED for a float-attention layer and for a layer
+ * whose accumulators leave the kernels' range (no image); for ita_encoder_layer_long_heads ITA_ERR_UNSUPPORTED for a
+ * float-FFN layer and ITA_ERR_BAD_BLOB for missing norm parameters.
+ * On an H = 1 blob each entry forwards to its H = 1 sibling: a caller need not branch on the head count. */
+int ita_mha_long_heads_q8(ita_handle h, int layer, const int8_t* x_q_dev, int8_t* out_q_dev, int batch, int seq_len, void* stream);
+int ita_mha_long_heads_int8(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_len, void* stream);
+int ita_mha_long_heads_int8_taps(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_len,
+                                 const ita_mha_long_taps* taps, void* stream);
+int ita_encoder_layer_long_heads(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_len, void* stream);
 
 /* ITAFeedForward_QAT.forward (models/ITA/QAT/layers.py:61-75). */
 int ita_ffn_int8(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, void* stream);
