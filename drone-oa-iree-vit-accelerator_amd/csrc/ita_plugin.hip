@@ -29,6 +29,7 @@
 #include "ita_long_attn_kernel.h"
 #include "ita_long_heads_kernel.h"
 #include "ita_long_stats_kernel.h"
+#include "ita_long_heads_stats_kernel.h"
 #include "ita_long_hist_kernel.h"
 #include "ita_long_prop_kernel.h"
 #include "ita_ffn_f32_kernel.h"
@@ -1132,6 +1133,9 @@ int ita_mha_long_int8_stats(ita_handle h, int layer, const float* x, int batch, 
   if (!x || !st || layer < 0 || layer >= h->w.hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
   const Layer& L = h->w.layers[layer];
   hipStream_t s = (hipStream_t)stream;
+  if (h->w.hdr.H > 1)
+    return fail(ITA_ERR_UNSUPPORTED, "ita_mha_long_int8_stats reads one head: ita_mha_long_heads_int8_stats gives the statistics of "
+                                     "every head of an H > 1 blob");
   if (int rc = check_long(L, batch, seq_len)) return rc;
   if (int rc = check_long_stats_outputs({st->row_max, st->row_sum, st->row_mass, st->row_nnz, st->col_mass, st->col_nnz}, 1,   // row_max: int8
                                         "ita_mha_long_int8_stats: all six outputs are null",
@@ -1160,6 +1164,57 @@ int ita_mha_long_int8_stats(ita_handle h, int layer, const float* x, int batch, 
     return launch<ita_long_stats_kernel<FAST>, ItaLongStatsLds::TOTAL>(grid, dim3(512), s, sa);
   };
   return with_E(h->w.hdr.E, [&](auto e) { return fast ? run(e, std::true_type{}) : run(e, std::false_type{}); });
+}
+
+// The same for H = 2, 3, 4 or 6 heads, every array (B, H, S): launch_long_heads' refusals, workspace and projection launch
+// on Layer::limg_mha, then ita_long_heads_stats_kernel<FAST, H> (ita_long_heads_stats_kernel.h).  An H = 1 blob goes to the
+// entry above: the bytes of (B, 1, S) are those of (B, S).
+int ita_mha_long_heads_int8_stats(ita_handle h, int layer, const float* x, int batch, int seq_len, const ita_mha_long_stats* st,
+                                  void* stream) {
+  if (int rc = check(h, batch)) return rc;
+  if (h->w.hdr.H == 1) return ita_mha_long_int8_stats(h, layer, x, batch, seq_len, st, stream);
+  if (!x || !st || layer < 0 || layer >= h->w.hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
+  const Layer& L = h->w.layers[layer];
+  hipStream_t s = (hipStream_t)stream;
+  if (L.attn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's attention is float32 (ITAW0003 blob): no int8 long attention");
+  if (int rc = check_long_shape(batch, seq_len)) return rc;
+  if (!L.limg_mha) return fail(ITA_ERR_UNSUPPORTED, "this layer has no long multi-head attention image (accumulator range)");
+  if (int rc = check_long_stats_outputs({st->row_max, st->row_sum, st->row_mass, st->row_nnz, st->col_mass, st->col_nnz}, 1,   // row_max: int8
+                                        "ita_mha_long_heads_int8_stats: all six outputs are null",
+                                        "row_sum, row_mass, row_nnz, col_mass and col_nnz must be 4-byte aligned")) return rc;
+  const int H = h->w.hdr.H;
+  const size_t ntile = (size_t)batch * (seq_len / 128);
+  if (int rc = ensure_long_ws(h, long_int8_ws(ntile), s)) return rc;
+  ItaLongArgs a = long_args(h, L, ntile, batch, seq_len);
+  a.image = L.limg_mha;
+  a.x = x;
+  ItaLongHeadsStatsArgs sa{};
+  sa.qfrag = a.qfrag; sa.kimg = a.kimg; sa.ml = a.ml; sa.B = batch; sa.S = seq_len;
+  sa.row_max = st->row_max; sa.row_sum = st->row_sum; sa.row_mass = st->row_mass; sa.row_nnz = st->row_nnz;
+  sa.col_mass = st->col_mass; sa.col_nnz = st->col_nnz;
+  // the kernel ADDS into the column arrays: zeroed on the stream first, by a kernel (a captured call is kernel nodes only)
+  if (sa.col_mass || sa.col_nnz) {
+    const size_t n = (size_t)batch * H * seq_len, blocks = (n + 255) / 256;
+    if (int rc = launch<ita_long_stats_zero_kernel>(dim3(blocks < 2048 ? (int)blocks : 2048), dim3(256), s, sa.col_mass, sa.col_nnz, n))
+      return rc;
+  }
+  const dim3 proj_grid(ntile < (size_t)h->num_cus ? (int)ntile : h->num_cus), grid(seq_len / 128, batch);
+  auto run = [&](auto e, auto hh, auto fst) {
+    constexpr int E = decltype(e)::value, HH = decltype(hh)::value;
+    constexpr bool FAST = decltype(fst)::value;
+    if (int rc = launch<ita_long_proj_kernel<FAST, E, true>, ItaStreamLds<E, false, false>::TOTAL>(proj_grid, dim3(512), s, a)) return rc;
+    return launch<ita_long_heads_stats_kernel<FAST, HH>, ItaLongHeadsStatsLds<HH>::TOTAL>(grid, dim3(512), s, sa);
+  };
+  auto forms = [&](auto e, auto hh) { return L.long_fast ? run(e, hh, std::true_type{}) : run(e, hh, std::false_type{}); };
+  return with_E(h->w.hdr.E, [&](auto e) {
+    switch (H) {   // (check_blob admits these four besides 1)
+      case 2: return forms(e, std::integral_constant<int, 2>{});
+      case 3: return forms(e, std::integral_constant<int, 3>{});
+      case 4: return forms(e, std::integral_constant<int, 4>{});
+      case 6: return forms(e, std::integral_constant<int, 6>{});
+    }
+    return fail(ITA_ERR_UNSUPPORTED, "the long multi-head statistics kernel is built for H in {2,3,4,6}");
+  });
 }
 
 // The production projection launch (f32 form), then ita_long_hist_kernel over its workspace (ita_long_hist_kernel.h): two

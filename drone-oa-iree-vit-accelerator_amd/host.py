@@ -35,7 +35,7 @@ HEAD_TIMEOUT = 1
 EXPORTED_SYMBOLS = (
     "ita_abi_version", "ita_create", "ita_destroy", "ita_load_weights", "ita_validate_blob", "ita_reserve", "ita_get_dims",
     "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_mha_long_int8", "ita_mha_long_int8_taps", "ita_mha_long_int8_stats", "ita_mha_long_int8_hist", "ita_mha_long_int8_propagate", "ita_encoder_layer_long",
-    "ita_mha_long_heads_q8", "ita_mha_long_heads_int8", "ita_mha_long_heads_int8_taps", "ita_encoder_layer_long_heads", "ita_ffn_int8", "ita_ffn_int8_taps",
+    "ita_mha_long_heads_q8", "ita_mha_long_heads_int8", "ita_mha_long_heads_int8_taps", "ita_mha_long_heads_int8_stats", "ita_encoder_layer_long_heads", "ita_ffn_int8", "ita_ffn_int8_taps",
     "ita_ffn_f32", "ita_get_ffn_kind", "ita_mha_f32", "ita_get_attn_kind", "ita_mha_long_f32", "ita_mha_long_f32_taps", "ita_mha_long_f32_stats", "ita_mha_long_f32_propagate", "ita_encoder_layer_long_f32",
     "ita_encoder_layer", "ita_tokenizer", "ita_fusion_tail", "ita_vitlstm_forward", "ita_bind_dispatch",
     "ita_profile_begin", "ita_profile_begin_sampled", "ita_profile_end", "ita_set_tail_mode", "ita_debug_encoder_stamps",
@@ -216,6 +216,7 @@ def lib():
         L.ita_mha_long_heads_q8.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_heads_int8.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_heads_int8_taps.argtypes = [vp, i, vp, vp, i, i, C.POINTER(_MhaLongTaps), vp]
+        L.ita_mha_long_heads_int8_stats.argtypes = [vp, i, vp, i, i, C.POINTER(_MhaLongStats), vp]
         L.ita_encoder_layer_long_heads.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_f32.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_f32_taps.argtypes = [vp, i, vp, vp, i, i, C.POINTER(_MhaLongF32Taps), vp]
@@ -864,17 +865,25 @@ class Engine:
 
     def _long_stats(self, x, layer, want):
         """ita_mha_long_int8_stats asking for the statistics named in `want` only -> dict of those"""
+        return self._long_stats_entry(lib().ita_mha_long_int8_stats, x, layer, want, ())
+
+    def _long_stats_entry(self, entry, x, layer, want, heads):
+        """either int8 statistics entry -> dict of (B, *heads, S) tensors: heads is () or (H,)"""
         torch = _torch()
         x = self._long_f32(x)
         B, S = x.shape[0], x.shape[1]
         unknown = [k for k in want if k not in LONG_STATS]
         if unknown:
             raise ITAError(f"no such long statistic: {unknown}")
-        t = {k: torch.empty((B, S), dtype=torch.int8 if k == "row_max" else torch.int32, device=x.device)
+        t = {k: torch.empty((B, *heads, S), dtype=torch.int8 if k == "row_max" else torch.int32, device=x.device)
              for k in LONG_STATS if k in want}
         st = _MhaLongStats(**{k: v.data_ptr() for k, v in t.items()})
-        _chk(lib().ita_mha_long_int8_stats(self._h, layer, x.data_ptr(), B, S, C.byref(st), _stream_ptr(self.device)))
+        _chk(entry(self._h, layer, x.data_ptr(), B, S, C.byref(st), _stream_ptr(self.device)))
         return t
+
+    def _long_heads_stats(self, x, layer, want):
+        """ita_mha_long_heads_int8_stats asking for the statistics named in `want` only -> dict of (B, H, S) tensors"""
+        return self._long_stats_entry(lib().ita_mha_long_heads_int8_stats, x, layer, want, (self.H,))
 
     def attention_stats_long(self, x, layer: int = 0):
         """row and column statistics of the whole S x S integer-softmax matrix of a long sequence, which is never held
@@ -894,6 +903,27 @@ class Engine:
         attention_received_long of `layer` -> (N, tok_h, tok_w) int32"""
         y = self._tokens_below(frames, int(tok_h), int(tok_w), layer, depth_scale)
         return self.attention_received_long(y, int(layer)).reshape(y.shape[0], int(tok_h), int(tok_w))
+
+    def attention_stats_long_heads(self, x, layer: int = 0):
+        """attention_stats_long per head, for a blob with any head count (ita_mha_long_heads_int8_stats): x (B,S,E) f32 ->
+        dict of (B,H,S) tensors, the six statistics of each head's own S x S integer-softmax matrix -- one head can be dead
+        while the sum over heads looks healthy.  Equal to attention_stats_heads_ref.stats_heads; an H = 1 blob runs
+        attention_stats_long's kernels and gives an H axis of length 1."""
+        return self._long_heads_stats(x, layer, LONG_STATS)
+
+    def attention_received_long_heads(self, x, layer: int = 0):
+        """attention received by every token from each head: x (B,S,E) f32 -> col_mass (B,H,S) int32 (the columns-only call)"""
+        return self._long_heads_stats(x, layer, ("col_mass",))["col_mass"]
+
+    def attention_received_map_long_heads(self, frames, tok_h: int, tok_w: int, layer: int = 0, depth_scale: Optional[float] = None):
+        """attention received per head on the token grid of camera frames: tokenize_long, the encoder layers below `layer`
+        (encoder_layer_long_heads), then attention_received_long_heads of `layer` -> (N, H, tok_h, tok_w) int32"""
+        if not 0 <= int(layer) < self.num_layers:
+            raise ValueError(f"layer {layer} out of range")
+        y = self.tokenize_long(frames, int(tok_h), int(tok_w), depth_scale)
+        for l in range(int(layer)):
+            self.encoder_layer_long_heads(y, l, out=y)
+        return self.attention_received_long_heads(y, int(layer)).reshape(y.shape[0], self.H, int(tok_h), int(tok_w))
 
     def _long_hist(self, x, layer, want):
         """ita_mha_long_int8_hist asking for the outputs named in `want` only -> dict of those"""

@@ -55,7 +55,7 @@ int ita_destroy(ita_handle h);
  * ITA_ERR_UNSUPPORTED before any launch: ita_mha_q8, ita_mha_long_q8, ita_mha_long_int8, ita_mha_long_int8_taps,
  * ita_mha_long_int8_stats, ita_mha_long_int8_hist, ita_mha_long_int8_propagate, ita_encoder_layer_long, ita_debug_encoder_stamps, ita_vitlstm_forward_slots (and ita_mha_long_f32 / ita_mha_long_f32_stats / ita_mha_long_f32_propagate / ita_encoder_layer_long_f32, which take
  * float layers only).  On long sequences an H > 1 layer runs through ita_mha_long_heads_q8, ita_mha_long_heads_int8,
- * ita_mha_long_heads_int8_taps and ita_encoder_layer_long_heads.
+ * ita_mha_long_heads_int8_taps, ita_mha_long_heads_int8_stats and ita_encoder_layer_long_heads.
  * The reference pre-loads weights into the accelerator out of band
  * (docs/HOW-TO-run-the-full-project-workflow.md:55); this is that step. */
 int ita_load_weights(ita_handle h, const void* blob, size_t nbytes);
@@ -215,6 +215,19 @@ int ita_mha_long_heads_int8(ita_handle h, int layer, const float* x_dev, float* 
 int ita_mha_long_heads_int8_taps(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_len,
                                  const ita_mha_long_taps* taps, void* stream);
 int ita_encoder_layer_long_heads(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_len, void* stream);
+/* ita_mha_long_int8_stats for a blob with H = 2, 3, 4 or 6 heads (csrc/ita_long_heads_stats_kernel.h): the same six
+ * statistics of each head's own seq_len x seq_len probability matrix -- the probabilities ita_mha_long_heads_int8
+ * multiplies with V -- with every array (batch, H, seq_len): one head can be dead while the sum over heads looks healthy.
+ * Equal, bit for bit, to attention_stats_heads_ref.py.  The production projection launch, then one sweep kernel in which
+ * a staged K tile serves all H heads; the column arrays are zeroed on `stream` by a small kernel and added to with integer
+ * atomics: the same bytes on every call, a captured call is kernel nodes only.  Workspace, growth and capture rules of the
+ * other heads entries.  Refusals, all before any launch, outputs untouched: ITA_ERR_UNSUPPORTED for a float-attention
+ * layer, a seq_len or batch outside ita_mha_long_q8's limits and a layer without a long multi-head image;
+ * ITA_ERR_INVALID_ARG for a NULL x_dev or stats, a bad layer, all six pointers NULL, or an s32 output that is not 4-byte
+ * aligned.  On an H = 1 blob it forwards to ita_mha_long_int8_stats: the bytes of (batch, 1, seq_len) are those of
+ * (batch, seq_len).  ita_mha_long_int8_stats itself keeps refusing H > 1. */
+int ita_mha_long_heads_int8_stats(ita_handle h, int layer, const float* x_dev, int batch, int seq_len,
+                                  const ita_mha_long_stats* stats, void* stream);
 
 /* ITAFeedForward_QAT.forward (models/ITA/QAT/layers.py:61-75). */
 int ita_ffn_int8(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, void* stream);
