@@ -29,6 +29,7 @@
 #include "ita_long_attn_kernel.h"
 #include "ita_long_heads_kernel.h"
 #include "ita_long_stats_kernel.h"
+#include "ita_long_heads_prop_kernel.h"
 #include "ita_long_heads_stats_kernel.h"
 #include "ita_long_hist_kernel.h"
 #include "ita_long_prop_kernel.h"
@@ -1297,6 +1298,61 @@ int ita_mha_long_int8_propagate(ita_handle h, int layer, const float* x, int bat
     return launch<ita_long_prop_kernel<FAST>, ItaLongPropLds::TOTAL>(grid, dim3(512), s, ka);
   };
   return with_E(h->w.hdr.E, [&](auto e) { return fast ? run(e, std::true_type{}) : run(e, std::false_type{}); });
+}
+
+// The same for H = 2, 3, 4 or 6 heads, out (B, H, n_w, S) (ita_long_heads_prop_kernel.h): the heads statistics entry's
+// refusals, workspace and projection launch on Layer::limg_mha, then the row-parameter kernel, the weight preparation and
+// the transposed sweep.  An H = 1 blob goes to the entry above: the bytes of (B, 1, n_w, S) are those of (B, n_w, S).
+int ita_mha_long_heads_int8_propagate(ita_handle h, int layer, const float* x, int batch, int seq_len, const int8_t* w, int n_w,
+                                      int32_t* out, void* stream) {
+  if (int rc = check(h, batch)) return rc;
+  if (h->w.hdr.H == 1) return ita_mha_long_int8_propagate(h, layer, x, batch, seq_len, w, n_w, out, stream);
+  if (!x || !w || !out || layer < 0 || layer >= h->w.hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
+  const Layer& L = h->w.layers[layer];
+  hipStream_t s = (hipStream_t)stream;
+  if (L.attn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's attention is float32 (ITAW0003 blob): no int8 long attention");
+  if (int rc = check_long_shape(batch, seq_len)) return rc;
+  if (!L.limg_mha) return fail(ITA_ERR_UNSUPPORTED, "this layer has no long multi-head attention image (accumulator range)");
+  if (n_w < 1 || n_w > 64) return fail(ITA_ERR_INVALID_ARG, "ita_mha_long_heads_int8_propagate: n_w must be in [1, 64]");
+  if (misaligned(w, 4) || misaligned(out, 16))
+    return fail(ITA_ERR_INVALID_ARG, "ita_mha_long_heads_int8_propagate: w_dev must be 4-byte aligned, out_dev 16-byte aligned");
+  const int H = h->w.hdr.H;
+  const size_t ntile = (size_t)batch * (seq_len / 128), ng = (size_t)(n_w + 15) / 16;
+  // behind the int8 workspace: H row-parameter images per tile, weight images, 128 * weight row sums
+  const size_t base = long_int8_ws(ntile), rowp = ntile * H * 1024, wimg = ntile * ng * 2048, wsum = (size_t)batch * 64 * 4;
+  if (int rc = ensure_long_ws(h, base + rowp + wimg + wsum, s)) return rc;
+  ItaLongArgs a = long_args(h, L, ntile, batch, seq_len);
+  a.image = L.limg_mha;
+  a.x = x;
+  char* p = a.qfrag + base;
+  ItaLongHeadsRowsArgs ra{};
+  ra.qfrag = a.qfrag; ra.kimg = a.kimg; ra.ml = a.ml; ra.B = batch; ra.S = seq_len; ra.rowp = p;
+  ItaLongHeadsPropWArgs wa{};
+  wa.w = w; wa.wimg = p + rowp; wa.wsum = (int*)(p + rowp + wimg); wa.B = batch; wa.S = seq_len; wa.n_w = n_w;
+  ItaLongHeadsPropArgs ka{};
+  ka.qfrag = a.qfrag; ka.kimg = a.kimg; ka.rowp = ra.rowp; ka.wimg = wa.wimg; ka.wsum = wa.wsum; ka.ml = a.ml;
+  ka.B = batch; ka.S = seq_len; ka.n_w = n_w; ka.out = out;
+  const dim3 proj_grid(ntile < (size_t)h->num_cus ? (int)ntile : h->num_cus), grid(seq_len / 128, batch);
+  const dim3 wprep_grid(seq_len / 128 + 16 * (int)ng, batch);
+  auto run = [&](auto e, auto hh, auto fst) {
+    constexpr int E = decltype(e)::value, HH = decltype(hh)::value, NG = ita_long_heads_prop_ng<HH>;
+    constexpr bool FAST = decltype(fst)::value;
+    const dim3 sweep_grid(seq_len / 128, batch, ((int)ng + NG - 1) / NG);
+    if (int rc = launch<ita_long_proj_kernel<FAST, E, true>, ItaStreamLds<E, false, false>::TOTAL>(proj_grid, dim3(512), s, a)) return rc;
+    if (int rc = launch<ita_long_heads_rows_kernel<FAST, HH>, 2 * ItaLongLds::KB>(grid, dim3(512), s, ra)) return rc;
+    if (int rc = launch<ita_long_heads_prop_wprep_kernel>(wprep_grid, dim3(512), s, wa)) return rc;
+    return launch<ita_long_heads_prop_kernel<FAST, HH, NG>, ItaLongHeadsPropLds<HH>::TOTAL>(sweep_grid, dim3(512), s, ka);
+  };
+  auto forms = [&](auto e, auto hh) { return L.long_fast ? run(e, hh, std::true_type{}) : run(e, hh, std::false_type{}); };
+  return with_E(h->w.hdr.E, [&](auto e) {
+    switch (H) {   // (check_blob admits these four besides 1)
+      case 2: return forms(e, std::integral_constant<int, 2>{});
+      case 3: return forms(e, std::integral_constant<int, 3>{});
+      case 4: return forms(e, std::integral_constant<int, 4>{});
+      case 6: return forms(e, std::integral_constant<int, 6>{});
+    }
+    return fail(ITA_ERR_UNSUPPORTED, "the long multi-head propagate kernel is built for H in {2,3,4,6}");
+  });
 }
 
 // x1 = LN1(x + attn(x)) into y by the two long launches, then the FFN block + residual + LN2 in place on y: the FFN is per

@@ -35,7 +35,7 @@ HEAD_TIMEOUT = 1
 EXPORTED_SYMBOLS = (
     "ita_abi_version", "ita_create", "ita_destroy", "ita_load_weights", "ita_validate_blob", "ita_reserve", "ita_get_dims",
     "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_mha_long_int8", "ita_mha_long_int8_taps", "ita_mha_long_int8_stats", "ita_mha_long_int8_hist", "ita_mha_long_int8_propagate", "ita_encoder_layer_long",
-    "ita_mha_long_heads_q8", "ita_mha_long_heads_int8", "ita_mha_long_heads_int8_taps", "ita_mha_long_heads_int8_stats", "ita_encoder_layer_long_heads", "ita_ffn_int8", "ita_ffn_int8_taps",
+    "ita_mha_long_heads_q8", "ita_mha_long_heads_int8", "ita_mha_long_heads_int8_taps", "ita_mha_long_heads_int8_stats", "ita_mha_long_heads_int8_propagate", "ita_encoder_layer_long_heads", "ita_ffn_int8", "ita_ffn_int8_taps",
     "ita_ffn_f32", "ita_get_ffn_kind", "ita_mha_f32", "ita_get_attn_kind", "ita_mha_long_f32", "ita_mha_long_f32_taps", "ita_mha_long_f32_stats", "ita_mha_long_f32_propagate", "ita_encoder_layer_long_f32",
     "ita_encoder_layer", "ita_tokenizer", "ita_fusion_tail", "ita_vitlstm_forward", "ita_bind_dispatch",
     "ita_profile_begin", "ita_profile_begin_sampled", "ita_profile_end", "ita_set_tail_mode", "ita_debug_encoder_stamps",
@@ -217,6 +217,7 @@ def lib():
         L.ita_mha_long_heads_int8.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_heads_int8_taps.argtypes = [vp, i, vp, vp, i, i, C.POINTER(_MhaLongTaps), vp]
         L.ita_mha_long_heads_int8_stats.argtypes = [vp, i, vp, i, i, C.POINTER(_MhaLongStats), vp]
+        L.ita_mha_long_heads_int8_propagate.argtypes = [vp, i, vp, i, i, vp, i, vp, vp]
         L.ita_encoder_layer_long_heads.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_f32.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_f32_taps.argtypes = [vp, i, vp, vp, i, i, C.POINTER(_MhaLongF32Taps), vp]
@@ -971,6 +972,10 @@ class Engine:
         attention_received_long, a one-hot row gives that probability row.  Every partial sum fits int32 for any int8
         weight at S <= 32768 and at S = 65536 for weights in [-127, 127] (127 * 128 * 65536 < 2^30, twice); the weights
         are not scanned."""
+        return self._long_propagate_entry(lib().ita_mha_long_int8_propagate, x, w, layer, ())
+
+    def _long_propagate_entry(self, entry, x, w, layer, heads):
+        """either int8 propagate entry -> (B, *heads, R, S) int32: heads is () or (H,)"""
         torch = _torch()
         x = self._long_f32(x)
         B, S = x.shape[0], x.shape[1]
@@ -979,10 +984,18 @@ class Engine:
         if w.dim() == 2:
             w = w.unsqueeze(0).expand(B, -1, -1)
         w = w.contiguous()
-        out = torch.empty((B, w.shape[1], S), dtype=torch.int32, device=x.device)
-        _chk(lib().ita_mha_long_int8_propagate(self._h, layer, x.data_ptr(), B, S, w.data_ptr(), w.shape[1], out.data_ptr(),
-                                               _stream_ptr(self.device)))
+        out = torch.empty((B, *heads, w.shape[1], S), dtype=torch.int32, device=x.device)
+        _chk(entry(self._h, layer, x.data_ptr(), B, S, w.data_ptr(), w.shape[1], out.data_ptr(), _stream_ptr(self.device)))
         return out
+
+    def attention_propagate_long_heads(self, x, w, layer: int = 0):
+        """attention_propagate_long per head, for a blob with any head count (ita_mha_long_heads_int8_propagate): x (B,S,E)
+        f32, w as there (shared by the heads) -> out (B,H,R,S) int32, out[b,hd,r,j] = sum_i w[b,r,i] p_hd[b,i,j] with p_hd
+        the uint8 probabilities of attention_rows_long_heads.  Exact: equal to attention_propagate_heads_ref.propagate_heads.
+        All-ones weights give attention_received_long_heads, a one-hot row gives that probability row of every head.  The
+        range statement of attention_propagate_long holds per head.  An H = 1 blob runs attention_propagate_long's kernels
+        and gives an H axis of length 1."""
+        return self._long_propagate_entry(lib().ita_mha_long_heads_int8_propagate, x, w, layer, (self.H,))
 
     def attention_rollout_long(self, x, rows=None, first_layer: int = 0):
         """attention rollout (Abnar & Zuidema) through the int8 attention layers first_layer .. num_layers - 1 of a long
@@ -995,6 +1008,22 @@ class Engine:
             v <- 0.5 * (v + ((float64(q . P_l) * (s / 2097151)) / 256))
         where q . P_l comes from attention_propagate_long on the three base-128 digit rows of q (rollout_digits,
         rollout_combine): 21 vectors per call, more in chunks.  Equal to attention_rollout_ref.rollout bit for bit."""
+        def step(y, l):
+            return (self.encoder_layer_long_f32 if self.ffn_kind(l) == FFN_F32 else self.encoder_layer_long)(y, l)
+        return self._rollout_long(x, rows, first_layer, step, lambda y, d, l: self.attention_propagate_long(y, d, l)[:, None], 1)
+
+    def attention_rollout_long_heads(self, x, rows=None, first_layer: int = 0):
+        """attention_rollout_long for a blob with any head count: the same walk with encoder_layer_long_heads, the attention
+        matrix of a layer being the mean of its H heads,
+            s = max_j v (1 where that is 0);  q = rint((v / s) * 2097151)
+            v <- 0.5 * (v + ((float64(sum_hd q . P_l,hd) * (s / 2097151)) / (256 * H)))
+        where q . P_l,hd per head comes from attention_propagate_long_heads on the three base-128 digit rows of q and the
+        sum over the heads is taken in int64 (below 2^21 * 255 * 65536 * 6 < 2^53: its float64 is exact).  Equal to
+        attention_rollout_heads_ref.rollout bit for bit; on an H = 1 blob equal to attention_rollout_long."""
+        return self._rollout_long(x, rows, first_layer, self.encoder_layer_long_heads, self.attention_propagate_long_heads, self.H)
+
+    def _rollout_long(self, x, rows, first_layer, step, propagate, H):
+        """what the two int8 rollouts share.  step(y, l): layer l out of place; propagate(y, d, l) -> (B, H, R, S) int32"""
         import numpy as np
         torch = _torch()
         x = self._long_f32(x)
@@ -1015,24 +1044,30 @@ class Engine:
                 v[:, n, r] = 1.0
         xs = [x]
         for l in range(first_layer, self.num_layers - 1):
-            step = self.encoder_layer_long_f32 if self.ffn_kind(l) == FFN_F32 else self.encoder_layer_long
             xs.append(step(xs[-1], l))
         for l in range(self.num_layers - 1, first_layer - 1, -1):
             s = v.max(-1, keepdims=True)
             s = np.where(s == 0, 1.0, s)
             q = np.rint((v / s) * float(ROLLOUT_QMAX)).astype(np.int64)
-            qp = np.empty(v.shape, np.int64)
+            qp = np.empty(v.shape, np.int64)     # the sum over the layer's heads
             for c0 in range(0, v.shape[1], ROLLOUT_CHUNK):
                 c = slice(c0, min(c0 + ROLLOUT_CHUNK, v.shape[1]))
                 d = torch.from_numpy(rollout_digits(q[:, c])).to(x.device)
-                qp[:, c] = rollout_combine(self.attention_propagate_long(xs[l - first_layer], d, l).cpu().numpy())
-            v = 0.5 * (v + ((qp.astype(np.float64) * (s / float(ROLLOUT_QMAX))) / 256.0))
+                qp[:, c] = rollout_combine(propagate(xs[l - first_layer], d, l).cpu().numpy()).sum(1)
+            v = 0.5 * (v + ((qp.astype(np.float64) * (s / float(ROLLOUT_QMAX))) / (256.0 * H)))
         return torch.from_numpy(v).to(x.device)
 
     def attention_rollout_map_long(self, frames, tok_h: int, tok_w: int, queries=None, depth_scale: Optional[float] = None):
         """attention rollout on the token grid of camera frames: tokenize_long, then attention_rollout_long through every
         layer for the tokens queries = [(ty, tx), ...] (None: the single start vector 1 / S) -> (N, n, tok_h, tok_w)
         float64 in the order of queries.  Duplicate or out-of-grid queries raise ValueError."""
+        return self._rollout_map_long(frames, tok_h, tok_w, queries, depth_scale, self.attention_rollout_long)
+
+    def attention_rollout_map_long_heads(self, frames, tok_h: int, tok_w: int, queries=None, depth_scale: Optional[float] = None):
+        """attention_rollout_map_long for a blob with any head count (attention_rollout_long_heads)"""
+        return self._rollout_map_long(frames, tok_h, tok_w, queries, depth_scale, self.attention_rollout_long_heads)
+
+    def _rollout_map_long(self, frames, tok_h, tok_w, queries, depth_scale, rollout):
         tok_h, tok_w = int(tok_h), int(tok_w)
         toks = None
         if queries is not None:
@@ -1045,7 +1080,7 @@ class Engine:
             if len(set(toks)) != len(toks):
                 raise ValueError("duplicate queries")
         y = self.tokenize_long(frames, tok_h, tok_w, depth_scale)
-        v = self.attention_rollout_long(y, toks)
+        v = rollout(y, toks)
         return v.reshape(v.shape[0], v.shape[1], tok_h, tok_w)
 
     def _tokens_below(self, frames, tok_h, tok_w, layer, depth_scale):

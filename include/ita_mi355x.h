@@ -55,7 +55,8 @@ int ita_destroy(ita_handle h);
  * ITA_ERR_UNSUPPORTED before any launch: ita_mha_q8, ita_mha_long_q8, ita_mha_long_int8, ita_mha_long_int8_taps,
  * ita_mha_long_int8_stats, ita_mha_long_int8_hist, ita_mha_long_int8_propagate, ita_encoder_layer_long, ita_debug_encoder_stamps, ita_vitlstm_forward_slots (and ita_mha_long_f32 / ita_mha_long_f32_stats / ita_mha_long_f32_propagate / ita_encoder_layer_long_f32, which take
  * float layers only).  On long sequences an H > 1 layer runs through ita_mha_long_heads_q8, ita_mha_long_heads_int8,
- * ita_mha_long_heads_int8_taps, ita_mha_long_heads_int8_stats and ita_encoder_layer_long_heads.
+ * ita_mha_long_heads_int8_taps, ita_mha_long_heads_int8_stats, ita_mha_long_heads_int8_propagate and
+ * ita_encoder_layer_long_heads.
  * The reference pre-loads weights into the accelerator out of band
  * (docs/HOW-TO-run-the-full-project-workflow.md:55); this is that step. */
 int ita_load_weights(ita_handle h, const void* blob, size_t nbytes);
@@ -228,6 +229,31 @@ int ita_encoder_layer_long_heads(ita_handle h, int layer, const float* x_dev, fl
  * (batch, seq_len).  ita_mha_long_int8_stats itself keeps refusing H > 1. */
 int ita_mha_long_heads_int8_stats(ita_handle h, int layer, const float* x_dev, int batch, int seq_len,
                                   const ita_mha_long_stats* stats, void* stream);
+/* ita_mha_long_int8_propagate for a blob with H = 2, 3, 4 or 6 heads (csrc/ita_long_heads_prop_kernel.h): the weighted
+ * column sums of each head's own seq_len x seq_len probability matrix, none of which is held:
+ *     out[b, hd, r, j] = sum_i w[b, r, i] * p_hd[b, i, j]     w s8 (B, n_w, seq_len), shared by the heads, 1 <= n_w <= 64;
+ *                                                             out s32 (B, H, n_w, seq_len)
+ * with p_hd the u8 probabilities of head hd exactly as ita_mha_long_heads_int8 multiplies them with V, the bits of
+ * ita_mha_long_heads_int8_taps' probs.  col_mass of ita_mha_long_heads_int8_stats is w = all ones, a head's probability row
+ * is w = one-hot, attention rollout averages the heads of `out`.  The result is exact (equal to
+ * attention_propagate_heads_ref.py); the same input gives the same bytes on every call (no atomics).  Range, per head (each
+ * head has its own sums): every partial sum the kernel forms is 128 sum_i w + sum_{i < n} w (p - 128), with
+ * |sum w (p - 128)| and |128 sum w| each at most 128 * 128 * seq_len, so it and the result fit s32 for ANY s8 weight at
+ * seq_len <= 32 768, and at seq_len = 65 536 for weights in [-127, 127] (127 * 128 * 65 536 < 2^30 each).  The weights are
+ * not scanned: beyond that bound the sums wrap.  x (B, seq_len, E) f32 is read only; w and out must not overlap each other
+ * or x.  Launches: the production projection, a kernel that repeats the row-maximum and row-sum sweeps for all H heads and
+ * writes each query's softmax parameters per head, a small kernel that sums the weight rows and permutes w into MFMA operand
+ * images, and ita_long_heads_prop_kernel, the transposed sweep in which a staged query tile serves all H heads.  Workspace:
+ * ita_mha_long_q8's plus, per 128-token tile, 1024 H + 2048 ceil(n_w / 16) bytes and 256 bytes per frame; growth and
+ * capture rules of the other heads entries: once the workspace holds the call there is no host synchronisation and no
+ * allocation, the call may be captured and is kernel nodes only.  Refusals, all before any launch, out untouched: whatever
+ * ita_mha_long_heads_int8_stats refuses for the layer and the shape, with the same status (ITA_ERR_UNSUPPORTED for a
+ * float-attention layer, a seq_len or batch outside ita_mha_long_q8's limits and a layer without a long multi-head image);
+ * ITA_ERR_INVALID_ARG for a NULL x_dev, w_dev or out_dev, a bad layer, n_w outside [1, 64], w_dev off a 4-byte boundary or
+ * out_dev off a 16-byte boundary.  On an H = 1 blob it forwards to ita_mha_long_int8_propagate: the bytes of
+ * (batch, 1, n_w, seq_len) are those of (batch, n_w, seq_len).  ita_mha_long_int8_propagate itself keeps refusing H > 1. */
+int ita_mha_long_heads_int8_propagate(ita_handle h, int layer, const float* x_dev, int batch, int seq_len,
+                                      const int8_t* w_dev, int n_w, int32_t* out_dev, void* stream);
 
 /* ITAFeedForward_QAT.forward (models/ITA/QAT/layers.py:61-75). */
 int ita_ffn_int8(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, void* stream);
