@@ -30,6 +30,7 @@
 #include "ita_long_heads_kernel.h"
 #include "ita_long_stats_kernel.h"
 #include "ita_long_heads_prop_kernel.h"
+#include "ita_long_heads_hist_kernel.h"
 #include "ita_long_heads_stats_kernel.h"
 #include "ita_long_hist_kernel.h"
 #include "ita_long_prop_kernel.h"
@@ -1252,6 +1253,55 @@ int ita_mha_long_int8_hist(ita_handle h, int layer, const float* x, int batch, i
     return launch<ita_long_hist_kernel<FAST>, ItaLongHistLds::TOTAL>(grid, dim3(512), s, ha);
   };
   return with_E(h->w.hdr.E, [&](auto e) { return fast ? run(e, std::true_type{}) : run(e, std::false_type{}); });
+}
+
+// The same for H = 2, 3, 4 or 6 heads, the arrays (B, H, 256) and (B, H, 2): the heads statistics entry's refusals, workspace
+// and projection launch on Layer::limg_mha, ita_long_hist_zero_kernel on B H blocks, then ita_long_heads_hist_kernel<FAST, H>
+// (ita_long_heads_hist_kernel.h).  An H = 1 blob goes to the entry above: the bytes of (B, 1, 256) are those of (B, 256).
+int ita_mha_long_heads_int8_hist(ita_handle h, int layer, const float* x, int batch, int seq_len, const ita_mha_long_hist* hist,
+                                 void* stream) {
+  if (int rc = check(h, batch)) return rc;
+  if (h->w.hdr.H == 1) return ita_mha_long_int8_hist(h, layer, x, batch, seq_len, hist, stream);
+  if (!x || !hist || layer < 0 || layer >= h->w.hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad pointer or layer");
+  const Layer& L = h->w.layers[layer];
+  hipStream_t s = (hipStream_t)stream;
+  if (L.attn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's attention is float32 (ITAW0003 blob): no int8 long attention");
+  if (int rc = check_long_shape(batch, seq_len)) return rc;
+  if (!L.limg_mha) return fail(ITA_ERR_UNSUPPORTED, "this layer has no long multi-head attention image (accumulator range)");
+  if (!hist->logits && !hist->shifts && !hist->probs && !hist->logits_out && !hist->acc_range)
+    return fail(ITA_ERR_INVALID_ARG, "ita_mha_long_heads_int8_hist: all five outputs are null");
+  if (misaligned(hist->logits, 8) || misaligned(hist->shifts, 8) || misaligned(hist->probs, 8) || misaligned(hist->logits_out, 8) ||
+      misaligned(hist->acc_range, 4))
+    return fail(ITA_ERR_INVALID_ARG, "logits, shifts, probs and logits_out must be 8-byte aligned, acc_range 4-byte aligned");
+  const int H = h->w.hdr.H;
+  const size_t ntile = (size_t)batch * (seq_len / 128);
+  if (int rc = ensure_long_ws(h, long_int8_ws(ntile), s)) return rc;
+  ItaLongArgs a = long_args(h, L, ntile, batch, seq_len);
+  a.image = L.limg_mha;
+  a.x = x;
+  ItaLongHistArgs ha{};
+  ha.qfrag = a.qfrag; ha.kimg = a.kimg; ha.ml = a.ml; ha.B = batch; ha.S = seq_len;
+  ha.logits = (unsigned long long*)hist->logits; ha.shifts = (unsigned long long*)hist->shifts;
+  ha.probs = (unsigned long long*)hist->probs; ha.logits_out = (unsigned long long*)hist->logits_out;
+  ha.acc_range = hist->acc_range;
+  if (int rc = launch<ita_long_hist_zero_kernel>(dim3(batch * H), dim3(256), s, ha)) return rc;   // one block per (frame, head)
+  const dim3 proj_grid(ntile < (size_t)h->num_cus ? (int)ntile : h->num_cus), grid(seq_len / 128, batch);
+  auto run = [&](auto e, auto hh, auto fst) {
+    constexpr int E = decltype(e)::value, HH = decltype(hh)::value;
+    constexpr bool FAST = decltype(fst)::value;
+    if (int rc = launch<ita_long_proj_kernel<FAST, E, true>, ItaStreamLds<E, false, false>::TOTAL>(proj_grid, dim3(512), s, a)) return rc;
+    return launch<ita_long_heads_hist_kernel<FAST, HH>, ItaLongHeadsHistLds::TOTAL>(grid, dim3(512), s, ha);
+  };
+  auto forms = [&](auto e, auto hh) { return L.long_fast ? run(e, hh, std::true_type{}) : run(e, hh, std::false_type{}); };
+  return with_E(h->w.hdr.E, [&](auto e) {
+    switch (H) {   // (check_blob admits these four besides 1)
+      case 2: return forms(e, std::integral_constant<int, 2>{});
+      case 3: return forms(e, std::integral_constant<int, 3>{});
+      case 4: return forms(e, std::integral_constant<int, 4>{});
+      case 6: return forms(e, std::integral_constant<int, 6>{});
+    }
+    return fail(ITA_ERR_UNSUPPORTED, "the long multi-head histogram kernel is built for H in {2,3,4,6}");
+  });
 }
 
 // out = w . P (ita_long_prop_kernel.h): the production projection launch, ita_long_stats_kernel for the row maximum and row

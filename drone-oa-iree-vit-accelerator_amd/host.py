@@ -35,7 +35,7 @@ HEAD_TIMEOUT = 1
 EXPORTED_SYMBOLS = (
     "ita_abi_version", "ita_create", "ita_destroy", "ita_load_weights", "ita_validate_blob", "ita_reserve", "ita_get_dims",
     "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_mha_long_int8", "ita_mha_long_int8_taps", "ita_mha_long_int8_stats", "ita_mha_long_int8_hist", "ita_mha_long_int8_propagate", "ita_encoder_layer_long",
-    "ita_mha_long_heads_q8", "ita_mha_long_heads_int8", "ita_mha_long_heads_int8_taps", "ita_mha_long_heads_int8_stats", "ita_mha_long_heads_int8_propagate", "ita_encoder_layer_long_heads", "ita_ffn_int8", "ita_ffn_int8_taps",
+    "ita_mha_long_heads_q8", "ita_mha_long_heads_int8", "ita_mha_long_heads_int8_taps", "ita_mha_long_heads_int8_stats", "ita_mha_long_heads_int8_hist", "ita_mha_long_heads_int8_propagate", "ita_encoder_layer_long_heads", "ita_ffn_int8", "ita_ffn_int8_taps",
     "ita_ffn_f32", "ita_get_ffn_kind", "ita_mha_f32", "ita_get_attn_kind", "ita_mha_long_f32", "ita_mha_long_f32_taps", "ita_mha_long_f32_stats", "ita_mha_long_f32_propagate", "ita_encoder_layer_long_f32",
     "ita_encoder_layer", "ita_tokenizer", "ita_fusion_tail", "ita_vitlstm_forward", "ita_bind_dispatch",
     "ita_profile_begin", "ita_profile_begin_sampled", "ita_profile_end", "ita_set_tail_mode", "ita_debug_encoder_stamps",
@@ -217,6 +217,7 @@ def lib():
         L.ita_mha_long_heads_int8.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_heads_int8_taps.argtypes = [vp, i, vp, vp, i, i, C.POINTER(_MhaLongTaps), vp]
         L.ita_mha_long_heads_int8_stats.argtypes = [vp, i, vp, i, i, C.POINTER(_MhaLongStats), vp]
+        L.ita_mha_long_heads_int8_hist.argtypes = [vp, i, vp, i, i, C.POINTER(_MhaLongHist), vp]
         L.ita_mha_long_heads_int8_propagate.argtypes = [vp, i, vp, i, i, vp, i, vp, vp]
         L.ita_encoder_layer_long_heads.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_f32.argtypes = [vp, i, vp, vp, i, i, vp]
@@ -928,17 +929,21 @@ class Engine:
 
     def _long_hist(self, x, layer, want):
         """ita_mha_long_int8_hist asking for the outputs named in `want` only -> dict of those"""
+        return self._long_hist_entry(lib().ita_mha_long_int8_hist, x, layer, want, ())
+
+    def _long_hist_entry(self, entry, x, layer, want, heads):
+        """either int8 histogram entry -> dict of (B, *heads, 256) and (B, *heads, 2) tensors: heads is () or (H,)"""
         torch = _torch()
         x = self._long_f32(x)
         B, S = x.shape[0], x.shape[1]
         unknown = [k for k in want if k not in LONG_HIST]
         if unknown:
             raise ITAError(f"no such long histogram: {unknown}")
-        spec = dict(logits=((B, 256), torch.int64), logits_out=((B, 2), torch.int64), acc_range=((B, 2), torch.int32),
-                    shifts=((B, 256), torch.int64), probs=((B, 256), torch.int64))
-        t = {k: torch.empty(spec[k][0], dtype=spec[k][1], device=x.device) for k in LONG_HIST if k in want}
+        spec = dict(logits=(256, torch.int64), logits_out=(2, torch.int64), acc_range=(2, torch.int32),
+                    shifts=(256, torch.int64), probs=(256, torch.int64))
+        t = {k: torch.empty((B, *heads, spec[k][0]), dtype=spec[k][1], device=x.device) for k in LONG_HIST if k in want}
         st = _MhaLongHist(**{k: v.data_ptr() for k, v in t.items()})
-        _chk(lib().ita_mha_long_int8_hist(self._h, layer, x.data_ptr(), B, S, C.byref(st), _stream_ptr(self.device)))
+        _chk(entry(self._h, layer, x.data_ptr(), B, S, C.byref(st), _stream_ptr(self.device)))
         return t
 
     def attention_histograms_long(self, x, layer: int = 0, stages: bool = False):
@@ -963,6 +968,38 @@ class Engine:
         then attention_histograms_long of `layer` -> its dict"""
         y = self._tokens_below(frames, int(tok_h), int(tok_w), layer, depth_scale)
         return self.attention_histograms_long(y, int(layer))
+
+    def attention_histograms_long_heads(self, x, layer: int = 0, stages: bool = False):
+        """attention_histograms_long per head, for a blob with any head count (ita_mha_long_heads_int8_hist): x (B,S,E) f32
+        -> dict of logits, shifts, probs (B,H,256) int64, logits_out (B,H,2) int64 and acc_range (B,H,2) int32 of each
+        head's own S x S matrix -- one ml requantises all heads, so one head can waste the int8 range another fills, and
+        acc_range is what a per-head ml would be chosen from.  Equal to attention_hist_heads_ref.hist_heads; an H = 1 blob
+        runs attention_histograms_long's kernels and gives an H axis of length 1.  With stages=True also int64 histograms
+        (bin c + 128) of the int8 stage tensors of mha_long_heads_taps, counted with torch: x_q and out_q (B,256); Q, K, V
+        and ctx (B,H,256), each over the head's own P / H features."""
+        torch = _torch()
+        out = self._long_hist_entry(lib().ita_mha_long_heads_int8_hist, x, layer, LONG_HIST, (self.H,))
+        if stages:
+            _, taps = self._long_taps(x, (), layer, LONG_HIST_STAGES, heads=True)
+            for k in LONG_HIST_STAGES:
+                v = taps[k].to(torch.int64) + 128                      # (B, S, E) or (B, S, P)
+                B = v.shape[0]
+                if k in ("x_q", "out_q"):
+                    out[k] = torch.stack([torch.bincount(r, minlength=256) for r in v.reshape(B, -1)])
+                else:                                                   # head h holds features [h P/H, (h+1) P/H)
+                    v = v.reshape(B, v.shape[1], self.H, -1).transpose(1, 2).reshape(B * self.H, -1)
+                    out[k] = torch.stack([torch.bincount(r, minlength=256) for r in v]).reshape(B, self.H, 256)
+        return out
+
+    def attention_histograms_frames_long_heads(self, frames, tok_h: int, tok_w: int, layer: int = 0, depth_scale: Optional[float] = None):
+        """the per-head histograms for camera frames: tokenize_long, the encoder layers below `layer`
+        (encoder_layer_long_heads), then attention_histograms_long_heads of `layer` -> its dict"""
+        if not 0 <= int(layer) < self.num_layers:
+            raise ValueError(f"layer {layer} out of range")
+        y = self.tokenize_long(frames, int(tok_h), int(tok_w), depth_scale)
+        for l in range(int(layer)):
+            self.encoder_layer_long_heads(y, l, out=y)
+        return self.attention_histograms_long_heads(y, int(layer))
 
     def attention_propagate_long(self, x, w, layer: int = 0):
         """weighted column sums of the whole S x S integer-softmax matrix of a long sequence, which is never held

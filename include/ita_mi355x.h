@@ -55,8 +55,8 @@ int ita_destroy(ita_handle h);
  * ITA_ERR_UNSUPPORTED before any launch: ita_mha_q8, ita_mha_long_q8, ita_mha_long_int8, ita_mha_long_int8_taps,
  * ita_mha_long_int8_stats, ita_mha_long_int8_hist, ita_mha_long_int8_propagate, ita_encoder_layer_long, ita_debug_encoder_stamps, ita_vitlstm_forward_slots (and ita_mha_long_f32 / ita_mha_long_f32_stats / ita_mha_long_f32_propagate / ita_encoder_layer_long_f32, which take
  * float layers only).  On long sequences an H > 1 layer runs through ita_mha_long_heads_q8, ita_mha_long_heads_int8,
- * ita_mha_long_heads_int8_taps, ita_mha_long_heads_int8_stats, ita_mha_long_heads_int8_propagate and
- * ita_encoder_layer_long_heads.
+ * ita_mha_long_heads_int8_taps, ita_mha_long_heads_int8_stats, ita_mha_long_heads_int8_hist,
+ * ita_mha_long_heads_int8_propagate and ita_encoder_layer_long_heads.
  * The reference pre-loads weights into the accelerator out of band
  * (docs/HOW-TO-run-the-full-project-workflow.md:55); this is that step. */
 int ita_load_weights(ita_handle h, const void* blob, size_t nbytes);
@@ -229,6 +229,23 @@ int ita_encoder_layer_long_heads(ita_handle h, int layer, const float* x_dev, fl
  * (batch, seq_len).  ita_mha_long_int8_stats itself keeps refusing H > 1. */
 int ita_mha_long_heads_int8_stats(ita_handle h, int layer, const float* x_dev, int batch, int seq_len,
                                   const ita_mha_long_stats* stats, void* stream);
+/* ita_mha_long_int8_hist for a blob with H = 2, 3, 4 or 6 heads (csrc/ita_long_heads_hist_kernel.h): the same five results
+ * of each head's own seq_len x seq_len matrix requant(Q_hd K_hd^T, ml) -- the logits ita_mha_long_heads_int8 computes with
+ * -- in the same struct, its arrays read as logits, shifts, probs (batch, H, 256) s64, logits_out (batch, H, 2) s64 and
+ * acc_range (batch, H, 2) s32.  One ml requantises all heads and a head's accumulators are sums over P / H features: the
+ * per-head acc_range is what a per-head ml would be chosen from, the per-head shifts and probs show which head the integer
+ * softmax has flattened or killed.  Every histogram of a head sums to seq_len^2.  Equal, bit for bit, to
+ * attention_hist_heads_ref.py.  The production projection launch, then one kernel that takes the accumulator range of all
+ * heads in one sweep over the key tiles and counts head by head in one further sweep each; the outputs are set to zero on
+ * `stream` first by a small kernel and added to with integer atomics: the same bytes on every call, a captured call is
+ * kernel nodes only.  Workspace, growth and capture rules of ita_mha_long_heads_int8.  Refusals, all before any launch,
+ * outputs untouched: ITA_ERR_UNSUPPORTED for a float-attention layer, a seq_len or batch outside ita_mha_long_q8's limits
+ * and a layer without a long multi-head image; ITA_ERR_INVALID_ARG for a NULL x_dev or hist, a bad layer, all five pointers
+ * NULL, an s64 output off an 8-byte boundary or acc_range off a 4-byte boundary.  On an H = 1 blob it forwards to
+ * ita_mha_long_int8_hist: the bytes of (batch, 1, 256) are those of (batch, 256).  ita_mha_long_int8_hist itself keeps
+ * refusing H > 1. */
+int ita_mha_long_heads_int8_hist(ita_handle h, int layer, const float* x_dev, int batch, int seq_len,
+                                 const ita_mha_long_hist* hist, void* stream);
 /* ita_mha_long_int8_propagate for a blob with H = 2, 3, 4 or 6 heads (csrc/ita_long_heads_prop_kernel.h): the weighted
  * column sums of each head's own seq_len x seq_len probability matrix, none of which is held:
  *     out[b, hd, r, j] = sum_i w[b, r, i] * p_hd[b, i, j]     w s8 (B, n_w, seq_len), shared by the heads, 1 <= n_w <= 64;
