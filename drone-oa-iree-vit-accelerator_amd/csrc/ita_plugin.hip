@@ -38,6 +38,7 @@
 #include "ita_attn_f32_kernel.h"
 #include "ita_long_f32_kernel.h"
 #include "ita_long_f32_stats_kernel.h"
+#include "ita_long_f32_hist_kernel.h"
 #include "ita_long_f32_prop_kernel.h"
 #include "ita_ingest_kernel.h"
 #include "ita_ingest_wire_kernel.h"
@@ -1565,6 +1566,49 @@ int ita_mha_long_f32_stats(ita_handle h, int layer, const float* x, int batch, i
     const size_t n = (size_t)batch * seq_len, blocks = (n + 255) / 256;
     return launch<ita_lf32_colsum_kernel>(dim3(blocks < 4096 ? (unsigned)blocks : 4096u), dim3(256), s, (const float*)sa.part_mass,
                                           (const int*)sa.part_nnz, st->col_mass, st->col_nnz, (int)nqt, seq_len, n);
+  });
+}
+
+// The production projection launch, then ita_lf32_hist_kernel over its K image (ita_long_f32_hist_kernel.h): two sweeps, no
+// y.  The kernel ADDS into the outputs: they are set to zero (the range to +inf, -inf) on the stream first, by a kernel
+// (inside a stream capture the call is kernel nodes only).  The workspace is the float long workspace and nothing else.
+int ita_mha_long_f32_hist(ita_handle h, int layer, const float* x, int batch, int seq_len, float scale,
+                          const struct ita_mha_long_f32_hist* hist, void* stream) {
+  // the argument rules come first: they need neither the handle's contents nor the device
+  if (!h || !x || !hist) return fail(ITA_ERR_INVALID_ARG, "null handle, x_dev or hist");
+  if (!hist->logits && !hist->shifts && !hist->probs && !hist->logits_out && !hist->range)
+    return fail(ITA_ERR_INVALID_ARG, "ita_mha_long_f32_hist: all five outputs are null");
+  if (misaligned(hist->logits, 8) || misaligned(hist->shifts, 8) || misaligned(hist->probs, 8) || misaligned(hist->logits_out, 8) ||
+      misaligned(hist->range, 4))
+    return fail(ITA_ERR_INVALID_ARG, "logits, shifts, probs and logits_out must be 8-byte aligned, range 4-byte aligned");
+  if (!(scale > 0.0f && scale < __builtin_inff())) return fail(ITA_ERR_INVALID_ARG, "scale must be finite and > 0");   // NaN fails both
+  if (int rc = check(h, batch)) return rc;
+  if (layer < 0 || layer >= h->w.hdr.num_layers) return fail(ITA_ERR_INVALID_ARG, "bad layer");
+  const Layer& L = h->w.layers[layer];
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = check_long_f32(L, batch, seq_len,
+                              "this layer's attention is int8 (ITAW0001 / ITAW0002 blob): ita_mha_long_int8_hist reads it out")) return rc;
+  const size_t ntile = (size_t)batch * (seq_len / 128);
+  const size_t img = ntile * 2 * ItaLongF32Lds::UNIT;
+  if (int rc = ensure_long_ws(h, 2 * img, s)) return rc;
+  ItaLongF32Args a{};
+  a.x = x;
+  a.wk = L.wkf; a.wv = L.wvf; a.bk = L.bkf; a.bv = L.bvf;
+  a.kimg = (f32x4*)(char*)h->long_ws; a.vimg = (f32x4*)((char*)h->long_ws + img);
+  a.B = batch; a.S = seq_len;
+  ItaLongF32HistArgs ha{};
+  ha.x = x; ha.wq = L.wqf; ha.bq = L.bqf; ha.kimg = a.kimg;
+  ha.B = batch; ha.S = seq_len; ha.scale = scale;
+  ha.logits = (unsigned long long*)hist->logits; ha.shifts = (unsigned long long*)hist->shifts;
+  ha.probs = (unsigned long long*)hist->probs; ha.logits_out = (unsigned long long*)hist->logits_out;
+  ha.range = hist->range;
+  if (int rc = launch<ita_f32_hist::ita_lf32_hist_zero_kernel>(dim3(batch), dim3(256), s, ha)) return rc;
+  const size_t cap = 2 * (size_t)h->num_cus;
+  const dim3 proj_grid((unsigned)(ntile < cap ? ntile : cap)), grid(seq_len / 128, batch);
+  return with_E(h->w.hdr.E, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    if (int rc = launch<ita_lf32_proj_kernel<E>>(proj_grid, dim3(512), s, a)) return rc;
+    return launch<ita_f32_hist::ita_lf32_hist_kernel<E>, ItaLongF32Lds::TOTAL>(grid, dim3(512), s, ha);
   });
 }
 

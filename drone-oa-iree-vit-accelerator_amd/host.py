@@ -36,7 +36,7 @@ EXPORTED_SYMBOLS = (
     "ita_abi_version", "ita_create", "ita_destroy", "ita_load_weights", "ita_validate_blob", "ita_reserve", "ita_get_dims",
     "ita_last_error", "ita_error_string", "ita_mha_int8", "ita_mha_int8_taps", "ita_mha_q8", "ita_mha_long_q8", "ita_mha_long_int8", "ita_mha_long_int8_taps", "ita_mha_long_int8_stats", "ita_mha_long_int8_hist", "ita_mha_long_int8_propagate", "ita_encoder_layer_long",
     "ita_mha_long_heads_q8", "ita_mha_long_heads_int8", "ita_mha_long_heads_int8_taps", "ita_mha_long_heads_int8_stats", "ita_mha_long_heads_int8_hist", "ita_mha_long_heads_int8_propagate", "ita_encoder_layer_long_heads", "ita_ffn_int8", "ita_ffn_int8_taps",
-    "ita_ffn_f32", "ita_get_ffn_kind", "ita_mha_f32", "ita_get_attn_kind", "ita_mha_long_f32", "ita_mha_long_f32_taps", "ita_mha_long_f32_stats", "ita_mha_long_f32_propagate", "ita_encoder_layer_long_f32",
+    "ita_ffn_f32", "ita_get_ffn_kind", "ita_mha_f32", "ita_get_attn_kind", "ita_mha_long_f32", "ita_mha_long_f32_taps", "ita_mha_long_f32_stats", "ita_mha_long_f32_hist", "ita_mha_long_f32_propagate", "ita_encoder_layer_long_f32",
     "ita_encoder_layer", "ita_tokenizer", "ita_fusion_tail", "ita_vitlstm_forward", "ita_bind_dispatch",
     "ita_profile_begin", "ita_profile_begin_sampled", "ita_profile_end", "ita_set_tail_mode", "ita_debug_encoder_stamps",
     "ita_fusion_tail_load", "ita_fusion_tail_large",
@@ -156,6 +156,13 @@ class _MhaLongF32Stats(C.Structure):  # struct ita_mha_long_f32_stats
 LONG_F32_STATS = ("row_max", "row_sum", "row_gap", "row_nnz", "col_mass", "col_nnz")
 
 
+class _MhaLongF32Hist(C.Structure):   # struct ita_mha_long_f32_hist
+    _fields_ = [(n, C.c_void_p) for n in ("logits", "shifts", "probs", "logits_out", "range")]
+
+
+LONG_F32_HIST = ("logits", "logits_out", "range", "shifts", "probs")      # the order of attention_hist_f32_ref.NAMES
+
+
 class _FfnTaps(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("x_q", "h", "out_q")]
 
@@ -223,6 +230,7 @@ def lib():
         L.ita_mha_long_f32.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_f32_taps.argtypes = [vp, i, vp, vp, i, i, C.POINTER(_MhaLongF32Taps), vp]
         L.ita_mha_long_f32_stats.argtypes = [vp, i, vp, i, i, C.c_float, C.POINTER(_MhaLongF32Stats), vp]
+        L.ita_mha_long_f32_hist.argtypes = [vp, i, vp, i, i, C.c_float, C.POINTER(_MhaLongF32Hist), vp]
         L.ita_mha_long_f32_propagate.argtypes = [vp, i, vp, i, i, vp, i, vp, vp]
         L.ita_encoder_layer_long_f32.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_vitlstm_tail.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
@@ -1312,6 +1320,30 @@ class Engine:
         layers below `layer`, then attention_received_long_f32 of `layer` -> (N, tok_h, tok_w) f32"""
         y = self._tokens_below(frames, int(tok_h), int(tok_w), layer, depth_scale)
         return self.attention_received_long_f32(y, int(layer)).reshape(y.shape[0], int(tok_h), int(tok_w))
+
+    def attention_histograms_long_f32(self, x, layer: int = 0, scale: float = 1.0, want=LONG_F32_HIST):
+        """histograms of the whole S x S matrix of a float-attention layer over a long sequence, which is never held
+        (ita_mha_long_f32_hist): x (B,S,E) f32 -> dict of the outputs named in `want` (default all five).  With the
+        logits s, the row maximum m, the row sum l and the probability p of mha_long_f32_taps: range (B,2) f32, minimum
+        and maximum of s; logits (B,256) int64, bin clamp(rint(s * scale), -128, 127) + 128, the codes an int8 quantiser
+        of step 1 / scale would produce; logits_out (B,2) int64, the logits that clamp would change, below and above;
+        shifts (B,256) int64, bin min(rint((m - s) * scale), 255); probs (B,256) int64, bin = the biased binary exponent
+        of p (127: p = 1; below 119: nothing a u8 softmax can hold).  Every histogram of a frame sums to S * S; the same
+        input gives the same bytes on every call, whatever the batch around a frame.  Equal to
+        attention_hist_f32_ref.hist_f32 of the taps of all rows."""
+        torch = _torch()
+        x = self._long_f32(x)
+        B, S = x.shape[0], x.shape[1]
+        unknown = [k for k in want if k not in LONG_F32_HIST]
+        if unknown:
+            raise ITAError(f"no such long float histogram: {unknown}")
+        spec = dict(logits=(256, torch.int64), logits_out=(2, torch.int64), range=(2, torch.float32),
+                    shifts=(256, torch.int64), probs=(256, torch.int64))
+        t = {k: torch.empty((B, spec[k][0]), dtype=spec[k][1], device=x.device) for k in LONG_F32_HIST if k in want}
+        st = _MhaLongF32Hist(**{k: v.data_ptr() for k, v in t.items()})
+        _chk(lib().ita_mha_long_f32_hist(self._h, layer, x.data_ptr(), B, S, float(scale), C.byref(st),
+                                         _stream_ptr(self.device)))
+        return t
 
     def attention_propagate_long_f32(self, x, w, layer: int = 0):
         """weighted column sums of the whole S x S softmax matrix of a float-attention layer over a long sequence, which

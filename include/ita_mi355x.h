@@ -294,6 +294,7 @@ int ita_ffn_f32(ita_handle h, int layer, const float* x_dev, float* y_dev, int b
  * ita_mha_f32 / ita_mha_long_f32 / ita_mha_long_f32_taps / ita_mha_long_f32_stats / ita_mha_long_f32_propagate on an INT8 layer, fail with ITA_ERR_UNSUPPORTED; each message names the
  * sibling entry (ita_mha_long_int8 <-> ita_mha_long_f32, ita_mha_long_int8_taps <-> ita_mha_long_f32_taps,
  * ita_mha_long_int8_stats <-> ita_mha_long_f32_stats; ita_mha_long_f32_propagate names ita_mha_long_int8_propagate,
+ * ita_mha_long_f32_hist names ita_mha_long_int8_hist,
  * ita_encoder_layer_long <-> ita_encoder_layer_long_f32). */
 enum { ITA_ATTN_INT8 = 0, ITA_ATTN_F32 = 1 };
 int ita_get_attn_kind(ita_handle h, int layer, int* kind);
@@ -363,6 +364,38 @@ struct ita_mha_long_f32_stats {
 };
 int ita_mha_long_f32_stats(ita_handle h, int layer, const float* x_dev, int batch, int seq_len, float p_min,
                            const struct ita_mha_long_f32_stats* stats, void* stream);
+/* Histograms of the WHOLE seq_len x seq_len matrix of ita_mha_long_f32, which is never held -- the float sibling of
+ * ita_mha_long_int8_hist, for a checkpoint BEFORE quantisation-aware training: which logit scale fits, how many logits an
+ * int8 clamp would change at that scale, how far below the row maximum the keys sit, how many probabilities lie below what
+ * a u8 softmax can hold.  x (B, seq_len, E) f32 is read only, there is no y.  With s, m and l the logits, the final running
+ * maximum and the final row sum of the production sweep (the bits ita_mha_long_f32_taps reads out) and
+ * p = ita_expf(s - m) * (1.0f / l) the probability that entry defines, every operation a separately rounded f32 operation,
+ * per frame (device pointers, any may be NULL):
+ *   range      f32 (B, 2)    minimum and maximum of s over the whole matrix: the float sibling of acc_range
+ *   logits     s64 (B, 256)  r = rintf(s * scale); bin clamp(r, -128, 127) + 128: the codes of an int8 quantiser of step 1 / scale
+ *   logits_out s64 (B, 2)    #{r < -128}, #{r > 127}: what that clamp would change
+ *   shifts     s64 (B, 256)  d = m - s >= 0; bin min(rintf(d * scale), 255): the gap to the row maximum in quantiser steps
+ *   probs      s64 (B, 256)  bin bits(p) >> 23, the biased binary exponent: 127 is p = 1, 126 is [1/2, 1), 127 - k is
+ *                            [2^-k, 2^-(k-1)), 0 is zero and the subnormals; below bin 119 a u8 softmax holds nothing
+ * Every histogram of a frame sums to seq_len^2 (2^32 at 65536 keys, hence s64).  Counts are added with integer atomics and
+ * the range is kept with integer atomics on the floats' bits (csrc/ita_long_f32_hist_kernel.h; no floating-point atomics):
+ * the same input gives the same bytes on every call, in any batch position, and alone.  Non-finite x gives unspecified
+ * counts.  The production projection launch, a small kernel that zeroes the outputs and one kernel of two sweeps (one, when
+ * range alone is asked for): kernel launches only, no host synchronisation and no allocation once the workspace holds the
+ * call, so the call may be captured.  Workspace and shape limits: ita_mha_long_f32's; the workspace grows on demand (not
+ * inside a stream capture: ITA_ERR_INVALID_ARG).
+ * Refusals, all before any launch, outputs untouched: whatever ita_mha_long_f32 refuses, with the same status (an
+ * int8-attention layer: ITA_ERR_UNSUPPORTED, the message names ita_mha_long_int8_hist); ITA_ERR_INVALID_ARG for a NULL
+ * x_dev or hist, a bad layer, all five pointers NULL, logits, shifts, probs or logits_out off an 8-byte boundary, range off
+ * a 4-byte boundary, and a scale that is NaN, infinite or <= 0.
+ * As with ita_mha_long_f32_stats the struct has a tag and no typedef name -- that identifier is the entry's. */
+struct ita_mha_long_f32_hist {
+  int64_t *logits, *shifts, *probs;   /* (batch, 256) each, may be NULL */
+  int64_t *logits_out;                /* (batch, 2), may be NULL */
+  float   *range;                     /* (batch, 2), may be NULL */
+};
+int ita_mha_long_f32_hist(ita_handle h, int layer, const float* x_dev, int batch, int seq_len, float scale,
+                          const struct ita_mha_long_f32_hist* hist, void* stream);
 /* Weighted column sums of the WHOLE seq_len x seq_len probability matrix of ita_mha_long_f32, which is never held -- the
  * float sibling of ita_mha_long_int8_propagate:
  *     out[b, r, j] = sum_i w[b, r, i] * p[b, i, j]      w f32 (B, n_w, seq_len), out f32 (B, n_w, seq_len), 1 <= n_w <= 64
