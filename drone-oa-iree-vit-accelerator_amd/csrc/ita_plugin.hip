@@ -27,6 +27,7 @@
 #include "ita_int8_kernels.h"
 #include "ita_stream_kernel.h"
 #include "ita_long_attn_kernel.h"
+#include "ita_long_ragged_kernel.h"
 #include "ita_long_heads_kernel.h"
 #include "ita_long_stats_kernel.h"
 #include "ita_long_heads_prop_kernel.h"
@@ -1417,6 +1418,54 @@ int ita_encoder_layer_long(ita_handle h, int layer, const float* x, float* y, in
   if (!L.n1w || !L.n2w) return fail(ITA_ERR_BAD_BLOB, "LayerNorm parameters missing from the blob");
   if (int rc = launch_long(h, layer, nullptr, nullptr, x, y, true, batch, seq_len, (hipStream_t)stream)) return rc;
   return launch_ffn(h, layer, y, y, batch * (seq_len / 128), true, nullptr, (hipStream_t)stream);
+}
+
+namespace {
+
+// Ragged batches (ita_long_ragged_kernel.h): launch_long's refusals, workspace and projection launch over all
+// batch * seq_stride / 128 tiles, then ita_long_ragged_attn_kernel, which reads the frames' lengths on the device
+int launch_long_ragged(ita_context* h, int layer, const float* x, float* y, bool fuse_ln, int batch, int seq_stride,
+                       const int* lens, hipStream_t s) {
+  if (!lens || misaligned(lens, 4)) return fail(ITA_ERR_INVALID_ARG, "lens_dev must be a 4-byte aligned device pointer to batch int32");
+  if (h->w.hdr.H != 1)
+    return fail(ITA_ERR_UNSUPPORTED, "the ragged long entries run one-head blobs only (H > 1: ita_mha_long_heads_int8 on equal lengths)");
+  const Layer& L = h->w.layers[layer];
+  if (int rc = check_long(L, batch, seq_stride)) return rc;
+  if (fuse_ln && !L.n1w) return fail(ITA_ERR_BAD_BLOB, "norm1 parameters missing from the blob");
+  const size_t ntile = (size_t)batch * (seq_stride / 128);
+  if (int rc = ensure_long_ws(h, long_int8_ws(ntile), s)) return rc;
+  ItaLongArgs a = long_args(h, L, ntile, batch, seq_stride);
+  a.x = x; a.y = y; a.fuse_ln = fuse_ln ? 1 : 0;
+  const bool fast = L.fast_sites == ITA_SITES_ALL;
+  const dim3 proj_grid(ntile < (size_t)h->num_cus ? (int)ntile : h->num_cus), attn_grid(seq_stride / 128, batch);
+  auto run = [&](auto e, auto fst) {
+    constexpr int E = decltype(e)::value;
+    constexpr bool FAST = decltype(fst)::value;
+    if (int rc = launch<ita_long_proj_kernel<FAST, E, true>, ItaStreamLds<E, false, false>::TOTAL>(proj_grid, dim3(512), s, a)) return rc;
+    return launch<ita_long_ragged_attn_kernel<FAST, E>, ItaLongLds::TOTAL>(attn_grid, dim3(512), s, a, lens);
+  };
+  return with_E(h->w.hdr.E, [&](auto e) { return fast ? run(e, std::true_type{}) : run(e, std::false_type{}); });
+}
+
+}  // namespace
+
+int ita_mha_long_int8_ragged(ita_handle h, int layer, const float* x, float* y, int batch, int seq_stride, const int* lens,
+                             void* stream) {
+  if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
+  return launch_long_ragged(h, layer, x, y, false, batch, seq_stride, lens, (hipStream_t)stream);
+}
+
+// ita_encoder_layer_long on a ragged batch: rows past a frame's length leave the attention launch as zeros, and the FFN
+// launch runs over all batch * seq_stride / 128 blocks as it does there (finite rows in, finite rows out)
+int ita_encoder_layer_long_ragged(ita_handle h, int layer, const float* x, float* y, int batch, int seq_stride, const int* lens,
+                                  void* stream) {
+  if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
+  const Layer& L = h->w.layers[layer];
+  // (launch_long_ragged checks the rest before its first launch: no partial work is left behind an error)
+  if (L.ffn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's FFN is float32 (ITAW0002 blob): no long-sequence encoder layer");
+  if (!L.n1w || !L.n2w) return fail(ITA_ERR_BAD_BLOB, "LayerNorm parameters missing from the blob");
+  if (int rc = launch_long_ragged(h, layer, x, y, true, batch, seq_stride, lens, (hipStream_t)stream)) return rc;
+  return launch_ffn(h, layer, y, y, batch * (seq_stride / 128), true, nullptr, (hipStream_t)stream);
 }
 
 // the same layer with H = 2, 3, 4 or 6 heads: launch_long_heads, then the same FFN launch (an H = 1 blob: the entry above)

@@ -200,6 +200,28 @@ int ita_mha_long_int8_propagate(ita_handle h, int layer, const float* x_dev, int
  * norm parameters ITA_ERR_BAD_BLOB -- all before any launch. */
 int ita_encoder_layer_long(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_len, void* stream);
 
+/* Long-sequence RAGGED batches (csrc/ita_long_ragged_kernel.h): ita_mha_long_int8 and ita_encoder_layer_long for frames of
+ * any token count, each frame with its own.  x, y (B, seq_stride, E) f32 with seq_stride (the row stride of a frame, the
+ * caller pads the allocation) under ita_mha_long_q8's shape rule; lens_dev: B int32 in DEVICE memory, read by the kernel
+ * only -- nothing comes back to the host, and a captured graph follows new lengths on replay.  Frame b has
+ * len_b = min(max(lens[b], 0), seq_stride) tokens:
+ *   rows [0, len_b) of y are the one-head definition on the UNPADDED frame, bit for bit (queries and keys are tokens
+ *     [0, len_b) and nothing else: mha_heads_ref.mha(x[b, :len_b], H = 1); the layer entry: ita_encoder_layer_long of it).
+ *     Whatever lies in x[b, len_b:] -- NaN and Inf included -- has no influence on them: padded keys are masked in all
+ *     three sweeps of the attention kernel (padding on the host cannot do that: the integer softmax takes the row's
+ *     global maximum and sum);
+ *   rows [len_b, seq_stride) of y are 0.0f from ita_mha_long_int8_ragged, and unspecified finite values from
+ *     ita_encoder_layer_long_ragged (its FFN launch runs over all B * seq_stride / 128 blocks);
+ *   len_b == 0 gives a frame of zeros.  The cost of a frame follows len_b squared, not seq_stride squared.
+ * x_dev may equal y_dev.  Workspace and capture rules of ita_mha_long_q8 (sized by seq_stride); kernel launches only.
+ * Refusals, all before any launch, y untouched: whatever ita_mha_long_int8 / ita_encoder_layer_long refuse (the shape rule
+ * applied to seq_stride), with the same status; a blob with H > 1 heads: ITA_ERR_UNSUPPORTED; a NULL lens_dev or one off a
+ * 4-byte boundary: ITA_ERR_INVALID_ARG. */
+int ita_mha_long_int8_ragged(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_stride,
+                             const int* lens_dev, void* stream);
+int ita_encoder_layer_long_ragged(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_stride,
+                                  const int* lens_dev, void* stream);
+
 /* The long-sequence entries for a blob with H = 2, 3, 4 or 6 heads (csrc/ita_long_heads_kernel.h): ita_mha_long_q8,
  * ita_mha_long_int8, ita_mha_long_int8_taps and ita_encoder_layer_long with matmul1, the integer softmax over all seq_len
  * keys and matmul2 run per head of P / H features, the contexts concatenated, one logit and one context multiplier for
