@@ -40,6 +40,7 @@
 #include "ita_long_f32_kernel.h"
 #include "ita_long_f32_stats_kernel.h"
 #include "ita_long_f32_hist_kernel.h"
+#include "ita_long_f32_ragged_kernel.h"
 #include "ita_long_f32_prop_kernel.h"
 #include "ita_ingest_kernel.h"
 #include "ita_ingest_wire_kernel.h"
@@ -1715,6 +1716,60 @@ int ita_encoder_layer_long_f32(ita_handle h, int layer, const float* x, float* y
   if (int rc = L.attn_f32 ? launch_long_f32(h, layer, x, y, true, batch, seq_len, (hipStream_t)stream)
                           : launch_long(h, layer, nullptr, nullptr, x, y, true, batch, seq_len, (hipStream_t)stream)) return rc;
   return launch_ffn_f32(h, layer, y, y, batch * (seq_len / 128), true, (hipStream_t)stream);
+}
+
+namespace {
+
+// Ragged batches on the float path (ita_long_f32_ragged_kernel.h): launch_long_f32's refusals and workspace, the lens
+// checks of launch_long_ragged, then the ragged projection (which stores the units a frame's length reaches, padded tokens
+// as the biases) and the ragged attention launch.  Kernel nodes only: the call can be captured.
+int launch_long_f32_ragged(ita_context* h, int layer, const float* x, float* y, bool fuse_ln, int batch, int seq_stride,
+                           const int* lens, hipStream_t s) {
+  if (!lens || misaligned(lens, 4)) return fail(ITA_ERR_INVALID_ARG, "lens_dev must be a 4-byte aligned device pointer to batch int32");
+  const Layer& L = h->w.layers[layer];
+  if (int rc = check_long_f32(L, batch, seq_stride,
+                              "this layer's attention is int8 (ITAW0001 / ITAW0002 blob): ita_mha_long_int8_ragged runs it")) return rc;
+  if (fuse_ln && !L.n1w) return fail(ITA_ERR_BAD_BLOB, "norm1 parameters missing from the blob");
+  const size_t ntile = (size_t)batch * (seq_stride / 128);
+  const size_t img = ntile * 2 * ItaLongF32Lds::UNIT;
+  if (int rc = ensure_long_ws(h, 2 * img, s)) return rc;
+  ItaLongF32Args a{};
+  a.x = x; a.y = y;
+  a.wq = L.wqf; a.wk = L.wkf; a.wv = L.wvf; a.bq = L.bqf; a.bk = L.bkf; a.bv = L.bvf; a.wo = L.wof; a.bo = L.bof;
+  a.ln_w = L.n1w; a.ln_b = L.n1b;
+  a.kimg = (f32x4*)(char*)h->long_ws; a.vimg = (f32x4*)((char*)h->long_ws + img);
+  a.B = batch; a.S = seq_stride; a.fuse_ln = fuse_ln ? 1 : 0;
+  const size_t cap = 2 * (size_t)h->num_cus;
+  const dim3 proj_grid((unsigned)(ntile < cap ? ntile : cap)), attn_grid(seq_stride / 128, batch);
+  return with_E(h->w.hdr.E, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    if (int rc = launch<ita_f32_ragged::ita_lf32_ragged_proj_kernel<E>>(proj_grid, dim3(512), s, a, lens)) return rc;
+    return launch<ita_f32_ragged::ita_lf32_ragged_attn_kernel<E>, ItaLongF32Lds::TOTAL>(attn_grid, dim3(512), s, a, lens);
+  });
+}
+
+}  // namespace
+
+int ita_mha_long_f32_ragged(ita_handle h, int layer, const float* x, float* y, int batch, int seq_stride, const int* lens,
+                            void* stream) {
+  if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
+  return launch_long_f32_ragged(h, layer, x, y, false, batch, seq_stride, lens, (hipStream_t)stream);
+}
+
+// ita_encoder_layer_long_f32 on a ragged batch: the float ragged launches (ITAW0003) or the int8 ragged launches
+// (ITAW0002) leave rows past a frame's length as zeros, and the float FFN launch runs over all batch * seq_stride / 128
+// blocks as it does there (finite rows in, finite rows out)
+int ita_encoder_layer_long_f32_ragged(ita_handle h, int layer, const float* x, float* y, int batch, int seq_stride,
+                                      const int* lens, void* stream) {
+  if (int rc = check_layer_io(h, layer, x, y, batch)) return rc;
+  const Layer& L = h->w.layers[layer];
+  // (the ragged launch functions check the rest before their first launch: no partial work is left behind an error)
+  if (!L.ffn_f32) return fail(ITA_ERR_UNSUPPORTED, "this layer's FFN is int8 (ITAW0001 blob): ita_encoder_layer_long_ragged runs it");
+  if (h->w.hdr.E != 64 && !L.w1p) return fail(ITA_ERR_UNSUPPORTED, "the float32 FFN of an ITAW0002 blob is built for E = 64");
+  if (!L.n1w || !L.n2w) return fail(ITA_ERR_BAD_BLOB, "LayerNorm parameters missing from the blob");
+  if (int rc = L.attn_f32 ? launch_long_f32_ragged(h, layer, x, y, true, batch, seq_stride, lens, (hipStream_t)stream)
+                          : launch_long_ragged(h, layer, x, y, true, batch, seq_stride, lens, (hipStream_t)stream)) return rc;
+  return launch_ffn_f32(h, layer, y, y, batch * (seq_stride / 128), true, (hipStream_t)stream);
 }
 
 int ita_mha_q8(ita_handle h, int layer, const int8_t* x_q, int8_t* out_q, int batch, void* stream) {

@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = (
     "ita_mha_long_int8_ragged", "ita_encoder_layer_long_ragged",
     "ita_mha_long_heads_q8", "ita_mha_long_heads_int8", "ita_mha_long_heads_int8_taps", "ita_mha_long_heads_int8_stats", "ita_mha_long_heads_int8_hist", "ita_mha_long_heads_int8_propagate", "ita_encoder_layer_long_heads", "ita_ffn_int8", "ita_ffn_int8_taps",
     "ita_ffn_f32", "ita_get_ffn_kind", "ita_mha_f32", "ita_get_attn_kind", "ita_mha_long_f32", "ita_mha_long_f32_taps", "ita_mha_long_f32_stats", "ita_mha_long_f32_hist", "ita_mha_long_f32_propagate", "ita_encoder_layer_long_f32",
+    "ita_mha_long_f32_ragged", "ita_encoder_layer_long_f32_ragged",
     "ita_encoder_layer", "ita_tokenizer", "ita_fusion_tail", "ita_vitlstm_forward", "ita_bind_dispatch",
     "ita_profile_begin", "ita_profile_begin_sampled", "ita_profile_end", "ita_set_tail_mode", "ita_debug_encoder_stamps",
     "ita_fusion_tail_load", "ita_fusion_tail_large",
@@ -223,6 +224,8 @@ def lib():
         L.ita_encoder_layer_long.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_int8_ragged.argtypes = [vp, i, vp, vp, i, i, vp, vp]
         L.ita_encoder_layer_long_ragged.argtypes = [vp, i, vp, vp, i, i, vp, vp]
+        L.ita_mha_long_f32_ragged.argtypes = [vp, i, vp, vp, i, i, vp, vp]
+        L.ita_encoder_layer_long_f32_ragged.argtypes = [vp, i, vp, vp, i, i, vp, vp]
         L.ita_mha_long_heads_q8.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_heads_int8.argtypes = [vp, i, vp, vp, i, i, vp]
         L.ita_mha_long_heads_int8_taps.argtypes = [vp, i, vp, vp, i, i, C.POINTER(_MhaLongTaps), vp]
@@ -1489,6 +1492,39 @@ class Engine:
         y = self.encoder_layer_long_f32(x, 0)
         for layer in range(1, self.num_layers):
             self.encoder_layer_long_f32(y, layer, out=y)
+        return y
+
+    def mha_long_f32_ragged(self, x, lens, layer: int = 0):
+        """mha_long_f32 on a ragged batch: x (B,S_pad,E) f32, S_pad a multiple of 128, frame b holds lens[b] tokens (clamped
+        to [0, S_pad]) -> rows below lens[b] are attn of the unpadded frame, the rest 0 (ita_mha_long_f32_ragged)"""
+        torch = _torch()
+        x = self._long_f32(x)
+        lens = self._long_lens(x, lens)
+        y = torch.empty_like(x)
+        _chk(lib().ita_mha_long_f32_ragged(self._h, layer, x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1],
+                                           lens.data_ptr(), _stream_ptr(self.device)))
+        return y
+
+    def encoder_layer_long_f32_ragged(self, x, lens, layer: int = 0, out=None):
+        """encoder_layer_long_f32 on a ragged batch (ita_encoder_layer_long_f32_ragged; ITAW0002 / ITAW0003 blob): rows
+        below lens[b] are the layer on the unpadded frame, the rest unspecified finite values; out as in
+        encoder_layer_long_f32"""
+        torch = _torch()
+        x = self._long_f32(x)
+        lens = self._long_lens(x, lens)
+        if out is None:
+            out = torch.empty_like(x)
+        elif not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.shape != x.shape:
+            raise ITAError(f"out must be a contiguous f32 GPU tensor of shape {tuple(x.shape)}")
+        _chk(lib().ita_encoder_layer_long_f32_ragged(self._h, layer, x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1],
+                                                     lens.data_ptr(), _stream_ptr(self.device)))
+        return out
+
+    def encode_long_f32_ragged(self, x, lens):
+        """all num_layers float-FFN encoder layers in order on a ragged batch: (B,S_pad,E) f32 -> (B,S_pad,E) f32"""
+        y = self.encoder_layer_long_f32_ragged(x, lens, 0)
+        for layer in range(1, self.num_layers):
+            self.encoder_layer_long_f32_ragged(y, lens, layer, out=y)
         return y
 
     def encode_frames_long_f32(self, frames, tok_h: int, tok_w: int, depth_scale: Optional[float] = None):

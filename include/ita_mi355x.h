@@ -451,6 +451,31 @@ int ita_mha_long_f32_propagate(ita_handle h, int layer, const float* x_dev, int 
  * layer (ITAW0001 blob: ita_encoder_layer_long runs it) is ITA_ERR_UNSUPPORTED and a blob without the layer's norm
  * parameters ITA_ERR_BAD_BLOB -- all before any launch. */
 int ita_encoder_layer_long_f32(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_len, void* stream);
+/* Long-sequence RAGGED batches on the float path (csrc/ita_long_f32_ragged_kernel.h): ita_mha_long_f32 and
+ * ita_encoder_layer_long_f32 for frames of any token count, under the contract of ita_mha_long_int8_ragged.  x, y
+ * (B, seq_stride, E) f32 with seq_stride under ita_mha_long_f32's shape rule; lens_dev: B int32 in DEVICE memory, read by
+ * the kernels only, so a captured graph follows new lengths on replay.  Frame b has len_b = min(max(lens[b], 0), seq_stride)
+ * tokens:
+ *   rows [0, len_b) of y are the float attention (the float layer) of the UNPADDED frame: queries and keys are tokens
+ *     [0, len_b) and nothing else, within ita_mha_long_f32's accuracy of float64; with every len_b a multiple of 64 they
+ *     carry the bits ita_mha_long_f32 gives x[b, :len_b].  Whatever lies in x[b, len_b:] -- NaN and Inf included -- has no
+ *     influence on them, bit for bit: the projection launch writes padded tokens' K and V rows as the biases and skips
+ *     64-key units past len_b, the attention launch masks the padded keys of the last unit;
+ *   rows [len_b, seq_stride) of y are 0.0f from ita_mha_long_f32_ragged, and unspecified finite values from
+ *     ita_encoder_layer_long_f32_ragged (its FFN launch runs over all B * seq_stride / 128 blocks);
+ *   len_b == 0 gives a frame of zeros.  The cost of a frame follows len_b squared, not seq_stride squared.
+ * x_dev may equal y_dev.  Workspace and capture rules of ita_mha_long_f32 (sized by seq_stride); kernel launches only.
+ * ita_encoder_layer_long_f32_ragged serves both blob kinds ita_encoder_layer_long_f32 serves: ITAW0003 by the float ragged
+ * launches, ITAW0002 by those of ita_mha_long_int8_ragged (valid rows: bit for bit the layer on the unpadded frame), each
+ * followed by the float FFN launch.  Refusals, all before any launch, y untouched: whatever ita_mha_long_f32 /
+ * ita_encoder_layer_long_f32 refuse (the shape rule applied to seq_stride), with the same status -- an int8-attention layer
+ * handed to ita_mha_long_f32_ragged: ITA_ERR_UNSUPPORTED, the message names ita_mha_long_int8_ragged; an int8-FFN layer
+ * handed to the layer entry: ITA_ERR_UNSUPPORTED, the message names ita_encoder_layer_long_ragged; missing LayerNorm
+ * parameters: ITA_ERR_BAD_BLOB; a NULL lens_dev or one off a 4-byte boundary: ITA_ERR_INVALID_ARG. */
+int ita_mha_long_f32_ragged(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_stride,
+                            const int* lens_dev, void* stream);
+int ita_encoder_layer_long_f32_ragged(ita_handle h, int layer, const float* x_dev, float* y_dev, int batch, int seq_stride,
+                                      const int* lens_dev, void* stream);
 /* One encoder layer as the model wires it (QAT/model.py:100-113):
  * y = LN2(x1 + ffn(x1)),  x1 = LN1(x + mha(x)).  x_dev and y_dev may alias.
  * A float-FFN layer (ITA_FFN_F32) runs ffn, the residual and LN2 in float32 (QAT_only_attn/model.py:76-88); a
